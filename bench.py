@@ -26,6 +26,11 @@ BASELINE.json asks to be reported at 1 / 2 / 4 / 8 GPUs; a second, shorter run o
 times the pixels (side x sqrt(N): pixels per GPU as at N = 1) is reported next to it as
 config.weak_scaling. `--weak` makes the weak run the reported one.
 
+The scenes are generated for each run (tools/make_scenes.py, seeded) in a directory of the run's own, removed at its end;
+YHAIR_SCENES names a directory to keep them in instead. `--dump-outputs DIR` writes, after the timed steps, what the
+timed path computed: the (H, W, 4) float32 image of the last timed step as DIR/image.npy (above 64 MB a fixed, seeded
+sample of its pixels, DIR/image_sample.npy, with their flat indices in DIR/image_sample_pixels.npy).
+
 The JSON line also carries
   roofline      the sample-loop kernel against the HBM roofline (the contract's bound) — achieved =
                 algorithmic bytes per launch / average launch duration (HIP events on the kernel's
@@ -52,6 +57,7 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 K_SIGMA = 4.0
+DUMP_LIMIT_BYTES = 64_000_000  # --dump-outputs writes at most this much, .npy headers included
 
 # BASELINE.json configs[1..4]
 CONFIGS = {
@@ -314,6 +320,38 @@ def summary_scalars(others, projected, parity, e2e):
     return flat
 
 
+_own_scenes = []
+
+
+def scenes_dir():
+    """YHAIR_SCENES, else a directory of this process's own (made once, removed at exit): a fixed shared directory could hold
+    scenes of another version of tools/make_scenes.py, and then two builds would not render the same inputs."""
+    if os.environ.get("YHAIR_SCENES"):
+        return os.environ["YHAIR_SCENES"]
+    if not _own_scenes:
+        import atexit
+        import shutil
+        import tempfile
+        _own_scenes.append(tempfile.mkdtemp(prefix="yhair_scenes_"))
+        atexit.register(shutil.rmtree, _own_scenes[0], True)
+    return _own_scenes[0]
+
+
+def dump_outputs(np, directory, image):
+    """--dump-outputs: the image the timed path computed, whole when it fits DUMP_LIMIT_BYTES, else a fixed, seeded
+    sample of its pixels next to their flat indices (float64: exact for any image size)."""
+    os.makedirs(directory, exist_ok=True)
+    image = np.ascontiguousarray(image, dtype=np.float32)
+    if image.nbytes <= DUMP_LIMIT_BYTES:
+        np.save(os.path.join(directory, "image.npy"), image)
+        return
+    flat = image.reshape(-1, image.shape[-1])
+    n = (DUMP_LIMIT_BYTES - 4096) // (flat.shape[1] * 4 + 8)  # (4096: room for the two headers)
+    pixels = np.sort(np.random.default_rng(0).choice(len(flat), size=n, replace=False))
+    np.save(os.path.join(directory, "image_sample.npy"), flat[pixels])
+    np.save(os.path.join(directory, "image_sample_pixels.npy"), pixels.astype(np.float64))
+
+
 def spawn_ranks(n):
     """Bare `bench.py --gpus N`: N rank processes of this script (RANK / LOCAL_RANK / WORLD_SIZE / MASTER_* as the
     launcher would set them). The parent never touches the GPU; it waits, ends the others when one fails, and
@@ -326,7 +364,7 @@ def spawn_ranks(n):
     procs = []
     for r in range(n):
         env = dict(os.environ, RANK=str(r), LOCAL_RANK=str(r), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n),
-                   MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0")
+                   MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), HSA_ENABLE_IPC_MODE_LEGACY="0", YHAIR_SCENES=scenes_dir())
         procs.append(subprocess.Popen([sys.executable, os.path.abspath(__file__)] + sys.argv[1:], env=env))
     rc = 0
     pending = set(range(n))
@@ -365,6 +403,8 @@ def main():
                     help="headline run at N = 1: skip config.end_to_end (the yscenetrace command line on the config's scene file, cold and warm trial record, next to the reference's)")
     ap.add_argument("--no-trial-cache", action="store_true", help="do not keep the kernel-trial record on disk (yh_set_trial_cache_dir; the environment's YHAIR_NO_DISK_CACHE does the same)")
     ap.add_argument("--save", default="", help="write the final image (.pfm/.hdr) on rank 0")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="rank 0, after the timed steps: write the image of the last timed step as DIR/image.npy (float32; above 64 MB a fixed, seeded sample of its pixels)")
     ap.add_argument("--weak", action="store_true", help="N > 1: report the weak-scaling run (image side x sqrt(N))")
     ap.add_argument("--strong", action="store_true", help="(default for N > 1; kept for compatibility)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
@@ -377,6 +417,8 @@ def main():
                     help="N = 1: still create the process group and run the framebuffer gather through the collective "
                          "(a one-rank RCCL communicator: how a one-GPU box executes the nccl branch)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(a.gpus))
 
@@ -446,12 +488,12 @@ def main():
         torch.cuda.synchronize()
 
     # ---- scene (rank 0 writes the files, everyone loads them) ------------------------------------
-    scenes_dir = os.environ.get("YHAIR_SCENES", "/tmp/yhair_scenes")
+    scenes = scenes_dir()
     if rank == 0:
-        scene_json = make_scenes.ensure_scene(scene_name, scenes_dir, scale=a.scale, **scene_kw)
+        scene_json = make_scenes.ensure_scene(scene_name, scenes, scale=a.scale, **scene_kw)
     if world > 1:
         dist.barrier()
-    scene_json = make_scenes.ensure_scene(scene_name, scenes_dir, scale=a.scale, **scene_kw)
+    scene_json = make_scenes.ensure_scene(scene_name, scenes, scale=a.scale, **scene_kw)
     ctx = yh.Context(local_rank)
     sf = yh.SceneFile(scene_json)
     t0 = time.time()
@@ -500,7 +542,7 @@ def main():
         the timed steps): value, ms per step, the kernel chosen and its roofline against the committed work counts and
         counter passes. The scene replaces the context's; the caller is done with the headline scene."""
         c = CONFIGS[name]
-        path = make_scenes.ensure_scene(c["scene"], scenes_dir, scale=1.0, **kw)
+        path = make_scenes.ensure_scene(c["scene"], scenes, scale=1.0, **kw)
         osf = yh.SceneFile(path)
         try:
             ctx.upload_scene(osf.desc)
@@ -579,6 +621,9 @@ def main():
     # ---- the reported run (strong: the config's own image; --weak: N times the pixels) ---------------
     res_main = weak_res if (a.weak and world > 1) else base_res
     width, height, elapsed, kernel_ms, p = timed_run(res_main, step_spp, a.warmup)
+    # --dump-outputs: the image of the last timed step. One rank: the context's framebuffer, now (the runs below reuse it);
+    # N > 1: the image gathered after the timed steps (img below)
+    timed_image = ctx.download() if a.dump_outputs and world == 1 else None
     ctx_launches_main = list(ctx_launches)
     shape_used = ctx.launch_shape() if hasattr(ctx, "launch_shape") else None
     trials = {KERNELS.get(k, str(k)): {"ms_per_spp": v[0], "trials": v[1]} for k, v in ctx.kernel_trials().items()}
@@ -655,6 +700,8 @@ def main():
                  "value": round(ow * oh * sum(step_spp[:k_other]) / oel / 1e6, 2), "unit": "Msamples/s"}
 
     img = image.cpu().numpy() if rank == 0 else None  # (a copy: the context's buffers are about to be reused)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(np, a.dump_outputs, timed_image if timed_image is not None else img)
     # ---- how closely device paths FOLLOW the reference's on the scene where the default BSDF arithmetic shows most: the
     # reference's own sphere-hairblock.json (light hair, colour 0.8: eight-bounce paths) against the reference's images of it
     # (tests/golden/refscenes.npz), with the default arithmetic and with yh_trace_params::hair_exact -------------------
@@ -663,7 +710,7 @@ def main():
         try:
             g = np.load(os.path.join(ROOT, "tests", "golden", "refscenes.npz"))
             ref8, ref8_other_seed = g["sphere-hairblock|8"], g["sphere-hairblock|8_seed777"]
-            rsf = yh.SceneFile(make_scenes.ensure_scene("ref-sphere-hairblock", scenes_dir, scale=0.05))
+            rsf = yh.SceneFile(make_scenes.ensure_scene("ref-sphere-hairblock", scenes, scale=0.05))
             ctx.upload_scene(rsf.desc)
             ctx.set_shard(0, 1)
             relrmse = lambda a, b: float(np.sqrt(np.mean((a[..., :3] - b[..., :3]) ** 2)) / max(1e-12, np.mean(b[..., :3])))

@@ -1,6 +1,8 @@
 import os
+import shutil
 import subprocess
 import sys
+import tempfile
 
 import numpy as np
 import pytest
@@ -11,7 +13,10 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 sys.path.insert(0, os.path.join(ROOT, "yocto-hair_amd", "python"))
 GOLD = os.path.join(ROOT, "tests", "golden")
-SCENES = os.environ.get("YHAIR_SCENES", "/tmp/yhair_test_scenes")
+# The scenes are generated for each session (tools/make_scenes.py, about a second for all of them) in a directory of its own: a
+# fixed shared one could hold scenes of another version of the generator, or belong to another user. YHAIR_SCENES names one to keep.
+_OWN_SCENES = not os.environ.get("YHAIR_SCENES")
+SCENES = tempfile.mkdtemp(prefix="yhair_test_scenes_") if _OWN_SCENES else os.environ["YHAIR_SCENES"]
 # The kernel-trial record on disk is opt-in (yh_set_trial_cache_dir / YHAIR_CACHE_DIR) and bench.py opts in: keep every process this
 # suite starts off it, so that no test depends on what an earlier run left behind and the suite leaves nothing behind for the bench
 # (ADVICE r04). test_kernel_trials_persist_on_disk drops the variable for its own subprocesses and names its own directory.
@@ -22,13 +27,16 @@ def pytest_configure(config):
     config.addinivalue_line("markers", "gpu: needs a real MI355X (run with -m gpu on the GPU box)")
 
 
+def pytest_unconfigure(config):
+    if _OWN_SCENES:
+        shutil.rmtree(SCENES, ignore_errors=True)
+
+
 def _ensure_built():
-    """The in-tree shared libraries travel with the snapshot; build whatever is missing."""
-    lib = os.path.join(ROOT, "yocto-hair_amd", "libyhair.so")
-    if not os.path.exists(lib):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "yocto-hair_amd"), "libyhair.so"])
-    if not os.path.exists(os.path.join(ROOT, "oracle", "libyh_oracle.so")):
-        subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "oracle"])
+    """Brings the library, its command lines and the oracle up to date: whatever is missing or older than its sources is
+    rebuilt (after build(), nothing is)."""
+    subprocess.check_call(["make", "-j4", "-s", "-C", os.path.join(ROOT, "yocto-hair_amd"), "all"])
+    subprocess.check_call(["make", "-s", "-C", os.path.join(ROOT, "oracle"), "oracle"])
 
 
 @pytest.fixture(scope="session")

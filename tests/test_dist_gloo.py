@@ -25,17 +25,19 @@ def _worker(rank, world, port, w, h, out_path):
     os.environ["MASTER_ADDR"] = "127.0.0.1"
     os.environ["MASTER_PORT"] = str(port)
     dist.init_process_group("gloo", rank=rank, world_size=world)
+    # gloo's own barrier: dist.barrier() looks for an accelerator first, which initialises HIP on a GPU machine and opens
+    # the device from every one of these CPU-only ranks
     rng = np.random.default_rng(5)
     image = rng.uniform(0, 1, (h, w, 4)).astype(np.float32)  # same on every rank
     packed = torch.from_numpy(yhair_dist.pack_tiles_host(image, rank, world))
     assert packed.shape[0] == yhair_dist.shard_pixels(w, h, rank, world)
-    dist.barrier()
+    dist.monitored_barrier()
     full = yhair_dist.gather_framebuffer(packed, w, h, rank, world)
     if rank == 0:
         np.save(out_path, np.stack([full.numpy(), image]))
     else:
         assert full is None
-    dist.barrier()
+    dist.monitored_barrier()
     dist.destroy_process_group()
 
 
@@ -80,7 +82,7 @@ def test_pack_unpack_roundtrip_host():
     assert np.array_equal(out, img)
 
 
-def test_bare_bench_gpus_2_starts_its_own_ranks_and_reports_their_failure():
+def test_bare_bench_gpus_2_starts_its_own_ranks_and_reports_their_failure(built):
     """`python bench.py --gpus 2` without a launcher: the script starts the two ranks itself. Here (no GPU) both
     ranks fail at yh_create — there is no CPU fallback — and the parent must exit non-zero without printing a line."""
     import subprocess
