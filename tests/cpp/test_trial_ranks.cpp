@@ -9,9 +9,10 @@
 //                                line and a second record for one key): no rank runs a trial, every first request is ONE launch, nobody writes;
 //                                R:S = rank R must run shape S (the LAST complete line of a key counts, torn and damaged ones do not).
 //
-// What is mocked: the launch itself (trace_impl's bookkeeping restated in fake_launch below, the kernel's duration and item costs from a model)
-// and the five launch-geometry queries of csrc/*.hip. What is real: pick_launch_shape, trial_pending, record_launch, trials_load / trials_store,
-// the record's line format, its O_APPEND writes and its reader, replan_after_launch, upload_work_items and the hand-out layouts.
+// What is mocked: the launch itself (fake_launch below: the kernel's duration and item costs from a model) and the
+// launch-geometry queries of csrc/*.hip (the block sizes from the table of launch shapes). What is real: settle_launch_shape and
+// pick_launch_shape, trial_pending, record_launch, trials_load / trials_store, the record's line format, its O_APPEND writes and its reader,
+// replan_after_launch, upload_work_items and the hand-out layouts.
 #include <atomic>
 #include <condition_variable>
 #include <cstdio>
@@ -26,7 +27,7 @@ extern "C" {
 hipError_t  hipFree(void* p) { free(p); return hipSuccess; }
 hipError_t  hipMemcpy(void* dst, const void* src, size_t n, hipMemcpyKind) { memcpy(dst, src, n); return hipSuccess; }
 const char* hipGetErrorString(hipError_t) { return "mock"; }
-int yhk_block_threads(int shape) { return shape == 0 || shape == 5 ? 512 : 256; }
+int yhk_block_threads(int shape) { return yhd_shapes[shape].block_threads; }
 int yhk_trace_lds_bytes(const yhd_scene*, int) { return 32768; }
 int yhk_trace_occupancy(int, int, int shape) { return yhk_block_threads(shape) == 512 ? 2 : 4; }  // 16 waves per CU either way
 int yhk_trace_sbs_lds_bytes(const yhd_scene*) { return 32768; }
@@ -86,8 +87,8 @@ struct Rank {
     ctx.owned.clear();
     for (int t = rank; t < ctx.num_tiles_total; t += world) ctx.owned.push_back(t);
     ctx.item_cost.assign((size_t)ctx.num_tiles_total * 4, 0);
-    ctx.have_costs = false, ctx.costs_settled = false, ctx.dense = -1, ctx.chain = -1, ctx.chain16 = -1, ctx.launch_shape = 0;
-    ctx.state.width = w, ctx.state.height = h, ctx.state.tiles_x = tx, ctx.state.bounces = 8, ctx.state.shader = YH_SHADER_PATH, ctx.state.launch_shape = 0;
+    ctx.have_costs = false, ctx.costs_settled = false, ctx.dense = -1, ctx.chain = -1, ctx.chain16 = -1, ctx.launch_shape = YH_SHAPE_QUAD;
+    ctx.state.width = w, ctx.state.height = h, ctx.state.tiles_x = tx, ctx.state.bounces = 8, ctx.state.shader = YH_SHADER_PATH, ctx.state.launch_shape = YH_SHAPE_QUAD;
     ctx.state.shard_rank = rank, ctx.state.shard_world = world;
     ctx.d_tile_cost.p = calloc((size_t)ctx.num_tiles_total * 4, 4), ctx.d_tile_cost.bytes = (size_t)ctx.num_tiles_total * 16;
     ctx.d_tiles.p = calloc((size_t)ctx.num_tiles_total * 16 + 16, 4), ctx.d_tiles.bytes = ((size_t)ctx.num_tiles_total * 16 + 16) * 4;
@@ -102,13 +103,10 @@ struct Rank {
     ctx.have_costs = true;
     launches = 0, trials_seen = 0;
   }
-  // trace_impl (trace_launch.cpp): the kernel for this launch, the list for it, the launch, the bookkeeping behind it
+  // trace_impl (trace_launch.cpp): the kernel for this launch and the list for it (settle_launch_shape), the launch, the bookkeeping behind it
   int fake_launch(int n) {
-    const int want = pick_launch_shape(&ctx, n);
-    if (want != ctx.state.launch_shape) {
-      ctx.launch_shape = ctx.state.launch_shape = want;
+    if (settle_launch_shape(&ctx, false, n, true))
       if (int rc = upload_work_items(&ctx)) return rc;
-    }
     const int shape = ctx.state.launch_shape;
     ctx.last_shape = shape, ctx.last_counted = false, ctx.planned_settled = ctx.costs_settled;
     const bool was_trial = ctx.costs_settled && n >= YH_TRIAL_SPP && n < 2 * YH_TRIAL_SPP;
@@ -218,7 +216,7 @@ int main(int argc, char** argv) {
         CHECK(one_kernel[sc][r]);
         CHECK(shape[sc][r] == shape[sc][0]);  // ranks whose candidates tie settle on ONE kernel (the fixed order decides, not a rank's noise)
       }
-    CHECK(shape[0][0] == 8 && shape[1][0] == 3);
+    CHECK(shape[0][0] == YH_SHAPE_HEX_GROUPS && shape[1][0] == YH_SHAPE_STREAM);
     const auto lines = read_lines(file);
     CHECK(lines.size() == (size_t)R * 42);  // one line per (rank, image): nobody wrote twice, nobody's line was lost
     std::set<std::string> keys;
@@ -231,7 +229,7 @@ int main(int argc, char** argv) {
   } else {
     const size_t before = read_lines(file).size();
     int expect[R];
-    for (int r = 0; r < R; r++) expect[r] = 8;
+    for (int r = 0; r < R; r++) expect[r] = YH_SHAPE_HEX_GROUPS;
     for (int a = 3; a < argc; a++) {
       int r, s;
       if (sscanf(argv[a], "%d:%d", &r, &s) == 2 && r >= 0 && r < R) expect[r] = s;

@@ -1316,6 +1316,37 @@ def test_stream_shares_render_the_quad_kernels_pixels(ctx, yh, res, shard, monke
     sf.close()
 
 
+@pytest.mark.parametrize("name,kw,general", [("sphere-hairblock", dict(scale=0.05, zoom=True), False), ("lobes", dict(scale=0.05), True)],
+                         ids=["sphere-hairblock", "lobes"])
+def test_counted_launches_fall_back_to_a_shape_with_an_instrumented_build(ctx, yh, name, kw, general, monkeypatch):
+    """The instrumented build (yh_trace_samples_counted) exists for the quad shapes and, on plain scenes only, for the octets and the
+    sixteen lanes without leaf pairs / groups (csrc/yh_device.h: yhd_shapes). Under every forced YHAIR_SHAPE a counted launch runs the
+    table's fallback where it has none — k_stream the quad shape the dense / sparse reading picks, the others 512 x 4 — and the next
+    launch the forced shape again, on a list of its own; pixels and RNG states are the quad kernel's."""
+    sf = yh.SceneFile(scene_path(name, **kw))
+    ctx.upload_scene(sf.desc)
+    ctx.set_shard(0, 1)
+    p = yh.TraceParams.default(resolution=88)
+    fallback = {"0": {0}, "1": {1}, "3": {0, 1}, "4": {4}, "5": {0}, "6": {6}, "7": {0}, "8": {0}}
+    if general:
+        fallback.update({s: {0} for s in "45678"})
+    got = {}
+    for shape in ("0", "1", "3", "4", "5", "6", "7", "8"):
+        monkeypatch.setenv("YHAIR_SHAPE", shape)
+        ctx.init_state(p)
+        ctx.trace_samples_counted(1)
+        assert ctx.launch_shape() in fallback[shape], f"forced {shape}: the counted launch ran shape {ctx.launch_shape()}"
+        ctx.trace_samples(3)
+        assert ctx.launch_shape() == int(shape)
+        got[shape] = (ctx.download(), ctx.download_rng())
+    monkeypatch.delenv("YHAIR_SHAPE")
+    assert got["0"][0][..., 3].max() > 0
+    for shape, (img, rng) in got.items():
+        assert np.array_equal(img, got["0"][0]), f"shape {shape} renders different pixels"
+        assert np.array_equal(rng, got["0"][1]), f"shape {shape} leaves different RNG states"
+    sf.close()
+
+
 @pytest.mark.parametrize("res", [100, 61, 7])
 def test_every_launch_shape_on_ragged_image_sizes(ctx, yh, res, monkeypatch):
     """Image sizes that are not multiples of the 8x8 tile, down to less than one tile: every kernel (quads, octets with

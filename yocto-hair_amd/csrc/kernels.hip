@@ -415,46 +415,42 @@ __global__ void k_curves_to_lines(int n, const float* P, const float* width0, co
 
 extern "C" {
 
-trace_kernel_t yhk_wide_kernel(int counted, int general, int shape);  // csrc/wide.hip: launch shapes 4, 6, 7, 8
+trace_kernel_t yhk_wide_kernel(int counted, int general, int shape);  // csrc/wide.hip: the wide launch shapes
 #define YH_DENSE_WAVES 5 /* 96 VGPRs: at 6 (80 VGPRs) the traversal loop itself spills and the kernel is at the mercy of the register allocator (measured 0.6-0.75x after an unrelated change of the shading code, profiles/r02) */
-// shape 0 = 512 threads x 4 waves per SIMD, shape 1 = 256 threads x YH_DENSE_WAVES (5) waves per SIMD: quads over 4-wide nodes;
-// (shape 2 was the quad form over 8-wide nodes, a closed experiment: never chosen, not built;) shape 4 = 256 x 4, octets over 8-wide nodes (YH_MODE_OCT);
-// shape 6 = 256 x 4, sixteen lanes per path over 16-wide nodes (YH_MODE_HEX); shape 7 = shape 4 with leaf pairs (YH_MODE_OCTP). (3 is k_stream, csrc/stream.hip; 5 the host's
-// side-by-side launch of shapes 0 and 4.) shape 8 = shape 6 with leaf groups (YH_MODE_HEXP).
-static bool shape_oct(int shape) { return shape == 4 || shape == 7; }
-static bool shape_hex(int shape) { return shape == 6 || shape == 8; }
-static int shape_block(int shape) { return shape == 1 ? 256 : (shape_oct(shape) || shape_hex(shape)) ? YH_OCT_BLOCK : YH_BLOCK; }
-static int shape_groups(int shape) { return shape_block(shape) / (shape_hex(shape) ? 16 : shape_oct(shape) ? 8 : 4); }
+// The k_trace launch shapes (csrc/yh_device.h: yhd_shapes): quads over 4-wide nodes at 512 x 4 and at 256 x YH_DENSE_WAVES, and the wide forms
+static_assert(yhd_shapes[YH_SHAPE_QUAD].block_threads == YH_BLOCK && yhd_shapes[YH_SHAPE_OCT].block_threads == YH_OCT_BLOCK && yhd_shapes[YH_SHAPE_HEX].block_threads == YH_OCT_BLOCK, "yhd_shapes");
+static int shape_block(int shape) { return yhd_shapes[shape].block_threads; }
+static int shape_groups(int shape) { return shape_block(shape) / yhd_shapes[shape].lanes_per_path; }
 static trace_kernel_t trace_kernel(bool counted, bool general, int shape, int shader = YH_SHADER_PATH) {
   if (shader == YH_SHADER_NAIVE) return k_trace_shader<YH_SHADER_NAIVE>;
   if (shader == YH_SHADER_EYELIGHT) return k_trace_shader<YH_SHADER_EYELIGHT>;
   if (shader == YH_SHADER_NORMAL) return k_trace_shader<YH_SHADER_NORMAL>;
-  // (instrumented builds of the 8-wide forms: plain scenes only; their per-quad counters count an octet twice, the wave-level ones hold)
-  if (shape_oct(shape) || shape_hex(shape)) return yhk_wide_kernel(counted ? 1 : 0, general ? 1 : 0, shape);  // csrc/wide.hip
-  if (shape == 2) return nullptr;
+  if (yhd_shapes[shape].kind == YH_SHAPE_KIND_WIDE) return yhk_wide_kernel(counted ? 1 : 0, general ? 1 : 0, shape);  // csrc/wide.hip
+  if (yhd_shapes[shape].kind == YH_SHAPE_KIND_RETIRED) return nullptr;
   // The GENERAL variants carry the surface lobes, volumes, textures and the through-memory light code. The dense shape
   // spilled 184 registers at the plain variant's 96 (7 scratch instructions inside its traversal loops): it runs at 256 x 4
   // (128 registers, 49 spilled, none in the traversal loops; lobes / volumes +15-20 %, profiles/r03/general_waves_ab.txt).
   // The 512-thread shape stays at 4 waves per SIMD (68 spilled, none in the traversal loops): at 3 (168 registers, 2
   // spilled) its expensive items no longer fit the resident waves and it loses a third.
-  if (general && !counted && shape == 1) return k_trace<false, true, 256, YH_DENSE_WAVES - 1>;
-  if (shape == 1)
+  if (general && !counted && shape == YH_SHAPE_QUAD_DENSE) return k_trace<false, true, 256, YH_DENSE_WAVES - 1>;
+  if (shape == YH_SHAPE_QUAD_DENSE)
     return counted ? (general ? k_trace<true, true, 256, YH_DENSE_WAVES> : k_trace<true, false, 256, YH_DENSE_WAVES>)
                    : (general ? k_trace<false, true, 256, YH_DENSE_WAVES> : k_trace<false, false, 256, YH_DENSE_WAVES>);
   return counted ? (general ? k_trace<true, true, YH_BLOCK, YH_MIN_WAVES> : k_trace<true, false, YH_BLOCK, YH_MIN_WAVES>)
                  : (general ? k_trace<false, true, YH_BLOCK, YH_MIN_WAVES> : k_trace<false, false, YH_BLOCK, YH_MIN_WAVES>);
 }
 static size_t trace_lds(const yhd_scene* sc, int shape) {
-  const int entries = shape_hex(shape) ? sc->stack_entries16 : shape_oct(shape) ? sc->stack_entries8 : sc->stack_entries;
+  const int lanes   = yhd_shapes[shape].lanes_per_path;
+  const int entries = lanes == 16 ? sc->stack_entries16 : lanes == 8 ? sc->stack_entries8 : sc->stack_entries;
   return (size_t)(entries + YH_HITROWS) * shape_groups(shape) * 4 + (size_t)YHD_LDS_TABLES_F4(sc) * 16;
 }
-// `shape`: 0, 1, 4, 6, 7 or 8 (above); the caller built the work list for it (shape 4: half-quadrant entries)
+// `shape`: a k_trace one (quad or wide); the caller built the work list for it (yhd_shape_info::entries_per_item)
 int yhk_trace(const yhd_scene* sc, const yhd_state* st, int nsamples, yhd_counters* counters, int shape,
     int grid_blocks, hipStream_t stream) {
   const bool path  = st->shader == YH_SHADER_PATH;
-  if (!path) shape = 0;  // the other shaders have one shape (512 x 4)
+  if (!path) shape = YH_SHAPE_QUAD;  // the other shaders have one shape (512 x 4)
   if (!path && counters) return (int)hipErrorInvalidValue;
-  if (shape == 3 || shape == 5 || shape < 0 || shape > 8) return (int)hipErrorInvalidValue;
+  if ((unsigned)shape >= YH_SHAPES || yhd_shapes[shape].kind == YH_SHAPE_KIND_STREAM || yhd_shapes[shape].kind == YH_SHAPE_KIND_SBS) return (int)hipErrorInvalidValue;
   size_t    lds   = trace_lds(sc, shape);
   trace_kernel_t k     = trace_kernel(counters != nullptr, sc->general_materials != 0, shape, st->shader);
   if (!k) return (int)hipErrorInvalidValue;

@@ -1,5 +1,5 @@
-// wide.hip — the sample-loop kernels that give a path MORE than four lanes (gfx950): octets over 8-wide nodes (launch shapes 4, 7),
-// sixteen lanes over 16-wide nodes (6, 8), and the side-by-side launch (5: quads + the top items as octets in one kernel).
+// wide.hip — the sample-loop kernels that give a path MORE than four lanes (gfx950): octets over 8-wide nodes (YH_SHAPE_OCT,
+// _OCT_PAIRS), sixteen lanes over 16-wide nodes (_HEX, _HEX_GROUPS) and the side-by-side launch (_SBS: quads + the top items as octets in one kernel).
 // Split from kernels.hip in round 4 (one translation unit took 77 s to compile); same templates (csrc/dev_items.h), same bits.
 // Compiled with -ffp-contract=off (see dev_math.h).
 #include <hip/hip_runtime.h>
@@ -11,15 +11,16 @@
 
 extern "C" {
 
-// the kernel of a wide launch shape, or NULL when this build does not contain it
+// the kernel of a wide launch shape, or NULL when this build does not contain it. Of the instrumented builds, only those the table of launch
+// shapes lists (csrc/yh_device.h: yhd_shapes; the 8-wide forms on plain scenes: their per-quad counters count an octet twice, the wave-level ones hold).
 trace_kernel_t yhk_wide_kernel(int counted, int general, int shape) {
-  // (instrumented builds of the 8-wide forms: plain scenes only; their per-quad counters count an octet twice, the wave-level ones hold)
-  if (shape == 4 && counted && !general) return k_trace<true, false, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_OCT>;
-  if (shape == 4 && !counted) return general ? k_trace<false, true, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_OCT> : k_trace<false, false, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_OCT>;
-  if (shape == 6 && !counted) return general ? k_trace<false, true, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_HEX> : k_trace<false, false, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_HEX>;
-  if (shape == 6 && counted && !general) return k_trace<true, false, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_HEX>;
-  if (shape == 7 && !counted) return general ? k_trace<false, true, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_OCTP> : k_trace<false, false, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_OCTP>;
-  if (shape == 8 && !counted) return general ? k_trace<false, true, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_HEXP> : k_trace<false, false, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_HEXP>;
+  if (counted && !(general ? yhd_shapes[shape].counted_general : yhd_shapes[shape].counted_plain)) return nullptr;
+  if (shape == YH_SHAPE_OCT && counted && !general) return k_trace<true, false, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_OCT>;
+  if (shape == YH_SHAPE_OCT && !counted) return general ? k_trace<false, true, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_OCT> : k_trace<false, false, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_OCT>;
+  if (shape == YH_SHAPE_HEX && !counted) return general ? k_trace<false, true, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_HEX> : k_trace<false, false, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_HEX>;
+  if (shape == YH_SHAPE_HEX && counted && !general) return k_trace<true, false, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_HEX>;
+  if (shape == YH_SHAPE_OCT_PAIRS && !counted) return general ? k_trace<false, true, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_OCTP> : k_trace<false, false, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_OCTP>;
+  if (shape == YH_SHAPE_HEX_GROUPS && !counted) return general ? k_trace<false, true, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_HEXP> : k_trace<false, false, YH_OCT_BLOCK, YH_MIN_WAVES, YH_MODE_HEXP>;
   return nullptr;
 }
 

@@ -1,5 +1,5 @@
 // yh_device.h — layout of the scene and render state in HBM, shared by the
-// host upload code (g++) and the HIP kernels (hipcc). Plain C structs only.
+// host upload code (g++) and the HIP kernels (hipcc). Plain C structs, and the table of launch shapes.
 //
 // Everything a ray touches is a 16-byte-aligned record fetched with dwordx4
 // loads, laid out so that one traversal step is ONE dependent fetch:
@@ -210,7 +210,7 @@ typedef struct yhd_state {
   unsigned int* tile_cost;  // per item: wall-clock ticks (100 MHz) its last launch took
   int         num_tiles;  // number of work items in `tiles`
   int         shader;        // YH_SHADER_* (yhair.h): path is the product path, the others preview / debug
-  int         launch_shape;  // 0: k_trace 512 threads x 4 waves per SIMD; 1: k_trace 256 x 5 (dense scenes); 3: k_stream; 4-8: the wide forms (host/context_internal.h)
+  int         launch_shape;  // yhd_shape: the sample-loop kernel the list is laid out for (yhd_shapes below)
   int         width, height;
   int         tiles_x;
   int         samples_done;
@@ -219,8 +219,45 @@ typedef struct yhd_state {
   int         shard_rank, shard_world;  // tile ids owned: rank, rank + world, ...
   // (k_trace hands the first grid x waves-per-workgroup entries of `tiles` out BY POSITION — wave w of workgroup b starts
   // with entry b * (waves per workgroup) + w, the rest go through the cursor — and the host lays that head of the list out by
-  // hardware wave slot, host/launch_plan.cpp: lay_out_first_round.)
+  // hardware wave slot, host/launch_plan.cpp: prepare_work_list.)
 } yhd_state;
+
+// LAUNCH SHAPES: the sample-loop kernels the host chooses between, per launch (host/launch_plan.cpp: pick_launch_shape and
+// settle_launch_shape). The numbers are ABI (yh_launch_shape, yh_kernel_trials, YHAIR_SHAPE) and the format of the trial record on disk.
+enum yhd_shape {
+  YH_SHAPE_QUAD       = 0,  // k_trace, a quad per path over 4-wide nodes, 512 threads x 4 waves per SIMD
+  YH_SHAPE_QUAD_DENSE = 1,  // the same at 256 x 5 (dense scenes; GENERAL ones at 256 x 4)
+  YH_SHAPE_RETIRED    = 2,  // was: quads over 8-wide nodes, a closed experiment (profiles/r03/w8_oct_ab.txt); never built
+  YH_SHAPE_STREAM     = 3,  // k_stream, one lane per path (csrc/stream.hip)
+  YH_SHAPE_OCT        = 4,  // k_trace, eight lanes per path over 8-wide nodes (csrc/wide.hip)
+  YH_SHAPE_SBS        = 5,  // side by side: the top items as octets, the others as quads, in one launch (k_trace_sbs)
+  YH_SHAPE_HEX        = 6,  // k_trace, sixteen lanes per path over 16-wide nodes
+  YH_SHAPE_OCT_PAIRS  = 7,  // YH_SHAPE_OCT with leaf pairs
+  YH_SHAPE_HEX_GROUPS = 8,  // YH_SHAPE_HEX with leaf groups
+  YH_SHAPES  // how many there are
+};
+enum yhd_shape_kind { YH_SHAPE_KIND_QUAD, YH_SHAPE_KIND_WIDE, YH_SHAPE_KIND_STREAM, YH_SHAPE_KIND_SBS, YH_SHAPE_KIND_RETIRED };
+typedef struct yhd_shape_info {
+  const char* name;                    // in YHAIR_TIMING's kernel times
+  int kind;                            // yhd_shape_kind
+  int entries_per_item;                // k_trace: work-list entries per work item (a quadrant, its halves or its rows; k_stream and side by side lay out their own)
+  int block_threads, lanes_per_path;
+  int counted_plain, counted_general;  // an instrumented build exists (yh_trace_samples_counted) for plain / GENERAL scenes
+  int fallback;                        // what a launch runs when this shape has no instrumented build or cannot run here; -1: the quad shape the dense / sparse reading picks
+  int tie_rank;                        // among candidates within YH_FINAL_TIE of the fastest, the lowest rank runs (pick_launch_shape)
+} yhd_shape_info;
+static constexpr yhd_shape_info yhd_shapes[YH_SHAPES] = {
+    // name       kind                   entries block lanes counted: plain GENERAL  fallback tie
+    {"quad",       YH_SHAPE_KIND_QUAD,    1, 512, 4,  1, 1, YH_SHAPE_QUAD, 7},
+    {"quad-dense", YH_SHAPE_KIND_QUAD,    1, 256, 4,  1, 1, YH_SHAPE_QUAD, 1},
+    {"retired",    YH_SHAPE_KIND_RETIRED, 1, 512, 4,  0, 0, YH_SHAPE_QUAD, 8},
+    {"stream",     YH_SHAPE_KIND_STREAM,  1, 256, 1,  0, 0, -1, 0},
+    {"oct",        YH_SHAPE_KIND_WIDE,    2, 256, 8,  1, 0, YH_SHAPE_QUAD, 6},
+    {"sbs",        YH_SHAPE_KIND_SBS,     1, 512, 4,  0, 0, YH_SHAPE_QUAD, 2},
+    {"hex",        YH_SHAPE_KIND_WIDE,    4, 256, 16, 1, 0, YH_SHAPE_QUAD, 5},
+    {"oct-pairs",  YH_SHAPE_KIND_WIDE,    2, 256, 8,  0, 0, YH_SHAPE_QUAD, 4},
+    {"hex-groups", YH_SHAPE_KIND_WIDE,    4, 256, 16, 0, 0, YH_SHAPE_QUAD, 3},
+};
 
 // Path pool of the streaming integrator (csrc/stream.hip): one lane per path, `slots_per_wave` slots owned by
 // each WAVEFRONT (no workgroup-level synchronisation), SoA over the slots.

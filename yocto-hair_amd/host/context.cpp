@@ -129,8 +129,6 @@ int yh_image_size(const yh_context* ctx, int* width, int* height) {
   return YH_OK;
 }
 
-// The hand-out order of the work items for the kernel in ctx->state.launch_shape, from the item costs the host holds
-// (it depends on the kernel: k_stream's items are dealt, not queued).
 int yh_download(yh_context* ctx, float* rgba) {
   if (!ctx || !rgba) return YH_E_INVALID;
   if (!ctx->have_state) return fail(ctx, YH_E_STATE, "yh_download before yh_init_state");

@@ -200,12 +200,11 @@ void parallel_for(int n, F&& fn) {
   for (auto& th : pool) th.join();
 }
 
-constexpr int YH_SHAPES = 9;  // launch shapes: 0, 1 k_trace (4-wide nodes) | 2 (was: quads over 8-wide nodes; not built) | 3 k_stream | 4 k_trace with octets | 5 quads and octets side by side | 6 k_trace with sixteen lanes per path | 7 octets with leaf pairs | 8 sixteen lanes with leaf groups
 struct yh_context {
   int         device = 0;
   hipStream_t stream = nullptr;
   hipEvent_t  ev0 = nullptr, ev1 = nullptr;
-  int         hy_quad_items = 0, hy_oct_entries = 0;  // layout of the work list for shape 5: [quad items][octet entries]
+  int         hy_quad_items = 0, hy_oct_entries = 0;  // layout of the work list for YH_SHAPE_SBS: [quad items][octet entries]
   std::vector<int> hy_oct_items;                       // ... and the items that run as octets
   int         num_cus = 0;
   std::string device_name;  // gcnArchName / marketing name / CU count: part of the key of the trial record on disk
@@ -238,7 +237,7 @@ struct yh_context {
   int              last_nsamples = 0;   // samples of the launch the item costs come from
   unsigned         launches_of_image = 0;  // synchronous launches since this IMAGE (scene, resolution, sampler, bounces) was first initialised: the re-planning schedule. A
                                            // re-initialised render of a known image is planned already (item_cost survives it) and goes on where the schedule was
-  int              launch_shape = 0;  // decided from launches of at least 16 spp (shorter ones have flat, noisy item costs)
+  int              launch_shape = YH_SHAPE_QUAD;  // yhd_shape (csrc/yh_device.h: yhd_shapes), decided from launches of at least 16 spp (shorter ones have flat, noisy item costs)
   int              last_shape = -1;   // the kernel the most recent launch ran (yh_launch_shape)
   bool             async_pending = false;  // an asynchronous launch whose time yh_synchronize has still to read
   bool             last_counted = false;  // ... and whether it was the instrumented build (its time ranks nothing)
@@ -259,9 +258,9 @@ struct yh_context {
   bool             costs_settled = false;   // the item costs come from a launch of at least YH_TRIAL_SPP samples (not from the 1-spp probe)
   bool             planned_settled = false; // ... and the most recent launch was planned from such costs (only then does its time rank a kernel)
   int              dense = -1;
-  int              chain16 = -1; // 1: ... and four times as many: the sixteen-lane form (shape 6) is a candidate too
+  int              chain16 = -1; // 1: ... and four times as many: the sixteen-lane forms are candidates too
   int              chain = -1;   // 1: so few expensive items that even twice as many waves would all be resident: the launch is bound by the
-                                 // chain of steps of ONE path, and the octet kernel (half the paths per wave, shape 4) is a candidate
+                                 // chain of steps of ONE path, and the octet kernels (half the paths per wave) are candidates
   // path pool of the streaming integrator (csrc/stream.hip): per-wave slots, allocated at its first launch
   DevBuf           d_st_slots, d_st_medium, d_st_ovf, d_st_prof, d_st_wave_log, d_st_wave_begin, d_st_wave_fill, d_scene_copy;
   int              st_items = 0;         // work items of the list k_stream's hand-out was made for (deal_items_for_stream): what its launch geometry follows
@@ -304,21 +303,20 @@ int upload_keep(yh_context* ctx, DevBuf& buf, const void* src, size_t bytes);  /
 int alloc_zero(yh_context* ctx, DevBuf& buf, size_t bytes);
 yhd_float4 node_lo(const yhh::Node& n);
 yhd_float4 node_hi(const yhh::Node& n);
-int choose_launch_shape(const yh_context* ctx);
+int forced_shape();  // YHAIR_SHAPE, -1 when unset
 void trials_load(yh_context* ctx);
 bool trials_off();
 void record_launch(yh_context* ctx, int nsamples, bool fresh_costs);
 bool trial_pending(const yh_context* ctx);
 int pick_launch_shape(const yh_context* ctx, int nsamples);
+bool settle_launch_shape(yh_context* ctx, bool counted, int nsamples, bool sync);  // true: the list has to be rebuilt
 void build_work_items(const yh_context* ctx, std::vector<int>& items);
-void split_items_for_octets(std::vector<int>& items);
-void split_items_for_hex(std::vector<int>& items);
+void prepare_work_list(yh_context* ctx, std::vector<int>& items, int shape);
 int upload_work_items(yh_context* ctx);
 int expensive_items(const yh_context* ctx, const std::vector<int>& items);
 bool side_by_side_grids(const yh_context* ctx, int* oct_blocks, int* quad_blocks);
 void split_items_side_by_side(yh_context* ctx, std::vector<int>& items);
 void lay_out_range(const yh_context* ctx, int* items, size_t n, int wpb, int G, int block_offset = 0);
-void lay_out_first_round(const yh_context* ctx, std::vector<int>& items, int shape);
 int replan_after_launch(yh_context* ctx, int nsamples);
 bool lane_kernels_can_address(const yh_context* ctx);  // launch_plan.cpp: the lane blob fits the one-lane kernels' 32-bit offsets
 int stream_geometry(const yh_context* ctx, int num_items, int* slots_per_wave, int* grid_blocks, int* lds_out, bool* single_generation = nullptr);

@@ -10,7 +10,7 @@
 // max-cost work items the last launch was worth (sum of item costs over the largest) against the
 // resident wave slots — measured 3 066 (C1), 4 777 (C4), 8 989 (C2), 24 970 (C3) against 4 096: with
 // fewer expensive items than slots every wave that can run already does. This only picks the CANDIDATES; which
-// kernel runs is measured (pick_launch_shape). YHAIR_SHAPE=0..3 overrides.
+// kernel runs is measured (pick_launch_shape).
 // Is the launch worth more max-cost work items than there are resident waves? (item costs of a k_trace launch)
 static bool dense_by_costs(const yh_context* ctx, bool* known, bool* chain_bound = nullptr, bool* chain16 = nullptr) {
   uint64_t sum = 0, mx = 0;
@@ -23,12 +23,12 @@ static bool dense_by_costs(const yh_context* ctx, bool* known, bool* chain_bound
   if (mx == 0) return false;
   // YHAIR_DEVICE_SHARE=k: k processes render on this device at once (bench.py with more ranks than devices): a k-th of the waves is ours
   static const double share = std::max(1, getenv("YHAIR_DEVICE_SHARE") ? atoi(getenv("YHAIR_DEVICE_SHARE")) : 1);
-  int    lds      = yhk_trace_lds_bytes(&ctx->scene, 0);
-  double resident = (double)ctx->num_cus * std::max(1, yhk_trace_occupancy(lds, ctx->scene.general_materials, 0)) * (yhk_block_threads(0) / 64) / share;
+  int    lds      = yhk_trace_lds_bytes(&ctx->scene, YH_SHAPE_QUAD);
+  double resident = (double)ctx->num_cus * std::max(1, yhk_trace_occupancy(lds, ctx->scene.general_materials, YH_SHAPE_QUAD)) * (yhk_block_threads(YH_SHAPE_QUAD) / 64) / share;
   if (getenv("YHAIR_TIMING")) fprintf(stderr, "[yhair] launch shape: worth %.0f items, resident waves %.0f\n", (double)sum / (double)mx, resident);
   if (chain_bound) {  // the octet kernel needs two waves per expensive item: all of them resident at once, with room to spare
-    const int    lds4 = yhk_trace_lds_bytes(&ctx->scene, 4);
-    const double res4 = (double)ctx->num_cus * std::max(1, yhk_trace_occupancy(lds4, ctx->scene.general_materials, 4)) * (yhk_block_threads(4) / 64) / share;
+    const int    lds4 = yhk_trace_lds_bytes(&ctx->scene, YH_SHAPE_OCT);
+    const double res4 = (double)ctx->num_cus * std::max(1, yhk_trace_occupancy(lds4, ctx->scene.general_materials, YH_SHAPE_OCT)) * (yhk_block_threads(YH_SHAPE_OCT) / 64) / share;
     // (candidacy only — the trials decide: generous bounds cost a wasted trial, tight ones a missed kernel; `textured`, whose
     // item costs are very uneven, is worth 1 500 items and still renders 1.45 x faster with sixteen lanes per path)
     *chain_bound      = 2.0 * (double)sum / (double)mx <= 1.1 * res4;  // (C1 at 720^2 is worth 2 400-3 100 items: not one; half of it 1 400-1 700: one)
@@ -36,11 +36,10 @@ static bool dense_by_costs(const yh_context* ctx, bool* known, bool* chain_bound
   }
   return (double)sum / (double)mx >= resident;
 }
-int choose_launch_shape(const yh_context* ctx) {
-  if (const char* env = getenv("YHAIR_SHAPE")) return std::max(0, std::min(YH_SHAPES - 1, atoi(env)));
-  bool known = false;
-  return dense_by_costs(ctx, &known) ? 1 : 0;
+int forced_shape() {  // YHAIR_SHAPE=s (developer switch): every launch runs shape s, or its fallback (settle_launch_shape); -1 when unset
+  return getenv("YHAIR_SHAPE") ? std::max(0, std::min(YH_SHAPES - 1, atoi(getenv("YHAIR_SHAPE")))) : -1;
 }
+static int quad_by_costs(const yh_context* ctx) { return ctx->dense > 0 ? YH_SHAPE_QUAD_DENSE : YH_SHAPE_QUAD; }
 // Kernel selection by MEASUREMENT (every kernel renders the same bits, so trying one costs time only). k_trace at
 // 512 x 4 suits launches bound by a few expensive pixels (C1), k_trace at 256 x 5 and the one-lane-per-path k_stream
 // suit dense scenes, and which of those two wins depends on how many expensive pixels there are per wave
@@ -222,23 +221,23 @@ void trials_load(yh_context* ctx) {
 }
 bool trials_off() {
   static const bool off = getenv("YHAIR_NO_TRIALS") != nullptr;  // developer switch: the cost heuristic only
-  return off || getenv("YHAIR_SHAPE") != nullptr;
+  return off || forced_shape() >= 0;
 }
 // k_trace 512 x 4 always; the dense quad shape unless the image is chain-bound; k_stream on dense images; the side-by-side
 // launch on sparse ones; on chain-bound
 // ones (a shard of a sparse image on one of several GPUs, a small image) the octet kernel and, when even four waves per
-// expensive item are all resident, the sixteen-lane one. (Shape 2 is never tried: profiles/r03/.)
+// expensive item are all resident, the sixteen-lane one. (The retired shape is never tried: profiles/r03/.)
 static int candidates(const yh_context* ctx, int cand[6]) {
   int n = 0;
-  cand[n++] = 0;
+  cand[n++] = YH_SHAPE_QUAD;
   if (ctx->chain > 0 && ctx->dense <= 0) {  // chain-bound: more lanes per path for every item (the dense quad shape and the side-by-side launch are not tried there)
-    cand[n++] = 4, cand[n++] = 7;  // octets, without and with leaf pairs (which of the two wins depends on the share of leaf steps)
-    if (ctx->chain16 > 0) cand[n++] = 6, cand[n++] = 8;  // (likewise without and with leaf groups)
+    cand[n++] = YH_SHAPE_OCT, cand[n++] = YH_SHAPE_OCT_PAIRS;  // octets, without and with leaf pairs (which of the two wins depends on the share of leaf steps)
+    if (ctx->chain16 > 0) cand[n++] = YH_SHAPE_HEX, cand[n++] = YH_SHAPE_HEX_GROUPS;  // (likewise without and with leaf groups)
     return n;
   }
-  if (ctx->dense == 0) cand[n++] = 5;  // sparse, not chain-bound: the few items that top every launch as octets beside the quads (side by side in one launch)
-  cand[n++] = 1;
-  if (ctx->dense > 0) cand[n++] = 3;
+  if (ctx->dense == 0) cand[n++] = YH_SHAPE_SBS;  // sparse, not chain-bound: the few items that top every launch as octets beside the quads (side by side in one launch)
+  cand[n++] = YH_SHAPE_QUAD_DENSE;
+  if (ctx->dense > 0) cand[n++] = YH_SHAPE_STREAM;
   return n;
 }
 // After a synchronous launch: its time if it was a trial-length one, and dense / sparse from fresh item costs of a
@@ -256,7 +255,7 @@ void record_launch(yh_context* ctx, int nsamples, bool fresh_costs) {
   if (fresh_costs && nsamples >= YH_TRIAL_SPP) ctx->costs_settled = true;
   // dense / sparse from the item costs of a k_trace launch long enough to mean something: a trial-length launch, or —
   // while nothing is known yet — one of a few samples (the 1-spp probe's costs are too flat to decide on)
-  if (fresh_costs && (last == 0 || last == 1) && (nsamples >= YH_TRIAL_SPP || (ctx->dense < 0 && nsamples >= 4))) {
+  if (fresh_costs && (last == YH_SHAPE_QUAD || last == YH_SHAPE_QUAD_DENSE) && (nsamples >= YH_TRIAL_SPP || (ctx->dense < 0 && nsamples >= 4))) {
     bool known = false, chain = false, chain16 = false, d = dense_by_costs(ctx, &known, &chain, &chain16);
     if (known) ctx->dense = d ? 1 : 0, ctx->chain = (!d && chain) ? 1 : 0, ctx->chain16 = (!d && chain16) ? 1 : 0;
   }
@@ -293,10 +292,10 @@ bool trial_pending(const yh_context* ctx) {
 }
 // The kernel for a launch of `nsamples`.
 int pick_launch_shape(const yh_context* ctx, int nsamples) {
-  if (ctx->params.hair_exact) return 0;  // the exact arithmetic exists as the 512 x 4 quad kernel only (csrc/exact.hip)
-  if (const char* env = getenv("YHAIR_SHAPE")) return std::max(0, std::min(YH_SHAPES - 1, atoi(env)));
+  if (ctx->params.hair_exact) return YH_SHAPE_QUAD;  // the exact arithmetic exists as the 512 x 4 quad kernel only (csrc/exact.hip)
+  if (const int forced = forced_shape(); forced >= 0) return forced;
   if (!ctx->have_costs) return ctx->launch_shape;  // the first launch of an image: unplanned, not a measurement
-  const int by_costs = ctx->dense > 0 ? 1 : 0;
+  const int by_costs = quad_by_costs(ctx);
   if (trials_off()) return by_costs;
   int cand[6], n = candidates(ctx, cand), best = -1;
   const bool trial_length = ctx->costs_settled && nsamples >= YH_TRIAL_SPP && nsamples < 2 * YH_TRIAL_SPP && !(ctx->trials_from_disk && !trial_pending(ctx));
@@ -307,14 +306,13 @@ int pick_launch_shape(const yh_context* ctx, int nsamples) {
     if (best < 0 || ctx->shape_ms[c] < ctx->shape_ms[best]) best = c;
   }
   if (best < 0) return by_costs;
-  // A tie is decided by a FIXED order, not by the noise of the last 32-sample launch: among the candidates within
+  // A tie is decided by a FIXED order (yhd_shape_info::tie_rank), not by the noise of the last 32-sample launch: among the candidates within
   // YH_FINAL_TIE of the fastest the first of k_stream, the dense quad shape, the side-by-side launch, the wide forms
   // (leaf groups before plain), the plain quad kernel — so that two renders (two ranks, two boxes) of one image run the same kernel.
-  static const int order[YH_SHAPES] = {3, 1, 5, 8, 7, 6, 4, 0, 2};
-  for (int o = 0; o < YH_SHAPES; o++)
-    for (int k = 0; k < n; k++)
-      if (cand[k] == order[o] && ctx->shape_ms[cand[k]] != 0 && ctx->shape_ms[cand[k]] <= YH_FINAL_TIE * ctx->shape_ms[best]) return cand[k];
-  return best;
+  int pick = best;
+  for (int k = 0; k < n; k++)
+    if (ctx->shape_ms[cand[k]] != 0 && ctx->shape_ms[cand[k]] <= YH_FINAL_TIE * ctx->shape_ms[best] && yhd_shapes[cand[k]].tie_rank < yhd_shapes[pick].tie_rank) pick = cand[k];
+  return pick;
 }
 void build_work_items(const yh_context* ctx, std::vector<int>& items) {
   // Expensive items first, in decreasing cost (they bound the launch); the cheap
@@ -339,42 +337,13 @@ void build_work_items(const yh_context* ctx, std::vector<int>& items) {
   items.resize(keys.size());
   for (size_t i = 0; i < keys.size(); i++) items[i] = (int)(keys[i] & 0xFFFFFFFFu);
 }
-// The octet kernel (launch shape 4: eight lanes per path) takes HALF a quadrant per wave: entry = item << 1 | half, the two
-// halves of an item next to each other in the cost-sorted order.
-void split_items_for_octets(std::vector<int>& items) {
-  std::vector<int> out;
-  out.reserve(items.size() * 2);
-  for (int it : items) out.push_back(it << 1), out.push_back((it << 1) | 1);
-  items.swap(out);
-}
-// ... and the sixteen-lane form (shape 6) a QUARTER: entry = item << 2 | row of the 4x4 block.
-void split_items_for_hex(std::vector<int>& items) {
-  std::vector<int> out;
-  out.reserve(items.size() * 4);
-  for (int it : items)
-    for (int k = 0; k < 4; k++) out.push_back((it << 2) | k);
-  items.swap(out);
-}
-int upload_work_items(yh_context* ctx) {
-  std::vector<int> tiles;
-  build_work_items(ctx, tiles);
-  ctx->state.num_groups = 1, ctx->state.group_begin[0] = 0, ctx->state.group_begin[1] = (int)tiles.size();
-  if (ctx->state.shader == YH_SHADER_PATH && ctx->state.launch_shape == 3) deal_items_for_stream(ctx, tiles);
-  if (ctx->state.shader == YH_SHADER_PATH && (ctx->state.launch_shape == 4 || ctx->state.launch_shape == 7)) split_items_for_octets(tiles);
-  if (ctx->state.shader == YH_SHADER_PATH && ctx->state.launch_shape == 5) split_items_side_by_side(ctx, tiles);
-  if (ctx->state.shader == YH_SHADER_PATH && (ctx->state.launch_shape == 6 || ctx->state.launch_shape == 8)) split_items_for_hex(tiles);
-  lay_out_first_round(ctx, tiles, ctx->state.shader == YH_SHADER_PATH ? ctx->state.launch_shape : 0);
-  ctx->state.num_tiles = (int)tiles.size();
-  HIPCHK(ctx, hipMemcpy(ctx->d_tiles.p, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice));
-  return YH_OK;
-}
 
-// SIDE BY SIDE (launch shape 5). The launch of a sparse image ends with its most expensive items: every expensive item runs
+// SIDE BY SIDE (YH_SHAPE_SBS). The launch of a sparse image ends with its most expensive items: every expensive item runs
 // from the start, and the launch is as long as the longest chain (C1: the most expensive quadrant takes 14.8 ms per 64
 // samples, the median expensive one 9 ms). The same handful of quadrants tops EVERY launch, and the octet form runs an item
 // in 0.74 x the time for two waves instead of one — so the first K items of the cost-sorted list run as octets and
 // everything else as quads, in ONE launch (csrc/kernels.hip: k_trace_sbs): its first workgroups take the octet entries,
-// the others the quad items. The first workgroups of a launch get the fastest wave slots (lay_out_first_round below), the
+// the others the quad items. The first workgroups of a launch get the fastest wave slots (prepare_work_list below), the
 // workgroups are of one size, and there is one dispatch order — the three things the earlier forms of this idea lacked
 // (two kernels on two streams: the streams raced for the slots and the workgroup sizes did not pack, 14.8 -> 18.7 ms;
 // one kernel whose waves pick the form per item: 5-10 % behind before any item was widened). Both forms render the quad
@@ -444,13 +413,60 @@ void lay_out_range(const yh_context* ctx, int* items, size_t n, int wpb, int G, 
   for (size_t k = 0; k < P; k++) head[order[k].second] = items[k];  // the k-th most expensive item on the k-th fastest wave
   std::copy(head.begin(), head.end(), items);
 }
-void lay_out_first_round(const yh_context* ctx, std::vector<int>& items, int shape) {
-  if (shape == 3 || shape == 5 || items.empty()) return;  // (k_stream deals its items itself; side by side lays its two lists out when it splits them)
-  const int wpb = yhk_block_threads(shape) / 64;
+// The work list of a launch of `shape` (the preview shaders: YH_SHAPE_QUAD) from the cost-sorted items: k_stream deals them, side by side
+// splits and lays out its two lists, and k_trace's wide forms take part of a quadrant per wave (yhd_shape_info::entries_per_item): the
+// octets half, entry = item << 1 | half, the sixteen-lane forms a row of the 4x4 block, entry = item << 2 | row, the parts of an item
+// next to each other in the cost-sorted order; then the head of a k_trace list is laid out by wave slot.
+void prepare_work_list(yh_context* ctx, std::vector<int>& items, int shape) {
+  ctx->state.num_groups = 1, ctx->state.group_begin[0] = 0, ctx->state.group_begin[1] = (int)items.size();
+  const yhd_shape_info& s = yhd_shapes[shape];
+  if (s.kind == YH_SHAPE_KIND_STREAM) return deal_items_for_stream(ctx, items);
+  if (s.kind == YH_SHAPE_KIND_SBS) return split_items_side_by_side(ctx, items);
+  if (s.entries_per_item > 1) {
+    std::vector<int> out;
+    out.reserve(items.size() * s.entries_per_item);
+    for (int it : items)
+      for (int k = 0; k < s.entries_per_item; k++) out.push_back(it * s.entries_per_item + k);
+    items.swap(out);
+  }
+  const int wpb = yhk_block_threads(shape) / 64;  // the head of the list by wave slot, for the grid trace_impl launches
   const int occ = yhk_trace_occupancy(yhk_trace_lds_bytes(&ctx->scene, shape), ctx->scene.general_materials, shape);
-  if (occ < 1 || wpb < 1) return;
-  const int G = std::max(1, std::min(((int)items.size() + wpb - 1) / wpb, ctx->num_cus * occ));  // the grid trace_impl launches
-  lay_out_range(ctx, items.data(), items.size(), wpb, G);
+  if (items.empty() || occ < 1 || wpb < 1) return;
+  lay_out_range(ctx, items.data(), items.size(), wpb, std::max(1, std::min(((int)items.size() + wpb - 1) / wpb, ctx->num_cus * occ)));
+}
+int upload_work_items(yh_context* ctx) {
+  std::vector<int> tiles;
+  build_work_items(ctx, tiles);
+  prepare_work_list(ctx, tiles, ctx->state.shader == YH_SHADER_PATH ? ctx->state.launch_shape : YH_SHAPE_QUAD);
+  ctx->state.num_tiles = (int)tiles.size();
+  HIPCHK(ctx, hipMemcpy(ctx->d_tiles.p, tiles.data(), tiles.size() * 4, hipMemcpyHostToDevice));
+  return YH_OK;
+}
+// The kernel of a path-shader launch, settled before it is queued: the picked one (or YHAIR_SHAPE's), its fallback
+// (yhd_shape_info::fallback) when it has no instrumented build for a counted launch, and — unless forced — when it cannot run here:
+// k_stream without its 32-bit offsets or its LDS layout, a wide form whose LDS stacks leave no workgroup resident (the occupancy of the
+// instrumented build is not asked). A candidate that cannot run is dropped (+inf), not an error: every kernel renders the same bits.
+// Returns whether the kernel changed: then its work list has to be rebuilt (upload_work_items).
+bool settle_launch_shape(yh_context* ctx, bool counted, int nsamples, bool sync) {
+  if (ctx->state.shader != YH_SHADER_PATH) return false;  // (the preview shaders have one launch shape)
+  int shape = counted ? ctx->state.launch_shape : pick_launch_shape(ctx, sync ? nsamples : 0);  // (an asynchronous launch is not timed: never a trial)
+  if (!counted && shape != ctx->state.launch_shape && getenv("YHAIR_TIMING")) {
+    for (int k = 0; k < YH_SHAPES; k++) fprintf(stderr, "%s %s: %.4f", k ? "," : "[yhair] kernel times (ms per spp):", yhd_shapes[k].name, ctx->shape_ms[k]);
+    fprintf(stderr, " -> %d (%d spp)\n", shape, nsamples);
+  }
+  auto fallback = [ctx](int s) { return yhd_shapes[s].fallback < 0 ? quad_by_costs(ctx) : yhd_shapes[s].fallback; };
+  const int general = ctx->scene.general_materials;
+  if (counted && !(general ? yhd_shapes[shape].counted_general : yhd_shapes[shape].counted_plain)) shape = fallback(shape);
+  if (forced_shape() < 0) {  // (a forced shape that cannot run fails at its launch)
+    const int kind = yhd_shapes[shape].kind;
+    int       P = 0, grid = 0;
+    if ((kind == YH_SHAPE_KIND_STREAM && !stream_geometry(ctx, (int)ctx->owned.size() * 4, &P, &grid, nullptr)) ||  // (as many items as deal_items_for_stream deals)
+        (kind == YH_SHAPE_KIND_WIDE && !counted && yhk_trace_occupancy(yhk_trace_lds_bytes(&ctx->scene, shape), general, shape) < 1))
+      ctx->shape_ms[shape] = std::numeric_limits<double>::infinity(), shape = fallback(shape);
+  }
+  if (shape == ctx->state.launch_shape) return false;
+  ctx->launch_shape = ctx->state.launch_shape = shape;
+  return true;
 }
 
 // Bookkeeping after a synchronous launch: its time (kernel selection) and, after launches 1, 2, 4, 8, ... of a state,
@@ -468,7 +484,7 @@ int replan_after_launch(yh_context* ctx, int nsamples) {
   const bool     refresh = (li & (li - 1)) == 0 || ctx->last_ms >= 50.0f || (!ctx->costs_settled && nsamples >= YH_TRIAL_SPP && ctx->state.shader == YH_SHADER_PATH);
   if (refresh) HIPCHK(ctx, hipMemcpy(ctx->item_cost.data(), ctx->d_tile_cost.p, ctx->item_cost.size() * 4, hipMemcpyDeviceToHost));
   if (refresh) ctx->last_nsamples = nsamples;
-  if (refresh && ctx->last_shape == 5)  // an item that ran as octets reports the time of its two halves, 2 x 0.74 of what it costs as a quad
+  if (refresh && ctx->last_shape == YH_SHAPE_SBS)  // an item that ran as octets reports the time of its two halves, 2 x 0.74 of what it costs as a quad
     for (int it : ctx->hy_oct_items) ctx->item_cost[(size_t)it] = (unsigned int)((double)ctx->item_cost[(size_t)it] * (1.0 / 1.48));
   if (ctx->state.shader == YH_SHADER_PATH && (refresh || ctx->have_costs)) record_launch(ctx, nsamples, refresh);
   if (!refresh) return YH_OK;

@@ -592,7 +592,7 @@ int yh_upload_scene(yh_context* ctx, const yh_scene_desc* sd) {
   ctx->d_scene_copy.reset();  // (stream_impl uploads the new table at its first launch)
   ctx->have_scene = true;
   ctx->have_state = false;
-  ctx->launch_shape = 0;  // a new scene: no measured costs yet
+  ctx->launch_shape = YH_SHAPE_QUAD;  // a new scene: no measured costs yet
   ctx->item_cost.clear();
   ctx->have_costs = false, ctx->costs_settled = false, ctx->dense = -1, ctx->chain = -1, ctx->chain16 = -1;
   for (double& t : ctx->shape_ms) t = 0;

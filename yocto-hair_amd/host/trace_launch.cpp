@@ -91,20 +91,15 @@ int yh_init_state(yh_context* ctx, const yh_trace_params* params) {
   if ((int)ctx->item_cost.size() != ctx->num_tiles_total * 4) {  // scheduling hints survive a re-init of the same image
     ctx->item_cost.assign((size_t)ctx->num_tiles_total * 4, 0);
     ctx->item_scale.clear(), ctx->st_log_fresh = false;
-    ctx->have_costs = false, ctx->costs_settled = false, ctx->dense = -1, ctx->chain = -1, ctx->chain16 = -1, ctx->launch_shape = 0;
+    ctx->have_costs = false, ctx->costs_settled = false, ctx->dense = -1, ctx->chain = -1, ctx->chain16 = -1, ctx->launch_shape = YH_SHAPE_QUAD;
     for (double& t : ctx->shape_ms) t = 0;
     for (int& t : ctx->shape_trials) t = 0;
     new_image = true;
   }
   std::vector<int> tiles;
   build_work_items(ctx, tiles);
-  const int first_shape = getenv("YHAIR_SHAPE") ? choose_launch_shape(ctx) : ctx->launch_shape;
-  ctx->state.tiles_x = tx, ctx->state.num_groups = 1, ctx->state.group_begin[0] = 0, ctx->state.group_begin[1] = (int)tiles.size();
-  if (params->shader == YH_SHADER_PATH && first_shape == 3) deal_items_for_stream(ctx, tiles);
-  if (params->shader == YH_SHADER_PATH && (first_shape == 4 || first_shape == 7)) split_items_for_octets(tiles);
-  if (params->shader == YH_SHADER_PATH && first_shape == 5) split_items_side_by_side(ctx, tiles);
-  if (params->shader == YH_SHADER_PATH && (first_shape == 6 || first_shape == 8)) split_items_for_hex(tiles);
-  lay_out_first_round(ctx, tiles, params->shader == YH_SHADER_PATH ? first_shape : 0);
+  const int first_shape = forced_shape() >= 0 ? forced_shape() : ctx->launch_shape;
+  prepare_work_list(ctx, tiles, params->shader == YH_SHADER_PATH ? first_shape : YH_SHAPE_QUAD);
   tiles.reserve(4 * (size_t)ctx->num_tiles_total * 4 + 4);  // (the list's buffer holds the octet / sixteen-lane kernels' longer lists too)
   int rc;
   if ((rc = upload(ctx, ctx->d_rng_state, st.data(), npix * 8))) return rc;
@@ -140,7 +135,7 @@ int yh_init_state(yh_context* ctx, const yh_trace_params* params) {
   for (int t : owned)
     for (int q = 0; q < 4 && !measured; q++) measured = ctx->item_cost[(size_t)t * 4 + q] != 0;
   if (!measured && !owned.empty() && params->shader == YH_SHADER_PATH && !getenv("YHAIR_NO_PROBE")) {
-    ctx->state.launch_shape = 0;
+    ctx->state.launch_shape = YH_SHAPE_QUAD;
     int prc = trace_impl(ctx, 1, false, true);  // blocking; re-plans the hand-out order from the measured costs
     if (prc) return prc;
     HIPCHK(ctx, hipMemcpy(ctx->d_rng_state.p, st.data(), npix * 8, hipMemcpyHostToDevice));
@@ -151,6 +146,20 @@ int yh_init_state(yh_context* ctx, const yh_trace_params* params) {
     lap("probe launch + plan");
   }
   return YH_OK;
+}
+
+// The end of every sample-loop launch: its stop event and samples and, for a blocking one, the bounded wait, its time, what the
+// kernel leaves to read back (`read_back`: k_stream's wave stamps) and the re-plan.
+template <typename F>
+static int end_launch(yh_context* ctx, int nsamples, bool sync, F&& read_back) {
+  HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  ctx->state.samples_done += nsamples;
+  ctx->last_launches = 1;
+  if (!sync) return YH_OK;
+  if (int wrc = wait_for_launch(ctx)) return wrc;
+  HIPCHK(ctx, hipEventElapsedTime(&ctx->last_ms, ctx->ev0, ctx->ev1));
+  if (int rc = read_back()) return rc;
+  return replan_after_launch(ctx, nsamples);
 }
 
 // One launch of the streaming integrator (csrc/stream.hip): persistent wavefronts, one path pool each, one lane per path.
@@ -226,12 +235,7 @@ int stream_impl(yh_context* ctx, int nsamples, bool sync) {
   HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   int e = yhk_stream(&ctx->scene, (const yhd_scene*)ctx->d_scene_copy.p, &ctx->state, nsamples, &ctx->stream_pool, grid, ctx->stream);
   if (e) return fail(ctx, YH_E_DEVICE, "k_stream launch: %s", hipGetErrorString((hipError_t)e));
-  HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  ctx->state.samples_done += nsamples;
-  ctx->last_launches = 1;
-  if (sync) {
-    if (int wrc = wait_for_launch(ctx)) return wrc;
-    HIPCHK(ctx, hipEventElapsedTime(&ctx->last_ms, ctx->ev0, ctx->ev1));
+  return end_launch(ctx, nsamples, sync, [&]() -> int {
     std::vector<unsigned long long> w(waves * 2);
     HIPCHK(ctx, hipMemcpy(w.data(), ctx->d_st_wave_log.p, w.size() * 8, hipMemcpyDeviceToHost));
     note_stream_wave_log(ctx, w.data(), waves);
@@ -296,9 +300,8 @@ int stream_impl(yh_context* ctx, int nsamples, bool sync) {
         fprintf(stderr, "[yhair]   branch %-9s ran in %5.1f %% of the wave steps (%llu times), %.1f lanes on average\n", br[b],
             c[32] ? 100.0 * (double)c[32 + 2 * b] / (double)c[32] : 0.0, c[32 + 2 * b], c[32 + 2 * b] ? (double)c[33 + 2 * b] / (double)c[32 + 2 * b] : 0.0);
     }
-    return replan_after_launch(ctx, nsamples);
-  }
-  return YH_OK;
+    return YH_OK;
+  });
 }
 
 int trace_impl(yh_context* ctx, int nsamples, bool counted, bool sync) {
@@ -314,53 +317,18 @@ int trace_impl(yh_context* ctx, int nsamples, bool counted, bool sync) {
   }
   const bool path = ctx->state.shader == YH_SHADER_PATH;
   if (counted && !path) return fail(ctx, YH_E_INVALID, "work counters exist for the path shader only");
-  if (path && !counted) {  // the kernel for this launch; the hand-out order follows it
-    const int want = pick_launch_shape(ctx, sync ? nsamples : 0);  // (an asynchronous launch is not timed: never a trial)
-    if (want != ctx->state.launch_shape) {
-      if (getenv("YHAIR_TIMING"))
-        fprintf(stderr, "[yhair] kernel times (ms per spp): 0: %.4f, 1: %.4f, 2: %.4f, 3: %.4f, 4: %.4f, 5: %.4f, 6: %.4f, 7: %.4f, 8: %.4f -> %d (%d spp)\n", ctx->shape_ms[0], ctx->shape_ms[1], ctx->shape_ms[2], ctx->shape_ms[3], ctx->shape_ms[4], ctx->shape_ms[5], ctx->shape_ms[6], ctx->shape_ms[7], ctx->shape_ms[8], want, nsamples);
-      ctx->launch_shape = ctx->state.launch_shape = want;
-      // The list is rewritten by a blocking copy on the null stream; the context's stream is non-blocking, so a launch
-      // queued by yh_trace_samples_async may still be reading it: wait for it first.
-      if (int wrc = wait_for_launch(ctx)) return wrc;
-      if (int rc = upload_work_items(ctx)) return rc;
-    }
-  }
-  if (counted && ctx->state.launch_shape == 3) {  // k_stream's list may be shared out per wave and padded with -1 (deal_shares_by_speed): the instrumented quad build needs a plain one
-    ctx->launch_shape = ctx->state.launch_shape = ctx->dense > 0 ? 1 : 0;
+  if (settle_launch_shape(ctx, counted, nsamples, sync)) {  // the kernel for this launch; the hand-out order follows it
+    // The list is rewritten by a blocking copy on the null stream; the context's stream is non-blocking, so a launch
+    // queued by yh_trace_samples_async may still be reading it: wait for it first.
     if (int wrc = wait_for_launch(ctx)) return wrc;
     if (int rc = upload_work_items(ctx)) return rc;
   }
-  if (counted && (ctx->state.launch_shape == 5 || (ctx->state.launch_shape >= 4 && (ctx->scene.general_materials || ctx->state.launch_shape >= 7)))) {  // the octet kernel's list holds half-quadrant entries: the instrumented (quad) build needs its own
-    ctx->launch_shape = ctx->state.launch_shape = 0;
-    if (int wrc = wait_for_launch(ctx)) return wrc;
-    if (int rc = upload_work_items(ctx)) return rc;
-  }
-  int shape = path ? ctx->state.launch_shape : 0;  // the preview shaders have one launch shape
-  if (counted && (shape == 3 || (shape >= 2 && ctx->scene.general_materials))) shape = shape == 3 ? 1 : 0;  // no instrumented build of k_stream, nor of the GENERAL 8-wide forms
-  if (shape == 3 && !getenv("YHAIR_SHAPE")) {      // a candidate that cannot run here is dropped, not an error: k_trace renders the same bits
-    int P = 0, grid = 0;
-    if (!stream_geometry(ctx, ctx->st_items > 0 ? ctx->st_items : ctx->state.num_tiles, &P, &grid, nullptr)) {
-      ctx->shape_ms[3] = std::numeric_limits<double>::infinity();
-      shape = ctx->dense > 0 ? 1 : 0;
-      ctx->launch_shape = ctx->state.launch_shape = shape;
-      if (int wrc = wait_for_launch(ctx)) return wrc;
-      if (int rc = upload_work_items(ctx)) return rc;
-    }
-  }
-  if ((shape == 4 || shape >= 6) && !counted && !getenv("YHAIR_SHAPE") &&
-      yhk_trace_occupancy(yhk_trace_lds_bytes(&ctx->scene, shape), ctx->scene.general_materials, shape) < 1) {  // (likewise: a tree too deep for the wide forms' LDS stacks)
-    ctx->shape_ms[shape] = std::numeric_limits<double>::infinity();
-    shape = 0;
-    ctx->launch_shape = ctx->state.launch_shape = shape;
-    if (int wrc = wait_for_launch(ctx)) return wrc;
-    if (int rc = upload_work_items(ctx)) return rc;
-  }
+  const int shape = path ? ctx->state.launch_shape : YH_SHAPE_QUAD;  // the preview shaders have one launch shape
   ctx->last_shape = shape, ctx->last_counted = counted, ctx->planned_settled = ctx->costs_settled;
-  if (shape == 3) return stream_impl(ctx, nsamples, sync);
-  if (shape == 2) return fail(ctx, YH_E_INVALID, "launch shape 2 (quads over 8-wide nodes) was a developer kernel and is not built (profiles/r03/w8_oct_ab.txt)");
-  if (shape == 5 && !counted) return side_by_side_impl(ctx, nsamples, sync);
-  if (shape == 5) shape = 0;  // (instrumented: guarded above, the list was rebuilt for the quad kernel)
+  const int kind = yhd_shapes[shape].kind;
+  if (kind == YH_SHAPE_KIND_STREAM) return stream_impl(ctx, nsamples, sync);
+  if (kind == YH_SHAPE_KIND_RETIRED) return fail(ctx, YH_E_INVALID, "launch shape 2 (quads over 8-wide nodes) was a developer kernel and is not built (profiles/r03/w8_oct_ab.txt)");
+  if (kind == YH_SHAPE_KIND_SBS) return side_by_side_impl(ctx, nsamples, sync);  // (never counted: no instrumented build)
   int waves_per_block = yhk_block_threads(shape) / 64;  // one work item per wave at a time
   int lds_bytes       = yhk_trace_lds_bytes(&ctx->scene, shape);
   const bool exact    = path && ctx->params.hair_exact && !counted;
@@ -375,15 +343,7 @@ int trace_impl(yh_context* ctx, int nsamples, bool counted, bool sync) {
   int e = exact ? yhk_trace_exact(&ctx->scene, &ctx->state, nsamples, lds_bytes, grid, ctx->stream)
                 : yhk_trace(&ctx->scene, &ctx->state, nsamples, counted ? (yhd_counters*)ctx->d_counters.p : nullptr, shape, grid, ctx->stream);
   if (e) return fail(ctx, YH_E_DEVICE, "k_trace launch: %s", hipGetErrorString((hipError_t)e));
-  HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  ctx->state.samples_done += nsamples;
-  ctx->last_launches = 1;
-  if (sync) {
-    if (int wrc = wait_for_launch(ctx)) return wrc;
-    HIPCHK(ctx, hipEventElapsedTime(&ctx->last_ms, ctx->ev0, ctx->ev1));
-    return replan_after_launch(ctx, nsamples);
-  }
-  return YH_OK;
+  return end_launch(ctx, nsamples, sync, [] { return YH_OK; });
 }
 // One side-by-side launch: k_trace_sbs over the whole list — its first G_o workgroups the octet entries behind the quad items,
 // the other G_q the quad items [0, hy_quad_items).
@@ -395,15 +355,7 @@ int side_by_side_impl(yh_context* ctx, int nsamples, bool sync) {
   HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
   int e = yhk_trace_sbs(&ctx->scene, &ctx->state, nsamples, G_o, ctx->hy_quad_items, ctx->hy_oct_entries, std::max(1, G_o + G_q), ctx->stream);
   if (e) return fail(ctx, YH_E_DEVICE, "k_trace_sbs launch: %s", hipGetErrorString((hipError_t)e));
-  HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  ctx->state.samples_done += nsamples;
-  ctx->last_launches = 1;
-  if (sync) {
-    if (int wrc = wait_for_launch(ctx)) return wrc;
-    HIPCHK(ctx, hipEventElapsedTime(&ctx->last_ms, ctx->ev0, ctx->ev1));
-    return replan_after_launch(ctx, nsamples);
-  }
-  return YH_OK;
+  return end_launch(ctx, nsamples, sync, [] { return YH_OK; });
 }
 int yh_trace_samples(yh_context* ctx, int nsamples) {
   if (!ctx) return YH_E_INVALID;
