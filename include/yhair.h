@@ -72,10 +72,11 @@ typedef struct yh_texture {
  * configs reach: emission, diffuse colour and the hair parameters
  * (yocto_extension.h:86-95). Specular, metallic, transmission / refraction,
  * delta (roughness 0) and opacity lobes follow yocto_pathtrace.cpp:405-471,
- * homogeneous volumes :498-533,1403-1414,1458-1497. Of the material textures
- * the colour ones are represented (emission_tex, color_tex, scattering_tex:
- * 1-based index into yh_scene_desc::textures, 0 = none); the scalar ones
- * (specular / metallic / roughness / opacity / normal maps) are not.         */
+ * homogeneous volumes :498-533,1403-1414,1458-1497. The colour textures are
+ * here (emission_tex, color_tex, scattering_tex: 1-based index into
+ * yh_scene_desc::textures, 0 = none); the scalar and normal maps of the same
+ * material are in a yh_material_maps of its own (yh_upload_scene_maps), so
+ * that this struct keeps its layout.                                         */
 typedef struct yh_material {
   float emission[3];
   float color[3];
@@ -90,6 +91,21 @@ typedef struct yh_material {
   float trdepth;      /* 0.01 (yocto_pathtrace.h:305)                          */
   int   emission_tex, color_tex, scattering_tex; /* 1-based, 0 = none          */
 } yh_material;
+
+/* The scalar and normal maps of a material (ptr::material, yocto_pathtrace.h:
+ * 311-320): 1-based index into yh_scene_desc::textures, 0 = none. Every map is
+ * looked up linear (bytes / 255, no sRGB decode) with the bilinear wrap lookup
+ * of the colour textures at the hit's texture coordinates. A scalar texture is
+ * passed as a grey RGB one: lookup_texture treats both alike (pt.cpp:147-164). */
+typedef struct yh_material_maps {
+  int specular_tex;     /* specular  *= eval_texture(specular_tex).x    (pt.cpp:413-414) */
+  int metallic_tex;     /* metallic  *= eval_texture(metallic_tex).x    (pt.cpp:415-416) */
+  int roughness_tex;    /* roughness *= eval_texture(roughness_tex).x   (pt.cpp:417-418), squared after */
+  int transmission_tex; /* read by no lookup: transmission is scaled by emission_tex (pt.cpp:421-422);
+                           checked and otherwise ignored                                             */
+  int opacity_tex;      /* opacity   *= mean(eval_texture(opacity_tex)) (pt.cpp:423-424), hair included */
+  int normal_tex;       /* eval_normalmap (pt.cpp:329-347): triangle shapes only (pt.cpp:350-369)    */
+} yh_material_maps;
 
 /* ptr::object (yocto_pathtrace.h:369-373) */
 typedef struct yh_object {
@@ -218,6 +234,11 @@ const char* yh_version(void);
  * of dense hair, large closest-hit batches) address that array with 32-bit byte offsets: beyond 4 GB of it (about fifty million
  * segments) they are not candidates and the quad kernels render — same pixels.                                                */
 int yh_upload_scene(yh_context* ctx, const yh_scene_desc* scene);
+/* The same with the materials' scalar and normal maps: `maps` holds scene->num_materials entries, or is NULL
+ * (yh_upload_scene(ctx, scene) is yh_upload_scene_maps(ctx, scene, NULL)). A material with a specular, metallic,
+ * roughness, opacity or normal map runs the GENERAL kernel variants, which look its maps up at every hit. An index
+ * outside [0, num_textures] is YH_E_INVALID and leaves the context's previous scene as it was.                     */
+int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* scene, const yh_material_maps* maps);
 
 /* init_state (yocto_pathtrace.cpp:1931-1946): image size from the camera film
  * and params->resolution, zeroed accumulators, per-pixel PCG32 streams
@@ -443,6 +464,10 @@ typedef struct yh_scene_file yh_scene_file;
 yh_scene_file*       yh_scene_load(const char* json_path, const char* camera,
           char* error, int error_len);
 const yh_scene_desc* yh_scene_get(const yh_scene_file* scene);
+/* The materials' maps of a loaded scene (the *_tex keys of sceneio.cpp:1298-1317): num_materials entries, for
+ * yh_upload_scene_maps. translucency_tex and displacement_tex are loaded (a missing file is an error) and used by
+ * nothing; coat_tex and spectint_tex, which the reference's loader does not read, are ignored.                      */
+const yh_material_maps* yh_scene_get_maps(const yh_scene_file* scene);
 void                 yh_scene_free(yh_scene_file* scene);
 /* save_image for .pfm (3 channels, top row first as the reference writes it,
  * yocto_image.cpp:1527-1556) and .hdr.                                       */

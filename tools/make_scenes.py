@@ -317,6 +317,126 @@ def make_textured(outdir, scale=1.0, name="textured"):
     return os.path.join(d, name + ".json"), nseg
 
 
+def write_png(path, img):
+    """8-bit PNG from a uint8 array (H, W) grey or (H, W, 3) RGB: one IDAT of zlib-compressed rows with filter 0."""
+    import struct
+    import zlib
+    img = np.ascontiguousarray(img, dtype=np.uint8)
+    h, w = img.shape[:2]
+    ctype = 0 if img.ndim == 2 else 2
+    raw = b"".join(b"\x00" + img[y].tobytes() for y in range(h))
+
+    def chunk(kind, body):
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
+    with open(path, "wb") as f:
+        f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, ctype, 0, 0, 0)) +
+                chunk(b"IDAT", zlib.compress(raw, 9)) + chunk(b"IEND", b""))
+
+
+def _write_plain_quad(path, half=0.6):
+    """A quad in the XY plane without normals or texture coordinates (texcoord = element uv, zero tangents)."""
+    with open(path, "w") as f:
+        f.write("ply\nformat ascii 1.0\nelement vertex 4\nproperty float x\nproperty float y\nproperty float z\n"
+                "element face 1\nproperty list uchar int vertex_indices\nend_header\n")
+        for x, y in ((-half, -half), (half, -half), (-half, half), (half, half)):
+            f.write(f"{x!r} {y!r} 0.0\n")
+        f.write("4 0 1 3 2\n")
+
+
+def _map_textures(d, seed=11, n=32):
+    """The maps of make_maps, seeded: grey scalar maps, one scalar map stored as RGB (read as grey with stb's weights
+    by the reference's scalar loader) and a tangent-space normal map of bumps. Returns {name: mean of the map in [0, 1]}."""
+    rng = np.random.default_rng(seed)
+    y, x = np.mgrid[0:n, 0:n].astype(np.float64) / n
+    maps = {
+        "spec": 0.15 + 0.85 * (0.5 + 0.5 * np.sin(2 * np.pi * 3 * x) * np.cos(2 * np.pi * 2 * y)),
+        "rough": np.clip(0.05 + 0.9 * (((x * 4).astype(int) + (y * 4).astype(int)) % 2) + 0.05 * rng.random((n, n)), 0, 1),
+        "holes": np.where(np.hypot((x * 4) % 1 - 0.5, (y * 4) % 1 - 0.5) < 0.3, 0.1, 1.0) * (0.9 + 0.1 * rng.random((n, n))),
+    }
+    means = {}
+    for k, v in maps.items():
+        b = np.round(np.clip(v, 0, 1) * 255).astype(np.uint8)
+        write_png(os.path.join(d, "textures", k + ".png"), b)
+        means[k] = float(b.mean() / 255)
+    metal = np.stack([0.3 + 0.7 * x, 0.6 + 0.3 * y, 0.2 + 0.6 * rng.random((n, n))], axis=2)
+    mb = np.round(np.clip(metal, 0, 1) * 255).astype(np.uint8)
+    write_png(os.path.join(d, "textures", "metal.png"), mb)
+    grey = (mb[..., 0].astype(int) * 77 + mb[..., 1].astype(int) * 150 + mb[..., 2].astype(int) * 29) >> 8
+    means["metal"] = float(grey.mean() / 255)
+    h = 0.5 * np.sin(2 * np.pi * 4 * x) * np.sin(2 * np.pi * 3 * y) + 0.1 * rng.random((n, n))
+    gx, gy = np.gradient(h, axis=1) * n / 8, np.gradient(h, axis=0) * n / 8
+    nrm = np.stack([-gx, -gy, np.ones_like(h)], axis=2)
+    nrm /= np.linalg.norm(nrm, axis=2, keepdims=True)
+    write_png(os.path.join(d, "textures", "bumps.png"), np.round((nrm * 0.5 + 0.5) * 255).astype(np.uint8))
+    return means
+
+
+MAP_KINDS = ("specular", "metallic", "roughness", "opacity", "normal")
+
+
+def make_maps(outdir, scale=1.0, name="maps", only="", notrans=False, flat=False):
+    """Scalar and normal maps (pt.cpp:329-347, 413-424): one material per map plus one with all of them, on the
+    reference's uv sphere, the tiled uv quad, a quad without texture coordinates (normal map on zero tangents) and
+    a small hair block under an opacity map, lit by an area light. A transmission_tex that changes no pixel.
+    only=<kind of MAP_KINDS>: that map alone (the others dropped); notrans: without the transmission_tex;
+    flat: every scalar map replaced by its mean as a constant factor and no normal map (the speed twin)."""
+    d = _prep(outdir, name)
+    shutil.copy(os.path.join(ASSETS, "sphere.ply"), os.path.join(d, "shapes", "sphere.ply"))
+    shutil.copy(os.path.join(ASSETS, "arealight.ply"), os.path.join(d, "shapes", "arealight.ply"))
+    _write_uv_quad(os.path.join(d, "shapes", "uvquad.ply"), tiles=3.0)
+    _write_plain_quad(os.path.join(d, "shapes", "plainquad.ply"))
+    nseg = write_hair_ply(os.path.join(d, "shapes", "hair-block.ply"),
+                          gen_hair_block(max(64, int(20_000 * scale))), 0.004, 0.001)
+    means = _map_textures(d)
+    tex_of = {"specular": "spec", "metallic": "metal", "roughness": "rough", "opacity": "holes", "normal": "bumps"}
+    materials = {
+        "specmap": {"color": [0.8, 0.3, 0.2], "specular": 1.0, "roughness": 0.15, "specular_tex": "spec"},
+        "metalmap": {"color": [0.9, 0.7, 0.3], "metallic": 1.0, "roughness": 0.3, "metallic_tex": "metal"},
+        "roughmap": {"color": [0.7, 0.7, 0.7], "specular": 1.0, "roughness": 0.9, "roughness_tex": "rough"},
+        "normalmap": {"color": [0.6, 0.6, 0.9], "specular": 0.5, "roughness": 0.3, "normal_tex": "bumps"},
+        "flatnormal": {"color": [0.5, 0.8, 0.5], "normal_tex": "bumps"},
+        "hairop": {"eumelanin": 0.8, "opacity_tex": "holes"},
+        "allmaps": {"color": [0.7, 0.5, 0.8], "specular": 1.0, "metallic": 0.6, "roughness": 0.5, "opacity": 0.9995,
+                    "specular_tex": "spec", "metallic_tex": "metal", "roughness_tex": "rough", "opacity_tex": "holes",
+                    "normal_tex": "bumps", "transmission_tex": "rough"},
+        "arealight": {"emission": [30, 30, 30]},
+    }
+    for mname, m in materials.items():
+        for kind in MAP_KINDS:
+            key = kind + "_tex"
+            if key not in m:
+                continue
+            if flat:
+                t = m.pop(key)
+                if kind == "opacity":
+                    m["opacity"] = m.get("opacity", 1.0) * means[t]
+                elif kind != "normal":
+                    m[kind] = m.get(kind, 1.0 if kind == "specular" else 0.0) * means[t]
+            elif only and kind != only:
+                m.pop(key)
+        if notrans or flat:
+            m.pop("transmission_tex", None)
+    objects = {
+        "floor": {"frame": [2, 0, 0, 0, 0, -2, 0, 2, 0, 0.0, -0.8, 0], "shape": "uvquad", "material": "roughmap"},
+        "ball0": {"frame": [0.6, 0, 0, 0, 0.6, 0, 0, 0, 0.6, -1.3, 0.0, 0.3], "shape": "sphere", "material": "specmap"},
+        "ball1": {"frame": [0.6, 0, 0, 0, 0.6, 0, 0, 0, 0.6, 0.0, 0.0, 0.3], "shape": "sphere", "material": "metalmap"},
+        "ball2": {"frame": [0.6, 0, 0, 0, 0.6, 0, 0, 0, 0.6, 1.3, 0.0, 0.3], "shape": "sphere", "material": "normalmap"},
+        "ball3": {"frame": [0.6, 0, 0, 0, 0.6, 0, 0, 0, 0.6, -0.65, 1.2, -0.6], "shape": "sphere", "material": "allmaps"},
+        "panel": {"frame": [0.8, 0, 0.6, 0, 1, 0, -0.6, 0, 0.8, 0.8, 1.2, -0.8], "shape": "plainquad", "material": "flatnormal"},
+        "hairblock": {"frame": [0.8, 0, 0, 0, 0, 0.8, 0, -0.8, 0, 1.6, 0.9, 0.2], "shape": "hair-block", "material": "hairop"},
+        "light": {"lookat": [0.0, 4, 3, 0.0, 0.0, 0, 0, 1, 0], "shape": "arealight", "material": "arealight"},
+    }
+    scene = {
+        "asset": {"copyright": "synthetic; sphere and arealight from the reference's test assets, maps generated (seeded)"},
+        "cameras": {"default": {"lens": 0.05, "aperture": 0.0, "aspect": 1.0, "lookat": [0.0, 1.6, 5.5, 0.0, 0.4, 0, 0, 1, 0]}},
+        "environments": {"sky": {"emission": [0.3, 0.3, 0.3]}},
+        "objects": objects,
+        "materials": materials,
+    }
+    _dump(scene, os.path.join(d, name + ".json"))
+    return os.path.join(d, name + ".json"), nseg
+
+
 def make_crowd(outdir, scale=1.0, name="crowd", count=70):
     """Many objects: a scene-level BVH several levels deep (the BASELINE configs have at most six
     objects) and more objects than the kernel stages in LDS, so the in-memory fallback of the scene
@@ -535,6 +655,7 @@ MAKERS = {
     "volumes": make_volumes,
     "textured": make_textured,
     "crowd": make_crowd,
+    "maps": make_maps,
 }
 
 
@@ -546,7 +667,8 @@ def ensure_scene(name, outdir, scale=1.0, **kw):
     """Builds the scene once per (name, scale, overrides) under outdir and returns the JSON path."""
     tag = name if scale == 1.0 else f"{name}-x{scale:g}"
     for k, v in sorted(kw.items()):
-        tag += f"-{k}{v:g}" if isinstance(v, (int, float)) and not isinstance(v, bool) else (f"-{k}" if v else "")
+        tag += (f"-{k}{v:g}" if isinstance(v, (int, float)) and not isinstance(v, bool) else
+                f"-{k}-{v}" if isinstance(v, str) and v else (f"-{k}" if v else ""))
     path = os.path.join(outdir, tag, tag + ".json")
     if not os.path.exists(path):
         MAKERS[name](outdir, scale=scale, name=tag, **kw)

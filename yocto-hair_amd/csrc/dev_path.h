@@ -421,6 +421,76 @@ YH_DEV void eval_texcoord(const yhd_scene& sc, const yhd_object& o, const hit_t&
   }
 }
 
+// The scalar maps of a material at texcoord (tu, tv), pt.cpp:413-424 and 453: the factors surface_brdf applies. Every map is
+// looked up linear (ldr_as_linear = true).
+YH_DEV surface_maps eval_maps(const yhd_scene& sc, const yhd_maps& mp, float tu, float tv) {
+  surface_maps f;
+  if (mp.specular_tex >= 0) f.specular = eval_texture(sc, mp.specular_tex, true, tu, tv).x;
+  if (mp.metallic_tex >= 0) f.metallic = eval_texture(sc, mp.metallic_tex, true, tu, tv).x;
+  if (mp.roughness_tex >= 0) f.roughness = eval_texture(sc, mp.roughness_tex, true, tu, tv).x;
+  if (mp.opacity_tex >= 0) {
+    f3 o      = eval_texture(sc, mp.opacity_tex, true, tu, tv);
+    f.opacity = mp.opacity * ((o.x + o.y + o.z) / 3);  // mean (math.h:2095)
+    if (f.opacity > 0.999f) f.opacity = 1;
+  }
+  return f;
+}
+
+// eval_normalmap (pt.cpp:329-347) of a TRIANGLE hit: `normal` = eval_normal, (tu, tv) = its texcoord. The tangents are
+// triangle_tangents_fromuv (math.h:3360-3383) of the element taken to world space (eval_element_tangents, pt.cpp:314-327);
+// a shape without texture coordinates has zero tangents, and the result is then +-normal, as the reference's.
+YH_DEV f3 eval_normalmap(const yhd_scene& sc, const yhd_object& o, const hit_t& isec, f3 normal, int normal_tex, float tu, float tv) {
+  f3 nm = eval_texture(sc, normal_tex, true, tu, tv);
+  nm    = f3{-1 + 2 * nm.x, -1 + 2 * nm.y, -1 + 2 * nm.z};
+  f3 tgu = mk3(0.0f), tgv = mk3(0.0f);
+  if (o.has_texcoords) {
+    const yhd_float4* rec = sc.prims + (size_t)o.prim_base + (size_t)isec.slot * 6;
+    const yhd_float4  r0  = rec[0];
+    yhd_int4          e   = sc.elems[o.elem_base + __float_as_int(r0.w)];
+    f3 p0 = xyz(r0), p1 = xyz(rec[1]), p2 = xyz(rec[2]);
+    const float* t0 = sc.vtex + 2 * (size_t)(o.vert_base + e.x);
+    const float* t1 = sc.vtex + 2 * (size_t)(o.vert_base + e.y);
+    const float* t2 = sc.vtex + 2 * (size_t)(o.vert_base + e.z);
+    f3    p = p1 - p0, q = p2 - p0;
+    float sx = t1[0] - t0[0], sy = t2[0] - t0[0];
+    float tx = t1[1] - t0[1], ty = t2[1] - t0[1];
+    float div = sx * ty - sy * tx;
+    f3    u = {1, 0, 0}, v = {0, 1, 0};
+    if (div != 0) {
+      u = f3{ty * p.x - tx * q.x, ty * p.y - tx * q.y, ty * p.z - tx * q.z} / div;
+      v = f3{sx * q.x - sy * p.x, sx * q.y - sy * p.y, sx * q.z - sy * p.z} / div;
+    }
+    frame fr = ldframe(o.frame);
+    tgu = transform_direction(fr, u), tgv = transform_direction(fr, v);
+  }
+  frame f;
+  f.z = normal;
+  f.x = orthonormalize(tgu, f.z);
+  f.y = normalize(cross(f.z, f.x));
+  nm.y *= dot(f.y, tgv) < 0 ? 1.0f : -1.0f;  // flip_v: the vertical axis
+  return normalize(transform_vector(f, nm));  // transform_normal (math.h:3145-3152)
+}
+
+// Texcoord, maps and shading normal of a triangle or line hit of a GENERAL kernel (pt.cpp:350-369 with the normal map of
+// 329-347): `normal` in = eval_normal, out = the shading normal.
+struct hit_maps {
+  float        tu, tv;
+  bool         have_tc;  // tu, tv hold the texcoord (else the element uv)
+  surface_maps f;
+};
+YH_DEV hit_maps eval_hit_maps(const yhd_scene& sc, const yhd_object& o, const hit_t& isec, bool mapped, f3& nrm) {
+  hit_maps h;
+  h.tu = isec.u, h.tv = isec.v, h.have_tc = false;
+  if (!mapped || !sc.maps) return h;
+  const yhd_maps mp = sc.maps[o.material];
+  if (!mp.any) return h;
+  eval_texcoord(sc, o, isec, h.tu, h.tv);
+  h.have_tc = true;
+  if (mp.normal_tex >= 0 && o.kind == YH_KIND_TRIANGLES) nrm = eval_normalmap(sc, o, isec, nrm, mp.normal_tex, h.tu, h.tv);
+  h.f = eval_maps(sc, mp, h.tu, h.tv);
+  return h;
+}
+
 // Entering / leaving a closed transmissive object (pt.cpp:1458-1467); the medium entered is
 // eval_vsdf at the crossing point (pt.cpp:504-527).
 YH_DEV void medium_crossing(const yhd_scene& sc, path_t& ps, const yhd_material& mat, f3 normal, f3 outgoing,
@@ -518,6 +588,8 @@ YH_DEV bool path_step(const trace_ctx& tc, path_t& ps, const hit_t& isec, rng_t&
   hit_geom hg = eval_hit(sc, o, isec.slot, isec.u, isec.v);
   f3 position = hg.position;
   f3 nrm      = hg.normal;
+  hit_maps hm;  // scalar and normal maps (GENERAL only: a material with maps is never plain)
+  if constexpr (GENERAL) hm = eval_hit_maps(sc, o, isec, !mat.plain, nrm);
   f3 normal;  // eval_shading_normal (pt.cpp:350-369)
   bool is_hair = o.kind == YH_KIND_LINES;
   if (is_hair) {
@@ -533,15 +605,19 @@ YH_DEV bool path_step(const trace_ctx& tc, path_t& ps, const hit_t& isec, rng_t&
   float          tu = isec.u, tv = isec.v, etex_x = 1.0f;  // texcoord; emission texture, linear (pt.cpp:421)
   f3             ctex = mk3(1.0f), etex = mk3(1.0f);      // colour and emission texture values
   if (general) {
+    if constexpr (GENERAL) tu = hm.tu, tv = hm.tv;
     if (mat.color_tex >= 0 || mat.emission_tex >= 0 || mat.scattering_tex >= 0) {
-      eval_texcoord(sc, o, isec, tu, tv);
+      if constexpr (GENERAL) {
+        if (!hm.have_tc) eval_texcoord(sc, o, isec, tu, tv);
+      }
       ctex = eval_texture(sc, mat.color_tex, false, tu, tv);
       if (mat.emission_tex >= 0) {
         etex   = eval_texture(sc, mat.emission_tex, false, tu, tv);
         etex_x = eval_texture(sc, mat.emission_tex, true, tu, tv).x;
       }
     }
-    sb = surface_brdf(mat, normal, outgoing, ctex, etex_x);
+    if constexpr (GENERAL) sb = surface_brdf(mat, normal, outgoing, ctex, etex_x, hm.f);
+    else sb = surface_brdf(mat, normal, outgoing, ctex, etex_x);
     if (sb.opacity < 1 && rand1f(rng) >= sb.opacity) {  // pt.cpp:1429-1433: pass through, same bounce
       ps.ray = mkray(position + ps.ray.d * 1e-2f, ps.ray.d);
       if (COUNT) tc.stats->c_rest += clock64() - k0;
@@ -650,6 +726,7 @@ YH_DEV bool shade_step(const trace_ctx& tc, path_t& ps, const hit_t& isec, rng_t
   const yhd_material& mat = sc.materials[o.material];
   hit_geom hg = eval_hit(sc, o, isec.slot, isec.u, isec.v);
   f3   position = hg.position, nrm = hg.normal;
+  const hit_maps hm = eval_hit_maps(sc, o, isec, true, nrm);  // scalar and normal maps
   bool is_hair  = o.kind == YH_KIND_LINES;
   f3   normal   = is_hair ? quad_orthonormalize(outgoing, nrm) : ((!mat.thin || dot(nrm, outgoing) >= 0) ? nrm : -nrm);
   if (SHADER == YH_SHADER_NORMAL) {
@@ -657,17 +734,17 @@ YH_DEV bool shade_step(const trace_ctx& tc, path_t& ps, const hit_t& isec, rng_t
     return false;
   }
   if (COUNT) count_quad<COUNT>(is_hair ? tc.stats->hair : tc.stats->surf);
-  float tu = isec.u, tv = isec.v, etex_x = 1.0f;
+  float tu = hm.tu, tv = hm.tv, etex_x = 1.0f;
   f3    ctex = mk3(1.0f), etex = mk3(1.0f);
   if (mat.color_tex >= 0 || mat.emission_tex >= 0) {
-    eval_texcoord(sc, o, isec, tu, tv);
+    if (!hm.have_tc) eval_texcoord(sc, o, isec, tu, tv);
     ctex = eval_texture(sc, mat.color_tex, false, tu, tv);
     if (mat.emission_tex >= 0) {
       etex   = eval_texture(sc, mat.emission_tex, false, tu, tv);
       etex_x = eval_texture(sc, mat.emission_tex, true, tu, tv).x;
     }
   }
-  surface_brdf_t sb = surface_brdf(mat, normal, outgoing, ctex, etex_x);
+  surface_brdf_t sb = surface_brdf(mat, normal, outgoing, ctex, etex_x, hm.f);
   if (sb.opacity < 1 && rand1f(rng) >= sb.opacity) {  // pass through, same bounce
     ps.ray = mkray(position + ps.ray.d * 1e-2f, ps.ray.d);
     return true;

@@ -11,7 +11,7 @@
 //
 // The homogeneous medium inside a closed transmissive object (SURVEY.md 8(f)
 // rank 2) follows at the end: pt.cpp:498-533,1360-1377 and math.h:4758-4822.
-// Textures are not represented.
+// Textures: the colour ones and the scalar maps are looked up by the caller (dev_path.h).
 #ifndef YH_DEV_SURFACE_H_
 #define YH_DEV_SURFACE_H_
 #include "dev_hair.h"
@@ -277,15 +277,22 @@ struct surface_brdf_t {
   f3    meta;  // metak is always zero (pt.cpp:440)
   float diffuse_pdf, specular_pdf, metal_pdf, transmission_pdf, refraction_pdf;
 };
+// The scalar maps of a hit (yhd_maps looked up at its texcoord, dev_path.h: eval_maps): the factors of
+// pt.cpp:413-418 (1 without a map) and the opacity of pt.cpp:423-424 with its snap (453) applied, or < 0:
+// the material's own, snapped on the host.
+struct surface_maps {
+  float specular = 1.0f, metallic = 1.0f, roughness = 1.0f;
+  float opacity  = -1.0f;
+};
 // color_tex = eval_texture(color_tex, texcoord) and emission_tex_x = eval_texture(emission_tex,
 // texcoord, ldr_as_linear).x — the reference scales TRANSMISSION by the emission texture
 // (pt.cpp:421-422); both are 1 for an untextured material.
 YH_DEV surface_brdf_t surface_brdf(const yhd_material& mat, f3 normal, f3 outgoing, f3 color_tex = {1.0f, 1.0f, 1.0f},
-    float emission_tex_x = 1.0f) {
+    float emission_tex_x = 1.0f, const surface_maps& maps = surface_maps{}) {
   f3    base         = ld3(mat.color) * color_tex;
-  float specular     = mat.specular * 1.0f;
-  float metallic     = mat.metallic * 1.0f;
-  float roughness    = mat.roughness * 1.0f;
+  float specular     = mat.specular * maps.specular;
+  float metallic     = mat.metallic * maps.metallic;
+  float roughness    = mat.roughness * maps.roughness;
   float transmission = mat.transmission * emission_tex_x;
   bool  thin         = mat.thin || !mat.transmission;
   surface_brdf_t b;
@@ -307,7 +314,7 @@ YH_DEV surface_brdf_t surface_brdf(const yhd_material& mat, f3 normal, f3 outgoi
   }
   b.roughness    = roughness * roughness;
   b.ior          = mat.ior;
-  b.opacity      = mat.opacity;    // > 0.999 already snapped to 1 on the host
+  b.opacity      = maps.opacity < 0 ? mat.opacity : maps.opacity;  // > 0.999 already snapped to 1
   if (!is_zero(b.diffuse) || b.roughness) b.roughness = fclamp(b.roughness, 0.03f * 0.03f, 1.0f);
   if (is_zero(b.specular) && is_zero(b.metal) && is_zero(b.transmission) && is_zero(b.refraction)) b.roughness = 1;
   b.diffuse_pdf      = hmax(b.diffuse);

@@ -100,6 +100,18 @@ typedef struct yhd_texture {
   int srgb_base, linear_base;
 } yhd_texture;
 
+// The scalar and normal maps of a material (yh_material_maps), one record per material in yhd_scene::maps, read by the
+// GENERAL kernel variants only (yhd_material stays 17 float4: it is staged in LDS). Indices into yhd_scene::textures, -1 =
+// none; every texture named here has a linear texel copy. `opacity` is the material's opacity before the > 0.999 snap
+// (pt.cpp:423-424,453): with an opacity map the snap happens per hit.
+typedef struct yhd_maps {
+  int   specular_tex, metallic_tex, roughness_tex, opacity_tex;
+  int   normal_tex;
+  int   any;      // one of the five above is set
+  float opacity;
+  int   pad;
+} yhd_maps;
+
 typedef struct yhd_light {
   int object;       // >= 0: area light on that object
   int environment;  // >= 0: environment light
@@ -133,7 +145,9 @@ typedef struct yhd_camera {
 
 typedef struct yhd_scene {
   // geometry
-  const yhd_float4* nodes;      // NULL since round 6: the node arrays exist only inside lane_blob (below); the field keeps the struct's layout
+  // per material (yhd_maps), NULL when no material of the scene has a map. (The slot held the 4-wide node array until round 6, which
+  // lives in lane_blob now: taking it keeps the struct's size, so the kernel arguments behind it keep their offsets.)
+  const yhd_maps*   maps;
   const yhd_float4* prims;      // leaf-ordered records (4 or 6 float4 each)
   const yhd_float4* vpos;       // per vertex {pos, radius}
   const yhd_int4*   elems;      // per element vertex indices (shape-local)

@@ -528,6 +528,7 @@ struct yh_scene_file {
   std::vector<yh_texture>         textures;   // material textures (yh_scene_desc::textures)
   std::vector<yh_shape>           shapes;
   std::vector<yh_material>        materials;
+  std::vector<yh_material_maps>   maps;       // per material (yh_scene_get_maps)
   std::vector<yh_object>          objects;
   std::vector<yh_environment>     environments;
   yh_scene_desc                   desc{};
@@ -650,6 +651,48 @@ static yh_scene_file* load_scene(const std::string& path, const std::string& cam
     }
     throw std::runtime_error(base + "/textures/" + tname + ".hdr: file not found");
   };
+  // scalar textures (sceneio.cpp:1139-1155, loaded at 1391-1398 as ONE channel: stbi_load(.., 1) makes grey of RGB with
+  // stb's (77 r + 150 g + 29 b) >> 8, stbi_loadf(.., 1) with (r + g + b) * f / 3), kept as grey RGB: lookup_texture treats a
+  // scalar texel and a grey colour texel alike (pt.cpp:147-164). A file that is grey already has the same pixels either
+  // way and is stored once; `keep` = false only checks that the file loads (maps that change no pixel).
+  std::map<std::string, int> scalar_tex_index;
+  auto get_scalar_texture = [&](const std::string& tname, bool keep) -> int {
+    auto it = scalar_tex_index.find(tname);
+    if (it != scalar_tex_index.end()) return it->second;
+    for (const char* ext : {".hdr", ".exr", ".png", ".jpg"}) {
+      auto file = base + "/textures/" + tname + ext;
+      if (!file_exists(file)) continue;
+      yh_texture t{};
+      if (!strcmp(ext, ".hdr")) {
+        std::vector<float> rgb;
+        load_hdr(file, t.width, t.height, rgb);
+        if (!keep) return 0;
+        for (size_t i = 0; i < rgb.size(); i += 3) rgb[i] = rgb[i + 1] = rgb[i + 2] = (rgb[i] + rgb[i + 1] + rgb[i + 2]) / 3;
+        sf->tex_data.push_back(std::move(rgb));
+        t.is_byte = 0, t.pixels = (const void*)(intptr_t)sf->tex_data.size();  // patched below
+      } else if (!strcmp(ext, ".png")) {
+        std::vector<unsigned char> rgb;
+        load_png(file, t.width, t.height, rgb);
+        if (!keep) return 0;
+        bool grey = true;
+        for (size_t i = 0; i < rgb.size(); i += 3) {
+          const unsigned char y = (unsigned char)((rgb[i] * 77 + rgb[i + 1] * 150 + rgb[i + 2] * 29) >> 8);
+          grey = grey && rgb[i] == y && rgb[i + 1] == y && rgb[i + 2] == y;
+          rgb[i] = rgb[i + 1] = rgb[i + 2] = y;
+        }
+        auto ct = mat_tex_index.find(tname);
+        if (grey && ct != mat_tex_index.end() && sf->textures[(size_t)ct->second - 1].is_byte)
+          return scalar_tex_index[tname] = ct->second;  // the colour texture of the same file: the same texels
+        sf->tex_bytes.push_back(std::move(rgb));
+        t.is_byte = 1, t.pixels = (const void*)(intptr_t)sf->tex_bytes.size();
+      } else {
+        throw std::runtime_error(file + ": only .hdr and .png textures are supported");
+      }
+      sf->textures.push_back(t);
+      return scalar_tex_index[tname] = (int)sf->textures.size();  // 1-based
+    }
+    throw std::runtime_error(base + "/textures/" + tname + ".hdr: file not found");
+  };
 
   // materials (sceneio.cpp:1268-1325; defaults yocto_sceneio.h:126-157)
   std::map<std::string, int> material_index;
@@ -669,15 +712,24 @@ static yh_scene_file* load_scene(const std::string& path, const std::string& cam
       get_floats(e, "scattering", m.scattering, 3), get_floats(e, "scanisotropy", &m.scanisotropy, 1);
       get_floats(e, "trdepth", &m.trdepth, 1);
       if (e.has("thin")) m.thin = e.at("thin").b ? 1 : 0;
+      yh_material_maps mm{};
       for (auto& [k, v] : e.obj) {
         if (!(k.size() > 4 && k.substr(k.size() - 4) == "_tex" && !v.str.empty())) continue;
         if (k == "emission_tex") m.emission_tex = get_material_texture(v.str);
         else if (k == "color_tex") m.color_tex = get_material_texture(v.str);
         else if (k == "scattering_tex") m.scattering_tex = get_material_texture(v.str);
-        else throw std::runtime_error(path + ": scalar and normal-map textures are not supported (" + name + "." + k + ")");
+        else if (k == "normal_tex") mm.normal_tex = get_material_texture(v.str);  // a colour texture (sceneio.cpp:1314)
+        else if (k == "specular_tex") mm.specular_tex = get_scalar_texture(v.str, true);
+        else if (k == "metallic_tex") mm.metallic_tex = get_scalar_texture(v.str, true);
+        else if (k == "roughness_tex") mm.roughness_tex = get_scalar_texture(v.str, true);
+        else if (k == "opacity_tex") mm.opacity_tex = get_scalar_texture(v.str, true);
+        else if (k == "transmission_tex") mm.transmission_tex = get_scalar_texture(v.str, true);
+        else if (k == "translucency_tex" || k == "displacement_tex") get_scalar_texture(v.str, false);  // loaded, read by nothing
+        // coat_tex, spectint_tex and any other key: not read by the reference's loader either
       }
       material_index[name] = (int)sf->materials.size();
       sf->materials.push_back(m);
+      sf->maps.push_back(mm);
     }
 
   // objects (sceneio.cpp:1327-1343) in alphabetical order; shapes by name
@@ -703,6 +755,7 @@ static yh_scene_file* load_scene(const std::string& path, const std::string& cam
           m.color[0] = m.color[1] = m.color[2] = 0.8f;
           default_material = (int)sf->materials.size();
           sf->materials.push_back(m);
+          sf->maps.push_back(yh_material_maps{});
         }
         o.material = default_material;
       }
@@ -756,6 +809,7 @@ yh_scene_file* yh_scene_load(const char* json_path, const char* camera, char* er
   }
 }
 const yh_scene_desc* yh_scene_get(const yh_scene_file* scene) { return scene ? &scene->desc : nullptr; }
+const yh_material_maps* yh_scene_get_maps(const yh_scene_file* scene) { return scene ? scene->maps.data() : nullptr; }
 void yh_scene_free(yh_scene_file* scene) { delete scene; }
 
 int yh_save_image(const char* path, int width, int height, const float* rgba, char* error, int error_len) {

@@ -82,7 +82,16 @@ void make_material(const yh_material& m, yhd_material& d) {
 }
 
 
-int yh_upload_scene(yh_context* ctx, const yh_scene_desc* sd) {
+// The maps of a material that change its pixels: all but transmission_tex (pt.cpp:421-422 reads emission_tex instead).
+static bool has_effective_map(const yh_material_maps& m) {
+  return m.specular_tex || m.metallic_tex || m.roughness_tex || m.opacity_tex || m.normal_tex;
+}
+
+static_assert(sizeof(yhd_maps) == 32, "yhd_maps");
+
+int yh_upload_scene(yh_context* ctx, const yh_scene_desc* sd) { return yh_upload_scene_maps(ctx, sd, nullptr); }
+
+int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_material_maps* maps) {
   if (!ctx) return YH_E_INVALID;
   if (!sd) return fail(ctx, YH_E_INVALID, "scene is NULL");
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -90,6 +99,15 @@ int yh_upload_scene(yh_context* ctx, const yh_scene_desc* sd) {
   YH_WAIT(ctx);  // (an asynchronous launch may still be reading the scene this call replaces: wait for it, within the deadline)
   if (sd->num_objects <= 0) return fail(ctx, YH_E_INVALID, "scene has no objects");
   if (sd->num_environments > YH_MAX_ENVS) return fail(ctx, YH_E_INVALID, "more than %d environments", YH_MAX_ENVS);
+  // the maps are checked before anything of the context is freed: a bad index leaves the previous scene in place
+  bool any_maps = false;
+  if (maps)
+    for (int i = 0; i < sd->num_materials; i++) {
+      const yh_material_maps& m = maps[i];
+      for (int id : {m.specular_tex, m.metallic_tex, m.roughness_tex, m.transmission_tex, m.opacity_tex, m.normal_tex})
+        if (id < 0 || id > sd->num_textures) return fail(ctx, YH_E_INVALID, "material %d: a map references a missing texture (%d of %d)", i, id, sd->num_textures);
+      any_maps = any_maps || has_effective_map(m);
+    }
   // YHAIR_TIMING=1: stage times of the upload on stderr
   const bool timing = getenv("YHAIR_TIMING") && atoi(getenv("YHAIR_TIMING")) != 0;
   auto       t_last = std::chrono::steady_clock::now();
@@ -384,8 +402,17 @@ int yh_upload_scene(yh_context* ctx, const yh_scene_desc* sd) {
   // ---- materials ---------------------------------------------------------
   std::vector<yhd_material> materials(sd->num_materials);
   int general_materials = 0;
+  std::vector<yhd_maps> mat_maps(any_maps ? (size_t)sd->num_materials : 0);
   for (int i = 0; i < sd->num_materials; i++) {
     make_material(sd->materials[i], materials[i]);
+    if (any_maps) {  // the lookups and the lobe set-up of a mapped material happen per hit (dev_path.h: eval_hit_maps)
+      const yh_material_maps& m = maps[i];
+      yhd_maps&               d = mat_maps[(size_t)i];
+      d.specular_tex = m.specular_tex - 1, d.metallic_tex = m.metallic_tex - 1, d.roughness_tex = m.roughness_tex - 1;
+      d.opacity_tex = m.opacity_tex - 1, d.normal_tex = m.normal_tex - 1;
+      d.any = has_effective_map(m) ? 1 : 0, d.opacity = sd->materials[i].opacity, d.pad = 0;
+      if (d.any) materials[i].plain = 0;
+    }
     if (!materials[i].plain) general_materials = 1;
   }
   // ---- lights (pt.cpp:1695-1740) -----------------------------------------
@@ -486,16 +513,31 @@ int yh_upload_scene(yh_context* ctx, const yh_scene_desc* sd) {
       for (int id : {m.emission_tex, m.color_tex, m.scattering_tex})
         if (id < 0 || id > sd->num_textures) return fail(ctx, YH_E_INVALID, "material %d references a missing texture", i);
       if (m.emission_tex > 0) need_linear[(size_t)m.emission_tex - 1] = 1;  // transmission *= emission_tex.x, linear (pt.cpp:421)
+      if (any_maps)  // every map is looked up linear (pt.cpp:413-424, 337)
+        for (int id : {maps[i].specular_tex, maps[i].metallic_tex, maps[i].roughness_tex, maps[i].opacity_tex, maps[i].normal_tex})
+          if (id > 0) need_linear[(size_t)id - 1] = 1;
     }
     auto srgb_to_rgb = [](float srgb) {  // math.h:3742-3745
       return (srgb <= 0.04045) ? srgb / 12.92f : std::pow((srgb + 0.055f) / (1.0f + 0.055f), 2.4f);
     };
+    std::vector<char> used(textures.size(), !any_maps);  // (with maps: a texture only a transmission map names is not uploaded)
+    if (any_maps)
+      for (int i = 0; i < sd->num_materials; i++) {
+        auto& m = sd->materials[i];
+        for (int id : {m.emission_tex, m.color_tex, m.scattering_tex})
+          if (id > 0) used[(size_t)id - 1] = 1;
+      }
+    for (size_t t = 0; t < textures.size(); t++) used[t] = used[t] || need_linear[t];
     for (size_t t = 0; t < textures.size(); t++) {
       auto& src = sd->textures[t];
       if (src.width <= 0 || src.height <= 0 || !src.pixels) return fail(ctx, YH_E_INVALID, "texture %d is empty", (int)t);
       size_t n = (size_t)src.width * src.height;
       auto&  d = textures[t];
       d.width = src.width, d.height = src.height, d.srgb_base = (int)tex_texels.size(), d.linear_base = -1;
+      if (!used[t]) {
+        d.srgb_base = -1;
+        continue;
+      }
       tex_texels.resize(tex_texels.size() + n);
       yhd_float4* out = tex_texels.data() + d.srgb_base;
       if (src.is_byte) {
@@ -534,8 +576,13 @@ int yh_upload_scene(yh_context* ctx, const yh_scene_desc* sd) {
   if ((rc = upload(ctx, ctx->d_textures, textures.data(), textures.size() * sizeof(yhd_texture)))) return rc;
   if ((rc = upload(ctx, ctx->d_tex_texels, tex_texels.data(), tex_texels.size() * 16))) return rc;
   if ((rc = upload(ctx, ctx->d_vtex, vtex.data(), vtex.size() * 4))) return rc;
+  if (any_maps) {
+    if ((rc = upload(ctx, ctx->d_maps, mat_maps.data(), mat_maps.size() * sizeof(yhd_maps)))) return rc;
+  } else {
+    ctx->d_maps.reset();
+  }
   lap("hipMalloc + H2D copies");
-  sc.nodes = nullptr, sc.prims = (const yhd_float4*)ctx->d_prims.p;  // (the 4-wide node array of rounds 1-5 exists only inside the lane blob)
+  sc.prims = (const yhd_float4*)ctx->d_prims.p;
   sc.vpos = (const yhd_float4*)ctx->d_vpos.p;
   sc.elems = (const yhd_int4*)ctx->d_elems.p;
   sc.objects = (const yhd_object*)ctx->d_objects.p, sc.materials = (const yhd_material*)ctx->d_materials.p;
@@ -550,6 +597,7 @@ int yh_upload_scene(yh_context* ctx, const yh_scene_desc* sd) {
   sc.lane_blob = (const yhd_float4*)ctx->d_lane_blob.p, sc.lane_blob_units = blob_units;
   sc.textures = (const yhd_texture*)ctx->d_textures.p, sc.tex_texels = (const yhd_float4*)ctx->d_tex_texels.p;
   sc.vtex = (const float*)ctx->d_vtex.p;
+  sc.maps = any_maps ? (const yhd_maps*)ctx->d_maps.p : nullptr;
   memcpy(sc.camera.frame, sd->camera.frame, 48);
   sc.camera.lens = sd->camera.lens, sc.camera.film_x = sd->camera.film[0], sc.camera.film_y = sd->camera.film[1];
   sc.camera.focus = sd->camera.focus, sc.camera.aperture = sd->camera.aperture;
@@ -587,6 +635,7 @@ int yh_upload_scene(yh_context* ctx, const yh_scene_desc* sd) {
       }
     }
     for (int i = 0; i < sd->num_environments; i++) mix(&sd->environments[i], offsetof(yh_environment, texels));
+    if (any_maps) mix(maps, sizeof(yh_material_maps) * (size_t)sd->num_materials);
     ctx->scene_key = h;
   }
   ctx->d_scene_copy.reset();  // (stream_impl uploads the new table at its first launch)

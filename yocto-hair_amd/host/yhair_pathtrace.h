@@ -180,7 +180,7 @@ using math::vec3i;
 using math::vec4f;
 
 struct vec3b { unsigned char x = 0, y = 0, z = 0; };
-struct texture {  // pt.h:282-287: the colour variants (colorf / colorb); scalar textures are not represented
+struct texture {  // pt.h:282-287: colorf / colorb; a scalar image (scalarf / scalarb) is kept as grey RGB, which lookup_texture treats alike (pt.cpp:147-164)
   int                width = 0, height = 0;
   std::vector<vec3f> colorf;
   std::vector<vec3b> colorb;
@@ -192,9 +192,11 @@ struct camera {  // pt.h:272-278
   float   focus    = 10000;
   float   aperture = 0;
 };
-struct material {  // pt.h:293-329 (of the textures: emission, colour, scattering)
+struct material {  // pt.h:293-329
   vec3f emission = {0, 0, 0}, color = {0, 0, 0};
   texture *emission_tex = nullptr, *color_tex = nullptr, *scattering_tex = nullptr;
+  texture *specular_tex = nullptr, *metallic_tex = nullptr, *roughness_tex = nullptr, *transmission_tex = nullptr;
+  texture *opacity_tex = nullptr, *normal_tex = nullptr;
   float specular = 0, roughness = 0, metallic = 0, ior = 1.5f, transmission = 0, opacity = 1;
   bool  thin = false;
   vec3f scattering = {0, 0, 0};
@@ -282,20 +284,30 @@ inline void set_eta(material* m, float v) { m->eta = v; }
 inline void set_texture(texture* t, int width, int height, const std::vector<vec3b>& img) {
   t->width = width, t->height = height, t->colorb = img, t->colorf.clear();
 }
+// scalar images (pt.h:117-118), expanded to grey RGB
+inline void set_texture(texture* t, int width, int height, const std::vector<float>& img) {
+  t->width = width, t->height = height, t->colorb.clear(), t->colorf.resize(img.size());
+  for (size_t i = 0; i < img.size(); i++) t->colorf[i] = {img[i], img[i], img[i]};
+}
+inline void set_texture(texture* t, int width, int height, const std::vector<unsigned char>& img) {
+  t->width = width, t->height = height, t->colorf.clear(), t->colorb.resize(img.size());
+  for (size_t i = 0; i < img.size(); i++) t->colorb[i] = {img[i], img[i], img[i]};
+}
 inline void set_emission(material* m, const vec3f& e, texture* tex = nullptr) { m->emission = e, m->emission_tex = tex; }
 inline void set_color(material* m, const vec3f& c, texture* tex = nullptr) { m->color = c, m->color_tex = tex; }
 inline void set_texcoords(shape* s, const std::vector<vec2f>& v) { s->texcoords = v; }
-inline void set_specular(material* m, float v = 1) { m->specular = v; }
+inline void set_specular(material* m, float v = 1, texture* tex = nullptr) { m->specular = v, m->specular_tex = tex; }
 inline void set_ior(material* m, float v) { m->ior = v; }
-inline void set_metallic(material* m, float v) { m->metallic = v; }
-inline void set_transmission(material* m, float t, bool thin, float trdepth) {
-  m->transmission = t, m->thin = thin, m->trdepth = trdepth;
+inline void set_metallic(material* m, float v, texture* tex = nullptr) { m->metallic = v, m->metallic_tex = tex; }
+inline void set_transmission(material* m, float t, bool thin, float trdepth, texture* tex = nullptr) {
+  m->transmission = t, m->thin = thin, m->trdepth = trdepth, m->transmission_tex = tex;
 }
 inline void set_scattering(material* m, const vec3f& scattering, float scanisotropy, texture* tex = nullptr) {
   m->scattering = scattering, m->scanisotropy = scanisotropy, m->scattering_tex = tex;
 }
-inline void set_roughness(material* m, float v) { m->roughness = v; }
-inline void set_opacity(material* m, float v) { m->opacity = v; }
+inline void set_roughness(material* m, float v, texture* tex = nullptr) { m->roughness = v, m->roughness_tex = tex; }
+inline void set_opacity(material* m, float v, texture* tex = nullptr) { m->opacity = v, m->opacity_tex = tex; }
+inline void set_normalmap(material* m, texture* tex) { m->normal_tex = tex; }
 inline void set_thin(material* m, bool thin) { m->thin = thin; }
 inline void set_lines(shape* s, const std::vector<vec2i>& v) { s->lines = v; }
 inline void set_triangles(shape* s, const std::vector<vec3i>& v) { s->triangles = v; }
@@ -318,6 +330,7 @@ inline void set_emission(environment* e, const vec3f& em, texture* tex = nullptr
 inline void upload_scene(const scene* sc, const camera* cam) {
   std::vector<yh_shape>       shapes;
   std::vector<yh_material>    materials;
+  std::vector<yh_material_maps> maps;
   std::vector<yh_object>      objects;
   std::vector<yh_environment> envs;
   std::vector<yh_texture>     textures;
@@ -369,6 +382,11 @@ inline void upload_scene(const scene* sc, const camera* cam) {
     o.emission_tex = material_texture(m->emission_tex), o.color_tex = material_texture(m->color_tex);
     o.scattering_tex = material_texture(m->scattering_tex);
     materials.push_back(o);
+    yh_material_maps mm{};
+    mm.specular_tex = material_texture(m->specular_tex), mm.metallic_tex = material_texture(m->metallic_tex);
+    mm.roughness_tex = material_texture(m->roughness_tex), mm.transmission_tex = material_texture(m->transmission_tex);
+    mm.opacity_tex = material_texture(m->opacity_tex), mm.normal_tex = material_texture(m->normal_tex);
+    maps.push_back(mm);
   }
   for (auto& ob : sc->objects) {
     yh_object o{};
@@ -397,7 +415,7 @@ inline void upload_scene(const scene* sc, const camera* cam) {
   memcpy(d.camera.frame, &cam->frame, 48);
   d.camera.lens = cam->lens, d.camera.film[0] = cam->film.x, d.camera.film[1] = cam->film.y;
   d.camera.focus = cam->focus, d.camera.aperture = cam->aperture;
-  detail::for_each_context([&](yh_context* ctx, int) { return yh_upload_scene(ctx, &d); });  // the scene is replicated
+  detail::for_each_context([&](yh_context* ctx, int) { return yh_upload_scene_maps(ctx, &d, maps.data()); });  // the scene is replicated
   sc->uploaded_for = cam;
 }
 // init_bvh / init_lights: same signatures as pt.h:207-217. They mark the scene;

@@ -20,7 +20,8 @@ using namespace yhair::math;
 
 // sio::model -> ptr::scene through the public scene-construction API, as
 // init_scene does in the reference CLI (cli.cpp:49-197).
-inline ptr::camera* init_scene(ptr::scene* scene, const yh_scene_desc* d) {
+// `maps`: the materials' scalar and normal maps (yh_scene_get_maps), or NULL.
+inline ptr::camera* init_scene(ptr::scene* scene, const yh_scene_desc* d, const yh_material_maps* maps = nullptr) {
   auto frame_of = [](const float* f) {
     frame3f r;
     memcpy(&r, f, 48);
@@ -30,7 +31,7 @@ inline ptr::camera* init_scene(ptr::scene* scene, const yh_scene_desc* d) {
   ptr::set_frame(camera, frame_of(d->camera.frame));
   camera->lens = d->camera.lens, camera->film = {d->camera.film[0], d->camera.film[1]};
   ptr::set_focus(camera, d->camera.aperture, d->camera.focus);
-  std::vector<ptr::texture*> textures;  // material colour textures (yh_scene_desc::textures)
+  std::vector<ptr::texture*> textures;  // material textures and maps (yh_scene_desc::textures)
   for (int i = 0; i < d->num_textures; i++) {
     auto&  t = d->textures[i];
     auto   o = ptr::add_texture(scene);
@@ -56,10 +57,13 @@ inline ptr::camera* init_scene(ptr::scene* scene, const yh_scene_desc* d) {
     ptr::set_beta_m(o, m.beta_m), ptr::set_beta_n(o, m.beta_n), ptr::set_alpha(o, m.alpha), ptr::set_eta(o, m.eta);
     ptr::set_emission(o, vec3f{m.emission[0], m.emission[1], m.emission[2]}, texture_of(m.emission_tex));
     ptr::set_color(o, {m.color[0], m.color[1], m.color[2]}, texture_of(m.color_tex));
-    ptr::set_specular(o, m.specular), ptr::set_ior(o, m.ior), ptr::set_metallic(o, m.metallic);
-    ptr::set_transmission(o, m.transmission, m.thin != 0, m.trdepth);
+    const yh_material_maps mm = maps ? maps[i] : yh_material_maps{};
+    ptr::set_specular(o, m.specular, texture_of(mm.specular_tex)), ptr::set_ior(o, m.ior);
+    ptr::set_metallic(o, m.metallic, texture_of(mm.metallic_tex));
+    ptr::set_transmission(o, m.transmission, m.thin != 0, m.trdepth, texture_of(mm.transmission_tex));
     ptr::set_scattering(o, {m.scattering[0], m.scattering[1], m.scattering[2]}, m.scanisotropy, texture_of(m.scattering_tex));
-    ptr::set_roughness(o, m.roughness), ptr::set_opacity(o, m.opacity), ptr::set_thin(o, m.thin != 0);
+    ptr::set_roughness(o, m.roughness, texture_of(mm.roughness_tex)), ptr::set_opacity(o, m.opacity, texture_of(mm.opacity_tex));
+    ptr::set_thin(o, m.thin != 0), ptr::set_normalmap(o, texture_of(mm.normal_tex));
     materials.push_back(o);
   }
   std::vector<ptr::shape*> shapes;

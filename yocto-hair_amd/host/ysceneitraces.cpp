@@ -64,7 +64,7 @@ int main(int argc, const char* argv[]) {
     auto ioscene = yh_scene_load(filename.c_str(), camera_name.c_str(), error, sizeof(error));
     if (!ioscene) print_fatal(error);
     auto scene  = std::make_unique<ptr::scene>();
-    auto camera = init_scene(scene.get(), yh_scene_get(ioscene));
+    auto camera = init_scene(scene.get(), yh_scene_get(ioscene), yh_scene_get_maps(ioscene));
     yh_scene_free(ioscene);
     ptr::init_bvh(scene.get(), params);
     ptr::init_lights(scene.get(), params);

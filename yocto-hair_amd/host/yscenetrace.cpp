@@ -94,7 +94,7 @@ int main(int argc, const char* argv[]) {
     printf("load scene: %.2fs\n", ph_load);
 
     auto scene  = std::make_unique<ptr::scene>();
-    auto camera = init_scene(scene.get(), yh_scene_get(ioscene));
+    auto camera = init_scene(scene.get(), yh_scene_get(ioscene), yh_scene_get_maps(ioscene));
     yh_scene_free(ioscene);
     ph_convert = lap();
 

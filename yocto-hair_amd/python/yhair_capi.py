@@ -45,6 +45,12 @@ class Material(C.Structure):
                 ("scattering_tex", C.c_int)]
 
 
+class MaterialMaps(C.Structure):
+    """yh_material_maps: a material's scalar and normal maps, 1-based into SceneDesc.textures, 0 = none."""
+    _fields_ = [("specular_tex", C.c_int), ("metallic_tex", C.c_int), ("roughness_tex", C.c_int),
+                ("transmission_tex", C.c_int), ("opacity_tex", C.c_int), ("normal_tex", C.c_int)]
+
+
 class Object(C.Structure):
     _fields_ = [("frame", C.c_float * 12), ("shape", C.c_int), ("material", C.c_int)]
 
@@ -132,6 +138,7 @@ _SIGS = {
     "yh_last_error": (C.c_char_p, [C.c_void_p]),
     "yh_version": (C.c_char_p, []),
     "yh_upload_scene": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
+    "yh_upload_scene_maps": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(MaterialMaps)]),
     "yh_init_state": (C.c_int, [C.c_void_p, C.POINTER(TraceParams)]),
     "yh_image_size": (C.c_int, [C.c_void_p, c_int_p, c_int_p]),
     "yh_set_shard": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -173,6 +180,7 @@ _SIGS = {
     "yh_selftest": (C.c_int, [C.c_void_p, C.c_int, c_float_p]),
     "yh_scene_load": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]),
     "yh_scene_get": (C.POINTER(SceneDesc), [C.c_void_p]),
+    "yh_scene_get_maps": (C.POINTER(MaterialMaps), [C.c_void_p]),
     "yh_scene_free": (None, [C.c_void_p]),
     "yh_save_image": (C.c_int, [C.c_char_p, C.c_int, C.c_int, c_float_p, C.c_char_p, C.c_int]),
 }
@@ -229,6 +237,8 @@ class SceneFile:
         if not self.handle:
             raise YhError(err.value.decode())
         self.desc = lib.yh_scene_get(self.handle)
+        # yh_scene_get_maps: one MaterialMaps per material (index it like desc.contents.materials)
+        self.maps = lib.yh_scene_get_maps(self.handle)
 
     def close(self):
         if self.handle and load is not None:
@@ -278,8 +288,13 @@ class Context:
             pass
 
     # whole path -----------------------------------------------------------
-    def upload_scene(self, desc):
-        self._chk(self.lib.yh_upload_scene(self.h, desc))
+    def upload_scene(self, desc, maps=None):
+        """yh_upload_scene, or yh_upload_scene_maps with `maps`: one MaterialMaps per material (a ctypes array or pointer,
+        e.g. SceneFile.maps)."""
+        if maps is None:
+            self._chk(self.lib.yh_upload_scene(self.h, desc))
+        else:
+            self._chk(self.lib.yh_upload_scene_maps(self.h, desc, C.cast(maps, C.POINTER(MaterialMaps))))
 
     def set_shard(self, rank, world):
         self._chk(self.lib.yh_set_shard(self.h, rank, world))
