@@ -7,7 +7,7 @@ reference's hair-block.ply is not distributed); per-pixel L2 against the CPU ref
 samples = width * height * spp; the timed region is the sample loop only
 (apps/yscenetrace/yscenetrace.cpp:256-268), scene already resident in HBM.
 
-    python bench.py --gpus N --steps K --warmup W [--config C1|C2|C3|C4]
+    python bench.py --gpus N --steps K --warmup W [--config C1|C2|C3|C4] [--full]
 
 A "step" is ONE pass of the hot path: yh_trace_samples(spp) over the whole image = one launch of
 the sample-loop kernel. The K steps of a run add up to EXACTLY the config's sample count (1536 spp
@@ -22,8 +22,8 @@ data-path collective, and ONE RCCL gather of the packed float4 tiles follows the
 (gather_ms). With fewer devices than ranks (a one-GPU box) the ranks share devices and the gather
 goes through gloo (RCCL refuses two ranks on one device); config.collective says which ran.
 The run is on the CONFIG'S OWN IMAGE (strong scaling, "scaling": "strong") — that is what
-BASELINE.json asks to be reported at 1 / 2 / 4 / 8 GPUs; a second, shorter run on an image with N
-times the pixels (side x sqrt(N): pixels per GPU as at N = 1) is reported next to it as
+BASELINE.json asks to be reported at 1 / 2 / 4 / 8 GPUs; with --full, a second, shorter run on an image
+with N times the pixels (side x sqrt(N): pixels per GPU as at N = 1) is reported next to it as
 config.weak_scaling. `--weak` makes the weak run the reported one.
 
 The scenes are generated for each run (tools/make_scenes.py, seeded) in a directory of the run's own, removed at its end;
@@ -31,11 +31,22 @@ YHAIR_SCENES names a directory to keep them in instead. `--dump-outputs DIR` wri
 timed path computed: the (H, W, 4) float32 image of the last timed step as DIR/image.npy (above 64 MB a fixed, seeded
 sample of its pixels, DIR/image_sample.npy, with their flat indices in DIR/image_sample_pixels.npy).
 
+A plain run does only what the headline figure needs: it sets up, warms up, times the K steps, writes --dump-outputs,
+gathers the image and prints the line. Whatever else the bench measures or checks runs only with `--full` (the --no-*
+switches leave parts of it out): the CPU leg with `parity` and `cpu_baseline`, the instrumented kernel's work counts,
+config.projected_strong_scaling, config.other_configs, parity.path_following_light_hair, config.end_to_end and, at
+N > 1, the shard check and the other scaling mode. The bench does not ask for the kernel-trial record on disk
+(yh_set_trial_cache_dir): every run times the kernel candidates in its own warm-up, and no run reads what an earlier one
+wrote.
+
 The JSON line also carries
   roofline      the sample-loop kernel against the HBM roofline (the contract's bound) — achieved =
                 algorithmic bytes per launch / average launch duration (HIP events on the kernel's
                 own stream) — and, in `valu`, the bound that actually binds: vector-instruction
-                issue x active lanes from the committed counter passes (profiles/).
+                issue x active lanes from the committed counter passes (profiles/). A plain run takes
+                the algorithmic bytes from the committed work counts (tests/golden/workcounts.json);
+                a scene without them has `achieved: null` unless --full counts them.
+--full adds
   parity        the metric's second half: per-pixel L2 and relRMSE of the GPU image against the CPU
                 image at equal spp and seed, the seed-to-seed floor of the CPU path, and the share
                 of pixels within 4 sigma (variance pooled over both seeds of both sides).
@@ -393,15 +404,17 @@ def main():
     ap.add_argument("--scene", default="", help="override the config's scene")
     ap.add_argument("--beta-m", type=float, default=None, help="C2: straight-hair beta_m sweep value")
     ap.add_argument("--scale", type=float, default=1.0, help="hair strand-count multiplier (1.0 = the config's scene)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: CPU baseline and parity, the instrumented kernel's work counts, "
+                         "projected strong scaling, the other configs, path following, end to end; N > 1: the shard check and the other scaling mode")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU leg (cpu_baseline and parity)")
     ap.add_argument("--cpu-budget", type=float, default=10.0, help="seconds of CPU rendering per seed (two seeds)")
     ap.add_argument("--cpu-spp", type=int, default=0, help="samples of the CPU leg and of the parity field (default: the config's OWN sample count when one seed of it "
                                                            "fits --cpu-full-budget on this host — C1's 1536 spp take about 40 s per seed on 256 threads — else what --cpu-budget allows, at most 256)")
     ap.add_argument("--cpu-full-budget", type=float, default=75.0, help="seconds one seed of the CPU leg may take at the config's own sample count (two seeds are rendered)")
     ap.add_argument("--other-cpu-budget", type=float, default=6.0, help="seconds of CPU rendering per seed for the parity / cpu_baseline of each of config.other_configs")
     ap.add_argument("--no-end-to-end", dest="end_to_end", action="store_false",
-                    help="headline run at N = 1: skip config.end_to_end (the yscenetrace command line on the config's scene file, cold and warm trial record, next to the reference's)")
-    ap.add_argument("--no-trial-cache", action="store_true", help="do not keep the kernel-trial record on disk (yh_set_trial_cache_dir; the environment's YHAIR_NO_DISK_CACHE does the same)")
+                    help="with --full, headline run at N = 1: skip config.end_to_end (the yscenetrace command line on the config's scene file, cold and warm trial record, next to the reference's)")
     ap.add_argument("--save", default="", help="write the final image (.pfm/.hdr) on rank 0")
     ap.add_argument("--dump-outputs", default="", metavar="DIR",
                     help="rank 0, after the timed steps: write the image of the last timed step as DIR/image.npy (float32; above 64 MB a fixed, seeded sample of its pixels)")
@@ -410,9 +423,9 @@ def main():
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="collective backend; gloo (CPU staging) lets the N > 1 flow be exercised on a one-GPU box")
     ap.add_argument("--no-project-scaling", dest="project_scaling", action="store_false",
-                    help="N = 1: skip the three extra renders of shard 0 of 2 / 4 / 8 (config.projected_strong_scaling)")
+                    help="with --full, N = 1: skip the three extra renders of shard 0 of 2 / 4 / 8 (config.projected_strong_scaling)")
     ap.add_argument("--no-other-configs", dest="other_configs", action="store_false",
-                    help="headline run at N = 1: skip the renders of C2 (beta_m 0.25), C3 and C4 at their full sample counts (config.other_configs)")
+                    help="with --full, headline run at N = 1: skip the renders of C2 (beta_m 0.25), C3 and C4 at their full sample counts (config.other_configs)")
     ap.add_argument("--force-collective", action="store_true",
                     help="N = 1: still create the process group and run the framebuffer gather through the collective "
                          "(a one-rank RCCL communicator: how a one-GPU box executes the nccl branch)")
@@ -430,9 +443,9 @@ def main():
     import yhair_capi as yh
     import yhair_dist
 
-    # the kernel-trial record on disk is opt-in for library callers (include/yhair.h: yh_set_trial_cache_dir); the bench opts in like the
-    # command lines do, so that the ranks of a run and the runs on a node settle on one kernel per image
-    trial_cache = None if a.no_trial_cache else yh.set_trial_cache_dir(default=True)
+    # the kernel-trial record on disk is opt-in for library callers (include/yhair.h: yh_set_trial_cache_dir) and the bench does not opt in:
+    # every run times its kernel candidates afresh, reading nothing an earlier run wrote (YHAIR_CACHE_DIR in the environment still opts in)
+    trial_cache = None if os.environ.get("YHAIR_NO_DISK_CACHE") or os.environ.get("YHAIR_NO_TRIAL_CACHE") else os.environ.get("YHAIR_CACHE_DIR")
 
     cfg = dict(CONFIGS[a.config])
     scene_name = a.scene or cfg["scene"]
@@ -600,14 +613,16 @@ def main():
         finally:
             osf.close()
 
-    # ---- work counts and the CPU leg (outside the timed region, rank 0 at N = 1 only) --------------
-    ctx.init_state(yh.TraceParams.default(resolution=base_res))
-    gpu_counts = ctx.trace_samples_counted(2).as_dict()
+    # ---- --full: work counts and the CPU leg (outside the timed region, the CPU leg rank 0 at N = 1 only) --------------
+    gpu_counts = None
+    if a.full:
+        ctx.init_state(yh.TraceParams.default(resolution=base_res))
+        gpu_counts = ctx.trace_samples_counted(2).as_dict()
     gpu_general = any(sf.desc.contents.materials[i].specular or sf.desc.contents.materials[i].metallic or sf.desc.contents.materials[i].transmission
                       or sf.desc.contents.materials[i].opacity < 1 or sf.desc.contents.materials[i].color_tex or sf.desc.contents.materials[i].emission_tex
                       for i in range(sf.desc.contents.num_materials))  # (label only: the GENERAL dense shape runs at 256 x 4)
     cpu = ref_wc = parity = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline:
+    if a.full and rank == 0 and world == 1 and not a.no_cpu_baseline:
         cpu, cpu_a, cpu_b, cpu_spp, seed_b, ref_wc = cpu_leg(scene_json, base_res, a.cpu_budget, a.cpu_spp, full_spp=spp_total if headline else 0,
                                                              full_budget_s=a.cpu_full_budget)
         imgs = []
@@ -628,9 +643,9 @@ def main():
     shape_used = ctx.launch_shape() if hasattr(ctx, "launch_shape") else None
     trials = {KERNELS.get(k, str(k)): {"ms_per_spp": v[0], "trials": v[1]} for k, v in ctx.kernel_trials().items()}
 
-    # ---- one rank: what ONE GPU of N would take on this image (its shard rendered alone here) ----------
+    # ---- --full, one rank: what ONE GPU of N would take on this image (its shard rendered alone here) ----------
     projected = None
-    if world == 1 and a.project_scaling:
+    if a.full and world == 1 and a.project_scaling:
         projected = []
         try:
             for n_proj in (2, 4, 8):
@@ -660,10 +675,10 @@ def main():
     torch.cuda.synchronize()
     gather_ms = (time.perf_counter() - t0) * 1e3
 
-    # ---- N > 1: "pixels do not depend on the shard", checked on the real collective: the ranks render the config's image
+    # ---- --full, N > 1: "pixels do not depend on the shard", checked on the real collective: the ranks render the config's image
     # once more at a few spp and gather it; rank 0 then renders the WHOLE image alone at the same spp and seed — bitwise equal
     shard_check = None
-    if world > 1:
+    if a.full and world > 1:
         check_spp = 4
         pc = yh.TraceParams.default(resolution=res_main)
         ctx.set_shard(rank, world)
@@ -690,9 +705,9 @@ def main():
         ctx.set_shard(rank, world)
         dist.barrier()
 
-    # ---- N > 1: the other scaling mode, a shorter run, reported next to the main one -------------------
+    # ---- --full, N > 1: the other scaling mode, a shorter run, reported next to the main one -------------------
     other = None
-    if world > 1:
+    if a.full and world > 1:
         res_other = base_res if a.weak else weak_res
         k_other = max(1, min(4, a.steps))
         ow, oh, oel, _, _ = timed_run(res_other, step_spp[:k_other], 1)
@@ -702,11 +717,11 @@ def main():
     img = image.cpu().numpy() if rank == 0 else None  # (a copy: the context's buffers are about to be reused)
     if a.dump_outputs and rank == 0:
         dump_outputs(np, a.dump_outputs, timed_image if timed_image is not None else img)
-    # ---- how closely device paths FOLLOW the reference's on the scene where the default BSDF arithmetic shows most: the
+    # ---- --full: how closely device paths FOLLOW the reference's on the scene where the default BSDF arithmetic shows most: the
     # reference's own sphere-hairblock.json (light hair, colour 0.8: eight-bounce paths) against the reference's images of it
     # (tests/golden/refscenes.npz), with the default arithmetic and with yh_trace_params::hair_exact -------------------
     follow = None
-    if rank == 0 and world == 1 and headline:
+    if a.full and rank == 0 and world == 1 and headline:
         try:
             g = np.load(os.path.join(ROOT, "tests", "golden", "refscenes.npz"))
             ref8, ref8_other_seed = g["sphere-hairblock|8"], g["sphere-hairblock|8_seed777"]
@@ -726,10 +741,10 @@ def main():
         except Exception as e:  # never at the expense of the reported line
             follow = {"error": str(e)}
 
-    # ---- the other BASELINE configs, after everything the headline line needs has been measured -----------
+    # ---- --full: the other BASELINE configs, after everything the headline line needs has been measured -----------
     main_launches = sum(ctx_launches_main)
     others = None
-    if rank == 0 and world == 1 and headline and a.other_configs:
+    if a.full and rank == 0 and world == 1 and headline and a.other_configs:
         others = {}
         for oname, okw, osteps, oproj in OTHER_CONFIGS:
             try:
@@ -738,7 +753,7 @@ def main():
                 others[oname] = {"error": str(e)}
 
     e2e = None
-    if rank == 0 and world == 1 and headline and a.end_to_end:
+    if a.full and rank == 0 and world == 1 and headline and a.end_to_end:
         e2e = end_to_end(scene_json, base_res, spp_total, cpu["value"] if cpu else None)
 
     if rank == 0:
@@ -754,8 +769,8 @@ def main():
             counts, counts_from = ref_wc.as_dict(), "reference algorithm (CPU oracle, 2 spp)"
             bytes_per_sample = ref_wc.bytes_per_sample(spp_launch, env_tex)
         else:
-            # no oracle run here (N > 1 or --no-cpu-baseline): the committed counts of the reference algorithm for this
-            # scene, else the kernel's own counters with its 4-wide nodes counted as 128 B
+            # no oracle run here (a plain run, N > 1 or --no-cpu-baseline): the committed counts of the reference algorithm for this
+            # scene, else (--full) the kernel's own counters with its 4-wide nodes counted as 128 B
             fixture = committed_workcounts(scene_name, scene_kw, base_res, a.scale)
             if fixture is not None:
                 p_ = fixture["per_sample"]
@@ -763,12 +778,17 @@ def main():
                 counts["samples"] = 1
                 counts_from = "reference algorithm (committed fixture tests/golden/workcounts.json)"
                 bytes_per_sample = algorithmic_bytes_per_sample(p_, spp_launch, env_tex)
-            else:
+            elif gpu_counts is not None:
                 counts, counts_from = gpu_counts, "instrumented kernel (4-wide BVH; no oracle run, no fixture for this scene)"
                 g = {k: gpu_counts[k] / max(1, gpu_counts["samples"]) for k in ALGO[1:]}
                 bytes_per_sample = algorithmic_bytes_per_sample(g, spp_launch, env_tex, node_bytes=128)
-        bytes_per_launch = bytes_per_sample * width * height * spp_launch / world
-        achieved = bytes_per_launch / launch_s / 1e9
+            else:  # a plain run counts nothing of its own
+                counts, counts_from, bytes_per_sample = None, "none (no fixture for this scene; --full counts the instrumented kernel)", None
+        bytes_per_launch = achieved = None  # (None where nothing was counted)
+        if bytes_per_sample is not None:
+            bytes_per_launch = bytes_per_sample * width * height * spp_launch / world
+            achieved = bytes_per_launch / launch_s / 1e9
+        rnd = lambda x, scale, n: None if x is None else round(x / scale, n)
         traffic = None
         pmc, traffic_src = committed_counters(scene_name, scene_kw, res_main, a.scale, world, shape_used)
         if pmc:
@@ -799,9 +819,9 @@ def main():
                        "collective_ranks": dist.get_world_size() if grouped else 1,
                        "upload_s": round(upload_s, 2), "gather_ms": round(gather_ms, 2),
                        "image_mean_rgb": [round(float(x), 5) for x in img[..., :3].mean(axis=(0, 1))]},
-            "roofline": {"bound": "hbm", "achieved": round(achieved, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(achieved / HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_unit": "GB per launch",
-                         "traffic_source": traffic_src, "algorithmic_gb_per_launch": round(bytes_per_launch / 1e9, 3),
+            "roofline": {"bound": "hbm", "achieved": rnd(achieved, 1, 2), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                         "frac": rnd(achieved, HBM_PEAK_GBS, 5), "traffic": traffic, "traffic_unit": "GB per launch",
+                         "traffic_source": traffic_src, "algorithmic_gb_per_launch": rnd(bytes_per_launch, 1e9, 3),
                          "binds": "valu" if valu else None,
                          "note": "hbm is the contract's designated roofline; the scene lives in L2 / Infinity Cache and the kernel is bound by "
                                  "vector-instruction issue (see valu)",
@@ -809,10 +829,10 @@ def main():
                          "kernel": KERNELS.get(shape_used, "k_trace") if not (shape_used == 1 and gpu_general) else "k_trace<256 x 4>", "launch_shape": shape_used,
                          "kernel_trials": trials,  # what the choice rests on: the fastest 32-sample trial of every candidate on this image
                          "avg_launch_ms": round(launch_s * 1e3, 3), "avg_spp_per_launch": round(spp_launch, 2),
-                         "algorithmic_bytes_per_sample": round(bytes_per_sample, 1),
+                         "algorithmic_bytes_per_sample": rnd(bytes_per_sample, 1, 1),
                          "work_counts_from": counts_from,
-                         "work_counts_per_sample": {k: round(counts[k] / max(1, counts["samples"]), 3) for k in ALGO[1:]},
-                         "kernel_counts_per_sample": {k: round(gpu_counts[k] / max(1, gpu_counts["samples"]), 3) for k in ALGO[1:]}},
+                         "work_counts_per_sample": {k: round(counts[k] / max(1, counts["samples"]), 3) for k in ALGO[1:]} if counts else None,
+                         "kernel_counts_per_sample": {k: round(gpu_counts[k] / max(1, gpu_counts["samples"]), 3) for k in ALGO[1:]} if gpu_counts else None},
         }
         if other is not None:
             out["config"]["weak_scaling" if other["mode"] == "weak" else "strong_scaling"] = other

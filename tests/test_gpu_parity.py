@@ -1101,11 +1101,13 @@ def _bench(args, timeout=600):
 
 def test_bench_runs_as_a_bare_command_with_two_ranks():
     """`python bench.py --gpus 2` with no launcher around it: the script starts its two ranks itself (they share
-    device 0 on a one-GPU box, so the gather goes through gloo), renders the same image as one rank, and prints one line."""
+    device 0 on a one-GPU box, so the gather goes through gloo), renders the same image as one rank, and prints one line.
+    The shard check and the other scaling mode are --full's; a plain run leaves out whatever the headline figure does not need."""
     common = ["--scale", "0.05", "--resolution", "96", "--steps", "2", "--warmup", "1", "--spp-per-step", "4", "--no-cpu-baseline"]
     one = _bench(["--gpus", "1"] + common)
-    two = _bench(["--gpus", "2"] + common)
+    two = _bench(["--gpus", "2", "--full"] + common)
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2 and two["scaling"] == "strong"
+    assert "projected_strong_scaling" not in one["config"] and one["roofline"]["kernel_counts_per_sample"] is None  # plain
     assert two["config"]["image_mean_rgb"] == one["config"]["image_mean_rgb"]  # pixels do not depend on the shard
     assert "weak_scaling" in two["config"] and two["value"] > 0
     # the N > 1 line carries its own parity statement: the gathered image against rank 0's render of the whole image, bitwise
@@ -1187,7 +1189,7 @@ def test_kernel_trials_persist_on_disk(yh, tmp_path, monkeypatch):
     assert out.returncode == 0, out.stderr[-2000:]
     d = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][-1])
     assert d["first_launches"] > 1 and d["md5"] == a["md5"] and not any(f for _, _, fs in os.walk(home) for f in fs if f.startswith("trials_"))
-    # ... and yh_set_trial_cache_dir is the call that opts in (what the command lines and bench.py do)
+    # ... and yh_set_trial_cache_dir is the call that opts in (what the command lines do)
     code2 = code.replace("c = yh.Context(0)", "yh.set_trial_cache_dir(%r); c = yh.Context(0)" % str(tmp_path / "api"))
     out = subprocess.run([sys.executable, "-c", code2], env=env3, capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and os.path.exists(tmp_path / "api" / "trials_v2.txt"), out.stderr[-2000:]
