@@ -229,8 +229,12 @@ const char* yh_version(void);
  * LIMITS (YH_E_INVALID with a message beyond them): a shape holds fewer than 2^27 elements; the traversal kernels address a
  * scene's trees as one array of 32-byte units with 27-bit leaf references and 30-bit node references — a line segment takes one
  * unit, a triangle two, a 4- / 8- / 16-wide node four / eight / sixteen — i.e. about 134 M segments or 67 M triangles in ALL shapes together (instances share
- * their shape); at most 4 environments and 16 lights. Scenes of more than ~46 objects or 24 materials run the GENERAL
- * kernel variants (their tables do not fit the LDS budget): slower, same pixels. The one-lane kernels (the streaming integrator
+ * their shape); at most 4 environments and 16 lights (every object with an emissive material is one, so every instance of an emitter
+ * is). Scenes of more than ~46 objects or 24 materials run the GENERAL
+ * kernel variants (their tables do not fit the LDS budget): slower, same pixels. The scene level of a scene of more than ~46 objects
+ * — what an instanced scene file expands to — is collapsed like a shape's tree, two levels per node, and walked as 4-wide nodes out of the same
+ * array, in the reference's visiting order: four more units per scene node, about a third of a node per object (4096 objects: ~1 400
+ * nodes), counted in the limits above. The one-lane kernels (the streaming integrator
  * of dense hair, large closest-hit batches) address that array with 32-bit byte offsets: beyond 4 GB of it (about fifty million
  * segments) they are not candidates and the quad kernels render — same pixels.                                                */
 int yh_upload_scene(yh_context* ctx, const yh_scene_desc* scene);
@@ -459,6 +463,13 @@ int yh_selftest(yh_context* ctx, int which, float* worst);
 /* PLY + Radiance-HDR reader for the hair scenes, with the reference loader's */
 /* semantics (yocto_sceneio.cpp:1064-1418: alphabetical objects, lookat,      */
 /* add_radius 0.001, quads_to_triangles).                                     */
+/* INSTANCES: an object's "instance": "<name>" names instances/<name>.ply (element `instance`, the twelve float or double properties xx xy xz yx
+ * yy yz zx zy zz ox oy oz looked up by name; yocto_sceneio.cpp:848-867,1198-1217). The loaded description holds them EXPANDED, as the
+ * reference's command line expands them (apps/yscenetrace/yscenetrace.cpp:150-181): in the object's alphabetical place one yh_object per
+ * frame, in file order, frame = instance_frame * object_frame (yocto_math.h:2871-2873, the same float operations), all with the object's
+ * shape and material; a file without frames makes the object vanish, "" is no instance, a file named by several objects is read once. Each
+ * copy of an emissive object is a light of its own. A missing file, element or property is an error that names the file. "subdiv"
+ * (subdivision surfaces) is refused.                                                                                                    */
 /* ------------------------------------------------------------------------ */
 typedef struct yh_scene_file yh_scene_file;
 yh_scene_file*       yh_scene_load(const char* json_path, const char* camera,

@@ -477,6 +477,104 @@ def make_crowd(outdir, scale=1.0, name="crowd", count=70):
     return os.path.join(d, name + ".json"), nseg
 
 
+def write_instance_ply(path, frames, ascii=False, order=None):
+    """frames: (N, 12) float32 rows `xx xy xz yx yy yz zx zy zz ox oy oz` -> instances/<name>.ply in the reference's layout
+    (element `instance`, twelve float properties; yocto_sceneio.cpp:848-898). order: the header's property order."""
+    names = ["xx", "xy", "xz", "yx", "yy", "yz", "zx", "zy", "zz", "ox", "oy", "oz"]
+    order = list(order) if order is not None else list(range(12))
+    frames = np.asarray(frames, np.float32).reshape(-1, 12)
+    header = (f"ply\nformat {'ascii' if ascii else 'binary_little_endian'} 1.0\ncomment instances (tools/make_scenes.py)\n"
+              f"element instance {len(frames)}\n" + "".join(f"property float {names[k]}\n" for k in order) + "end_header\n")
+    with open(path, "wb") as f:
+        f.write(header.encode())
+        if ascii:
+            for row in frames[:, order]:
+                f.write((" ".join(repr(float(v)) for v in row) + "\n").encode())
+        else:
+            f.write(frames[:, order].astype("<f4").tobytes())
+
+
+def compose_frames(a, b):
+    """a * b of two frames in float32 with the reference's operation order (yocto_math.h:2871-2873: rotation(a) * rotation(b),
+    rotation(a) * b.o + a.o, a matrix times a vector being a.x * v.x + a.y * v.y + a.z * v.z): a (N, 12), b (12,)."""
+    a = np.asarray(a, np.float32).reshape(-1, 12)
+    b = np.asarray(b, np.float32)
+    out = np.empty_like(a)
+    for c in range(4):
+        for k in range(3):
+            v = (a[:, k] * b[3 * c] + a[:, 3 + k] * b[3 * c + 1]) + a[:, 6 + k] * b[3 * c + 2]
+            out[:, 3 * c + k] = v + a[:, 9 + k] if c == 3 else v
+    return out
+
+
+def _field_frames(rng, n, extent, lo, hi):
+    """n frames on a jittered grid over [-extent, extent]^2 (y = 0): rotated about y, scaled differently along each axis
+    and sheared a little, so that their inverse is not the transpose."""
+    side = int(np.ceil(np.sqrt(n)))
+    k = np.arange(n)
+    cell = 2.0 * extent / side
+    x = -extent + cell * (k % side + 0.5) + rng.uniform(-0.3, 0.3, n) * cell
+    z = -extent + cell * (k // side + 0.5) + rng.uniform(-0.3, 0.3, n) * cell
+    a = rng.uniform(0, 2 * np.pi, n)
+    sx, sy, sz = (rng.uniform(lo, hi, n) for _ in range(3))
+    tx, tz = rng.uniform(-0.15, 0.15, n), rng.uniform(-0.15, 0.15, n)
+    zero = np.zeros(n)
+    return np.stack([sx * np.cos(a), zero, -sx * np.sin(a), sy * tx, sy, sy * tz, sz * np.sin(a), zero, sz * np.cos(a),
+                     x, zero, z], axis=1).astype(np.float32)
+
+
+def make_fur_field(outdir, scale=1.0, name="fur-field", count=2048, expanded=False):
+    """Instances (yocto_sceneio.cpp:848-867,1198-1217; yscenetrace.cpp:150-181): one small hair tuft with `count` frames and
+    one sphere with count/8 frames, from two instance files, both objects with a frame of their own (so that
+    instance * object and object * instance differ); a floor, one area light that is not instanced, a constant
+    environment. expanded: the same scene with one JSON object per frame, named so that the alphabetical order keeps
+    every copy in its object's place — what a reader without instances can load."""
+    d = _prep(outdir, name)
+    shutil.copy(os.path.join(ASSETS, "sphere.ply"), os.path.join(d, "shapes", "sphere.ply"))
+    shutil.copy(os.path.join(ASSETS, "arealight.ply"), os.path.join(d, "shapes", "arealight.ply"))
+    nseg = write_hair_ply(os.path.join(d, "shapes", "tuft.ply"), gen_hair_block(max(32, int(600 * scale)), 8), 0.02, 0.005)
+    rng = np.random.default_rng(23)
+    side = int(np.ceil(np.sqrt(count)))
+    extent = max(1.0, 0.15 * side)
+    tufts = _field_frames(rng, count, extent, 0.25, 0.45)
+    pebbles = _field_frames(rng, max(1, count // 8), extent, 0.08, 0.2)
+    objects = {
+        "floor": {"frame": [0.6 * extent, 0, 0, 0, 0, -0.6 * extent, 0, 0.6 * extent, 0, 0, 0, 0], "shape": "arealight", "material": "floor"},
+        "light": {"lookat": [0.3 * extent, 2.5 * extent + 3, 0.8 * extent, 0, 0, 0, 0, 1, 0], "shape": "arealight",
+                  "material": "arealight"},
+        "pebble": {"frame": [0.8, 0, 0.6, 0, 1, 0, -0.6, 0, 0.8, 0, 0.4, 0], "shape": "sphere", "material": "stone",
+                   "instance": "pebbles"},
+        "tuft": {"frame": [0.6, 0, 0, 0, 0, 0.6, 0, -0.6, 0, 0.02, 0, -0.03], "shape": "tuft", "material": "fur",
+                 "instance": "tufts"},
+    }
+    if expanded:
+        for oname, frames in (("pebble", pebbles), ("tuft", tufts)):
+            o = objects.pop(oname)
+            o.pop("instance")
+            for k, fr in enumerate(compose_frames(frames, o["frame"])):
+                objects["%s#%05d" % (oname, k)] = dict(o, frame=[float(v) for v in fr])
+    else:
+        os.makedirs(os.path.join(d, "instances"), exist_ok=True)
+        write_instance_ply(os.path.join(d, "instances", "tufts.ply"), tufts)
+        write_instance_ply(os.path.join(d, "instances", "pebbles.ply"), pebbles)
+    power = 5.0 * max(1.0, extent * extent / 4)
+    scene = {
+        "asset": {"copyright": "synthetic; sphere and quad from the reference's test assets"},
+        "cameras": {"default": {"lens": 0.035, "aperture": 0.0, "aspect": 1.0,
+                                "lookat": [0.4 * extent, 0.9 * extent + 0.6, 2.0 * extent + 1.0, 0.0, 0.1, 0, 0, 1, 0]}},
+        "environments": {"sky": {"emission": [0.9, 0.9, 0.9]}},
+        "objects": objects,
+        "materials": {"fur": {"eumelanin": 0.8}, "stone": {"color": [0.55, 0.5, 0.45], "specular": 0.5, "roughness": 0.4},
+                      "floor": {"color": [0.35, 0.45, 0.25]}, "arealight": {"emission": [power, power, power]}},
+    }
+    _dump(scene, os.path.join(d, name + ".json"))
+    return os.path.join(d, name + ".json"), nseg * count
+
+
+def make_fur_field_expanded(outdir, scale=1.0, name="fur-field-expanded", count=2048):
+    return make_fur_field(outdir, scale, name, count, expanded=True)
+
+
 def _head_scene(outdir, name, shape, pos, emission, lights, hair_mat):
     d = _prep(outdir, name)
     shutil.copy(os.path.join(ASSETS, "sky.hdr"), os.path.join(d, "textures", "sky.hdr"))
@@ -656,6 +754,8 @@ MAKERS = {
     "textured": make_textured,
     "crowd": make_crowd,
     "maps": make_maps,
+    "fur-field": make_fur_field,
+    "fur-field-expanded": make_fur_field_expanded,
 }
 
 

@@ -187,7 +187,10 @@ YH_DEV hit_t lane_hit_retest(const trace_ctx& tc, hit_t raw, bool hit_lines, f3 
 // is accepted when !(t > tmax) with tmax = the last accepted distance — minimum t, the later segment on a tie; a test made with the step's
 // first tmax and re-checked against the running one gives the same answer) and pulls u, d2, r of the survivor. Tests that do not fit the 64
 // lanes stay in the entry for the next step. Triangle leaves and nodes are the lane's own as before.
-template <bool EXACT, bool PROF = false, bool COOP = false>
+// WIDE_SCENE: the kernel can meet a scene whose level is walked as 4-wide nodes out of the blob (yh_device.h: scene_wide_root — a scene table
+// too big for LDS, so only the GENERAL variants and the ray batches): a scene node is then a node of the step like any other, fetched by the
+// step's own loads and tested against the world ray. Compiled out of the plain kernels.
+template <bool EXACT, bool PROF = false, bool COOP = false, bool WIDE_SCENE = false>
 YH_DEV bool lane_step(const trace_ctx& tc, lane_trav& t, lane_stack& s, int sp0, bool& redo, float* pc = nullptr, bool active = true,
     YH_LDS unsigned long long* cmap = nullptr, unsigned long long* tacc = nullptr) {
   const yhd_scene& sc = *tc.sc;
@@ -214,6 +217,7 @@ YH_DEV bool lane_step(const trace_ctx& tc, lane_trav& t, lane_stack& s, int sp0,
   };
   unsigned int tag  = 0;
   bool         skip = true;
+  bool         scene_node = false;  // WIDE_SCENE: this step's node is a 4-wide node of the scene level
   // The head of a step — pop, scene level, ENTER: what the lane does before its fetch. false: the ray has to be traced again (redo).
   auto head = [&]() -> bool {
   if (!EXACT && !t.wnonan) {
@@ -229,7 +233,21 @@ YH_DEV bool lane_step(const trace_ctx& tc, lane_trav& t, lane_stack& s, int sp0,
   t.steps++;
   tag  = t.cur & YH_TAG_MASK;
   skip = t.cur == YH_NONE;  // only a scene without objects
-  if (!skip && tag == YH_TAG_SCENE) {  // scene-level node (binary, the reference's layout)
+  if (WIDE_SCENE && !skip && tag == YH_TAG_SCENE && sc.scene_wide_root >= 0) {
+    // a node's offset in the blob: the step's node, tested against the world ray (ENTER sets the ray in the object's space anew, so those registers
+    // take it) — or a leaf's count << 27 | first: its objects are entered in order (pt.cpp:1005-1023)
+    YH_LPROF(LP_SCENE)
+    const unsigned int low = t.cur & ~YH_TAG_MASK;
+    if (low >= (1u << 27)) {
+      const int start = (int)(low & 0x07FFFFFFu), num = (int)(low >> 27);
+      for (int i = num - 1; i >= 1; i--) lane_push(s, YH_TAG_ENTER | (unsigned)sc.scene_prims[start + i]);
+      t.cur = YH_TAG_ENTER | (unsigned)sc.scene_prims[start];
+      tag   = YH_TAG_ENTER;
+    } else {
+      t.lo = t.ro, t.ldinv = t.wdinv, t.lsign = t.wsign;
+      scene_node = true, tag = YH_TAG_SHAPE;
+    }
+  } else if (!skip && tag == YH_TAG_SCENE) {  // scene-level node (binary, the reference's layout)
     YH_MARK("scene");
     YH_LPROF(LP_SCENE)
     int idx = (int)(t.cur & ~YH_TAG_MASK);
@@ -318,7 +336,9 @@ YH_DEV bool lane_step(const trace_ctx& tc, lane_trav& t, lane_stack& s, int sp0,
       YH_MARK("node");
       YH_LPROF(LP_NODE)
       const unsigned int axes = __float_as_uint(B0.w);
-      const unsigned int r0 = __float_as_uint(B0.z), r1 = __float_as_uint(B1.z), r2 = __float_as_uint(B2.z), r3 = __float_as_uint(B3.z);
+      unsigned int r0 = __float_as_uint(B0.z), r1 = __float_as_uint(B1.z), r2 = __float_as_uint(B2.z), r3 = __float_as_uint(B3.z);
+      if (WIDE_SCENE && scene_node)  // children of a scene node are scene entries (an empty slot's is never looked at: bits 8-11 of axes)
+        r0 = (r0 & ~YH_TAG_MASK) | YH_TAG_SCENE, r1 = (r1 & ~YH_TAG_MASK) | YH_TAG_SCENE, r2 = (r2 & ~YH_TAG_MASK) | YH_TAG_SCENE, r3 = (r3 & ~YH_TAG_MASK) | YH_TAG_SCENE;
       if (COOP) asm volatile("" ::"v"(B1.w), "v"(B2.w), "v"(B3.w));  // (words nobody reads: their registers stay the loads' until the loads are back — handed to another value, that value's write would wait for the load)
       unsigned int hm = 0;
       hm |= box_test(t.lo, t.ldinv, ray_eps, t.tmax, f3{A0.x, A0.y, A0.z}, f3{A0.w, B0.x, B0.y}) ? 1u : 0u;
@@ -540,8 +560,9 @@ struct lane_exact_result {
   int   hit_lines;
   int   base;  // the stack's window base afterwards (sp is back where it was)
 };
-__device__ __attribute__((noinline)) lane_exact_result lane_trace_exact(const yhd_scene* sc, const YH_LDS v4f* lds_scene,
-    YH_LDS unsigned int* lds, unsigned int* ovf, int sp, int base, f3 ro, f3 rd, int first_object) {
+template <bool WIDE_SCENE>
+YH_DEV lane_exact_result lane_trace_exact_body(const yhd_scene* sc, const YH_LDS v4f* lds_scene, YH_LDS unsigned int* lds, unsigned int* ovf, int sp, int base,
+    f3 ro, f3 rd, int first_object) {
   trace_ctx tc;
   tc.sc = sc, tc.lds_stack = nullptr, tc.lds_scene = lds_scene, tc.stats = nullptr, tc.ls = nullptr, tc.sc_dev = sc;
   tc.lds_lights = nullptr, tc.lds_envtab = nullptr, tc.lds_mats = nullptr;
@@ -550,11 +571,20 @@ __device__ __attribute__((noinline)) lane_exact_result lane_trace_exact(const yh
   lane_trav t;
   lane_begin(*sc, t, ro, rd, first_object);
   bool dummy = false;
-  while (!lane_step<true>(tc, t, s, sp, dummy)) {
+  while (!lane_step<true, false, false, WIDE_SCENE>(tc, t, s, sp, dummy)) {
   }
   lane_exact_result r;
   r.hit = t.hit, r.hit_r = t.hit_r, r.hit_lines = t.hit_lines ? 1 : 0, r.base = s.base;
   return r;
+}
+__device__ __attribute__((noinline)) lane_exact_result lane_trace_exact(const yhd_scene* sc, const YH_LDS v4f* lds_scene,
+    YH_LDS unsigned int* lds, unsigned int* ovf, int sp, int base, f3 ro, f3 rd, int first_object) {
+  return lane_trace_exact_body<false>(sc, lds_scene, lds, ovf, sp, base, ro, rd, first_object);
+}
+// ... and for the kernels that can meet a scene level of 4-wide nodes (lane_step: WIDE_SCENE): the redo starts the ray again from the root, on the same walk
+__device__ __attribute__((noinline)) lane_exact_result lane_trace_exact_wide(const yhd_scene* sc, const YH_LDS v4f* lds_scene,
+    YH_LDS unsigned int* lds, unsigned int* ovf, int sp, int base, f3 ro, f3 rd, int first_object) {
+  return lane_trace_exact_body<true>(sc, lds_scene, lds, ovf, sp, base, ro, rd, first_object);
 }
 
 // A whole ray in one call (the light-pdf rays of sample_lights_pdf, pt.cpp:1315-1334): closest hit

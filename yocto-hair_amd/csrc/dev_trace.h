@@ -357,6 +357,7 @@ YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_obj
   unsigned int       n_steps = 0;
 
   const bool in_lds = LDS_SCENE || tc.lds_scene != nullptr;
+  const bool wide_scene = !LDS_SCENE && sc.scene_wide_root >= 0;  // a property of the uploaded scene, not of who staged what (k_intersect stages nothing)
   const YH_LDS v4f* lds_snodes = in_lds ? tc.lds_scene + YH_OBJECT_F4 * sc.num_objects : nullptr;
   auto scene_prim = [&](int i) -> int {
     if (in_lds) return ((const YH_LDS int*)(lds_snodes + 2 * sc.num_scene_nodes))[i];
@@ -385,7 +386,27 @@ YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_obj
     // of the tiny scene BVH), the ENTER it leads to and the root fetch of the entered
     // shape chain inside ONE iteration, so a ray pays one memory round trip per
     // object it enters instead of three.
-    if (tag == YH_TAG_SCENE) {
+    bool scene_node = false;  // this step's node is a 4-wide node of the scene level
+    if (!LDS_SCENE && tag == YH_TAG_SCENE && wide_scene) {
+      // THE SCENE LEVEL AS 4-WIDE NODES (a scene table in memory, yh_device.h: scene_wide_root): the entry is a node's offset in the blob
+      // — fetched and tested below like a shape's, lane q slot q, against the WORLD ray: the ray-in-the-object registers are free up here
+      // (ENTER sets every one of them anew), so they take the world ray and the node code is the shape's — or a leaf's count << 27 | first:
+      // its objects are entered in order, as the binary walk does it
+      if (COUNT) count_branch<COUNT>(tc.stats->t_scene, tc.stats->l_scene);
+      const unsigned int low = cur & ~YH_TAG_MASK;
+      if (low >= (1u << 27)) {
+        const int start = (int)(low & 0x07FFFFFFu), num = (int)(low >> 27);
+        if ((int)q >= 1 && (int)q < num) YH_STK(sp + (num - 1 - (int)q)) = YH_TAG_ENTER | (unsigned)sc.scene_prims[start + (int)q];
+        sp += num - 1;
+        cur = YH_TAG_ENTER | (unsigned)sc.scene_prims[start];
+        tag = YH_TAG_ENTER;
+      } else {
+        scene_node = true;
+        lo = ray.o, ldinv = wdinv, lsign = (lsign & 0x70) | (lsign >> 4);
+        cur = low;  // (YH_TAG_SHAPE is 0: the offset is the address below)
+        tag = YH_TAG_SHAPE;
+      }
+    } else if (tag == YH_TAG_SCENE) {
       // scene-level node (binary, reference layout; every lane of the quad does it)
       if (COUNT) count_branch<COUNT>(tc.stats->t_scene, tc.stats->l_scene);
       int idx = (int)(cur & ~YH_TAG_MASK);
@@ -489,11 +510,11 @@ YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_obj
       bool mine       = !is_leaf || (int)q < leaf_num;  // lanes beyond the leaf's count re-read its last record
       int  pq         = mine ? (int)q : leaf_num - 1;
       // the lane's 32 bytes in the blob: slot (lane of the group) of the node, or the test record of primitive pq of the leaf (leaf_start: its first test record)
-      const unsigned int nslot = MODE == YH_MODE_QUAD ? q : (__lane_id() & (YH_IS_HEX(MODE) ? 15u : 7u));
+      const unsigned int nslot = (MODE == YH_MODE_QUAD || scene_node) ? q : (__lane_id() & (YH_IS_HEX(MODE) ? 15u : 7u));  // (a scene node is 4-wide under every MODE: each quad of an octet or a sixteen runs it)
       const yhd_float4*  addr  = sc.lane_blob + 2 * (size_t)(is_leaf ? (unsigned)leaf_start + (unsigned)pq * (kind == YH_KIND_LINES ? 1u : 2u) : cur + nslot);
       if (GROUPS) mine = mine && !idle;
       const v4f s0 = ldg4(addr), s1 = ldg4(addr + 1);
-      if (YH_IS_HEX(MODE) && !is_leaf) {
+      if (YH_IS_HEX(MODE) && !is_leaf && !scene_node) {
         // ---- 16-wide node: slot o = s1 << 3 | s2 << 2 | s3 << 1 | s4, one per lane of the sixteen; the rank of a slot in the
         // reference's visiting order is the four near / far decisions of pt.cpp:887-893 at the four collapsed levels.
         if (q == 0) n_nodes++;
@@ -522,7 +543,7 @@ YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_obj
         int nh = __popc(M);
         sp += nh > 0 ? nh - 1 : 0;
         cur = nh > 0 ? mine : YH_NONE;
-      } else if (MODE != YH_MODE_QUAD && !is_leaf) {
+      } else if (MODE != YH_MODE_QUAD && !is_leaf && !scene_node) {
         // ---- 8-wide node: slot o = s1 << 2 | s2 << 1 | s3 (host/bvh_build.h), one per lane of the octet. The visiting order applies
         // pt.cpp:887-893 at the three collapsed levels: rank bit 2 = side of the node's own axis, bit 1 = side of the child's, bit 0 =
         // side of the grandchild's, each flipped when the ray runs against that axis. Every hit slot pushes itself so
@@ -558,6 +579,7 @@ YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_obj
         unsigned int ref  = __float_as_uint(s1.z);
         unsigned int axes = __float_as_uint(s1.w);
         h = h && ref != YH_NONE;  // an empty slot's inverted box still passes the min/max slab test
+        if (!LDS_SCENE && scene_node) ref = (ref & ~YH_TAG_MASK) | YH_TAG_SCENE;  // children of a scene node are scene entries: a node's offset, or count << 27 | first of a leaf
         // Visiting order of the four slots (pt.cpp:887-893 applied at both collapsed
         // levels): the pair on the near side of the node's own axis first, and
         // inside each pair the slot on the near side of that child's axis first.

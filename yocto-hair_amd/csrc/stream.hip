@@ -211,8 +211,9 @@ __global__ __launch_bounds__(YH_ST_BLOCK, WAVES) void k_stream(const yhd_scene s
           if (kd == K_REDO) {  // axis-parallel ray: the reference's compare-and-select box test (dev_trace.h)
             const size_t g = base + sl;
             yhd_float4 o = SLOT_RAY_O(pl, g), d = SLOT_RAY_D(pl, g);
-            lane_exact_result r = lane_trace_exact(sc_dev, tc.lds_scene, stk.lds, stk.ovf, stk.sp, stk.base, f3{o.x, o.y, o.z},
-                f3{d.x, d.y, d.z}, -1);
+            // (the redo starts the ray again from the root, on the walk the scene has: a stack never holds entries of the other form)
+            lane_exact_result r = (GENERAL && sc.scene_wide_root >= 0) ? lane_trace_exact_wide(sc_dev, tc.lds_scene, stk.lds, stk.ovf, stk.sp, stk.base, f3{o.x, o.y, o.z}, f3{d.x, d.y, d.z}, -1)
+                                          : lane_trace_exact(sc_dev, tc.lds_scene, stk.lds, stk.ovf, stk.sp, stk.base, f3{o.x, o.y, o.z}, f3{d.x, d.y, d.z}, -1);
             stk.base = r.base;
             kd       = publish(pl, base + sl, r.hit, r.hit_lines != 0, 1u);
           }
@@ -347,7 +348,7 @@ __global__ __launch_bounds__(YH_ST_BLOCK, WAVES) void k_stream(const yhd_scene s
         int  kind = 0;
         {
           bool redo = false;
-          if (lane_step<false, PROF, true>(tc, t, stk, 0, redo, PROF && pl.prof_parts_only ? nullptr : pc, have, w_cmap, PROF ? tacc : nullptr)) {  // (every lane: the wave tests its line leaves together)
+          if (lane_step<false, PROF, true, GENERAL>(tc, t, stk, 0, redo, PROF && pl.prof_parts_only ? nullptr : pc, have, w_cmap, PROF ? tacc : nullptr)) {  // (every lane: the wave tests its line leaves together)
             YH_MARK("trace_retire");
             have = false, fin = true;
             if (redo) {
@@ -463,13 +464,14 @@ __global__ __launch_bounds__(256, WAVES) void k_intersect_lanes(const yhd_scene 
     }
     {
       bool redo = false;
-      if (lane_step<false, false, true>(tc, t, stk, 0, redo, nullptr, have, w_cmap)) {
+      if (lane_step<false, false, true, true>(tc, t, stk, 0, redo, nullptr, have, w_cmap)) {  // (WIDE_SCENE: a batch is traced against whatever scene is uploaded)
         have = false;
         hit_t h = lane_hit_retest(tc, t.hit, t.hit_lines, t.ro, t.rd);
         if (redo) {  // axis-parallel ray: the reference's compare-and-select box test throughout
           stk.sp = 0, stk.base = 0;
           const float*      r = rays + 8 * (size_t)ray;
-          lane_exact_result e = lane_trace_exact(sc_dev, tc.lds_scene, stk.lds, stk.ovf, 0, 0, ld3(r), ld3(r + 3), -1);
+          lane_exact_result e = sc.scene_wide_root >= 0 ? lane_trace_exact_wide(sc_dev, tc.lds_scene, stk.lds, stk.ovf, 0, 0, ld3(r), ld3(r + 3), -1)
+                                                        : lane_trace_exact(sc_dev, tc.lds_scene, stk.lds, stk.ovf, 0, 0, ld3(r), ld3(r + 3), -1);
           stk.base = e.base;
           h        = lane_hit_retest(tc, e.hit, e.hit_lines != 0, ld3(r), ld3(r + 3));
           if (h.object >= 0 && h.distance > r[7]) h.object = -1, h.slot = -1, h.u = 0, h.v = 0, h.distance = 0;  // (the exact form starts from tmax = flt_max)

@@ -177,6 +177,12 @@ typedef struct yhd_scene {
   // tables the kernels stage in LDS next to the scene-level table (dev_trace.h: stage_tables)
   const yhd_float4* light_table;     // small area lights, YH_SMALL_LIGHT_F4 float4 each
   int               light_table_f4;
+  // THE SCENE LEVEL AS 4-WIDE NODES (a scene whose table does not fit LDS: lds_scene_f4 == 0): the scene tree collapsed two levels per node
+  // like a shape's, at the FRONT of lane_blob — its root's offset there (0), or -1: the scene level is walked through the binary scene_nodes.
+  // A leaf reference names up to four consecutive scene_prims entries (count << 27 | first). On a traversal stack a YH_TAG_SCENE entry of
+  // such a scene is a node's offset (< 2^27: the nodes lie in front of every test record) or a leaf's count << 27 | first (>= 2^27).
+  // (The field fills what was padding: the struct's size and every other offset are as they were.)
+  int               scene_wide_root;
   // coarse index of ONE environment light's texel cdf: env_tab[k] = cdf[min(n, (k + 1) * env_tab_stride) - 1], so that
   // the first log2(env_tab_k) steps of the binary search of sample_lights (math.h:4957-4962, 21 dependent
   // fetches for sky.hdr) read LDS

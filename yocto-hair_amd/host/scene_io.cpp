@@ -219,54 +219,59 @@ inline double ply_read_bin(const unsigned char*& p, PlyType t) {
   p += ply_size(t);
   return v;
 }
-void load_ply(const std::string& path, ShapeData& shape) {
-  std::string data;
-  if (!read_file(path, data)) throw std::runtime_error(path + ": file not found");
-  size_t pos = 0;
-  auto   line = [&]() {
-    auto e = data.find('\n', pos);
-    if (e == std::string::npos) throw std::runtime_error(path + ": bad ply header");
-    auto s = data.substr(pos, e - pos);
-    pos    = e + 1;
-    while (!s.empty() && (s.back() == '\r' || s.back() == ' ')) s.pop_back();
-    return s;
-  };
-  if (line() != "ply") throw std::runtime_error(path + ": not a ply file");
-  bool ascii = false;
+// header and value stream of one file, shared by the shape and the instance reader
+struct PlyFile {
+  std::string          path, data;
+  bool                 ascii = false;
   std::vector<PlyElem> elems;
-  while (true) {
-    auto l = line();
-    char a[64] = "", b[64] = "", c[64] = "", d[64] = "";
-    auto n = sscanf(l.c_str(), "%63s %63s %63s %63s %63s", a, b, c, d, d);
-    if (n < 1) continue;
-    if (!strcmp(a, "end_header")) break;
-    if (!strcmp(a, "format")) {
-      if (!strcmp(b, "ascii")) ascii = true;
-      else if (!strcmp(b, "binary_little_endian")) ascii = false;
-      else throw std::runtime_error(path + ": unsupported ply format");
-    } else if (!strcmp(a, "element")) {
-      PlyElem e;
-      e.name  = b;
-      e.count = strtoull(c, nullptr, 10);
-      elems.push_back(e);
-    } else if (!strcmp(a, "property")) {
-      if (elems.empty()) throw std::runtime_error(path + ": property before element");
-      PlyProp p;
-      if (!strcmp(b, "list")) {
-        char t1[64], t2[64], nm[64];
-        if (sscanf(l.c_str(), "property list %63s %63s %63s", t1, t2, nm) != 3)
-          throw std::runtime_error(path + ": bad list property");
-        p.list = true, p.ltype = ply_type(t1), p.type = ply_type(t2), p.name = nm;
-      } else {
-        p.type = ply_type(b), p.name = c;
+  const unsigned char *bp = nullptr, *bend = nullptr;
+  const char*          ap = nullptr;
+  explicit PlyFile(const std::string& path_) : path(path_) {
+    if (!read_file(path, data)) throw std::runtime_error(path + ": file not found");
+    size_t pos = 0;
+    auto   line = [&]() {
+      auto e = data.find('\n', pos);
+      if (e == std::string::npos) throw std::runtime_error(path + ": bad ply header");
+      auto s = data.substr(pos, e - pos);
+      pos    = e + 1;
+      while (!s.empty() && (s.back() == '\r' || s.back() == ' ')) s.pop_back();
+      return s;
+    };
+    if (line() != "ply") throw std::runtime_error(path + ": not a ply file");
+    while (true) {
+      auto l = line();
+      char a[64] = "", b[64] = "", c[64] = "", d[64] = "";
+      auto n = sscanf(l.c_str(), "%63s %63s %63s %63s %63s", a, b, c, d, d);
+      if (n < 1) continue;
+      if (!strcmp(a, "end_header")) break;
+      if (!strcmp(a, "format")) {
+        if (!strcmp(b, "ascii")) ascii = true;
+        else if (!strcmp(b, "binary_little_endian")) ascii = false;
+        else throw std::runtime_error(path + ": unsupported ply format");
+      } else if (!strcmp(a, "element")) {
+        PlyElem e;
+        e.name  = b;
+        e.count = strtoull(c, nullptr, 10);
+        elems.push_back(e);
+      } else if (!strcmp(a, "property")) {
+        if (elems.empty()) throw std::runtime_error(path + ": property before element");
+        PlyProp p;
+        if (!strcmp(b, "list")) {
+          char t1[64], t2[64], nm[64];
+          if (sscanf(l.c_str(), "property list %63s %63s %63s", t1, t2, nm) != 3)
+            throw std::runtime_error(path + ": bad list property");
+          p.list = true, p.ltype = ply_type(t1), p.type = ply_type(t2), p.name = nm;
+        } else {
+          p.type = ply_type(b), p.name = c;
+        }
+        elems.back().props.push_back(p);
       }
-      elems.back().props.push_back(p);
     }
+    bp   = (const unsigned char*)data.data() + pos;
+    bend = (const unsigned char*)data.data() + data.size();
+    ap   = data.c_str() + pos;
   }
-  auto bp   = (const unsigned char*)data.data() + pos;
-  auto bend = (const unsigned char*)data.data() + data.size();
-  auto ap   = data.c_str() + pos;
-  auto next = [&](PlyType t) -> double {
+  double next(PlyType t) {
     if (ascii) {
       char* e = nullptr;
       auto  v = strtod(ap, &e);
@@ -276,7 +281,15 @@ void load_ply(const std::string& path, ShapeData& shape) {
     }
     if (bp + ply_size(t) > bend) throw std::runtime_error(path + ": truncated ply");
     return ply_read_bin(bp, t);
-  };
+  }
+};
+void load_ply(const std::string& path, ShapeData& shape) {
+  PlyFile ply(path);
+  const bool ascii = ply.ascii;
+  auto&      elems = ply.elems;
+  auto&      bp    = ply.bp;
+  auto       bend  = ply.bend;
+  auto       next  = [&](PlyType t) { return ply.next(t); };
   std::vector<std::vector<int>> faces;
   bool has_normals = false, has_radius = false;
   for (auto& e : elems) {
@@ -368,6 +381,56 @@ void load_ply(const std::string& path, ShapeData& shape) {
   if (shape.positions.empty()) throw std::runtime_error(path + ": empty shape");
   if (!shape.lines.empty() && shape.radius.empty())
     shape.radius.assign(shape.positions.size() / 3, 0.001f);  // add_radius
+}
+
+// instances/<name>.ply (load_instance, sceneio.cpp:848-867): element `instance`, one frame per row, the twelve
+// properties looked up by name as get_values does (yocto_ply.h), whatever their order in the header
+void load_instance_ply(const std::string& path, std::vector<float>& frames) {
+  PlyFile ply(path);
+  static const char* names[12] = {"xx", "xy", "xz", "yx", "yy", "yz", "zx", "zy", "zz", "ox", "oy", "oz"};
+  bool found = false;
+  for (auto& e : ply.elems) {
+    const bool wanted = e.name == "instance" && !found;
+    int        col[12];
+    if (wanted) {
+      found = true;
+      for (int k = 0; k < 12; k++) {
+        col[k] = -1;
+        for (int c = 0; c < (int)e.props.size(); c++)
+          if (!e.props[c].list && e.props[c].name == names[k]) { col[k] = c; break; }
+        if (col[k] < 0) throw std::runtime_error(path + ": instance element without property " + names[k]);
+      }
+      frames.resize(12 * e.count);
+    }
+    std::vector<double> row(e.props.size());
+    for (size_t i = 0; i < e.count; i++) {  // elements ahead of `instance` are read past
+      for (int c = 0; c < (int)e.props.size(); c++) {
+        auto& pr = e.props[c];
+        if (pr.list) {
+          auto n = (int)ply.next(pr.ltype);
+          if (n < 0) throw std::runtime_error(path + ": negative list length");
+          for (int z = 0; z < n; z++) ply.next(pr.type);
+        } else {
+          row[c] = ply.next(pr.type);
+        }
+      }
+      if (wanted)
+        for (int k = 0; k < 12; k++) frames[12 * i + k] = (float)row[col[k]];
+    }
+    if (wanted) break;
+  }
+  if (!found) throw std::runtime_error(path + ": no instance element");
+}
+
+// frame composition a * b (math.h:2871-2873): {rotation(a) * rotation(b), rotation(a) * b.o + a.o}, a matrix times a
+// vector being a.x * v.x + a.y * v.y + a.z * v.z (math.h:2535-2537) — the same sums in the same order, so that an
+// instanced object's frame has the reference's bits
+void compose_frames(const float* a, const float* b, float* out) {
+  for (int c = 0; c < 4; c++)
+    for (int k = 0; k < 3; k++) {
+      float v = a[k] * b[3 * c] + a[3 + k] * b[3 * c + 1] + a[6 + k] * b[3 * c + 2];
+      out[3 * c + k] = c == 3 ? v + a[9 + k] : v;
+    }
 }
 
 // ---------------------------------------------------------------------------
@@ -734,6 +797,7 @@ static yh_scene_file* load_scene(const std::string& path, const std::string& cam
 
   // objects (sceneio.cpp:1327-1343) in alphabetical order; shapes by name
   std::map<std::string, int> shape_index;
+  std::map<std::string, std::vector<float>> instances;  // by name: a file named by several objects is read once
   int default_material = -1;
   if (js.has("objects"))
     for (auto& [name, e] : js.at("objects").obj) {
@@ -742,7 +806,18 @@ static yh_scene_file* load_scene(const std::string& path, const std::string& cam
       get_floats(e, "frame", o.frame, 12);
       float l[9];
       if (get_floats(e, "lookat", l, 9)) lookat_frame(l, true, o.frame);
-      if (e.has("instance") || e.has("subdiv")) throw std::runtime_error(path + ": instances/subdivs are outside the hair path");
+      if (e.has("subdiv")) throw std::runtime_error(path + ": subdivision surfaces are outside the hair path: " + name);
+      // "instance": "<name>" -> instances/<name>.ply (sceneio.cpp:1198-1217,1404), one file read once; "" is no instance
+      const std::vector<float>* frames = nullptr;
+      if (e.has("instance") && !e.at("instance").str.empty()) {
+        auto iname = e.at("instance").str;
+        auto it    = instances.find(iname);
+        if (it == instances.end()) {
+          it = instances.emplace(iname, std::vector<float>()).first;
+          load_instance_ply(base + "/instances/" + iname + ".ply", it->second);
+        }
+        frames = &it->second;
+      }
       if (e.has("material") && !e.at("material").str.empty()) {
         auto it = material_index.find(e.at("material").str);
         if (it == material_index.end()) throw std::runtime_error(path + ": missing material " + e.at("material").str);
@@ -768,7 +843,18 @@ static yh_scene_file* load_scene(const std::string& path, const std::string& cam
         it = shape_index.emplace(sname, (int)sf->shape_data.size() - 1).first;
       }
       o.shape = it->second;
-      sf->objects.push_back(o);
+      if (!frames) {
+        sf->objects.push_back(o);
+        continue;
+      }
+      // the reference's command line puts one object per frame in the object's place, in file order, each with
+      // instance_frame * object_frame and the object's shape and material (yscenetrace.cpp:150-166); no frame, no object.
+      // Every copy of an emissive object is a light of its own (init_lights walks objects, pt.cpp:1695-1740).
+      for (size_t k = 0; k + 12 <= frames->size(); k += 12) {
+        auto inst = o;
+        compose_frames(frames->data() + k, o.frame, inst.frame);
+        sf->objects.push_back(inst);
+      }
     }
 
   for (auto& sd : sf->shape_data) {

@@ -89,6 +89,20 @@ static bool has_effective_map(const yh_material_maps& m) {
 
 static_assert(sizeof(yhd_maps) == 32, "yhd_maps");
 
+// The levels of a host-built tree as the device builder reports them: their number and the first node of each (level_first[0 .. levels],
+// 130 entries). false: more than 128 levels.
+static bool tree_levels(const yhh::Tree& tree, int& levels, int* level_first) {
+  std::vector<int> level(tree.nodes.size(), 0);
+  for (size_t n = 0; n < tree.nodes.size(); n++)
+    if (tree.nodes[n].internal) level[(size_t)tree.nodes[n].start] = level[(size_t)tree.nodes[n].start + 1] = level[n] + 1;
+  const int num_nodes = (int)tree.nodes.size();
+  levels = level.empty() ? 1 : level.back() + 1;  // (breadth-first numbering: levels are contiguous, the last node is on the last one)
+  if (levels > 128) return false;
+  for (int l = 0; l <= levels; l++) level_first[l] = num_nodes;
+  for (size_t n = tree.nodes.size(); n-- > 0;) level_first[level[n]] = (int)n;
+  return true;
+}
+
 int yh_upload_scene(yh_context* ctx, const yh_scene_desc* sd) { return yh_upload_scene_maps(ctx, sd, nullptr); }
 
 int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_material_maps* maps) {
@@ -233,15 +247,8 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
       // the tree as the device builder leaves it: 8 floats per node (yhh::Node has that layout byte for byte), the first node of every level
       static_assert(sizeof(yhh::Node) == 32 && offsetof(yhh::Node, start) == 24 && offsetof(yhh::Node, num) == 28 && offsetof(yhh::Node, internal) == 30 && offsetof(yhh::Node, axis) == 31,
           "yhh::Node is the device's node record");
-      {
-        std::vector<int> level(tree.nodes.size(), 0);
-        for (size_t n = 0; n < tree.nodes.size(); n++)
-          if (tree.nodes[n].internal) level[(size_t)tree.nodes[n].start] = level[(size_t)tree.nodes[n].start + 1] = level[n] + 1;
-        I.num_nodes = (int)tree.nodes.size(), I.levels = level.empty() ? 1 : level.back() + 1;  // (breadth-first numbering: levels are contiguous, the last node is on the last one)
-        if (I.levels > 128) return fail(ctx, YH_E_INVALID, "shape %d: tree of %d levels", si, I.levels);
-        for (int l = 0; l <= I.levels; l++) I.level_first[l] = I.num_nodes;
-        for (size_t n = tree.nodes.size(); n-- > 0;) I.level_first[level[n]] = (int)n;
-      }
+      I.num_nodes = (int)tree.nodes.size();
+      if (!tree_levels(tree, I.levels, I.level_first)) return fail(ctx, YH_E_INVALID, "shape %d: tree of %d levels", si, I.levels);
       if ((rc = upload(ctx, d_tree[si], tree.nodes.data(), tree.nodes.size() * 32))) return rc;
       I.root = tree.nodes[0].bbox;
       auto nrm = [&](int v) { return s.normals ? ld3(s.normals + 3 * (size_t)v) : F3{0, 0, 0}; };
@@ -300,8 +307,48 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
       }
     }
   }
+  // ---- the scene-level BVH (pt.cpp:792-814): the reference's tree over the objects' world boxes, made here because a scene too big for the
+  // kernels' LDS table has its scene level collapsed into the blob like a shape (below) ----
+  std::vector<yhh::Box> obj_boxes(sd->num_objects);
+  for (int oi = 0; oi < sd->num_objects; oi++) {
+    auto& o = sd->objects[oi];
+    if (o.shape < 0 || o.shape >= sd->num_shapes || o.material < 0 || o.material >= sd->num_materials)
+      return fail(ctx, YH_E_INVALID, "object %d references a missing shape or material", oi);
+    // transform_bbox (math.h:3174-3185)
+    const yhh::Box& b = info[o.shape].root;
+    float lo[3] = {std::numeric_limits<float>::max(), std::numeric_limits<float>::max(), std::numeric_limits<float>::max()};
+    float hi[3] = {std::numeric_limits<float>::lowest(), std::numeric_limits<float>::lowest(),
+        std::numeric_limits<float>::lowest()};
+    for (int c = 0; c < 8; c++) {
+      F3 corner = {(c & 4) ? b.max[0] : b.min[0], (c & 2) ? b.max[1] : b.min[1], (c & 1) ? b.max[2] : b.min[2]};
+      F3 t      = transform_point(o.frame, corner);
+      float tv[3] = {t.x, t.y, t.z};
+      for (int k = 0; k < 3; k++) lo[k] = fmin_(lo[k], tv[k]), hi[k] = fmax_(hi[k], tv[k]);
+    }
+    for (int k = 0; k < 3; k++) obj_boxes[oi].min[k] = lo[k], obj_boxes[oi].max[k] = hi[k];
+  }
+  yhh::Tree scene_tree;
+  yhh::build_bvh(scene_tree, obj_boxes);
+  // scene-level LDS table: objects (YH_OBJECT_F4 = 11 float4 each), scene BVH nodes (2 float4 each), primitive ids; up to 10 KB = 46
+  // objects (a scene with more runs the GENERAL kernel variants, which read the table from memory)
+  static_assert(sizeof(yhd_object) == 16 * YH_OBJECT_F4, "yhd_object is staged to LDS as float4");
+  const int  lds_scene_f4 = YH_OBJECT_F4 * sd->num_objects + 2 * (int)scene_tree.nodes.size() + (sd->num_objects + 3) / 4;
+  const bool scene_wide   = lds_scene_f4 * 16 > 10240;  // ... and walk the scene level as 4-wide nodes out of the blob (an instanced scene has thousands of objects)
+  DevBuf d_stree, d_sflag, d_sidx;
+  int    scene_wide_count = 0, scene_wide_depth = 0;
+  if (scene_wide) {
+    int levels = 1, level_first[130] = {0};
+    const int nn = (int)scene_tree.nodes.size();
+    if (!tree_levels(scene_tree, levels, level_first)) return fail(ctx, YH_E_INVALID, "scene tree of %d levels", levels);
+    if ((rc = upload(ctx, d_stree, scene_tree.nodes.data(), scene_tree.nodes.size() * 32))) return rc;
+    if ((rc = dev_alloc(ctx, d_sflag, ((size_t)nn + 1) * 4))) return rc;
+    if ((rc = dev_alloc(ctx, d_sidx, ((size_t)nn + 1) * 4))) return rc;
+    int e = yhk_wide_index(nn, (const float*)d_stree.p, levels, level_first, 2, (unsigned int*)d_sflag.p, (unsigned int*)d_sidx.p, &scene_wide_count, ctx->stream);
+    if (e) return fail(ctx, YH_E_DEVICE, "wide-node index of the scene tree: %s", hipGetErrorString((hipError_t)e));
+    scene_wide_depth = 1 + std::max(0, levels - 2) / 2;
+  }
   // ---- the wide collapses: the index of every wide node (one flag pass + one scan per width), then the layout of the ONE array the traversal
-  // kernels read (yh_device.h: lane_blob, 32-byte units): [test records of every shape][4-wide nodes][8-wide nodes][16-wide nodes] ----
+  // kernels read (yh_device.h: lane_blob, 32-byte units): [4-wide nodes of the scene tree, if any][test records of every shape][4-wide nodes][8-wide nodes][16-wide nodes] ----
   std::vector<DevBuf> d_wflag((size_t)sd->num_shapes * 3), d_widx((size_t)sd->num_shapes * 3);
   for (int si = 0; si < sd->num_shapes; si++)
     for (int w = 0; w < 3; w++) {
@@ -315,7 +362,7 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
   ctx->lane_shapes.assign((size_t)sd->num_shapes, yh_context::LaneShape{});
   long long U8 = 0, U16 = 0, blob_units = 0;
   {
-    long long at = 0;
+    long long at = 4ll * scene_wide_count;  // (in front of the test records: a scene node's offset stays below 2^27, what tells it from a scene leaf on a stack)
     for (int si = 0; si < sd->num_shapes; si++) {
       auto& L = ctx->lane_shapes[(size_t)si];
       L.kind = info[si].kind, L.num_nodes = info[si].wide_count[0], L.prim_base = info[si].prim_base, L.num_prims = info[si].num_prims;
@@ -344,16 +391,17 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
           L.kind == YH_KIND_LINES ? 1 : 0, offs[w], L.test_off, ctx->d_lane_blob.p, ctx->stream);
     if (e) return fail(ctx, YH_E_DEVICE, "wide collapse: %s", hipGetErrorString((hipError_t)e));
   }
+  if (scene_wide) {  // leaf references as of a line shape whose test records start at 0: count << 27 | first scene primitive
+    int e = yhk_wide_collapse(2, (int)scene_tree.nodes.size(), (const float*)d_stree.p, (const unsigned int*)d_sflag.p, (const unsigned int*)d_sidx.p, 1, 0, 0, ctx->d_lane_blob.p, ctx->stream);
+    if (e) return fail(ctx, YH_E_DEVICE, "wide collapse of the scene tree: %s", hipGetErrorString((hipError_t)e));
+  }
   YH_WAIT(ctx);
-  d_tree.clear(), d_wflag.clear(), d_widx.clear();
+  d_tree.clear(), d_wflag.clear(), d_widx.clear(), d_stree.reset(), d_sflag.reset(), d_sidx.reset();
   lap("device: wide collapses, blob");
-  // ---- objects and the scene-level BVH (pt.cpp:792-814) -------------------
+  // ---- objects ------------------------------------------------------------
   std::vector<yhd_object> objects(sd->num_objects);
-  std::vector<yhh::Box>   obj_boxes(sd->num_objects);
   for (int oi = 0; oi < sd->num_objects; oi++) {
     auto& o = sd->objects[oi];
-    if (o.shape < 0 || o.shape >= sd->num_shapes || o.material < 0 || o.material >= sd->num_materials)
-      return fail(ctx, YH_E_INVALID, "object %d references a missing shape or material", oi);
     auto& I = info[o.shape];
     auto& d = objects[oi];
     memcpy(d.frame, o.frame, 48);
@@ -362,19 +410,8 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
     d.elem_base = I.elem_base, d.has_normals = I.has_normals, d.material = o.material, d.has_texcoords = sd->shapes[o.shape].texcoords != nullptr;
     const auto& LS = ctx->lane_shapes[(size_t)o.shape];
     d.lane_root = (int)LS.node_off, d.lane_test = (int)LS.test_off, d.lane_root8 = (int)LS.node_off8, d.lane_root16 = (int)LS.node_off16;
-    // transform_bbox (math.h:3174-3185)
-    const yhh::Box& b = I.root;
-    float lo[3] = {std::numeric_limits<float>::max(), std::numeric_limits<float>::max(), std::numeric_limits<float>::max()};
-    float hi[3] = {std::numeric_limits<float>::lowest(), std::numeric_limits<float>::lowest(),
-        std::numeric_limits<float>::lowest()};
-    for (int c = 0; c < 8; c++) {
-      F3 corner = {(c & 4) ? b.max[0] : b.min[0], (c & 2) ? b.max[1] : b.min[1], (c & 1) ? b.max[2] : b.min[2]};
-      F3 t      = transform_point(o.frame, corner);
-      float tv[3] = {t.x, t.y, t.z};
-      for (int k = 0; k < 3; k++) lo[k] = fmin_(lo[k], tv[k]), hi[k] = fmax_(hi[k], tv[k]);
-    }
-    for (int k = 0; k < 3; k++) obj_boxes[oi].min[k] = lo[k], obj_boxes[oi].max[k] = hi[k];
-    {  // the same box with a margin a thousand times the rounding of either box test
+    {  // the object's world box with a margin a thousand times the rounding of either box test
+      const float *lo = obj_boxes[oi].min, *hi = obj_boxes[oi].max;
       float ext = fmax_(fmax_(hi[0] - lo[0], hi[1] - lo[1]), hi[2] - lo[2]);
       float eps = 1e-3f * ext + 1e-5f;
       for (int k = 0; k < 3; k++) d.wbox_min[k] = lo[k] - eps, d.wbox_max[k] = hi[k] + eps;
@@ -383,20 +420,20 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
   }
   // array offsets on the device are 32-bit float4 indices
   if (vpos.size() > (size_t)std::numeric_limits<int>::max()) return fail(ctx, YH_E_INVALID, "scene too large for 32-bit vertex offsets (%zu)", vpos.size());
-  yhh::Tree scene_tree;
-  yhh::build_bvh(scene_tree, obj_boxes);
-  std::vector<yhd_float4> scene_nodes;
+  std::vector<yhd_float4> scene_nodes;  // (binary, also of a scene walked through its wide nodes: the counted builds' yardstick)
   for (auto& n : scene_tree.nodes) scene_nodes.push_back(node_lo(n)), scene_nodes.push_back(node_hi(n));
   int max_shape_depth = 0;
   for (auto& I : info) max_shape_depth = std::max(max_shape_depth, I.depth);
-  // a wide node pushes at most three entries and keeps the fourth in a register
-  ctx->stack_need = scene_tree.max_depth + 4 + 3 * max_shape_depth + 2;
+  // a wide node pushes at most three entries and keeps the fourth in a register; the scene level: a binary node pushes one, a leaf up to three
+  // objects — or, walked as 4-wide nodes, three per node and the leaf's three (the same quad form under every launch shape)
+  const int scene_need = scene_wide ? 3 * scene_wide_depth + 4 : scene_tree.max_depth + 4;
+  ctx->stack_need = scene_need + 3 * max_shape_depth + 2;
   int max_shape_depth8 = 0;
   for (auto& I : info) max_shape_depth8 = std::max(max_shape_depth8, I.depth8);
-  ctx->stack_need8 = scene_tree.max_depth + 4 + 7 * max_shape_depth8 + 2;  // an 8-wide node pushes at most seven
+  ctx->stack_need8 = scene_need + 7 * max_shape_depth8 + 2;  // an 8-wide node pushes at most seven
   int max_shape_depth16 = 0;
   for (auto& I : info) max_shape_depth16 = std::max(max_shape_depth16, I.depth16);
-  ctx->stack_need16 = scene_tree.max_depth + 4 + 15 * max_shape_depth16 + 2;
+  ctx->stack_need16 = scene_need + 15 * max_shape_depth16 + 2;
   if (ctx->stack_need > yhk_stack_entries())
     return fail(ctx, YH_E_INVALID, "BVH too deep for the traversal stack (%d > %d)", ctx->stack_need, yhk_stack_entries());
   // ---- materials ---------------------------------------------------------
@@ -426,7 +463,8 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
     if (m.emission[0] == 0 && m.emission[1] == 0 && m.emission[2] == 0) continue;
     auto& s = sd->shapes[o.shape];
     if (s.num_lines > 0 || s.num_triangles <= 0) continue;
-    if (sc.num_lights >= YH_MAX_LIGHTS) return fail(ctx, YH_E_INVALID, "more than %d lights", YH_MAX_LIGHTS);
+    // (every object with an emissive material is a light of its own, so every frame of an instanced emitter is one: init_lights walks objects)
+    if (sc.num_lights >= YH_MAX_LIGHTS) return fail(ctx, YH_E_INVALID, "more than %d lights: object %d of %d is emissive too (each instance of an emitter counts)", YH_MAX_LIGHTS, oi, sd->num_objects);
     auto& L = sc.lights[sc.num_lights++];
     L.object = oi, L.environment = -1, L.cdf_base = (int)light_cdf.size(), L.cdf_count = s.num_triangles, L.small_base = -1;
     if (s.num_triangles <= YH_SMALL_LIGHT_TRIS) small_lights.push_back(sc.num_lights - 1);  // its record is made below, once the cdf exists
@@ -604,12 +642,8 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
   sc.num_nodes_total = 0, sc.num_prim_f4 = (int)total_prim_f4;
   for (auto& I : info) sc.num_nodes_total += I.wide_count[0];
   sc.general_materials = general_materials;
-  {  // scene-level LDS table: objects (YH_OBJECT_F4 = 11 float4 each), scene BVH nodes (2 float4 each), primitive ids; up to 10 KB = 46
-     // objects (a scene with more runs the GENERAL kernel variants, which read the table from memory)
-    static_assert(sizeof(yhd_object) == 16 * YH_OBJECT_F4, "yhd_object is staged to LDS as float4");
-    int f4 = YH_OBJECT_F4 * sd->num_objects + 2 * (int)scene_tree.nodes.size() + (sd->num_objects + 3) / 4;
-    sc.lds_scene_f4 = f4 * 16 <= 10240 ? f4 : 0;
-  }
+  sc.lds_scene_f4    = scene_wide ? 0 : lds_scene_f4;  // (made with the scene tree, above)
+  sc.scene_wide_root = scene_wide ? 0 : -1;
   {  // the material table in LDS; the plain kernel variants rely on it and on the scene-level table (dev_path.h)
     static_assert(sizeof(yhd_material) == 16 * YH_MATERIAL_F4, "yhd_material is staged to LDS as float4");
     sc.lds_materials = sd->num_materials <= 24 ? sd->num_materials : 0;
