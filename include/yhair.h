@@ -451,6 +451,18 @@ int yh_surface_bsdf_batch(yh_context* ctx, int n, const yh_material* materials,
 int yh_intersect_batch(yh_context* ctx, int n, const float* rays, int* object,
     int* element, float* uv, float* distance);
 
+/* The light code on the uploaded scene, row by row: sample_lights and
+ * sample_lights_pdf (yocto_pathtrace.cpp:1283-1358) and eval_environment
+ * (:536-547), the very functions the sample-loop kernels call, with their
+ * tables staged as a launch stages them. form 0: a quad per row as in the
+ * quad kernels (the scene's plain or general variant, as a launch picks it);
+ * form 1: a lane per row as in the streaming kernel. position, direction: 3n;
+ * rn: 4n (rl, rel, ruv.x, ruv.y); out: 8n = sampled direction[3],
+ * sample_lights_pdf at it, sample_lights_pdf at `direction`,
+ * eval_environment(direction)[3].                                            */
+int yh_lights_batch(yh_context* ctx, int form, int n, const float* position,
+    const float* direction, const float* rn, float* out);
+
 /* The four Monte-Carlo self-tests of yocto_extension.cpp:555-693 on the
  * device: 0 white_furnace, 1 white_furnace_sampled, 2 sampling_weights,
  * 3 sampling_consistency. Same seeds, counts and thresholds. `worst` (may be

@@ -1452,6 +1452,15 @@ V3 sample_lights(const yo_scene& scene, V3 position, float rl, float rel,
   }
   return {0, 0, 0};
 }
+// the texel of a textured environment that sample_lights_pdf takes a direction's probability from (pt.cpp:1338-1346)
+void env_texel(const Environment& env, V3 direction, int& i, int& j) {
+  auto wl = transform_direction(inverse(env.frame, false), direction);
+  auto tx = std::atan2(wl.z, wl.x) / (2 * pif);
+  auto ty = std::acos(fclamp(wl.y, -1.0f, 1.0f)) / pif;
+  if (tx < 0) tx += 1;
+  i = iclamp((int)(tx * env.w), 0, env.w - 1);
+  j = iclamp((int)(ty * env.h), 0, env.h - 1);
+}
 float sample_lights_pdf(const yo_scene& scene, V3 position, V3 direction) {
   auto pdf = 0.0f;  // pt.cpp:1311-1358
   for (auto& light : scene.lights) {
@@ -1476,12 +1485,8 @@ float sample_lights_pdf(const yo_scene& scene, V3 position, V3 direction) {
     } else if (light.environment >= 0) {
       auto& env = scene.environments[light.environment];
       if (!env.texels.empty()) {
-        auto wl = transform_direction(inverse(env.frame, false), direction);
-        auto tx = std::atan2(wl.z, wl.x) / (2 * pif);
-        auto ty = std::acos(fclamp(wl.y, -1.0f, 1.0f)) / pif;
-        if (tx < 0) tx += 1;
-        auto i    = iclamp((int)(tx * env.w), 0, env.w - 1);
-        auto j    = iclamp((int)(ty * env.h), 0, env.h - 1);
+        int i, j;
+        env_texel(env, direction, i, j);
         auto prob = sample_discrete_cdf_pdf(light.cdf, j * env.w + i) / light.cdf.back();
         auto angle = (2 * pif / env.w) * (pif / env.h) *
                      std::sin(pif * (j + 0.5f) / env.h);
@@ -2278,6 +2283,41 @@ void yo_scene_intersect(const yo_scene* scene, int n, const float* rays, int* ob
     auto  hit = intersect_scene_bvh(*scene, mkray(rays + 8 * i), o, e, u, d);
     object[i] = hit ? o : -1, element[i] = hit ? e : -1;
     uv[2 * i] = u[0], uv[2 * i + 1] = u[1], dist[i] = d;
+  }
+}
+
+// what init_lights made of light `light`: object, environment, and its cdf (returns the cdf's length; -1: no such light)
+int yo_scene_light(const yo_scene* scene, int light, int* object, int* environment, float* cdf) {
+  if (light < 0 || light >= (int)scene->lights.size()) return -1;
+  auto& l = scene->lights[(size_t)light];
+  if (object) *object = l.object;
+  if (environment) *environment = l.environment;
+  if (cdf && !l.cdf.empty()) std::memcpy(cdf, l.cdf.data(), sizeof(float) * l.cdf.size());
+  return (int)l.cdf.size();
+}
+// sample_lights, sample_lights_pdf and eval_environment as the renderer below calls them, row by row
+void yo_scene_lights_batch(const yo_scene* scene, int n, const float* position, const float* direction,
+    const float* rn, float* out, int* texel) {
+  for (int i = 0; i < n; i++) {
+    V3 p = v3(position + 3 * (size_t)i), d = v3(direction + 3 * (size_t)i);
+    const float* r = rn + 4 * (size_t)i;
+    V3     w = sample_lights(*scene, p, r[0], r[1], r[2], r[3]);
+    V3     e = eval_environment(*scene, d);
+    float* o = out + 8 * (size_t)i;
+    o[0] = w.x, o[1] = w.y, o[2] = w.z;
+    o[3] = sample_lights_pdf(*scene, p, w), o[4] = sample_lights_pdf(*scene, p, d);
+    o[5] = e.x, o[6] = e.y, o[7] = e.z;
+    if (texel) {
+      int k = 0;
+      for (auto& light : scene->lights) {
+        if (light.environment < 0 || scene->environments[light.environment].texels.empty() || k >= 4) continue;
+        auto& env = scene->environments[light.environment];
+        int   a, b;
+        env_texel(env, d, a, b);
+        texel[4 * (size_t)i + k++] = b * env.w + a;
+      }
+      for (; k < 4; k++) texel[4 * (size_t)i + k] = -1;
+    }
   }
 }
 

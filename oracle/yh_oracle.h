@@ -75,6 +75,17 @@ int       yo_scene_num_lights(const yo_scene* scene);
 /* pt.cpp:1039-1046; element/object -1 on miss */
 void yo_scene_intersect(const yo_scene* scene, int n, const float* rays,
     int* object, int* element, float* uv, float* dist);
+/* Light `light` as init_lights (pt.cpp:1695-1740) made it: its object and environment (-1: none) and its
+ * cdf (triangle areas or texel weights, accumulated); returns the cdf's length, -1 when there is no such
+ * light. Every pointer may be NULL.                                                                      */
+int yo_scene_light(const yo_scene* scene, int light, int* object, int* environment, float* cdf);
+/* The light code as yo_render calls it (pt.cpp:536-547, 1283-1358), row by row, the counterpart of
+ * yh_lights_batch: position 3n, direction 3n, rn 4n (rl, rel, ruv.x, ruv.y); out 8n = sample_lights
+ * direction[3], sample_lights_pdf at it, sample_lights_pdf at `direction`, eval_environment(direction)[3].
+ * texel (4n, may be NULL): for each textured environment light, in light order, the texel index
+ * sample_lights_pdf reads for `direction` (-1 where there is none).                                       */
+void yo_scene_lights_batch(const yo_scene* scene, int n, const float* position, const float* direction,
+    const float* rn, float* out, int* texel);
 void yo_scene_intersect_counted(const yo_scene* scene, int n, const float* rays, int* nodes, int* prims);
 /* BVH export for structural checks: returns node count of shape `shape`
  * (-1 = scene-level BVH); fills nodes (8 floats: bbox min/max, then start,

@@ -138,6 +138,8 @@ class Oracle(_UnitApi):
         lib.yo_scene_num_lights.argtypes = [C.c_void_p]
         lib.yo_scene_intersect.argtypes = [C.c_void_p, C.c_int, fp, ip, ip, fp, fp]
         lib.yo_scene_intersect_counted.argtypes = [C.c_void_p, C.c_int, fp, ip, ip]
+        lib.yo_scene_light.argtypes = [C.c_void_p, C.c_int, ip, ip, fp]
+        lib.yo_scene_lights_batch.argtypes = [C.c_void_p, C.c_int, fp, fp, fp, fp, ip]
         lib.yo_scene_bvh.argtypes = [C.c_void_p, C.c_int, fp, ip]
         lib.yo_render.argtypes = [C.c_void_p, C.POINTER(yh.TraceParams), C.c_int, C.c_int, ip, ip, fp, u64p,
                                   C.POINTER(yh.WorkCounts)]
@@ -182,6 +184,27 @@ class OracleScene:
         uv, dist = np.zeros((n, 2), np.float32), np.zeros(n, np.float32)
         self.o.lib.yo_scene_intersect(self.h, n, yh.fptr(rays), yh.iptr(obj), yh.iptr(elem), yh.fptr(uv), yh.fptr(dist))
         return obj, elem, uv, dist
+
+    def light(self, k):
+        """Light k as init_lights made it: (object, environment, cdf)."""
+        obj, env = C.c_int(), C.c_int()
+        n = self.o.lib.yo_scene_light(self.h, k, C.byref(obj), C.byref(env), None)
+        if n < 0:
+            raise IndexError(k)
+        cdf = np.zeros(n, np.float32)
+        self.o.lib.yo_scene_light(self.h, k, None, None, yh.fptr(cdf) if n else None)
+        return obj.value, env.value, cdf
+
+    def lights(self, position, direction, rn4, want_texels=False):
+        """sample_lights, sample_lights_pdf and eval_environment as the oracle's renderer calls them: (n, 8) = sampled
+        direction [3], pdf at it, pdf at `direction`, eval_environment(direction) [3]; with want_texels also (n, 4) int:
+        the texel of each textured environment light that the pdf at `direction` reads (-1: no such light)."""
+        position, direction, rn4 = _f(position).reshape(-1, 3), _f(direction).reshape(-1, 3), _f(rn4).reshape(-1, 4)
+        n = len(position)
+        out, tex = np.zeros((n, 8), np.float32), np.full((n, 4), -1, np.int32)
+        self.o.lib.yo_scene_lights_batch(self.h, n, yh.fptr(position), yh.fptr(direction), yh.fptr(rn4), yh.fptr(out),
+                                         yh.iptr(tex) if want_texels else None)
+        return (out, tex) if want_texels else out
 
     def intersect_counted(self, rays):
         rays = _f(rays).reshape(-1, 8)

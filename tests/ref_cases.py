@@ -25,6 +25,13 @@ IMAGE_CASES = [
     ("sphere-hairblock", dict(scale=0.1, dof=True), 120, 4),
     ("textured", dict(scale=0.1), 160, 8),
     ("crowd", dict(scale=0.1), 128, 4),
+    # the light and environment tables at their edges (tools/make_scenes.py: make_envs_unit)
+    ("envs-unit", dict(scale=0.05, variant="rot"), 80, 4),
+    ("envs-unit", dict(scale=0.05, variant="lookat"), 80, 4),
+    ("envs-unit", dict(scale=0.05, variant="multi"), 96, 4),
+    ("envs-unit", dict(scale=0.05, variant="tex-65x64"), 72, 4),
+    ("envs-unit", dict(scale=0.05, variant="tex-16x8"), 64, 4),
+    ("envs-unit", dict(scale=0.05, variant="lights-4"), 80, 4),
 ]
 SHADERS = ["naive", "eyelight", "normal"]
 SHADER_CASES = [

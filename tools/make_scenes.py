@@ -743,8 +743,107 @@ def make_lights_unit(outdir, scale=1.0, name="lights-unit", biglight=False):
     return os.path.join(d, name + ".json"), 0
 
 
+def rotation_frame(axis, degrees):
+    """A frame (x, y, z axes, origin 0) that rotates about `axis` by `degrees`, as float32-exact JSON numbers."""
+    a = np.asarray(axis, np.float64) / np.linalg.norm(axis)
+    t = np.radians(degrees)
+    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
+    R = np.eye(3) + np.sin(t) * K + (1 - np.cos(t)) * (K @ K)
+    return [float(np.float32(v)) for v in R.T.reshape(-1)] + [0.0, 0.0, 0.0]
+
+
+ENV_ROT = rotation_frame((1, 2, 3), 40)       # the sky of envs-unit
+ENV_ROT_SMALL = rotation_frame((3, -1, 2), 110)  # its small png environments
+ENV_LOOKAT = [1.0, 2.0, 3.0, 0.0, 0.5, -1.0, 0.0, 1.0, 0.0]
+
+
+def _write_env_png(path, w, h, seed=23):
+    """An 8-bit RGB environment map: seeded noise, its top third black (a flat stretch at the head of the texel cdf)
+    and one texel at 255."""
+    rng = np.random.default_rng(seed + 1000 * w + h)
+    img = rng.integers(20, 120, (h, w, 3), dtype=np.uint8)
+    img[: h // 3] = 0
+    img[h - 1 - h // 4, (2 * w) // 3] = 255
+    write_png(path, img)
+
+
+def _write_fan_light(path, n, degenerate=False):
+    """A fan of n triangles of different areas around the origin in the XY plane (z = 0, facing +z), without normals;
+    degenerate: two rim vertices coincide, so one triangle has no area (a tie in the light's area cdf)."""
+    rim = []
+    for k in range(n + 1):
+        th, r = 0.3 + k * 4.4 / n, 1.0 + 0.35 * ((5 * k) % 3)
+        rim.append((r * np.cos(th), r * np.sin(th), 0.0))
+    if degenerate:
+        rim[2] = rim[1]
+    with open(path, "w") as f:
+        f.write(f"ply\nformat ascii 1.0\nelement vertex {n + 2}\nproperty float x\nproperty float y\nproperty float z\n"
+                f"element face {n}\nproperty list uchar int vertex_indices\nend_header\n")
+        for v in [(0.0, 0.0, 0.0)] + rim:
+            f.write(f"{v[0]:.9g} {v[1]:.9g} {v[2]:.9g}\n")
+        for k in range(n):
+            f.write(f"3 0 {k + 1} {k + 2}\n")
+
+
+def make_envs_unit(outdir, scale=1.0, name="envs-unit", variant="rot"):
+    """The light and environment tables at their edges, on the diffuse-only stage of make_lights_unit (no hair: paths follow
+    the oracle draw for draw). `variant`:
+      rot        sky.hdr in a frame rotated about (1, 2, 3) by 40 degrees
+      lookat     the same texture placed with "lookat" (next to a "frame" that it overrides)
+      multi      four environments in name order: constant | textured with emission 0 (no light) | rotated sky.hdr | rotated 67x63 png
+      tex-WxH    one rotated W x H png environment (_write_env_png)
+      lights-N   ONE emitter, a fan of N triangles in an object frame with non-uniform scale, under a constant sky; N = 4 has
+                 a triangle without area"""
+    d = _prep(outdir, name)
+    shutil.copy(os.path.join(ASSETS, "sphere.ply"), os.path.join(d, "shapes", "sphere.ply"))
+    shutil.copy(os.path.join(ASSETS, "arealight.ply"), os.path.join(d, "shapes", "arealight.ply"))
+    objects = {
+        "floor": {"frame": [3, 0, 0, 0, 0, -3, 0, 3, 0, 0.0, 0, 0], "shape": "arealight", "material": "floor"},
+        "ball0": {"frame": [1, 0, 0, 0, 1, 0, 0, 0, 1, -0.7, 0.0, 0.2], "shape": "sphere", "material": "red"},
+        "ball1": {"frame": [0.6, 0, 0, 0, 0.6, 0, 0, 0, 0.6, 0.8, 0.0, 0.6], "shape": "sphere", "material": "white"},
+    }
+    materials = {"floor": {"color": [0.7, 0.7, 0.7]}, "red": {"color": [0.8, 0.2, 0.2]}, "white": {"color": [0.9, 0.9, 0.9]},
+                 "arealight": {"emission": [10, 10, 10]}, "arealight2": {"emission": [30, 25, 20]}}
+    sky = lambda: shutil.copy(os.path.join(ASSETS, "sky.hdr"), os.path.join(d, "textures", "sky.hdr"))  # noqa: E731
+    if variant.startswith("lights-"):
+        n = int(variant[7:])
+        _write_fan_light(os.path.join(d, "shapes", "fanlight.ply"), n, degenerate=(n == 4))
+        objects["light1"] = {"frame": [1.5, 0, 0, 0, 0, 0.7, 0, -1.2, 0, 0.2, 3.0, 0.5], "shape": "fanlight", "material": "arealight"}
+        envs = {"sky": {"emission": [0.5, 0.5, 0.5]}}
+    else:
+        objects["light1"] = {"lookat": [0.5, 4, 1.5, 0.0, 0.5, 0, 0, 1, 0], "shape": "arealight", "material": "arealight"}
+        objects["light2"] = {"lookat": [1.0, 8, 3.0, 0.0, 0.5, 0, 0, 1, 0], "shape": "arealight", "material": "arealight2"}
+        if variant == "rot":
+            sky()
+            envs = {"sky": {"emission": [1.5, 1.5, 1.5], "emission_tex": "sky", "frame": ENV_ROT}}
+        elif variant == "lookat":
+            sky()
+            envs = {"sky": {"emission": [1.5, 1.5, 1.5], "emission_tex": "sky", "frame": ENV_ROT, "lookat": ENV_LOOKAT}}
+        elif variant == "multi":
+            sky()
+            _write_env_png(os.path.join(d, "textures", "small.png"), 67, 63)
+            envs = {"a-constant": {"emission": [0.3, 0.4, 0.5]},
+                    "b-black": {"emission": [0, 0, 0], "emission_tex": "small", "frame": ENV_ROT_SMALL},
+                    "c-sky": {"emission": [1.5, 1.5, 1.5], "emission_tex": "sky", "frame": ENV_ROT},
+                    "d-small": {"emission": [2, 2, 2], "emission_tex": "small", "frame": ENV_ROT_SMALL}}
+        elif variant.startswith("tex-"):
+            w, h = (int(v) for v in variant[4:].split("x"))
+            _write_env_png(os.path.join(d, "textures", "small.png"), w, h)
+            envs = {"sky": {"emission": [2, 2, 2], "emission_tex": "small", "frame": ENV_ROT_SMALL}}
+        else:
+            raise ValueError(f"envs-unit: unknown variant {variant!r}")
+    scene = {
+        "asset": {"copyright": "synthetic; sphere, quad and sky.hdr from the reference's test assets"},
+        "cameras": {"default": {"lens": 0.05, "aperture": 0.0, "aspect": 1.0, "lookat": [0.0, 2.4, 5.5, 0.0, 0.5, 0, 0, 1, 0]}},
+        "environments": envs, "objects": objects, "materials": materials,
+    }
+    _dump(scene, os.path.join(d, name + ".json"))
+    return os.path.join(d, name + ".json"), 0
+
+
 MAKERS = {
     "lights-unit": make_lights_unit,
+    "envs-unit": make_envs_unit,
     "sphere-hairblock": make_sphere_hairblock,
     "straight-hair": make_straight_hair,
     "curly-hair": make_curly_hair,

@@ -270,6 +270,30 @@ int yh_intersect_batch(yh_context* ctx, int n, const float* rays, int* object, i
   return YH_OK;
 }
 
+int yh_lights_batch(yh_context* ctx, int form, int n, const float* position, const float* direction, const float* rn, float* out) {
+  if (!ctx || n < 0 || (form != 0 && form != 1) || (n && (!position || !direction || !rn || !out))) return YH_E_INVALID;
+  if (!ctx->have_scene) return fail(ctx, YH_E_STATE, "yh_lights_batch before yh_upload_scene");
+  if (n == 0) return YH_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  Staged s(ctx);
+  auto   dp = (float*)s.in(position, 12 * (size_t)n);
+  auto   dd = (float*)s.in(direction, 12 * (size_t)n);
+  auto   dr = (float*)s.in(rn, 16 * (size_t)n);
+  auto   o  = (float*)s.out(32 * (size_t)n);
+  if (s.rc) return s.rc;
+  if (form == 0) return finish(ctx, yhk_lights(&ctx->scene, n, dp, dd, dr, o, ctx->stream), out, o, 32 * (size_t)n);
+  if (!lane_kernels_can_address(ctx))
+    return fail(ctx, YH_E_INVALID, "yh_lights_batch: the one-lane form reads the scene's trees through 32-bit byte offsets and this scene's exceed 4 GB");
+  const int ovf_entries = 2 * std::max(8, ctx->stack_need);  // (as yh_intersect_batch sizes it)
+  auto      dovf        = (unsigned int*)s.out((size_t)((n + 255) / 256) * 4 * ovf_entries * 64 * 4);
+  if (s.rc) return s.rc;
+  if (!ctx->d_scene_copy.p) {
+    int rc = upload(ctx, ctx->d_scene_copy, &ctx->scene, sizeof(yhd_scene));
+    if (rc) return rc;
+  }
+  return finish(ctx, yhk_lights_lanes(&ctx->scene, (const yhd_scene*)ctx->d_scene_copy.p, n, dp, dd, dr, dovf, ovf_entries, o, ctx->stream), out, o, 32 * (size_t)n);
+}
+
 // ---- the four self-tests (ext.cpp:555-693) ---------------------------------
 // The host replays the reference's serial structure (seed, loop bounds with
 // the accumulating float counters, per-block draw counts) and hands every

@@ -77,6 +77,9 @@ int yhk_wide_collapse(int L, int num_nodes, const float* d_nodes, const unsigned
 int yhk_curves_to_lines(int, const float*, const float*, const float*, int, float*, float*, float*, int*, hipStream_t);
 int yhk_surface_lobe(int, int, const float*, const float*, const float*, const float*, const float*, float*, hipStream_t);
 int yhk_surface_bsdf(int, const void*, const float*, const float*, const float*, const float*, float*, hipStream_t);
+int yhk_lights(const yhd_scene*, int, const float*, const float*, const float*, float*, hipStream_t);
+int yhk_lights_lanes(const yhd_scene* sc, const yhd_scene* sc_dev, int n, const float* position, const float* direction, const float* rn,
+    unsigned int* stack_ovf, int ovf_entries, float* out, hipStream_t stream);
 int yhk_selftest(int, float, float, uint64_t, uint64_t, int, const float*, double*, unsigned int*, hipStream_t);
 }
 

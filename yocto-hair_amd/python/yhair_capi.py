@@ -177,6 +177,7 @@ _SIGS = {
     "yh_hair_pdf_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),
     "yh_hair_eval_pdf_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),
     "yh_intersect_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_int_p, c_int_p, c_float_p, c_float_p]),
+    "yh_lights_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),
     "yh_selftest": (C.c_int, [C.c_void_p, C.c_int, c_float_p]),
     "yh_scene_load": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]),
     "yh_scene_get": (C.POINTER(SceneDesc), [C.c_void_p]),
@@ -440,6 +441,15 @@ class Context:
         uv, dist = np.zeros((n, 2), np.float32), np.zeros(n, np.float32)
         self._chk(self.lib.yh_intersect_batch(self.h, n, fptr(rays), iptr(obj), iptr(elem), fptr(uv), fptr(dist)))
         return obj, elem, uv, dist
+
+    def lights(self, form, position, direction, rn4):
+        """yh_lights_batch on the uploaded scene (form 0: a quad per row, 1: a lane per row): (n, 8) = sample_lights
+        direction [3], sample_lights_pdf at it, sample_lights_pdf at `direction`, eval_environment(direction) [3]."""
+        a = [np.ascontiguousarray(x, np.float32) for x in (position, direction, rn4)]
+        n = len(a[0])
+        out = np.zeros((n, 8), np.float32)
+        self._chk(self.lib.yh_lights_batch(self.h, form, n, *(fptr(x) for x in a), fptr(out)))
+        return out
 
     def selftest(self, which):
         worst = C.c_float()
