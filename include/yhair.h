@@ -450,6 +450,21 @@ int yh_surface_bsdf_batch(yh_context* ctx, int n, const yh_material* materials,
  * (-1 on miss), uv[2], distance.                                             */
 int yh_intersect_batch(yh_context* ctx, int n, const float* rays, int* object,
     int* element, float* uv, float* distance);
+/* intersect_scene_bvh (yocto_pathtrace.cpp:934-1046) through the traversal of
+ * the PLAIN 512-thread sample-loop kernels, with the scene-level table staged
+ * in LDS as a launch stages it and in the form a launch on this scene takes
+ * (the scene level resolved once per ray where it is one leaf node). form 0:
+ * a quad per ray over 4-wide nodes (launch shape 0, the quad half of shape
+ * 5); form 1: an octet per ray over 8-wide nodes (the octet half of shape 5).
+ * Arguments and results as yh_intersect_batch. YH_E_INVALID for a scene that
+ * renders with the GENERAL kernel variants.                                  */
+int yh_intersect_plain_batch(yh_context* ctx, int form, int n, const float* rays,
+    int* object, int* element, float* uv, float* distance);
+/* Whether the plain 512-thread kernels resolve the uploaded scene's scene
+ * level once per ray, ahead of the traversal loop (a scene level of ONE leaf
+ * node: at most four objects): the number of objects, else 0; YH_E_STATE
+ * before yh_upload_scene.                                                    */
+int yh_scene_once(const yh_context* ctx);
 
 /* The light code on the uploaded scene, row by row: sample_lights and
  * sample_lights_pdf (yocto_pathtrace.cpp:1283-1358) and eval_environment

@@ -841,7 +841,55 @@ def make_envs_unit(outdir, scale=1.0, name="envs-unit", variant="rot"):
     return os.path.join(d, name + ".json"), 0
 
 
+SCENE_ONCE_VARIANTS = ("one", "disjoint", "overlap", "tie", "full", "five")
+
+
+def make_scene_once(outdir, scale=1.0, name="scene-once", variant="disjoint"):
+    """Small scenes for the scene level of the plain kernels (csrc/dev_trace.h: the scene level resolved once per ray): the
+    hair block of sphere-hairblock at 256 strands with
+      one       nothing else;
+      disjoint  the sphere beside it (sphere-hairblock's layout);
+      overlap   the block pushed into the sphere, whose frame is sheared and scaled differently along each axis (non-rigid);
+      tie       two COINCIDENT quads of two objects cutting through the block (every hit on them is an exact-t tie);
+      full      the sphere and two small area lights: four objects, a full leaf of the scene tree;
+      five      those and a floor quad: five objects, a scene tree of more than one node.
+    No material has a lobe beyond diffuse / hair and every light is a small one: the plain kernel variants render them."""
+    assert variant in SCENE_ONCE_VARIANTS, variant
+    d = _prep(outdir, name)
+    for a in ("sphere", "arealight"):
+        shutil.copy(os.path.join(ASSETS, a + ".ply"), os.path.join(d, "shapes", a + ".ply"))
+    nseg = write_hair_ply(os.path.join(d, "shapes", "hair-block.ply"), gen_hair_block(max(64, min(512, int(256 * scale)))), 0.004, 0.001)
+    hair_frame = [1, 0, 0, 0, 0, 1, 0, -1, 0, 0.5, 1, -0.5]
+    sphere_frame = [1, 0, 0, 0, 1, 0, 0, 0, 1, -0.5, 0, 0]
+    if variant == "overlap":
+        hair_frame = [1, 0, 0, 0, 0, 1, 0, -1, 0, -0.3, 0.8, -0.5]
+        sphere_frame = [1.3, 0, 0, 0, 0.7, 0, 0.2, 0, 1.1, -0.5, 0, 0]
+    objects = {"hairblock": {"frame": hair_frame, "shape": "hair-block", "material": "hair"}}
+    if variant in ("disjoint", "overlap", "full", "five"):
+        objects["sphere"] = {"frame": sphere_frame, "shape": "sphere", "material": "diffuse"}
+    quad = [0.25, 0, 0, 0, 0, -0.25, 0, 0.25, 0, 0.4, 0.4, -0.5]  # the 4 x 4 quad as a unit square facing +y, inside the block
+    if variant == "tie":
+        objects["quad-a"] = {"frame": quad, "shape": "arealight", "material": "floor"}
+        objects["quad-b"] = {"frame": quad, "shape": "arealight", "material": "floor2"}
+    if variant in ("full", "five"):
+        objects["light1"] = {"lookat": [0.5, 4, 1.5, 0.0, 0.5, 0, 0, 1, 0], "shape": "arealight", "material": "arealight"}
+        objects["light2"] = {"lookat": [1.0, 8, 3.0, 0.0, 0.5, 0, 0, 1, 0], "shape": "arealight", "material": "arealight2"}
+    if variant == "five":
+        objects["floor"] = {"frame": [1, 0, 0, 0, 0, -1, 0, 1, 0, 0.0, -1.2, 0], "shape": "arealight", "material": "floor"}
+    scene = {
+        "asset": {"copyright": "synthetic hair block; sphere and quad from the reference's test assets"},
+        "cameras": {"default": {"lens": 0.05, "aperture": 0.0, "aspect": 1.0, "lookat": [-0.5, 1.5, 5, 0.25, 0.5, 0, 0, 1, 0]}},
+        "environments": {"sky": {"emission": [1, 1, 1]}},
+        "objects": objects,
+        "materials": {"diffuse": {"color": [0.8, 0.4, 0.05]}, "hair": {"eumelanin": 1.3}, "floor": {"color": [0.7, 0.7, 0.7]},
+                      "floor2": {"color": [0.2, 0.3, 0.8]}, "arealight": {"emission": [10, 10, 10]}, "arealight2": {"emission": [30, 25, 20]}},
+    }
+    _dump(scene, os.path.join(d, name + ".json"))
+    return os.path.join(d, name + ".json"), nseg
+
+
 MAKERS = {
+    "scene-once": make_scene_once,
     "lights-unit": make_lights_unit,
     "envs-unit": make_envs_unit,
     "sphere-hairblock": make_sphere_hairblock,

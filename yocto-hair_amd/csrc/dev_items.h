@@ -37,14 +37,16 @@ using namespace yhd;
 // 4x4 block) — half the paths per wave, twice the waves, for launches bound by the chain of one path.
 // `block`, `blocks`: this workgroup's index among the workgroups that share `st`'s work list, and their number (the whole grid,
 // except in k_trace_sbs, where two lists share one launch).
-template <bool COUNT, bool GENERAL, int BLOCK, int SHADER, int MODE = YH_MODE_QUAD>
+// ONCE (dev_trace.h: trace_ray_loop): the scene level resolved once per ray ahead of the traversal loop, for a scene whose scene
+// level is one leaf node (yhd_scene::scene_once, set at upload): the host selects these variants, nothing in the loop asks.
+template <bool COUNT, bool GENERAL, int BLOCK, int SHADER, int MODE = YH_MODE_QUAD, bool ONCE = false>
 YH_DEV void trace_items(const yhd_scene& sc, const yhd_state& st, int nsamples, yhd_counters* counters, unsigned int block = blockIdx.x,
     unsigned int blocks = gridDim.x) {
   constexpr int LPP    = YH_IS_HEX(MODE) ? 16 : YH_IS_OCT(MODE) ? 8 : 4;  // lanes per path
   constexpr int GROUPS = BLOCK / LPP;                   // paths per block = columns of the LDS stack
   extern __shared__ v4f lds_dyn[];
   // LDS carve-out: [stacks: stack entries x GROUPS uint][tables: scene level | camera | small area lights | environment cdf index | materials]
-  // (dev_trace.h: stage_tables)
+  // (dev_trace.h: stage_tables)[ONCE: the per-object ray records, 4 float4 x GROUPS per object of the scene (YHD_ONCE_F4)]
   YH_LDS unsigned int* lds_stack = (YH_LDS unsigned int*)lds_dyn;
   YH_LDS v4f*          lds_tabs  = (YH_LDS v4f*)(lds_stack + ((MODE == YH_MODE_QUAD ? sc.stack_entries : YH_IS_HEX(MODE) ? sc.stack_entries16 : sc.stack_entries8) + YH_HITROWS) * GROUPS);
   trace_ctx tc;
@@ -55,6 +57,7 @@ YH_DEV void trace_items(const yhd_scene& sc, const yhd_state& st, int nsamples, 
   __syncthreads();
 
   tc.lds_stack = lds_stack + (threadIdx.x / LPP);
+  tc.lds_once  = ONCE ? lds_tabs + YHD_LDS_TABLES_F4(&sc) + (threadIdx.x / LPP) : nullptr;
   stats_t stats = {};
   tc.stats = COUNT ? &stats : nullptr;
 
@@ -112,7 +115,7 @@ YH_DEV void trace_items(const yhd_scene& sc, const yhd_state& st, int nsamples, 
       hit_t isec;
       if (alive) {
         if (COUNT) count_quad<COUNT>(stats.rays);
-        isec = trace_ray<COUNT, GROUPS, !GENERAL, MODE>(tc, ps.ray, -1, &steps);
+        isec = trace_ray<COUNT, GROUPS, !GENERAL, MODE, ONCE>(tc, ps.ray, -1, &steps);
       }
       if (COUNT) {
         c1 = clock64(), cyc_trace += c1 - c0;
@@ -177,27 +180,28 @@ YH_DEV void trace_items(const yhd_scene& sc, const yhd_state& st, int nsamples, 
 // ---------------------------------------------------------------------------
 typedef void (*trace_kernel_t)(const yhd_scene, const yhd_state, int, yhd_counters*);
 #define YH_OCT_BLOCK 256 /* workgroup of the wide forms (launch shapes 4, 6, 7, 8) */
-template <bool COUNT, bool GENERAL, int BLOCK, int WAVES, int MODE = YH_MODE_QUAD>
+template <bool COUNT, bool GENERAL, int BLOCK, int WAVES, int MODE = YH_MODE_QUAD, bool ONCE = false>
 __global__ __launch_bounds__(BLOCK, WAVES) void k_trace(const yhd_scene sc, const yhd_state st,
     int nsamples, yhd_counters* counters) {
-  trace_items<COUNT, GENERAL, BLOCK, YH_SHADER_PATH, MODE>(sc, st, nsamples, counters);
+  static_assert(!ONCE || !GENERAL, "the prologue form exists for the plain variants");
+  trace_items<COUNT, GENERAL, BLOCK, YH_SHADER_PATH, MODE, ONCE>(sc, st, nsamples, counters);
 }
 // SIDE BY SIDE in one launch (launch shape 5): the first `oct_blocks` workgroups run the octet form over the second part of
 // the work list (`oct_entries` half-quadrant entries behind the `quad_items` quad entries, its own cursor), the others the
 // quad form over the first part. The first workgroups of a launch get the fastest wave slots of their CUs (dev_items.h), so
 // the few items whose chain bounds the launch run with eight lanes per path AND in the best slots; same workgroup size, so
 // the two forms pack on a CU like one kernel's workgroups.
-template <bool GENERAL>
+template <bool GENERAL, bool ONCE = false>
 __global__ __launch_bounds__(YH_BLOCK, YH_MIN_WAVES) void k_trace_sbs(const yhd_scene sc, const yhd_state st, int nsamples, int oct_blocks,
     int quad_items, int oct_entries) {
   if ((int)blockIdx.x < oct_blocks) {
     yhd_state so   = st;
     so.tiles       = st.tiles + quad_items, so.num_tiles = oct_entries, so.tile_cursor = st.tile_cursor + 16;
-    trace_items<false, GENERAL, YH_BLOCK, YH_SHADER_PATH, YH_MODE_OCT>(sc, so, nsamples, nullptr, blockIdx.x, (unsigned)oct_blocks);
+    trace_items<false, GENERAL, YH_BLOCK, YH_SHADER_PATH, YH_MODE_OCT, ONCE>(sc, so, nsamples, nullptr, blockIdx.x, (unsigned)oct_blocks);
   } else {
     yhd_state sq = st;
     sq.num_tiles = quad_items;
-    trace_items<false, GENERAL, YH_BLOCK, YH_SHADER_PATH, YH_MODE_QUAD>(sc, sq, nsamples, nullptr, blockIdx.x - (unsigned)oct_blocks, gridDim.x - (unsigned)oct_blocks);
+    trace_items<false, GENERAL, YH_BLOCK, YH_SHADER_PATH, YH_MODE_QUAD, ONCE>(sc, sq, nsamples, nullptr, blockIdx.x - (unsigned)oct_blocks, gridDim.x - (unsigned)oct_blocks);
   }
 }
 #endif

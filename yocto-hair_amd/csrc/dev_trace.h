@@ -211,6 +211,7 @@ struct trace_ctx {
   lane_stack*           ls;         // one lane per path (YH_LANE, dev_lane.h): this lane's stack, else unused
   const yhd_scene*      sc_dev;     // YH_LANE: a copy of *sc in device memory, for out-of-line callees (the kernel
                                     // argument itself must not have its address escape: it would be copied to scratch)
+  YH_LDS v4f*           lds_once;   // ONCE (trace_ray_loop): this path's column of the per-object ray records, else unused
 };
 // Stages the tables every kernel keeps in LDS — the scene level (objects, scene BVH nodes and primitives; when it
 // fits), the camera, the small area lights and the environment cdf index — at `at` (YHD_LDS_TABLES_F4 float4) and
@@ -320,7 +321,17 @@ YH_DEV void count_quad(unsigned int& slot) {
                           on the stack); the merge keeps the reference's order. C1 at 180^2 +5-8 %, hair-curls at 320^2 1.47 x over YH_MODE_HEX, `textured` equal
                           (profiles/r03/hex_leaf_groups_ab.txt). Its own launch shape (8), the trials decide */
 #define YH_IS_HEX(MODE) ((MODE) == YH_MODE_HEX || (MODE) == YH_MODE_HEXP)
-template <bool COUNT, int STRIDE, bool EXACT, bool LDS_SCENE = false, int MODE = YH_MODE_QUAD>
+// ONCE (with LDS_SCENE, EXACT = false; the host selects it for a scene whose scene level is ONE leaf node, yhd_scene::scene_once):
+// the scene level is resolved once per ray, ahead of the loop. The scene node's box test, the padded-box slabs of each of the
+// leaf's (at most four) objects and the ENTER arithmetic of every object whose box passes at the ray's first `tmax` — pure
+// functions of (ray, object) — run in a prologue with all live quads of the wave together, instead of in whichever trips the
+// quads reach them, and leave one record per (path, object) in LDS:
+//   rows of STRIDE float4, row 4 k + r of the path's column:  {lo, t0} {ld, far} {1 / ld, dot(ld, ld)} {sign bits, kind, root, object}
+// Popping an ENTER entry culls with the CURRENT `tmax` from t0 and far alone, goes on to the next entry in the same trip when the
+// cull fails, and otherwise loads the record and fetches the shape's root; the loop has no scene-node branch and the world ray is
+// dead in it. A ray that would put a NaN into a slab takes the second pass, which keeps the in-loop scene level (ONCE = false): the
+// compare-and-select form's NaN semantics depend on operand order, so nothing precomputed is carried over to it.
+template <bool COUNT, int STRIDE, bool EXACT, bool LDS_SCENE = false, int MODE = YH_MODE_QUAD, bool ONCE = false>
 YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_object, unsigned int* steps_out, bool& redo) {
   const yhd_scene&     sc   = *tc.sc;
   const unsigned int   q    = __lane_id() & 3u;
@@ -363,8 +374,48 @@ YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_obj
     if (in_lds) return ((const YH_LDS int*)(lds_snodes + 2 * sc.num_scene_nodes))[i];
     return sc.scene_prims[i];
   };
+  static_assert(!ONCE || (LDS_SCENE && !EXACT), "the prologue form reads the scene level from LDS and leaves NaN slabs to the second pass");
   unsigned int cur;
-  if (first_object >= 0) {
+  if constexpr (ONCE) {
+    // THE PROLOGUE (first_object is -1: the sample loop's main rays). The scene's one node, counted and tested as the loop does
+    // (pt.cpp:1005-1023), then its objects from the last to the first, so that the entries behind the first survivor lie on the
+    // stack in reverse order, as the scene leaf pushes them.
+    cur = YH_NONE;
+    const v4f n0 = lds_snodes[0], n1 = lds_snodes[1];
+    if (q == 0) n_nodes++;
+    if (COUNT) count_branch<COUNT>(tc.stats->t_scene, tc.stats->l_scene);
+    if (COUNT) count_branch<COUNT>(tc.stats->t_enter, tc.stats->l_enter);  // (the prologue: one ENTER pass of the wave)
+    if (box_test(ray.o, wdinv, ray.tmin, tmax, xyz(n0), xyz(n1))) {
+      const int start = __float_as_int(n0.w), num = __float_as_int(n1.w) & 0xffff;
+      for (int k = num - 1; k >= 0; k--) {
+        const int         obj = scene_prim(start + k);
+        const YH_LDS v4f* ob  = tc.lds_scene + YH_OBJECT_F4 * obj;
+        // the padded world box's slabs (intersect_bbox_nonan's operations) without `tmax`: what a pop culls with
+        const f3    it_min = (xyz(ob[8]) - ray.o) * wdinv, it_max = (xyz(ob[9]) - ray.o) * wdinv;
+        const float t0  = __builtin_fmaxf(__builtin_fmaxf(__builtin_fminf(it_min.x, it_max.x), __builtin_fminf(it_min.y, it_max.y)),
+            __builtin_fmaxf(__builtin_fminf(it_min.z, it_max.z), ray.tmin));
+        const float far = __builtin_fminf(__builtin_fminf(__builtin_fmaxf(it_min.x, it_max.x), __builtin_fmaxf(it_min.y, it_max.y)),
+            __builtin_fmaxf(it_min.z, it_max.z));
+        if (!(t0 <= __builtin_fminf(far, tmax) * 1.00000024f)) continue;  // fails at the first `tmax`: at every later one too
+        // ENTER, operation for operation (below): transform_ray(inverse(object.frame, true), ray) (pt.cpp:1012-1013)
+        const v4f a = ob[3], b = ob[4], c = ob[5];
+        frame     inv;
+        inv.x = {a.x, a.y, a.z}, inv.y = {a.w, b.x, b.y}, inv.z = {b.z, b.w, c.x}, inv.o = {c.y, c.z, c.w};
+        const f3  o_ = transform_point(inv, ray.o), d_ = transform_vector(inv, ray.d), di = quad_rcp(d_);
+        const int sg = (di.x < 0 ? 1 : 0) | (di.y < 0 ? 2 : 0) | (di.z < 0 ? 4 : 0);
+        if (!(finite3(di) && finite3(o_))) redo = true;  // a slab of this object could hold a NaN: second pass
+        const int root = __float_as_int(YH_IS_HEX(MODE) ? ob[10].w : YH_IS_OCT(MODE) ? ob[10].z : ob[10].x);
+        YH_LDS v4f* rec = tc.lds_once + 4 * k * STRIDE;  // (every lane of the path's quads writes the same four rows)
+        rec[0]          = v4f{o_.x, o_.y, o_.z, t0};
+        rec[STRIDE]     = v4f{d_.x, d_.y, d_.z, far};
+        rec[2 * STRIDE] = v4f{di.x, di.y, di.z, dot(d_, d_)};
+        rec[3 * STRIDE] = v4f{__int_as_float(sg), ob[6].x, __int_as_float(root), __int_as_float(obj)};
+        if (cur != YH_NONE) push(cur);
+        cur = YH_TAG_ENTER | (unsigned)k;
+      }
+    }
+    if (redo) cur = YH_NONE, sp = 0;  // (leaves the loop at its head)
+  } else if (first_object >= 0) {
     cur = YH_TAG_ENTER | (unsigned)first_object;
   } else {
     if (sc.num_scene_nodes == 0) return hit;
@@ -387,6 +438,32 @@ YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_obj
     // shape chain inside ONE iteration, so a ray pays one memory round trip per
     // object it enters instead of three.
     bool scene_node = false;  // this step's node is a 4-wide node of the scene level
+    if constexpr (ONCE) {
+      if (tag == YH_TAG_ENTER) {
+        // An object of the prologue. The cull is the reference's box test with the CURRENT `tmax`, decomposed: the prologue kept
+        // t0 = max(slab mins, tmin) and far = min(slab maxes), and min(far, tmax) is the t1 intersect_bbox_nonan forms (min and
+        // max are exact and associative on NaN-free operands, and the sign of a zero is not observable through `* 1.00000024f`
+        // and `<=`): bit for bit the decision the in-loop ENTER takes. An object that fails costs no trip: the entries below an
+        // ENTER entry are ENTER entries (a shape's entries lie above it and are gone by now), so the next one is tried at once.
+        if (COUNT) count_branch<COUNT>(tc.stats->t_enter, tc.stats->l_enter);
+        const YH_LDS v4f* rec;
+        v4f               r0, r1;
+        while (true) {
+          rec = tc.lds_once + 4 * (int)(cur & 3u) * STRIDE;
+          r0 = rec[0], r1 = rec[STRIDE];
+          if (r0.w <= __builtin_fminf(r1.w, tmax) * 1.00000024f) break;
+          cur = YH_NONE;
+          if (sp == 0) break;
+          cur = pop();
+        }
+        if (cur == YH_NONE) continue;
+        const v4f r2 = rec[2 * STRIDE], r3 = rec[3 * STRIDE];
+        lo = xyz(r0), ld = xyz(r1), ldinv = xyz(r2), ld2 = r2.w;
+        lsign = __float_as_int(r3.x), kind = __float_as_int(r3.y), node_base = __float_as_int(r3.z), cur_obj = __float_as_int(r3.w);
+        cur = YH_TAG_SHAPE | (unsigned)node_base;  // shape root: fetched in this same iteration
+        tag = YH_TAG_SHAPE;
+      }
+    } else {
     if (!LDS_SCENE && tag == YH_TAG_SCENE && wide_scene) {
       // THE SCENE LEVEL AS 4-WIDE NODES (a scene table in memory, yh_device.h: scene_wide_root): the entry is a node's offset in the blob
       // — fetched and tested below like a shape's, lane q slot q, against the WORLD ray: the ray-in-the-object registers are free up here
@@ -483,6 +560,7 @@ YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_obj
       cur = YH_TAG_SHAPE | (unsigned)node_base;  // shape root: fetched in this same iteration
       tag = YH_TAG_SHAPE;
     }
+    }  // !ONCE
     {
       bool is_leaf    = tag == YH_TAG_LEAF;
       // LEAF GROUPS (YH_MODE_OCTP: pairs, YH_MODE_HEXP: up to four): when the entry is a leaf and the entries on top of the
@@ -690,10 +768,10 @@ YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_obj
 }
 #undef YH_STK
 
-template <bool COUNT, int STRIDE, bool LDS_SCENE = false, int MODE = YH_MODE_QUAD>
+template <bool COUNT, int STRIDE, bool LDS_SCENE = false, int MODE = YH_MODE_QUAD, bool ONCE = false>
 YH_DEV hit_t trace_ray(const trace_ctx& tc, const ray_t& ray, int first_object, unsigned int* steps_out = nullptr) {
   bool  redo = false;
-  hit_t hit  = trace_ray_loop<COUNT, STRIDE, false, LDS_SCENE, MODE>(tc, ray, first_object, steps_out, redo);
+  hit_t hit  = trace_ray_loop<COUNT, STRIDE, false, LDS_SCENE, MODE, ONCE>(tc, ray, first_object, steps_out, redo);
   if (__any(redo)) {
     if (redo) hit = trace_ray_loop<COUNT, STRIDE, true, LDS_SCENE, MODE>(tc, ray, first_object, steps_out, redo);
   }

@@ -421,7 +421,8 @@ trace_kernel_t yhk_wide_kernel(int counted, int general, int shape);  // csrc/wi
 static_assert(yhd_shapes[YH_SHAPE_QUAD].block_threads == YH_BLOCK && yhd_shapes[YH_SHAPE_OCT].block_threads == YH_OCT_BLOCK && yhd_shapes[YH_SHAPE_HEX].block_threads == YH_OCT_BLOCK, "yhd_shapes");
 static int shape_block(int shape) { return yhd_shapes[shape].block_threads; }
 static int shape_groups(int shape) { return shape_block(shape) / yhd_shapes[shape].lanes_per_path; }
-static trace_kernel_t trace_kernel(bool counted, bool general, int shape, int shader = YH_SHADER_PATH) {
+// `once`: the scene takes the form that resolves the scene level once per ray (yhd_scene::scene_once): shape 0's plain variants have it
+static trace_kernel_t trace_kernel(bool counted, bool general, int shape, int shader = YH_SHADER_PATH, bool once = false) {
   if (shader == YH_SHADER_NAIVE) return k_trace_shader<YH_SHADER_NAIVE>;
   if (shader == YH_SHADER_EYELIGHT) return k_trace_shader<YH_SHADER_EYELIGHT>;
   if (shader == YH_SHADER_NORMAL) return k_trace_shader<YH_SHADER_NORMAL>;
@@ -436,13 +437,17 @@ static trace_kernel_t trace_kernel(bool counted, bool general, int shape, int sh
   if (shape == YH_SHAPE_QUAD_DENSE)
     return counted ? (general ? k_trace<true, true, 256, YH_DENSE_WAVES> : k_trace<true, false, 256, YH_DENSE_WAVES>)
                    : (general ? k_trace<false, true, 256, YH_DENSE_WAVES> : k_trace<false, false, 256, YH_DENSE_WAVES>);
+  if (once && !general) return counted ? k_trace<true, false, YH_BLOCK, YH_MIN_WAVES, YH_MODE_QUAD, true> : k_trace<false, false, YH_BLOCK, YH_MIN_WAVES, YH_MODE_QUAD, true>;
   return counted ? (general ? k_trace<true, true, YH_BLOCK, YH_MIN_WAVES> : k_trace<true, false, YH_BLOCK, YH_MIN_WAVES>)
                  : (general ? k_trace<false, true, YH_BLOCK, YH_MIN_WAVES> : k_trace<false, false, YH_BLOCK, YH_MIN_WAVES>);
 }
 static size_t trace_lds(const yhd_scene* sc, int shape) {
   const int lanes   = yhd_shapes[shape].lanes_per_path;
   const int entries = lanes == 16 ? sc->stack_entries16 : lanes == 8 ? sc->stack_entries8 : sc->stack_entries;
-  return (size_t)(entries + YH_HITROWS) * shape_groups(shape) * 4 + (size_t)YHD_LDS_TABLES_F4(sc) * 16;
+  // (the records of the ONCE form behind the tables: shape 0 — its plain variants read them; k_trace_exact and the preview shaders,
+  // which launch with this geometry, leave them unused)
+  const size_t once = shape == YH_SHAPE_QUAD ? (size_t)YHD_ONCE_F4(sc, shape_groups(shape)) * 16 : 0;
+  return (size_t)(entries + YH_HITROWS) * shape_groups(shape) * 4 + (size_t)YHD_LDS_TABLES_F4(sc) * 16 + once;
 }
 // `shape`: a k_trace one (quad or wide); the caller built the work list for it (yhd_shape_info::entries_per_item)
 int yhk_trace(const yhd_scene* sc, const yhd_state* st, int nsamples, yhd_counters* counters, int shape,
@@ -452,7 +457,7 @@ int yhk_trace(const yhd_scene* sc, const yhd_state* st, int nsamples, yhd_counte
   if (!path && counters) return (int)hipErrorInvalidValue;
   if ((unsigned)shape >= YH_SHAPES || yhd_shapes[shape].kind == YH_SHAPE_KIND_STREAM || yhd_shapes[shape].kind == YH_SHAPE_KIND_SBS) return (int)hipErrorInvalidValue;
   size_t    lds   = trace_lds(sc, shape);
-  trace_kernel_t k     = trace_kernel(counters != nullptr, sc->general_materials != 0, shape, st->shader);
+  trace_kernel_t k     = trace_kernel(counters != nullptr, sc->general_materials != 0, shape, st->shader, sc->scene_once > 0);
   if (!k) return (int)hipErrorInvalidValue;
   if (lds > 64 * 1024) {  // above 64 KB the dynamic-LDS limit must be raised explicitly; the attribute is per
                           // device, so it is set for the current device at every such launch (no process-wide cache)
@@ -465,6 +470,8 @@ int yhk_trace(const yhd_scene* sc, const yhd_state* st, int nsamples, yhd_counte
 int yhk_block_threads(int shape) { return shape_block(shape); }
 int yhk_stack_entries(void) { return YH_QSTACK; }
 int yhk_trace_lds_bytes(const yhd_scene* sc, int shape) { return (int)trace_lds(sc, shape); }
+// (asked of the variant without the ONCE form: the two have one launch bound and differ in nothing the answer depends on but
+// `lds_bytes`, which the caller gives)
 int yhk_trace_occupancy(int lds_bytes, int general, int shape) {
   int            blocks = 0;
   trace_kernel_t k      = trace_kernel(false, general != 0, shape);

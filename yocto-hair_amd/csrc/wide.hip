@@ -26,10 +26,13 @@ trace_kernel_t yhk_wide_kernel(int counted, int general, int shape) {
 
 // (side by side: both forms at YH_BLOCK threads; the LDS of the larger layout)
 static size_t sbs_lds(const yhd_scene* sc) {
-  const size_t stacks = (size_t)std::max((sc->stack_entries + YH_HITROWS) * (YH_BLOCK / 4), (sc->stack_entries8 + YH_HITROWS) * (YH_BLOCK / 8)) * 4;
-  return stacks + (size_t)YHD_LDS_TABLES_F4(sc) * 16;
+  // (per form: its stacks in front of the tables and, behind them, its records of the ONCE form)
+  const size_t quads  = (size_t)(sc->stack_entries + YH_HITROWS) * (YH_BLOCK / 4) * 4 + (size_t)YHD_ONCE_F4(sc, YH_BLOCK / 4) * 16;
+  const size_t octets = (size_t)(sc->stack_entries8 + YH_HITROWS) * (YH_BLOCK / 8) * 4 + (size_t)YHD_ONCE_F4(sc, YH_BLOCK / 8) * 16;
+  return std::max(quads, octets) + (size_t)YHD_LDS_TABLES_F4(sc) * 16;
 }
 int yhk_trace_sbs_lds_bytes(const yhd_scene* sc) { return (int)sbs_lds(sc); }
+// (asked of the variant without the ONCE form, as yhk_trace_occupancy)
 int yhk_trace_sbs_occupancy(int lds_bytes, int general) {
   int  blocks = 0;
   auto k      = general ? k_trace_sbs<true> : k_trace_sbs<false>;
@@ -40,7 +43,7 @@ int yhk_trace_sbs_occupancy(int lds_bytes, int general) {
 int yhk_trace_sbs(const yhd_scene* sc, const yhd_state* st, int nsamples, int oct_blocks, int quad_items, int oct_entries, int grid_blocks,
     hipStream_t stream) {
   const size_t lds = sbs_lds(sc);
-  auto         k   = sc->general_materials ? k_trace_sbs<true> : k_trace_sbs<false>;
+  auto         k   = sc->general_materials ? k_trace_sbs<true> : sc->scene_once > 0 ? k_trace_sbs<false, true> : k_trace_sbs<false>;
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;

@@ -206,7 +206,15 @@ typedef struct yhd_scene {
   // the leaf records; the one-lane kernels read the part up to the end of the 4-wide nodes through 32-bit byte offsets.
   const yhd_float4* lane_blob;
   long long         lane_blob_units;
+  // THE SCENE LEVEL ONCE PER RAY (dev_trace.h: trace_ray_loop, ONCE): the scene's object count when the plain 512-thread kernels
+  // (launch shapes 0 and 5) run the form that resolves the scene level ahead of the traversal loop, else 0. Set at upload
+  // (host/scene_upload.cpp) for a plain scene whose scene level is ONE leaf node (at most four objects) in LDS, when the records
+  // cost those kernels no resident workgroup. (At the end: every other offset is as it was.)
+  int               scene_once;
+  int               pad_once;
 } yhd_scene;
+// float4 of the per-object ray records of the ONCE form behind the tables, for `groups` paths per workgroup: 4 per (path, object)
+#define YHD_ONCE_F4(sc, groups) (4 * (sc)->scene_once * (groups))
 #define YH_MATERIAL_F4 17 /* sizeof(yhd_material) / 16 */
 // float4 the kernels reserve in LDS for the tables: scene level | camera (5) | small lights | env cdf index | materials
 #define YHD_LDS_TABLES_F4(sc) ((sc)->lds_scene_f4 + 5 + (sc)->light_table_f4 + ((sc)->env_tab_k + 3) / 4 + YH_MATERIAL_F4 * (sc)->lds_materials)

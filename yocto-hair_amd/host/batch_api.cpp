@@ -270,6 +270,33 @@ int yh_intersect_batch(yh_context* ctx, int n, const float* rays, int* object, i
   return YH_OK;
 }
 
+// intersect_scene_bvh through the traversal of the PLAIN 512-thread sample-loop kernels (unit/intersect_quad.hip)
+int yh_intersect_plain_batch(yh_context* ctx, int form, int n, const float* rays, int* object, int* element, float* uv, float* distance) {
+  if (!ctx || n < 0 || (form != 0 && form != 1) || (n && (!rays || !object || !element || !uv || !distance))) return YH_E_INVALID;
+  if (!ctx->have_scene) return fail(ctx, YH_E_STATE, "yh_intersect_plain_batch before yh_upload_scene");
+  if (ctx->scene.general_materials || ctx->scene.lds_scene_f4 == 0)
+    return fail(ctx, YH_E_INVALID, "yh_intersect_plain_batch: this scene renders with the GENERAL kernel variants (materials beyond diffuse / hair, a light read through memory, or tables too large for LDS)");
+  if (n == 0) return YH_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  Staged s(ctx);
+  auto   dr  = (float*)s.in(rays, 32 * (size_t)n);
+  auto   dob = (int*)s.out(4 * (size_t)n);
+  auto   del = (int*)s.out(4 * (size_t)n);
+  auto   duv = (float*)s.out(8 * (size_t)n);
+  auto   dd  = (float*)s.out(4 * (size_t)n);
+  if (s.rc) return s.rc;
+  int e = yhk_intersect_plain(&ctx->scene, form, n, dr, dob, del, duv, dd, ctx->stream);
+  if (e) return fail(ctx, YH_E_DEVICE, "k_intersect_plain launch: %s", hipGetErrorString((hipError_t)e));
+  YH_WAIT(ctx);
+  HIPCHK(ctx, hipMemcpy(object, dob, 4 * (size_t)n, hipMemcpyDeviceToHost));
+  HIPCHK(ctx, hipMemcpy(element, del, 4 * (size_t)n, hipMemcpyDeviceToHost));
+  HIPCHK(ctx, hipMemcpy(uv, duv, 8 * (size_t)n, hipMemcpyDeviceToHost));
+  HIPCHK(ctx, hipMemcpy(distance, dd, 4 * (size_t)n, hipMemcpyDeviceToHost));
+  return YH_OK;
+}
+
+int yh_scene_once(const yh_context* ctx) { return !ctx ? YH_E_INVALID : !ctx->have_scene ? YH_E_STATE : ctx->scene.scene_once; }
+
 int yh_lights_batch(yh_context* ctx, int form, int n, const float* position, const float* direction, const float* rn, float* out) {
   if (!ctx || n < 0 || (form != 0 && form != 1) || (n && (!position || !direction || !rn || !out))) return YH_E_INVALID;
   if (!ctx->have_scene) return fail(ctx, YH_E_STATE, "yh_lights_batch before yh_upload_scene");

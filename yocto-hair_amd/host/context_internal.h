@@ -78,6 +78,7 @@ int yhk_curves_to_lines(int, const float*, const float*, const float*, int, floa
 int yhk_surface_lobe(int, int, const float*, const float*, const float*, const float*, const float*, float*, hipStream_t);
 int yhk_surface_bsdf(int, const void*, const float*, const float*, const float*, const float*, float*, hipStream_t);
 int yhk_lights(const yhd_scene*, int, const float*, const float*, const float*, float*, hipStream_t);
+int yhk_intersect_plain(const yhd_scene*, int form, int, const float*, int*, int*, float*, float*, hipStream_t);  // unit/intersect_quad.hip
 int yhk_lights_lanes(const yhd_scene* sc, const yhd_scene* sc_dev, int n, const float* position, const float* direction, const float* rn,
     unsigned int* stack_ovf, int ovf_entries, float* out, hipStream_t stream);
 int yhk_selftest(int, float, float, uint64_t, uint64_t, int, const float*, double*, unsigned int*, hipStream_t);

@@ -649,6 +649,17 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
     sc.lds_materials = sd->num_materials <= 24 ? sd->num_materials : 0;
     if (sc.lds_materials == 0 || sc.lds_scene_f4 == 0) sc.general_materials = 1;
   }
+  {  // THE SCENE LEVEL ONCE PER RAY (csrc/dev_trace.h: ONCE): a plain scene whose scene level is one leaf node. Its records (8 KB per
+     // object in the 512-thread quad form) must cost shapes 0 and 5 no resident workgroup, else the scene keeps the in-loop form
+    sc.scene_once = 0, sc.pad_once = 0;
+    if (!sc.general_materials && sc.num_scene_nodes == 1 && sc.num_objects >= 1 && sc.num_objects <= 4) {
+      const int quad0 = yhk_trace_occupancy(yhk_trace_lds_bytes(&sc, YH_SHAPE_QUAD), 0, YH_SHAPE_QUAD);
+      const int sbs0  = yhk_trace_sbs_occupancy(yhk_trace_sbs_lds_bytes(&sc), 0);
+      sc.scene_once = sc.num_objects;
+      if (yhk_trace_occupancy(yhk_trace_lds_bytes(&sc, YH_SHAPE_QUAD), 0, YH_SHAPE_QUAD) < quad0 || yhk_trace_sbs_occupancy(yhk_trace_sbs_lds_bytes(&sc), 0) < sbs0)
+        sc.scene_once = 0;
+    }
+  }
   ctx->scene      = sc;
   {  // fingerprint of the scene for the process-wide trial record: counts, camera, materials, objects, a sample of the geometry
     uint64_t h = 1469598103934665603ULL;

@@ -177,6 +177,8 @@ _SIGS = {
     "yh_hair_pdf_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),
     "yh_hair_eval_pdf_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),
     "yh_intersect_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_int_p, c_int_p, c_float_p, c_float_p]),
+    "yh_intersect_plain_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, c_int_p, c_int_p, c_float_p, c_float_p]),
+    "yh_scene_once": (C.c_int, [C.c_void_p]),
     "yh_lights_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),
     "yh_selftest": (C.c_int, [C.c_void_p, C.c_int, c_float_p]),
     "yh_scene_load": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]),
@@ -441,6 +443,23 @@ class Context:
         uv, dist = np.zeros((n, 2), np.float32), np.zeros(n, np.float32)
         self._chk(self.lib.yh_intersect_batch(self.h, n, fptr(rays), iptr(obj), iptr(elem), fptr(uv), fptr(dist)))
         return obj, elem, uv, dist
+
+    def intersect_plain(self, form, rays):
+        """yh_intersect_plain_batch: closest hits through the traversal of the plain 512-thread sample-loop kernels (form 0: a
+        quad per ray, 1: an octet per ray), the scene level staged in LDS and walked as a launch on this scene walks it."""
+        rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
+        n = len(rays)
+        obj, elem = np.zeros(n, np.int32), np.zeros(n, np.int32)
+        uv, dist = np.zeros((n, 2), np.float32), np.zeros(n, np.float32)
+        self._chk(self.lib.yh_intersect_plain_batch(self.h, form, n, fptr(rays), iptr(obj), iptr(elem), fptr(uv), fptr(dist)))
+        return obj, elem, uv, dist
+
+    def scene_once(self):
+        """yh_scene_once: the object count when the plain 512-thread kernels resolve this scene's scene level once per ray, else 0."""
+        rc = int(self.lib.yh_scene_once(self.h))
+        if rc < 0:
+            self._chk(rc)
+        return rc
 
     def lights(self, form, position, direction, rn4):
         """yh_lights_batch on the uploaded scene (form 0: a quad per row, 1: a lane per row): (n, 8) = sample_lights
