@@ -244,6 +244,34 @@ int yh_upload_scene(yh_context* ctx, const yh_scene_desc* scene);
  * outside [0, num_textures] is YH_E_INVALID and leaves the context's previous scene as it was.                     */
 int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* scene, const yh_material_maps* maps);
 
+/* EDITS OF THE UPLOADED SCENE that leave every acceleration structure as it is. The reference reads its scene structs live: its
+ * interactive caller edits app->camera->frame in place and the next sample uses it (apps/ysceneitraces/ysceneitraces.cpp:392-410).
+ * Here the description was flattened by yh_upload_scene, so an edit is a call:
+ *   yh_update_camera        set_frame / set_lens / set_focus on a camera (yocto_pathtrace.h:97-104): the whole yh_camera;
+ *   yh_update_materials     the material setters (yocto_pathtrace.h:106-140): rows [first, first + count) of the material table,
+ *                           `materials` holding `count` entries;
+ *   yh_update_environments  set_frame / set_emission on an environment (yocto_pathtrace.h:172-174): frame and emission of every
+ *                           environment; count must be the uploaded scene's num_environments; tex_width, tex_height and texels
+ *                           are ignored (the texel cdf depends on neither the emission scale nor the frame).
+ * CONTRACT. After a successful call the context is, for every later call, indistinguishable in its results from a context that got
+ * yh_upload_scene_maps of the edited description: pixels, RNG states, yh_lights_batch, yh_intersect_batch and yh_scene_once are the
+ * same bits (the kernel variant, the once-per-ray form and the fingerprint of the kernel-trial record follow the edit). The image
+ * state is gone, as after an upload: yh_trace_samples before a new yh_init_state returns YH_E_STATE, and that yh_init_state probes
+ * and plans as for a new scene. The calls are blocking and need an uploaded scene (else YH_E_STATE). No device work or allocation is
+ * proportional to the geometry: no tree, record, vertex array or light cdf is read, written or reallocated (1.6 M hair segments:
+ * an upload builds for 41 ms on the device alone, an edit copies a few hundred bytes).
+ * REFUSED with YH_E_INVALID, a message that names the entry point, and the context exactly as it was (it goes on rendering the
+ * earlier scene): a NULL argument; first / count outside the uploaded table; count != num_environments; a material or environment
+ * whose emission changes between all-zero and not all-zero (the light list, init_lights, yocto_pathtrace.cpp:1695-1740, depends on
+ * it and the shapes' host arrays were borrowed for the upload only); a material whose emission_tex, color_tex or scattering_tex
+ * differs from the uploaded one (which texel copies exist was decided at the upload). The materials' maps (yh_material_maps) are
+ * not editable.
+ * OUT OF SCOPE, for all of which the answer stays a new upload: object frames (the scene-level tree, the wide scene nodes at the
+ * front of the traversal array and the stack depths depend on them), geometry, textures and maps, turning emission on or off.   */
+int yh_update_camera(yh_context* ctx, const yh_camera* camera);
+int yh_update_materials(yh_context* ctx, int first, int count, const yh_material* materials);
+int yh_update_environments(yh_context* ctx, int count, const yh_environment* environments);
+
 /* init_state (yocto_pathtrace.cpp:1931-1946): image size from the camera film
  * and params->resolution, zeroed accumulators, per-pixel PCG32 streams
  * make_rng(seed, rand1i(master, 1<<31)/2+1) with master = make_rng(1301081). */
@@ -274,6 +302,12 @@ int yh_synchronize(yh_context* ctx);
 /* state->render (yocto_pathtrace.h:426-429): accumulated / samples, float4
  * per pixel, row-major top row first. Non-owned pixels are 0.                */
 int yh_download(yh_context* ctx, float* rgba);
+/* tonemap + float_to_byte (yocto_math.h:3820-3829, 3721-3729), the last step of the interactive caller's reset_display
+ * (apps/ysceneitraces/ysceneitraces.cpp:280,296), on the device: accumulated / samples, scaled by exp2(exposure) when
+ * exposure != 0, through the fitted ACES curve (yocto_math.h:3788-3794) when `filmic`, through rgb_to_srgb when `srgb`,
+ * then clamp(int(a * 256), 0, 255) per channel — alpha too, which no curve touches. rgba8: four bytes per pixel (r, g, b, a),
+ * row-major top row first; non-owned pixels are 0 and a non-finite value gives 0. Blocking; YH_E_STATE before yh_init_state.   */
+int yh_download_display(yh_context* ctx, float exposure, int filmic, int srgb, uint8_t* rgba8);
 /* Packs the owned tiles' float4 pixels into a DEVICE buffer (the payload of
  * the RCCL gather). `capacity` in float4 pixels; *count receives the number
  * written. Tiles are in increasing tile_id order, 64 pixels per tile. This

@@ -8,6 +8,8 @@
 //   trace_launch.cpp   yh_init_state (pt.cpp:1931-1946) and the launches: yh_trace_samples and friends
 //   gather.cpp         tile packing and the one collective (yh_gather_framebuffer: RCCL or peer copies)
 //   batch_api.cpp      the unit-level batch entry points (hair BSDF, intersection, BVH build, curves, self-tests)
+//   scene_edit.cpp     edits of an uploaded scene that leave its trees alone (yh_update_camera / _materials / _environments) and
+//                      yh_download_display
 #ifndef YH_CONTEXT_INTERNAL_H_
 #define YH_CONTEXT_INTERNAL_H_
 #include <hip/hip_runtime_api.h>
@@ -82,6 +84,7 @@ int yhk_intersect_plain(const yhd_scene*, int form, int, const float*, int*, int
 int yhk_lights_lanes(const yhd_scene* sc, const yhd_scene* sc_dev, int n, const float* position, const float* direction, const float* rn,
     unsigned int* stack_ovf, int ovf_entries, float* out, hipStream_t stream);
 int yhk_selftest(int, float, float, uint64_t, uint64_t, int, const float*, double*, unsigned int*, hipStream_t);
+int yhk_display(const yhd_state*, int samples, float exposure, int filmic, int srgb, void* rgba8, hipStream_t);  // unit/display.hip
 }
 
 // A device allocation owned by the context.
@@ -226,12 +229,22 @@ struct yh_context {
   std::vector<LaneShape>   lane_shapes;
   long long                lane_units = 0;
   DevBuf                   d_lane_blob;
+  // what an edit of the uploaded scene needs of its description (host/scene_edit.cpp): the material rows as they were passed in, their maps
+  // (empty: no material has an effective map) with the device's records of them, whether some area light is read through memory (one of
+  // the inputs of yhd_scene::general_materials), and the bytes the fingerprint mixes in its order — camera, materials, objects and
+  // geometry sample, environment heads, maps
+  std::vector<yh_material>      h_materials;
+  std::vector<yh_material_maps> h_maps;
+  std::vector<yhd_maps>         h_dmaps;
+  bool                          big_lights = false;
+  yh_camera                     key_camera{};
+  std::vector<unsigned char>    key_geometry, key_envs;
   // state
   bool             have_state = false;
   yhd_state        state{};
   yh_trace_params  params{};
   DevBuf           d_textures, d_tex_texels, d_vtex, d_maps;
-  DevBuf           d_rng_state, d_rng_inc, d_accum, d_tiles, d_image, d_counters, d_tile_cursor, d_tile_cost;
+  DevBuf           d_rng_state, d_rng_inc, d_accum, d_tiles, d_image, d_counters, d_tile_cursor, d_tile_cost, d_display;
   std::vector<int> owned;      // owned tile ids, increasing
   std::vector<unsigned int>  item_cost;  // per work item (tile * 4 + quadrant): last measured cost (scheduling hint, kept across init_state)
   int              rank = 0, world = 1;
@@ -334,5 +347,12 @@ int side_by_side_impl(yh_context* ctx, int nsamples, bool sync);
 void destroy_communicators(yh_context* ctx);
 inline int tiles_of(int n) { return (n + YH_TILE - 1) / YH_TILE; }
 void make_material(const yh_material& m, yhd_material& d);  // scene_upload.cpp
+// scene_upload.cpp, shared with scene_edit.cpp: the device rows of `count` materials (`maps` / `dmaps`: theirs, or NULL in a scene without effective
+// maps), true when one of them is not plain; the kernel variant and the once-per-ray form of a scene table whose materials are known; the
+// fingerprint of the description the context keeps; and what a new scene does to the image state and the launch planning
+bool make_material_rows(const yh_material* materials, const yh_material_maps* maps, int count, yhd_material* rows, yhd_maps* dmaps);
+void settle_scene_variant(const yh_context* ctx, yhd_scene& sc, bool general_rows);
+uint64_t scene_fingerprint(const yh_context* ctx);
+void forget_image_of_scene(yh_context* ctx);
 #pragma GCC visibility pop
 #endif

@@ -89,6 +89,71 @@ static bool has_effective_map(const yh_material_maps& m) {
 
 static_assert(sizeof(yhd_maps) == 32, "yhd_maps");
 
+// The material section of the upload, which yh_update_materials runs again for the rows it replaces (host/scene_edit.cpp).
+bool make_material_rows(const yh_material* materials, const yh_material_maps* maps, int count, yhd_material* rows, yhd_maps* dmaps) {
+  bool general = false;
+  for (int i = 0; i < count; i++) {
+    make_material(materials[i], rows[i]);
+    if (maps) {  // the lookups and the lobe set-up of a mapped material happen per hit (dev_path.h: eval_hit_maps)
+      const yh_material_maps& m = maps[i];
+      yhd_maps&               d = dmaps[i];
+      d.specular_tex = m.specular_tex - 1, d.metallic_tex = m.metallic_tex - 1, d.roughness_tex = m.roughness_tex - 1;
+      d.opacity_tex = m.opacity_tex - 1, d.normal_tex = m.normal_tex - 1;
+      d.any = has_effective_map(m) ? 1 : 0, d.opacity = materials[i].opacity, d.pad = 0;
+      if (d.any) rows[i].plain = 0;
+    }
+    if (!rows[i].plain) general = true;
+  }
+  return general;
+}
+
+// Which kernel variant a scene table runs, once its materials are known (`general_rows`: one of them is not plain), and whether the plain
+// 512-thread kernels resolve its scene level once per ray.
+void settle_scene_variant(const yh_context* ctx, yhd_scene& sc, bool general_rows) {
+  // a light sampled and intersected through memory: the general kernel variant (dev_path.h: BIG_LIGHTS); the plain variants rely on the
+  // material table and on the scene-level table in LDS (dev_path.h)
+  sc.general_materials = general_rows || ctx->big_lights || sc.lds_materials == 0 || sc.lds_scene_f4 == 0;
+  // THE SCENE LEVEL ONCE PER RAY (csrc/dev_trace.h: ONCE): a plain scene whose scene level is one leaf node. Its records (8 KB per
+  // object in the 512-thread quad form) must cost shapes 0 and 5 no resident workgroup, else the scene keeps the in-loop form
+  sc.scene_once = 0, sc.pad_once = 0;
+  if (!sc.general_materials && sc.num_scene_nodes == 1 && sc.num_objects >= 1 && sc.num_objects <= 4) {
+    const int quad0 = yhk_trace_occupancy(yhk_trace_lds_bytes(&sc, YH_SHAPE_QUAD), 0, YH_SHAPE_QUAD);
+    const int sbs0  = yhk_trace_sbs_occupancy(yhk_trace_sbs_lds_bytes(&sc), 0);
+    sc.scene_once = sc.num_objects;
+    if (yhk_trace_occupancy(yhk_trace_lds_bytes(&sc, YH_SHAPE_QUAD), 0, YH_SHAPE_QUAD) < quad0 || yhk_trace_sbs_occupancy(yhk_trace_sbs_lds_bytes(&sc), 0) < sbs0)
+      sc.scene_once = 0;
+  }
+}
+
+// Fingerprint of the scene for the process-wide trial record: counts, camera, materials, objects, a sample of the geometry, environment
+// heads, maps — over the bytes the context keeps of them, so that an edited scene has the key an upload of the edited description computes.
+uint64_t scene_fingerprint(const yh_context* ctx) {
+  uint64_t h = 1469598103934665603ULL;
+  auto mix = [&](const void* p, size_t n) {
+    const unsigned char* b = (const unsigned char*)p;
+    for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 1099511628211ULL;
+  };
+  mix(&ctx->key_camera, sizeof(ctx->key_camera));
+  mix(ctx->h_materials.data(), sizeof(yh_material) * ctx->h_materials.size());
+  mix(ctx->key_geometry.data(), ctx->key_geometry.size());
+  mix(ctx->key_envs.data(), ctx->key_envs.size());
+  mix(ctx->h_maps.data(), sizeof(yh_material_maps) * ctx->h_maps.size());
+  return h;
+}
+
+// A new scene, or an edited one: no image state, no measured costs, nothing planned; the streaming kernel's copy of the scene table is
+// made again at its first launch (stream_impl).
+void forget_image_of_scene(yh_context* ctx) {
+  ctx->d_scene_copy.reset();
+  ctx->have_state = false;
+  ctx->launch_shape = YH_SHAPE_QUAD;
+  ctx->item_cost.clear();
+  ctx->have_costs = false, ctx->costs_settled = false, ctx->dense = -1, ctx->chain = -1, ctx->chain16 = -1;
+  for (double& t : ctx->shape_ms) t = 0;
+  for (int& t : ctx->shape_trials) t = 0;
+  ctx->trials_from_disk = false;
+}
+
 // The levels of a host-built tree as the device builder reports them: their number and the first node of each (level_first[0 .. levels],
 // 130 entries). false: more than 128 levels.
 static bool tree_levels(const yhh::Tree& tree, int& levels, int* level_first) {
@@ -438,20 +503,9 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
     return fail(ctx, YH_E_INVALID, "BVH too deep for the traversal stack (%d > %d)", ctx->stack_need, yhk_stack_entries());
   // ---- materials ---------------------------------------------------------
   std::vector<yhd_material> materials(sd->num_materials);
-  int general_materials = 0;
   std::vector<yhd_maps> mat_maps(any_maps ? (size_t)sd->num_materials : 0);
-  for (int i = 0; i < sd->num_materials; i++) {
-    make_material(sd->materials[i], materials[i]);
-    if (any_maps) {  // the lookups and the lobe set-up of a mapped material happen per hit (dev_path.h: eval_hit_maps)
-      const yh_material_maps& m = maps[i];
-      yhd_maps&               d = mat_maps[(size_t)i];
-      d.specular_tex = m.specular_tex - 1, d.metallic_tex = m.metallic_tex - 1, d.roughness_tex = m.roughness_tex - 1;
-      d.opacity_tex = m.opacity_tex - 1, d.normal_tex = m.normal_tex - 1;
-      d.any = has_effective_map(m) ? 1 : 0, d.opacity = sd->materials[i].opacity, d.pad = 0;
-      if (d.any) materials[i].plain = 0;
-    }
-    if (!materials[i].plain) general_materials = 1;
-  }
+  const bool general_rows = make_material_rows(sd->materials, any_maps ? maps : nullptr, sd->num_materials, materials.data(), mat_maps.data());
+  bool big_lights = false;
   // ---- lights (pt.cpp:1695-1740) -----------------------------------------
   yhd_scene sc{};
   std::vector<float>      light_cdf;
@@ -468,7 +522,7 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
     auto& L = sc.lights[sc.num_lights++];
     L.object = oi, L.environment = -1, L.cdf_base = (int)light_cdf.size(), L.cdf_count = s.num_triangles, L.small_base = -1;
     if (s.num_triangles <= YH_SMALL_LIGHT_TRIS) small_lights.push_back(sc.num_lights - 1);  // its record is made below, once the cdf exists
-    else general_materials = 1;  // a light sampled and intersected through memory: the general kernel variant (dev_path.h: BIG_LIGHTS)
+    else big_lights = true;  // a light sampled and intersected through memory: the general kernel variant (settle_scene_variant)
     for (int t = 0; t < s.num_triangles; t++) {
       F3 p0 = ld3(s.positions + 3 * (size_t)s.triangles[3 * t]), p1 = ld3(s.positions + 3 * (size_t)s.triangles[3 * t + 1]),
          p2 = ld3(s.positions + 3 * (size_t)s.triangles[3 * t + 2]);
@@ -641,57 +695,35 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
   sc.camera.focus = sd->camera.focus, sc.camera.aperture = sd->camera.aperture;
   sc.num_nodes_total = 0, sc.num_prim_f4 = (int)total_prim_f4;
   for (auto& I : info) sc.num_nodes_total += I.wide_count[0];
-  sc.general_materials = general_materials;
   sc.lds_scene_f4    = scene_wide ? 0 : lds_scene_f4;  // (made with the scene tree, above)
   sc.scene_wide_root = scene_wide ? 0 : -1;
-  {  // the material table in LDS; the plain kernel variants rely on it and on the scene-level table (dev_path.h)
-    static_assert(sizeof(yhd_material) == 16 * YH_MATERIAL_F4, "yhd_material is staged to LDS as float4");
-    sc.lds_materials = sd->num_materials <= 24 ? sd->num_materials : 0;
-    if (sc.lds_materials == 0 || sc.lds_scene_f4 == 0) sc.general_materials = 1;
-  }
-  {  // THE SCENE LEVEL ONCE PER RAY (csrc/dev_trace.h: ONCE): a plain scene whose scene level is one leaf node. Its records (8 KB per
-     // object in the 512-thread quad form) must cost shapes 0 and 5 no resident workgroup, else the scene keeps the in-loop form
-    sc.scene_once = 0, sc.pad_once = 0;
-    if (!sc.general_materials && sc.num_scene_nodes == 1 && sc.num_objects >= 1 && sc.num_objects <= 4) {
-      const int quad0 = yhk_trace_occupancy(yhk_trace_lds_bytes(&sc, YH_SHAPE_QUAD), 0, YH_SHAPE_QUAD);
-      const int sbs0  = yhk_trace_sbs_occupancy(yhk_trace_sbs_lds_bytes(&sc), 0);
-      sc.scene_once = sc.num_objects;
-      if (yhk_trace_occupancy(yhk_trace_lds_bytes(&sc, YH_SHAPE_QUAD), 0, YH_SHAPE_QUAD) < quad0 || yhk_trace_sbs_occupancy(yhk_trace_sbs_lds_bytes(&sc), 0) < sbs0)
-        sc.scene_once = 0;
-    }
-  }
+  static_assert(sizeof(yhd_material) == 16 * YH_MATERIAL_F4, "yhd_material is staged to LDS as float4");
+  sc.lds_materials = sd->num_materials <= 24 ? sd->num_materials : 0;  // the material table in LDS
+  ctx->big_lights  = big_lights;
+  settle_scene_variant(ctx, sc, general_rows);
   ctx->scene      = sc;
-  {  // fingerprint of the scene for the process-wide trial record: counts, camera, materials, objects, a sample of the geometry
-    uint64_t h = 1469598103934665603ULL;
-    auto mix = [&](const void* p, size_t n) {
-      const unsigned char* b = (const unsigned char*)p;
-      for (size_t i = 0; i < n; i++) h = (h ^ b[i]) * 1099511628211ULL;
-    };
-    mix(&sd->camera, sizeof(sd->camera));
-    mix(sd->materials, sizeof(yh_material) * (size_t)sd->num_materials);
-    mix(sd->objects, sizeof(yh_object) * (size_t)sd->num_objects);
+  {  // what the edits of this scene start from (host/scene_edit.cpp), and the bytes its fingerprint mixes, in the fingerprint's order
+    auto bytes = [](std::vector<unsigned char>& to, const void* p, size_t n) { to.insert(to.end(), (const unsigned char*)p, (const unsigned char*)p + n); };
+    ctx->key_camera = sd->camera;
+    ctx->h_materials.assign(sd->materials, sd->materials + sd->num_materials);
+    ctx->key_geometry.clear(), ctx->key_envs.clear();
+    bytes(ctx->key_geometry, sd->objects, sizeof(yh_object) * (size_t)sd->num_objects);
     for (int i = 0; i < sd->num_shapes; i++) {
       const yh_shape& sh = sd->shapes[i];
       int counts[3] = {sh.num_vertices, sh.num_lines, sh.num_triangles};
-      mix(counts, sizeof(counts));
+      bytes(ctx->key_geometry, counts, sizeof(counts));
       if (sh.positions && sh.num_vertices > 0) {
         const size_t n = (size_t)sh.num_vertices, take = std::min<size_t>(n, 256);
-        mix(sh.positions, take * 12), mix(sh.positions + 3 * (n - take), take * 12);
+        bytes(ctx->key_geometry, sh.positions, take * 12), bytes(ctx->key_geometry, sh.positions + 3 * (n - take), take * 12);
       }
     }
-    for (int i = 0; i < sd->num_environments; i++) mix(&sd->environments[i], offsetof(yh_environment, texels));
-    if (any_maps) mix(maps, sizeof(yh_material_maps) * (size_t)sd->num_materials);
-    ctx->scene_key = h;
+    for (int i = 0; i < sd->num_environments; i++) bytes(ctx->key_envs, &sd->environments[i], offsetof(yh_environment, texels));
+    if (any_maps) ctx->h_maps.assign(maps, maps + sd->num_materials), ctx->h_dmaps = mat_maps;
+    else ctx->h_maps.clear(), ctx->h_dmaps.clear();
+    ctx->scene_key = scene_fingerprint(ctx);
   }
-  ctx->d_scene_copy.reset();  // (stream_impl uploads the new table at its first launch)
   ctx->have_scene = true;
-  ctx->have_state = false;
-  ctx->launch_shape = YH_SHAPE_QUAD;  // a new scene: no measured costs yet
-  ctx->item_cost.clear();
-  ctx->have_costs = false, ctx->costs_settled = false, ctx->dense = -1, ctx->chain = -1, ctx->chain16 = -1;
-  for (double& t : ctx->shape_ms) t = 0;
-  for (int& t : ctx->shape_trials) t = 0;
-  ctx->trials_from_disk = false;
+  forget_image_of_scene(ctx);  // a new scene: no measured costs yet
   lap("scene table, fingerprint");
   return YH_OK;
 }

@@ -86,6 +86,67 @@ inline void for_each_context(F&& fn) {
   for (auto& t : pool) t.join();
   for (size_t i = 0; i < ctxs.size(); i++) check(rcs[i], ctxs[i]);
 }
+// A scene graph flattened to the C ABI's description: what an upload passes, and what the scene remembers of its last one.
+struct flat_scene {
+  std::vector<yh_shape>         shapes;  // per shape its pointers and counts
+  std::vector<yh_material>      materials;
+  std::vector<yh_material_maps> maps;
+  std::vector<yh_object>        objects;
+  std::vector<yh_environment>   environments;
+  std::vector<yh_texture>       textures;
+  yh_camera                     camera{};
+  yh_scene_desc desc() const {
+    yh_scene_desc d{};
+    d.num_shapes = (int)shapes.size(), d.shapes = shapes.data();
+    d.num_materials = (int)materials.size(), d.materials = materials.data();
+    d.num_objects = (int)objects.size(), d.objects = objects.data();
+    d.num_environments = (int)environments.size(), d.environments = environments.data();
+    d.num_textures = (int)textures.size(), d.textures = textures.data();
+    d.camera = camera;
+    return d;
+  }
+};
+// What separates the description a scene last uploaded from the one it flattens to now: a set of edit_camera / edit_materials /
+// edit_environments — exactly the differences yh_update_camera / yh_update_materials / yh_update_environments accept
+// (include/yhair.h) — or edit_upload as soon as anything else differs: a shape's pointers or counts, an object (its frame too), a
+// texture, a map, the number of anything, a material's texture ids, an emission that turns on or off. No device, no context.
+enum : unsigned { edit_none = 0, edit_camera = 1, edit_materials = 2, edit_environments = 4, edit_upload = 8 };
+inline unsigned classify_edit(const flat_scene& was, const flat_scene& now) {
+  auto black = [](const float* e) { return e[0] == 0 && e[1] == 0 && e[2] == 0; };
+  if (was.shapes.size() != now.shapes.size() || was.materials.size() != now.materials.size() || was.maps.size() != now.maps.size() ||
+      was.objects.size() != now.objects.size() || was.environments.size() != now.environments.size() || was.textures.size() != now.textures.size())
+    return edit_upload;
+  for (size_t i = 0; i < now.shapes.size(); i++) {
+    const yh_shape &a = was.shapes[i], &b = now.shapes[i];
+    if (a.num_vertices != b.num_vertices || a.positions != b.positions || a.normals != b.normals || a.radius != b.radius || a.num_lines != b.num_lines ||
+        a.lines != b.lines || a.num_triangles != b.num_triangles || a.triangles != b.triangles || a.texcoords != b.texcoords)
+      return edit_upload;
+  }
+  for (size_t i = 0; i < now.textures.size(); i++) {
+    const yh_texture &a = was.textures[i], &b = now.textures[i];
+    if (a.width != b.width || a.height != b.height || a.is_byte != b.is_byte || a.pixels != b.pixels) return edit_upload;
+  }
+  for (size_t i = 0; i < now.objects.size(); i++) {
+    const yh_object &a = was.objects[i], &b = now.objects[i];
+    if (memcmp(a.frame, b.frame, 48) || a.shape != b.shape || a.material != b.material) return edit_upload;
+  }
+  static_assert(sizeof(yh_material_maps) == 6 * sizeof(int) && sizeof(yh_material) == 30 * 4 && sizeof(yh_camera) == 17 * 4, "compared as bytes: no padding");
+  if (!now.maps.empty() && memcmp(was.maps.data(), now.maps.data(), sizeof(yh_material_maps) * now.maps.size())) return edit_upload;
+  unsigned kind = edit_none;
+  for (size_t i = 0; i < now.materials.size(); i++) {
+    const yh_material &a = was.materials[i], &b = now.materials[i];
+    if (!memcmp(&a, &b, sizeof(a))) continue;
+    if (black(a.emission) != black(b.emission) || a.emission_tex != b.emission_tex || a.color_tex != b.color_tex || a.scattering_tex != b.scattering_tex) return edit_upload;
+    kind |= edit_materials;
+  }
+  for (size_t i = 0; i < now.environments.size(); i++) {
+    const yh_environment &a = was.environments[i], &b = now.environments[i];
+    if (a.tex_width != b.tex_width || a.tex_height != b.tex_height || a.texels != b.texels || black(a.emission) != black(b.emission)) return edit_upload;
+    if (memcmp(a.frame, b.frame, 48) || memcmp(a.emission, b.emission, 12)) kind |= edit_environments;
+  }
+  if (memcmp(&was.camera, &now.camera, sizeof(yh_camera))) kind |= edit_camera;
+  return kind;
+}
 // the state whose pixels the contexts hold (see init_state / trace_samples)
 inline const void*& bound_state() {
   static const void* st = nullptr;
@@ -233,6 +294,11 @@ struct scene {
   mutable bool          bvh_requested = false, lights_requested = false;
   mutable const camera* uploaded_for  = nullptr;
   mutable double        upload_seconds = 0;  // wall-clock of the last flatten + yh_upload_scene (init_bvh + init_lights of the reference), for the command line's --timing
+  // What the scene last uploaded, flattened: init_state compares it with the scene as it is now, so that an edit made through the set_*
+  // functions after an init_state takes effect as it does in the reference, which reads these structs live (see init_state). How many
+  // init_state calls uploaded the whole scene and how many only passed edits on:
+  mutable detail::flat_scene uploaded;
+  mutable int                uploads = 0, edits = 0;
 };
 struct state {  // pt.h:426-429; `render` is refreshed by trace_samples
   int                width = 0, height = 0, samples = 0;
@@ -327,13 +393,14 @@ inline void set_emission(environment* e, const vec3f& em, texture* tex = nullptr
 // the BVHs (init_bvh, pt.cpp:755-818) and the lights (init_lights,
 // pt.cpp:1695-1740) in that one call. The camera is part of the uploaded scene,
 // so the upload happens in init_state, the first call that receives it.
-inline void upload_scene(const scene* sc, const camera* cam) {
-  std::vector<yh_shape>       shapes;
-  std::vector<yh_material>    materials;
-  std::vector<yh_material_maps> maps;
-  std::vector<yh_object>      objects;
-  std::vector<yh_environment> envs;
-  std::vector<yh_texture>     textures;
+inline detail::flat_scene flatten_scene(const scene* sc, const camera* cam) {
+  detail::flat_scene flat;
+  auto &shapes = flat.shapes;
+  auto &materials = flat.materials;
+  auto &maps = flat.maps;
+  auto &objects = flat.objects;
+  auto &envs = flat.environments;
+  auto &textures = flat.textures;
   std::vector<int>            texture_slot(sc->textures.size(), 0);  // 1-based slot in `textures`, 0 = not a material texture
   auto material_texture = [&](const texture* t) -> int {
     if (!t) return 0;
@@ -405,18 +472,36 @@ inline void upload_scene(const scene* sc, const camera* cam) {
     }
     envs.push_back(o);
   }
-  yh_scene_desc d{};
-  d.num_shapes = (int)shapes.size(), d.shapes = shapes.data();
-  d.num_materials = (int)materials.size(), d.materials = materials.data();
-  d.num_objects = (int)objects.size(), d.objects = objects.data();
-  d.num_environments = (int)envs.size(), d.environments = envs.data();
-  d.num_textures = (int)textures.size(), d.textures = textures.data();
   if (!cam) throw std::runtime_error("yhair: no camera");
-  memcpy(d.camera.frame, &cam->frame, 48);
-  d.camera.lens = cam->lens, d.camera.film[0] = cam->film.x, d.camera.film[1] = cam->film.y;
-  d.camera.focus = cam->focus, d.camera.aperture = cam->aperture;
-  detail::for_each_context([&](yh_context* ctx, int) { return yh_upload_scene_maps(ctx, &d, maps.data()); });  // the scene is replicated
+  auto& c = flat.camera;
+  memcpy(c.frame, &cam->frame, 48);
+  c.lens = cam->lens, c.film[0] = cam->film.x, c.film[1] = cam->film.y;
+  c.focus = cam->focus, c.aperture = cam->aperture;
+  return flat;
+}
+inline void upload_scene(const scene* sc, const camera* cam, detail::flat_scene&& flat) {
+  const yh_scene_desc d = flat.desc();
+  detail::for_each_context([&](yh_context* ctx, int) { return yh_upload_scene_maps(ctx, &d, flat.maps.data()); });  // the scene is replicated
+  sc->uploaded     = std::move(flat);
   sc->uploaded_for = cam;
+}
+inline void upload_scene(const scene* sc, const camera* cam) { upload_scene(sc, cam, flatten_scene(sc, cam)); }
+// Passes the differences classify_edit found on to every context. false: a context refused one (YH_E_INVALID: the contexts that took
+// theirs are brought in line by the upload that follows).
+inline bool update_scene(const scene* sc, const camera* cam, detail::flat_scene&& flat, unsigned kind) {
+  std::atomic<bool> refused{false};  // (every context from a thread of its own)
+  detail::for_each_context([&](yh_context* ctx, int) {
+    int rc = YH_OK;
+    if (!rc && (kind & detail::edit_camera)) rc = yh_update_camera(ctx, &flat.camera);
+    if (!rc && (kind & detail::edit_materials)) rc = yh_update_materials(ctx, 0, (int)flat.materials.size(), flat.materials.data());
+    if (!rc && (kind & detail::edit_environments)) rc = yh_update_environments(ctx, (int)flat.environments.size(), flat.environments.data());
+    if (rc == YH_E_INVALID) refused = true, rc = YH_OK;
+    return rc;
+  });
+  if (refused) return false;
+  sc->uploaded     = std::move(flat);
+  sc->uploaded_for = cam;
+  return true;
 }
 // init_bvh / init_lights: same signatures as pt.h:207-217. They mark the scene;
 // the build itself runs inside the upload (see upload_scene).
@@ -434,10 +519,24 @@ inline void init_state(state* st, const scene* sc, const camera* cam, const trac
     throw std::runtime_error("sampler unknown");  // pt.cpp:1669
   if (!sc->bvh_requested || !sc->lights_requested)
     throw std::runtime_error("yhair: init_state before init_bvh / init_lights");
-  if (sc->uploaded_for != cam) {
-    const auto t0 = std::chrono::steady_clock::now();
-    upload_scene(sc, cam);
-    sc->upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+  // The reference reads its scene structs at every sample, so whatever a caller set since the last init_state is in force from here on
+  // (apps/ysceneitraces/ysceneitraces.cpp:392-410: the camera's frame, then reset_display). The contexts hold a flattened copy: compare.
+  // Nothing changed: nothing to do. Only what the yh_update_* calls accept (camera fields, material fields, the environments' frames
+  // and emission): those calls, which keep every tree. Anything else — an object's frame, a shape's arrays, a texture, an emission
+  // turned on or off, init_bvh / init_lights called again — is the whole upload.
+  {
+    auto     flat = flatten_scene(sc, cam);
+    unsigned kind = sc->uploaded_for ? detail::classify_edit(sc->uploaded, flat) : (unsigned)detail::edit_upload;
+    if (kind != detail::edit_none && !(kind & detail::edit_upload)) {
+      if (update_scene(sc, cam, std::move(flat), kind)) sc->edits++;
+      else kind = detail::edit_upload, flat = flatten_scene(sc, cam);
+    }
+    if (kind & detail::edit_upload) {
+      const auto t0 = std::chrono::steady_clock::now();
+      upload_scene(sc, cam, std::move(flat));
+      sc->upload_seconds = std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
+      sc->uploads++;
+    }
   }
   st->device_params = yh_trace_params{params.resolution, params.bounces, params.clamp, params.seed, (int)params.shader, params.hair_exact ? 1 : 0};
   detail::for_each_context([&](yh_context* ctx, int i) {

@@ -9,18 +9,50 @@
 //
 // Same flags as the app (ysceneitraces.cpp:313-327): --camera, --resolution,-r, --samples,-s, --shader,-t,
 // --bounces,-b, --clamp, --output,-o, positional scene. Extensions: --pratio (trace_params::pratio, default
-// 8), --preview-image FILE, --stop-after-ms N, --seed, --device, --gpus / --devices.
+// 8), --preview-image FILE, --stop-after-ms N, --seed, --device, --gpus / --devices, and --turntable STEPS: the app's one gesture, the
+// camera orbit (ysceneitraces.cpp:392-410: update_turntable on app->camera->frame, then reset_display), headless — after the first
+// reset_display, STEPS - 1 times a rotation by 2 pi / STEPS followed by reset_display again; step k is saved as <stem>-<kkk><ext>.
 #include <atomic>
 #include <chrono>
+#include <cmath>
 #include <future>
 #include <thread>
 
 #include "yscene_cli.h"
 
+// update_turntable for a frame parametrization with a rotation only (yocto_math.h:5072-5085) and the lookat_frame it calls (:3229-3239)
+static vec3f operator-(const vec3f& a, const vec3f& b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
+static vec3f operator+(const vec3f& a, const vec3f& b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
+static vec3f operator*(const vec3f& a, float b) { return {a.x * b, a.y * b, a.z * b}; }
+static vec3f cross(const vec3f& a, const vec3f& b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
+static float length(const vec3f& a) { return std::sqrt(a.x * a.x + a.y * a.y + a.z * a.z); }
+static vec3f normalize(const vec3f& a) {
+  auto l = length(a);
+  return (l != 0) ? vec3f{a.x / l, a.y / l, a.z / l} : a;
+}
+static frame3f lookat_frame(const vec3f& eye, const vec3f& center, const vec3f& up) {
+  auto w = normalize(eye - center);
+  auto u = normalize(cross(up, w));
+  auto v = normalize(cross(w, u));
+  return {u, v, w, eye};
+}
+static void update_turntable(frame3f& frame, float& focus, const vec2f& rotate) {
+  if (rotate.x == 0 && rotate.y == 0) return;
+  const float pif = (float)3.14159265358979323846;
+  auto phi   = std::atan2(frame.z.z, frame.z.x) + rotate.x;
+  auto theta = std::acos(frame.z.y) + rotate.y;
+  theta      = std::min(std::max(theta, 0.001f), pif - 0.001f);
+  auto new_z = vec3f{std::sin(theta) * std::cos(phi), std::cos(theta), std::sin(theta) * std::sin(phi)};
+  auto new_center = frame.o - frame.z * focus;
+  auto new_o      = new_center + new_z * focus;
+  frame           = lookat_frame(new_o, new_center, {0, 1, 0});
+  focus           = length(new_o - new_center);
+}
+
 int main(int argc, const char* argv[]) {
   auto        params = ptr::trace_params{};
   std::string camera_name, imagename = "out.hdr", preview_name, filename, shader = "path";
-  int         stop_after_ms = -1, gpus = 1, first_device = 0;
+  int         stop_after_ms = -1, gpus = 1, first_device = 0, turntable = 0;
   std::string device_list;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -31,7 +63,7 @@ int main(int argc, const char* argv[]) {
     if (a == "--help" || a == "-h") {
       printf("usage: ysceneitraces [--camera NAME] [--resolution,-r N] [--samples,-s N] [--shader,-t naive|path|eyelight|normal]\n"
              "                     [--bounces,-b N] [--clamp F] [--output,-o FILE] [--pratio N] [--preview-image FILE]\n"
-             "                     [--stop-after-ms N] [--seed N] [--device N] [--gpus N] [--devices A,B,..] scene\n"
+             "                     [--stop-after-ms N] [--seed N] [--device N] [--gpus N] [--devices A,B,..] [--turntable STEPS] scene\n"
              "Progressive path tracing of hair scenes on MI355X (headless: preview pass, then samples until done or stopped)\n");
       return 0;
     } else if (a == "--camera") camera_name = next();
@@ -48,6 +80,7 @@ int main(int argc, const char* argv[]) {
     else if (a == "--device") first_device = atoi(next().c_str());
     else if (a == "--gpus") gpus = std::max(1, atoi(next().c_str()));
     else if (a == "--devices") device_list = next();
+    else if (a == "--turntable") turntable = std::max(1, atoi(next().c_str()));
     else if (!a.empty() && a[0] == '-') print_fatal("unknown option " + a);
     else filename = a;
   }
@@ -70,6 +103,9 @@ int main(int argc, const char* argv[]) {
     ptr::init_lights(scene.get(), params);
 
     // ---- reset_display (ysceneitraces.cpp:255-300) -------------------------------------------------------
+    std::chrono::steady_clock::time_point t_edit;  // --turntable: when the camera was moved
+    auto reset_display = [&](const std::string& imagename, bool orbit) {
+    const int uploads0 = scene->uploads;
     auto render_state = std::make_unique<ptr::state>();
     ptr::init_state(render_state.get(), scene.get(), camera, params);
     const int          W = render_state->width, H = render_state->height;
@@ -89,6 +125,9 @@ int main(int argc, const char* argv[]) {
       }
     printf("preview: %dx%d at 1 spp upscaled to %dx%d, %.1f ms\n", pstate->width, pstate->height, W, H,
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
+    if (orbit)
+      printf("edit to preview: %.1f ms (%s)\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_edit).count(),
+          scene->uploads > uploads0 ? "the scene was uploaded again" : "the camera alone was passed on");
     if (!preview_name.empty() && yh_save_image(preview_name.c_str(), W, H, (const float*)render.data(), error, sizeof(error)) != YH_OK)
       print_fatal(error);
     // start render
@@ -112,6 +151,23 @@ int main(int argc, const char* argv[]) {
     printf("render: %d of %d samples in %.3fs%s\n", (int)render_counter, params.samples, dt, render_stop ? " (stopped)" : "");
     if (yh_save_image(imagename.c_str(), W, H, (const float*)render.data(), error, sizeof(error)) != YH_OK) print_fatal(error);
     printf("save image: %s\n", imagename.c_str());
+    };
+    if (turntable <= 0) {
+      reset_display(imagename, false);
+    } else {  // the orbit: one turn in `turntable` steps, step k saved as <stem>-<kkk><ext>
+      const size_t slash = imagename.find_last_of('/'), dot = imagename.find_last_of('.');
+      const bool   ext   = dot != std::string::npos && (slash == std::string::npos || dot > slash);
+      const std::string stem = ext ? imagename.substr(0, dot) : imagename, suffix = ext ? imagename.substr(dot) : "";
+      for (int k = 0; k < turntable; k++) {
+        if (k > 0) {
+          t_edit = std::chrono::steady_clock::now();
+          update_turntable(camera->frame, camera->focus, {2 * (float)3.14159265358979323846 / turntable, 0});
+        }
+        char number[16];
+        snprintf(number, sizeof(number), "-%03d", k);
+        reset_display(stem + number + suffix, k > 0);
+      }
+    }
   } catch (const std::exception& e) {
     print_fatal(e.what());
   }

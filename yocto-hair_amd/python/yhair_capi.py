@@ -139,6 +139,10 @@ _SIGS = {
     "yh_version": (C.c_char_p, []),
     "yh_upload_scene": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc)]),
     "yh_upload_scene_maps": (C.c_int, [C.c_void_p, C.POINTER(SceneDesc), C.POINTER(MaterialMaps)]),
+    "yh_update_camera": (C.c_int, [C.c_void_p, C.POINTER(Camera)]),
+    "yh_update_materials": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Material)]),
+    "yh_update_environments": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Environment)]),
+    "yh_download_display": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     "yh_init_state": (C.c_int, [C.c_void_p, C.POINTER(TraceParams)]),
     "yh_image_size": (C.c_int, [C.c_void_p, c_int_p, c_int_p]),
     "yh_set_shard": (C.c_int, [C.c_void_p, C.c_int, C.c_int]),
@@ -299,6 +303,24 @@ class Context:
         else:
             self._chk(self.lib.yh_upload_scene_maps(self.h, desc, C.cast(maps, C.POINTER(MaterialMaps))))
 
+    # edits of the uploaded scene that keep its trees (include/yhair.h): the image state is gone afterwards, call init_state again
+    def update_camera(self, camera):
+        """yh_update_camera: `camera` is a Camera (e.g. a copy of desc.contents.camera with fields changed)."""
+        self._chk(self.lib.yh_update_camera(self.h, C.byref(camera) if camera is not None else None))
+
+    def update_materials(self, first, materials):
+        """yh_update_materials: rows [first, first + len(materials)) of the material table; `materials` is a ctypes array of
+        Material, or a list of them."""
+        if materials is not None and not isinstance(materials, C.Array):
+            materials = (Material * len(materials))(*materials)
+        self._chk(self.lib.yh_update_materials(self.h, first, len(materials) if materials is not None else 0, materials))
+
+    def update_environments(self, environments):
+        """yh_update_environments: frame and emission of every environment (a ctypes array of Environment, or a list)."""
+        if environments is not None and not isinstance(environments, C.Array):
+            environments = (Environment * len(environments))(*environments)
+        self._chk(self.lib.yh_update_environments(self.h, len(environments) if environments is not None else 0, environments))
+
     def set_shard(self, rank, world):
         self._chk(self.lib.yh_set_shard(self.h, rank, world))
 
@@ -363,6 +385,12 @@ class Context:
     def download(self):
         img = np.zeros((self.height, self.width, 4), np.float32)
         self._chk(self.lib.yh_download(self.h, fptr(img)))
+        return img
+
+    def download_display(self, exposure=0.0, filmic=False, srgb=True):
+        """yh_download_display: the tone-mapped image as (H, W, 4) bytes, made on the device."""
+        img = np.zeros((self.height, self.width, 4), np.uint8)
+        self._chk(self.lib.yh_download_display(self.h, exposure, int(filmic), int(srgb), img.ctypes.data_as(C.POINTER(C.c_uint8))))
         return img
 
     def download_rng(self):
