@@ -234,7 +234,9 @@ const char* yh_version(void);
  * kernel variants (their tables do not fit the LDS budget): slower, same pixels. The scene level of a scene of more than ~46 objects
  * — what an instanced scene file expands to — is collapsed like a shape's tree, two levels per node, and walked as 4-wide nodes out of the same
  * array, in the reference's visiting order: four more units per scene node, about a third of a node per object (4096 objects: ~1 400
- * nodes), counted in the limits above. The one-lane kernels (the streaming integrator
+ * nodes) — and the upload RESERVES four units per OBJECT there (a wide node stands for an internal node of the binary tree, of which
+ * a tree over n objects has at most n - 1), so that yh_update_objects can write the nodes of any tree over the same objects; the
+ * reservation is what counts in the limits above. The one-lane kernels (the streaming integrator
  * of dense hair, large closest-hit batches) address that array with 32-bit byte offsets: beyond 4 GB of it (about fifty million
  * segments) they are not candidates and the quad kernels render — same pixels.                                                */
 int yh_upload_scene(yh_context* ctx, const yh_scene_desc* scene);
@@ -244,7 +246,7 @@ int yh_upload_scene(yh_context* ctx, const yh_scene_desc* scene);
  * outside [0, num_textures] is YH_E_INVALID and leaves the context's previous scene as it was.                     */
 int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* scene, const yh_material_maps* maps);
 
-/* EDITS OF THE UPLOADED SCENE that leave every acceleration structure as it is. The reference reads its scene structs live: its
+/* EDITS OF THE UPLOADED SCENE that leave every shape's acceleration structure as it is. The reference reads its scene structs live: its
  * interactive caller edits app->camera->frame in place and the next sample uses it (apps/ysceneitraces/ysceneitraces.cpp:392-410).
  * Here the description was flattened by yh_upload_scene, so an edit is a call:
  *   yh_update_camera        set_frame / set_lens / set_focus on a camera (yocto_pathtrace.h:97-104): the whole yh_camera;
@@ -252,25 +254,39 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* scene, const yh_m
  *                           `materials` holding `count` entries;
  *   yh_update_environments  set_frame / set_emission on an environment (yocto_pathtrace.h:172-174): frame and emission of every
  *                           environment; count must be the uploaded scene's num_environments; tex_width, tex_height and texels
- *                           are ignored (the texel cdf depends on neither the emission scale nor the frame).
+ *                           are ignored (the texel cdf depends on neither the emission scale nor the frame);
+ *   yh_update_objects       set_frame / set_material on an object (yocto_pathtrace.h:110-111): rows [first, first + count) of the
+ *                           object list, `objects` holding `count` entries. Shape trees live in object space, so no shape is touched:
+ *                           the rows' inverse frames and world boxes are made on the device, one lane per row, with the upload's own
+ *                           arithmetic (unit/objects.hip), the reference's scene-level tree over ALL world boxes is built again as the
+ *                           upload builds it, and with it the scene-level table sizes, the 4-wide scene nodes at the front of the
+ *                           traversal array (scenes of more than ~46 objects) and the stack depths.
  * CONTRACT. After a successful call the context is, for every later call, indistinguishable in its results from a context that got
- * yh_upload_scene_maps of the edited description: pixels, RNG states, yh_lights_batch, yh_intersect_batch and yh_scene_once are the
- * same bits (the kernel variant, the once-per-ray form and the fingerprint of the kernel-trial record follow the edit). The image
- * state is gone, as after an upload: yh_trace_samples before a new yh_init_state returns YH_E_STATE, and that yh_init_state probes
- * and plans as for a new scene. The calls are blocking and need an uploaded scene (else YH_E_STATE). No device work or allocation is
- * proportional to the geometry: no tree, record, vertex array or light cdf is read, written or reallocated (1.6 M hair segments:
- * an upload builds for 41 ms on the device alone, an edit copies a few hundred bytes).
+ * yh_upload_scene_maps of the edited description: pixels, RNG states, yh_lights_batch, yh_intersect_batch, yh_intersect_plain_batch and
+ * yh_scene_once are the same bits (the kernel variant, the once-per-ray form and the fingerprint of the kernel-trial record follow the
+ * edit). The image state is gone, as after an upload: yh_trace_samples before a new yh_init_state returns YH_E_STATE, and that
+ * yh_init_state probes and plans as for a new scene. The calls are blocking and need an uploaded scene (else YH_E_STATE). No device
+ * work or allocation is proportional to the geometry: no shape's tree, record, vertex array or light cdf is read, written or
+ * reallocated (1.6 M hair segments: an upload builds for 41 ms on the device alone, an edit copies a few hundred bytes);
+ * yh_update_objects works and allocates in proportion to the number of OBJECTS.
  * REFUSED with YH_E_INVALID, a message that names the entry point, and the context exactly as it was (it goes on rendering the
- * earlier scene): a NULL argument; first / count outside the uploaded table; count != num_environments; a material or environment
- * whose emission changes between all-zero and not all-zero (the light list, init_lights, yocto_pathtrace.cpp:1695-1740, depends on
- * it and the shapes' host arrays were borrowed for the upload only); a material whose emission_tex, color_tex or scattering_tex
- * differs from the uploaded one (which texel copies exist was decided at the upload). The materials' maps (yh_material_maps) are
- * not editable.
- * OUT OF SCOPE, for all of which the answer stays a new upload: object frames (the scene-level tree, the wide scene nodes at the
- * front of the traversal array and the stack depths depend on them), geometry, textures and maps, turning emission on or off.   */
+ * earlier scene): a NULL argument (with count != 0); first / count outside the uploaded table; count != num_environments; a material
+ * or environment whose emission changes between all-zero and not all-zero (the light list, init_lights,
+ * yocto_pathtrace.cpp:1695-1740, depends on it and the shapes' host arrays were borrowed for the upload only) — and likewise an object
+ * whose new material and uploaded one differ in that; a material whose emission_tex, color_tex or scattering_tex differs from the
+ * uploaded one (which texel copies exist was decided at the upload); an object row whose shape differs from the uploaded row's or
+ * whose material lies outside the uploaded table. Two refusals of yh_update_objects follow from the RESULT of the edit: the tree
+ * over the moved objects is too deep for the traversal stack (the upload's "BVH too deep" check), or the scene level changes its
+ * form between the kernels' LDS table and 4-wide nodes in the traversal array (the table's size counts the scene tree's nodes, so a
+ * scene of about 45 objects can cross the 10 KB line by moving them): room for wide scene nodes exists only where the upload put it,
+ * and the answer is a new upload. The materials' maps (yh_material_maps) are not editable. A HIP error once an edit has begun to
+ * write returns YH_E_DEVICE and leaves the context without a scene, as a failed upload does.
+ * OUT OF SCOPE, for all of which the answer stays a new upload: changing an object's shape, adding or removing objects, geometry
+ * (vertex edits), textures and maps, turning emission on or off.                                                                  */
 int yh_update_camera(yh_context* ctx, const yh_camera* camera);
 int yh_update_materials(yh_context* ctx, int first, int count, const yh_material* materials);
 int yh_update_environments(yh_context* ctx, int count, const yh_environment* environments);
+int yh_update_objects(yh_context* ctx, int first, int count, const yh_object* objects);
 
 /* init_state (yocto_pathtrace.cpp:1931-1946): image size from the camera film
  * and params->resolution, zeroed accumulators, per-pixel PCG32 streams

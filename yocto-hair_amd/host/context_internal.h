@@ -8,8 +8,8 @@
 //   trace_launch.cpp   yh_init_state (pt.cpp:1931-1946) and the launches: yh_trace_samples and friends
 //   gather.cpp         tile packing and the one collective (yh_gather_framebuffer: RCCL or peer copies)
 //   batch_api.cpp      the unit-level batch entry points (hair BSDF, intersection, BVH build, curves, self-tests)
-//   scene_edit.cpp     edits of an uploaded scene that leave its trees alone (yh_update_camera / _materials / _environments) and
-//                      yh_download_display
+//   scene_edit.cpp     edits of an uploaded scene that leave its shapes' trees alone (yh_update_camera / _materials / _environments /
+//                      _objects: the last one builds the scene-level tree again) and yh_download_display
 #ifndef YH_CONTEXT_INTERNAL_H_
 #define YH_CONTEXT_INTERNAL_H_
 #include <hip/hip_runtime_api.h>
@@ -37,6 +37,7 @@
 #include <vector>
 
 #include "../csrc/yh_device.h"
+#include "../unit/object_math.h"  // F3 and its helpers, inverse_frame, transform_point, transform_bbox, padded_world_box: shared with the device
 #include "bvh_build.h"
 #include "deadline.h"
 #include "yhair.h"
@@ -85,6 +86,9 @@ int yhk_lights_lanes(const yhd_scene* sc, const yhd_scene* sc_dev, int n, const 
     unsigned int* stack_ovf, int ovf_entries, float* out, hipStream_t stream);
 int yhk_selftest(int, float, float, uint64_t, uint64_t, int, const float*, double*, unsigned int*, hipStream_t);
 int yhk_display(const yhd_state*, int samples, float exposure, int filmic, int srgb, void* rgba8, hipStream_t);  // unit/display.hip
+// unit/objects.hip (yh_update_objects): a lane per row of `rows` (yh_object, device memory); root6 = per shape its root box, 6 floats; writes
+// frame, inv_frame, material and the padded world box into objects[0 .. count) unless NULL, and the world box proper, 6 floats per row, to boxes6
+int yhk_object_rows(int count, const void* rows, const float* root6, void* objects, float* boxes6, hipStream_t);
 }
 
 // A device allocation owned by the context.
@@ -107,40 +111,6 @@ namespace {
 
 
 const float pif = (float)3.14159265358979323846;
-
-// ---- tiny host vector helpers with the reference's operation order --------
-struct F3 {
-  float x, y, z;
-};
-F3    operator+(F3 a, F3 b) { return {a.x + b.x, a.y + b.y, a.z + b.z}; }
-F3    operator-(F3 a, F3 b) { return {a.x - b.x, a.y - b.y, a.z - b.z}; }
-F3    operator-(F3 a) { return {-a.x, -a.y, -a.z}; }
-F3    operator*(F3 a, float b) { return {a.x * b, a.y * b, a.z * b}; }
-float dot(F3 a, F3 b) { return a.x * b.x + a.y * b.y + a.z * b.z; }
-F3    cross(F3 a, F3 b) { return {a.y * b.z - a.z * b.y, a.z * b.x - a.x * b.z, a.x * b.y - a.y * b.x}; }
-float fmin_(float a, float b) { return (a < b) ? a : b; }
-float fmax_(float a, float b) { return (a > b) ? a : b; }
-F3    ld3(const float* p) { return {p[0], p[1], p[2]}; }
-void  st3(float* p, F3 a) { p[0] = a.x, p[1] = a.y, p[2] = a.z; }
-
-// inverse(frame, non_rigid = true) (math.h:2877-2885, 2721-2741)
-void inverse_frame(const float* f, bool non_rigid, float* out) {
-  F3 x = ld3(f), y = ld3(f + 3), z = ld3(f + 6), o = ld3(f + 9);
-  F3 rx, ry, rz;
-  if (non_rigid) {
-    F3    c0 = cross(y, z), c1 = cross(z, x), c2 = cross(x, y);
-    float det = dot(x, cross(y, z));
-    float s   = 1 / det;
-    rx = F3{c0.x, c1.x, c2.x} * s, ry = F3{c0.y, c1.y, c2.y} * s, rz = F3{c0.z, c1.z, c2.z} * s;
-  } else {
-    rx = {x.x, y.x, z.x}, ry = {x.y, y.y, z.y}, rz = {x.z, y.z, z.z};
-  }
-  F3 ro = -(rx * o.x + ry * o.y + rz * o.z);
-  st3(out, rx), st3(out + 3, ry), st3(out + 6, rz), st3(out + 9, ro);
-}
-F3 transform_point(const float* f, F3 b) {
-  return ld3(f) * b.x + ld3(f + 3) * b.y + ld3(f + 6) * b.z + ld3(f + 9);
-}
 
 // PCG32 (math.h:1396-1442) for init_state and the self-test drivers
 struct Rng {
@@ -239,6 +209,13 @@ struct yh_context {
   bool                          big_lights = false;
   yh_camera                     key_camera{};
   std::vector<unsigned char>    key_geometry, key_envs;
+  // ... and what yh_update_objects needs of the upload: every shape's root box (on the device too, 6 floats per shape: unit/objects.hip
+  // reads it), the deepest shape tree as 4- / 8- / 16-wide nodes, every object's world box (the scene tree is built over all of them),
+  // and how many 4-wide scene nodes the front of the lane blob has room for (0: the scene level is not walked from there)
+  std::vector<yhh::Box>         h_shape_roots, h_obj_boxes;
+  DevBuf                        d_shape_roots;
+  int                           max_shape_depth = 0, max_shape_depth8 = 0, max_shape_depth16 = 0;
+  int                           scene_wide_room = 0;
   // state
   bool             have_state = false;
   yhd_state        state{};
@@ -354,5 +331,12 @@ bool make_material_rows(const yh_material* materials, const yh_material_maps* ma
 void settle_scene_variant(const yh_context* ctx, yhd_scene& sc, bool general_rows);
 uint64_t scene_fingerprint(const yh_context* ctx);
 void forget_image_of_scene(yh_context* ctx);
+// scene_upload.cpp, shared with yh_update_objects: the levels of a host-built tree as the device builder reports them (false: more than 128);
+// whether a scene level of that size is walked as 4-wide nodes out of the lane blob (and the float4 count of its LDS table otherwise); what
+// the scene level adds to every traversal stack; and the three stack needs with the check every scene has to pass
+bool tree_levels(const yhh::Tree& tree, int& levels, int* level_first);
+bool scene_level_is_wide(int num_objects, int num_scene_nodes, int* lds_scene_f4);
+struct StackNeeds { int need, need8, need16; };
+StackNeeds stack_needs(bool scene_wide, int scene_wide_depth, int scene_tree_depth, int depth4, int depth8, int depth16);
 #pragma GCC visibility pop
 #endif

@@ -156,7 +156,7 @@ void forget_image_of_scene(yh_context* ctx) {
 
 // The levels of a host-built tree as the device builder reports them: their number and the first node of each (level_first[0 .. levels],
 // 130 entries). false: more than 128 levels.
-static bool tree_levels(const yhh::Tree& tree, int& levels, int* level_first) {
+bool tree_levels(const yhh::Tree& tree, int& levels, int* level_first) {
   std::vector<int> level(tree.nodes.size(), 0);
   for (size_t n = 0; n < tree.nodes.size(); n++)
     if (tree.nodes[n].internal) level[(size_t)tree.nodes[n].start] = level[(size_t)tree.nodes[n].start + 1] = level[n] + 1;
@@ -166,6 +166,23 @@ static bool tree_levels(const yhh::Tree& tree, int& levels, int* level_first) {
   for (int l = 0; l <= levels; l++) level_first[l] = num_nodes;
   for (size_t n = tree.nodes.size(); n-- > 0;) level_first[level[n]] = (int)n;
   return true;
+}
+
+// scene-level LDS table: objects (YH_OBJECT_F4 = 11 float4 each), scene BVH nodes (2 float4 each), primitive ids; up to 10 KB = 46
+// objects. A scene with more runs the GENERAL kernel variants, which read the table from memory, and walks its scene level as 4-wide
+// nodes out of the blob (an instanced scene has thousands of objects)
+bool scene_level_is_wide(int num_objects, int num_scene_nodes, int* lds_scene_f4) {
+  static_assert(sizeof(yhd_object) == 16 * YH_OBJECT_F4, "yhd_object is staged to LDS as float4");
+  *lds_scene_f4 = YH_OBJECT_F4 * num_objects + 2 * num_scene_nodes + (num_objects + 3) / 4;
+  return *lds_scene_f4 * 16 > 10240;
+}
+
+// a wide node pushes at most three entries and keeps the fourth in a register; the scene level: a binary node pushes one, a leaf up to three
+// objects — or, walked as 4-wide nodes, three per node and the leaf's three (the same quad form under every launch shape). An 8-wide node
+// pushes at most seven, a 16-wide one fifteen
+StackNeeds stack_needs(bool scene_wide, int scene_wide_depth, int scene_tree_depth, int depth4, int depth8, int depth16) {
+  const int scene_need = scene_wide ? 3 * scene_wide_depth + 4 : scene_tree_depth + 4;
+  return {scene_need + 3 * depth4 + 2, scene_need + 7 * depth8 + 2, scene_need + 15 * depth16 + 2};
 }
 
 int yh_upload_scene(yh_context* ctx, const yh_scene_desc* sd) { return yh_upload_scene_maps(ctx, sd, nullptr); }
@@ -379,26 +396,13 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
     auto& o = sd->objects[oi];
     if (o.shape < 0 || o.shape >= sd->num_shapes || o.material < 0 || o.material >= sd->num_materials)
       return fail(ctx, YH_E_INVALID, "object %d references a missing shape or material", oi);
-    // transform_bbox (math.h:3174-3185)
     const yhh::Box& b = info[o.shape].root;
-    float lo[3] = {std::numeric_limits<float>::max(), std::numeric_limits<float>::max(), std::numeric_limits<float>::max()};
-    float hi[3] = {std::numeric_limits<float>::lowest(), std::numeric_limits<float>::lowest(),
-        std::numeric_limits<float>::lowest()};
-    for (int c = 0; c < 8; c++) {
-      F3 corner = {(c & 4) ? b.max[0] : b.min[0], (c & 2) ? b.max[1] : b.min[1], (c & 1) ? b.max[2] : b.min[2]};
-      F3 t      = transform_point(o.frame, corner);
-      float tv[3] = {t.x, t.y, t.z};
-      for (int k = 0; k < 3; k++) lo[k] = fmin_(lo[k], tv[k]), hi[k] = fmax_(hi[k], tv[k]);
-    }
-    for (int k = 0; k < 3; k++) obj_boxes[oi].min[k] = lo[k], obj_boxes[oi].max[k] = hi[k];
+    transform_bbox(o.frame, b.min, b.max, obj_boxes[oi].min, obj_boxes[oi].max);  // (unit/object_math.h)
   }
   yhh::Tree scene_tree;
   yhh::build_bvh(scene_tree, obj_boxes);
-  // scene-level LDS table: objects (YH_OBJECT_F4 = 11 float4 each), scene BVH nodes (2 float4 each), primitive ids; up to 10 KB = 46
-  // objects (a scene with more runs the GENERAL kernel variants, which read the table from memory)
-  static_assert(sizeof(yhd_object) == 16 * YH_OBJECT_F4, "yhd_object is staged to LDS as float4");
-  const int  lds_scene_f4 = YH_OBJECT_F4 * sd->num_objects + 2 * (int)scene_tree.nodes.size() + (sd->num_objects + 3) / 4;
-  const bool scene_wide   = lds_scene_f4 * 16 > 10240;  // ... and walk the scene level as 4-wide nodes out of the blob (an instanced scene has thousands of objects)
+  int        lds_scene_f4 = 0;
+  const bool scene_wide   = scene_level_is_wide(sd->num_objects, (int)scene_tree.nodes.size(), &lds_scene_f4);
   DevBuf d_stree, d_sflag, d_sidx;
   int    scene_wide_count = 0, scene_wide_depth = 0;
   if (scene_wide) {
@@ -427,7 +431,10 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
   ctx->lane_shapes.assign((size_t)sd->num_shapes, yh_context::LaneShape{});
   long long U8 = 0, U16 = 0, blob_units = 0;
   {
-    long long at = 4ll * scene_wide_count;  // (in front of the test records: a scene node's offset stays below 2^27, what tells it from a scene leaf on a stack)
+    // (in front of the test records: a scene node's offset stays below 2^27, what tells it from a scene leaf on a stack. Room for as many
+    // nodes as the scene has objects: a wide node stands for an internal binary node, of which a tree over n objects has at most n - 1,
+    // so yh_update_objects can write the nodes of any tree over them; the slots behind scene_wide_count stay zero)
+    long long at = scene_wide ? 4ll * sd->num_objects : 0;
     for (int si = 0; si < sd->num_shapes; si++) {
       auto& L = ctx->lane_shapes[(size_t)si];
       L.kind = info[si].kind, L.num_nodes = info[si].wide_count[0], L.prim_base = info[si].prim_base, L.num_prims = info[si].num_prims;
@@ -475,13 +482,7 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
     d.elem_base = I.elem_base, d.has_normals = I.has_normals, d.material = o.material, d.has_texcoords = sd->shapes[o.shape].texcoords != nullptr;
     const auto& LS = ctx->lane_shapes[(size_t)o.shape];
     d.lane_root = (int)LS.node_off, d.lane_test = (int)LS.test_off, d.lane_root8 = (int)LS.node_off8, d.lane_root16 = (int)LS.node_off16;
-    {  // the object's world box with a margin a thousand times the rounding of either box test
-      const float *lo = obj_boxes[oi].min, *hi = obj_boxes[oi].max;
-      float ext = fmax_(fmax_(hi[0] - lo[0], hi[1] - lo[1]), hi[2] - lo[2]);
-      float eps = 1e-3f * ext + 1e-5f;
-      for (int k = 0; k < 3; k++) d.wbox_min[k] = lo[k] - eps, d.wbox_max[k] = hi[k] + eps;
-      d.wbox_min[3] = d.wbox_max[3] = 0;
-    }
+    padded_world_box(obj_boxes[oi].min, obj_boxes[oi].max, d.wbox_min, d.wbox_max);
   }
   // array offsets on the device are 32-bit float4 indices
   if (vpos.size() > (size_t)std::numeric_limits<int>::max()) return fail(ctx, YH_E_INVALID, "scene too large for 32-bit vertex offsets (%zu)", vpos.size());
@@ -489,16 +490,10 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
   for (auto& n : scene_tree.nodes) scene_nodes.push_back(node_lo(n)), scene_nodes.push_back(node_hi(n));
   int max_shape_depth = 0;
   for (auto& I : info) max_shape_depth = std::max(max_shape_depth, I.depth);
-  // a wide node pushes at most three entries and keeps the fourth in a register; the scene level: a binary node pushes one, a leaf up to three
-  // objects — or, walked as 4-wide nodes, three per node and the leaf's three (the same quad form under every launch shape)
-  const int scene_need = scene_wide ? 3 * scene_wide_depth + 4 : scene_tree.max_depth + 4;
-  ctx->stack_need = scene_need + 3 * max_shape_depth + 2;
-  int max_shape_depth8 = 0;
-  for (auto& I : info) max_shape_depth8 = std::max(max_shape_depth8, I.depth8);
-  ctx->stack_need8 = scene_need + 7 * max_shape_depth8 + 2;  // an 8-wide node pushes at most seven
-  int max_shape_depth16 = 0;
-  for (auto& I : info) max_shape_depth16 = std::max(max_shape_depth16, I.depth16);
-  ctx->stack_need16 = scene_need + 15 * max_shape_depth16 + 2;
+  int max_shape_depth8 = 0, max_shape_depth16 = 0;
+  for (auto& I : info) max_shape_depth8 = std::max(max_shape_depth8, I.depth8), max_shape_depth16 = std::max(max_shape_depth16, I.depth16);
+  const StackNeeds needs = stack_needs(scene_wide, scene_wide_depth, scene_tree.max_depth, max_shape_depth, max_shape_depth8, max_shape_depth16);
+  ctx->stack_need = needs.need, ctx->stack_need8 = needs.need8, ctx->stack_need16 = needs.need16;
   if (ctx->stack_need > yhk_stack_entries())
     return fail(ctx, YH_E_INVALID, "BVH too deep for the traversal stack (%d > %d)", ctx->stack_need, yhk_stack_entries());
   // ---- materials ---------------------------------------------------------
@@ -668,6 +663,9 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
   if ((rc = upload(ctx, ctx->d_textures, textures.data(), textures.size() * sizeof(yhd_texture)))) return rc;
   if ((rc = upload(ctx, ctx->d_tex_texels, tex_texels.data(), tex_texels.size() * 16))) return rc;
   if ((rc = upload(ctx, ctx->d_vtex, vtex.data(), vtex.size() * 4))) return rc;
+  std::vector<yhh::Box> shape_roots;  // (what yh_update_objects starts from: context_internal.h)
+  for (auto& I : info) shape_roots.push_back(I.root);
+  if ((rc = upload(ctx, ctx->d_shape_roots, shape_roots.data(), shape_roots.size() * sizeof(yhh::Box)))) return rc;
   if (any_maps) {
     if ((rc = upload(ctx, ctx->d_maps, mat_maps.data(), mat_maps.size() * sizeof(yhd_maps)))) return rc;
   } else {
@@ -720,6 +718,9 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
     for (int i = 0; i < sd->num_environments; i++) bytes(ctx->key_envs, &sd->environments[i], offsetof(yh_environment, texels));
     if (any_maps) ctx->h_maps.assign(maps, maps + sd->num_materials), ctx->h_dmaps = mat_maps;
     else ctx->h_maps.clear(), ctx->h_dmaps.clear();
+    ctx->h_shape_roots.swap(shape_roots), ctx->h_obj_boxes.swap(obj_boxes);
+    ctx->max_shape_depth = max_shape_depth, ctx->max_shape_depth8 = max_shape_depth8, ctx->max_shape_depth16 = max_shape_depth16;
+    ctx->scene_wide_room = scene_wide ? sd->num_objects : 0;
     ctx->scene_key = scene_fingerprint(ctx);
   }
   ctx->have_scene = true;

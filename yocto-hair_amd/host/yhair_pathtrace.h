@@ -110,8 +110,10 @@ struct flat_scene {
 // edit_environments — exactly the differences yh_update_camera / yh_update_materials / yh_update_environments accept
 // (include/yhair.h) — or edit_upload as soon as anything else differs: a shape's pointers or counts, an object (its frame too), a
 // texture, a map, the number of anything, a material's texture ids, an emission that turns on or off. No device, no context.
-enum : unsigned { edit_none = 0, edit_camera = 1, edit_materials = 2, edit_environments = 4, edit_upload = 8 };
-inline unsigned classify_edit(const flat_scene& was, const flat_scene& now) {
+// objects_too (EXTENSION, see set_object_edits): objects that differ in frame or material only are edit_objects, what
+// yh_update_objects accepts, unless the new material turns the object's emission on or off; an object's shape stays edit_upload.
+enum : unsigned { edit_none = 0, edit_camera = 1, edit_materials = 2, edit_environments = 4, edit_upload = 8, edit_objects = 16 };
+inline unsigned classify_edit(const flat_scene& was, const flat_scene& now, bool objects_too) {
   auto black = [](const float* e) { return e[0] == 0 && e[1] == 0 && e[2] == 0; };
   if (was.shapes.size() != now.shapes.size() || was.materials.size() != now.materials.size() || was.maps.size() != now.maps.size() ||
       was.objects.size() != now.objects.size() || was.environments.size() != now.environments.size() || was.textures.size() != now.textures.size())
@@ -126,13 +128,19 @@ inline unsigned classify_edit(const flat_scene& was, const flat_scene& now) {
     const yh_texture &a = was.textures[i], &b = now.textures[i];
     if (a.width != b.width || a.height != b.height || a.is_byte != b.is_byte || a.pixels != b.pixels) return edit_upload;
   }
+  unsigned kind = edit_none;
   for (size_t i = 0; i < now.objects.size(); i++) {
     const yh_object &a = was.objects[i], &b = now.objects[i];
-    if (memcmp(a.frame, b.frame, 48) || a.shape != b.shape || a.material != b.material) return edit_upload;
+    if (a.shape != b.shape) return edit_upload;
+    if (!memcmp(a.frame, b.frame, 48) && a.material == b.material) continue;
+    if (!objects_too) return edit_upload;
+    const size_t nm = now.materials.size();
+    if (a.material < 0 || b.material < 0 || (size_t)a.material >= nm || (size_t)b.material >= nm) return edit_upload;
+    if (black(was.materials[(size_t)a.material].emission) != black(now.materials[(size_t)b.material].emission)) return edit_upload;  // the light list changes
+    kind |= edit_objects;
   }
   static_assert(sizeof(yh_material_maps) == 6 * sizeof(int) && sizeof(yh_material) == 30 * 4 && sizeof(yh_camera) == 17 * 4, "compared as bytes: no padding");
   if (!now.maps.empty() && memcmp(was.maps.data(), now.maps.data(), sizeof(yh_material_maps) * now.maps.size())) return edit_upload;
-  unsigned kind = edit_none;
   for (size_t i = 0; i < now.materials.size(); i++) {
     const yh_material &a = was.materials[i], &b = now.materials[i];
     if (!memcmp(&a, &b, sizeof(a))) continue;
@@ -147,6 +155,7 @@ inline unsigned classify_edit(const flat_scene& was, const flat_scene& now) {
   if (memcmp(&was.camera, &now.camera, sizeof(yh_camera))) kind |= edit_camera;
   return kind;
 }
+inline unsigned classify_edit(const flat_scene& was, const flat_scene& now) { return classify_edit(was, now, false); }
 // the state whose pixels the contexts hold (see init_state / trace_samples)
 inline const void*& bound_state() {
   static const void* st = nullptr;
@@ -299,6 +308,7 @@ struct scene {
   // init_state calls uploaded the whole scene and how many only passed edits on:
   mutable detail::flat_scene uploaded;
   mutable int                uploads = 0, edits = 0;
+  bool                       object_edits = false;  // EXTENSION (set_object_edits): object frames and materials go through yh_update_objects
 };
 struct state {  // pt.h:426-429; `render` is refreshed by trace_samples
   int                width = 0, height = 0, samples = 0;
@@ -387,6 +397,11 @@ inline void set_positions(shape* s, std::vector<vec3f>&& v) { s->positions = std
 inline void set_normals(shape* s, std::vector<vec3f>&& v) { s->normals = std::move(v); }
 inline void set_radius(shape* s, std::vector<float>&& v) { s->radius = std::move(v); }
 inline void set_frame(environment* e, const frame3f& f) { e->frame = f; }
+// EXTENSION (no reference counterpart: the reference reads every struct live and has nothing to opt into). By default an object whose
+// frame or material changed since the last init_state costs the whole upload at the next one; with `on`, such objects are passed on
+// through yh_update_objects, which keeps every shape's tree and builds the scene-level tree again (include/yhair.h). What that call
+// refuses — an object's shape, emission on or off, a tree too deep, a scene level that changes its form — falls back to the upload.
+inline void set_object_edits(scene* s, bool on) { s->object_edits = on; }
 inline void set_emission(environment* e, const vec3f& em, texture* tex = nullptr) { e->emission = em, e->emission_tex = tex; }
 
 // Flattens the scene graph into a yh_scene_desc and uploads it; the C ABI builds
@@ -495,6 +510,7 @@ inline bool update_scene(const scene* sc, const camera* cam, detail::flat_scene&
     if (!rc && (kind & detail::edit_camera)) rc = yh_update_camera(ctx, &flat.camera);
     if (!rc && (kind & detail::edit_materials)) rc = yh_update_materials(ctx, 0, (int)flat.materials.size(), flat.materials.data());
     if (!rc && (kind & detail::edit_environments)) rc = yh_update_environments(ctx, (int)flat.environments.size(), flat.environments.data());
+    if (!rc && (kind & detail::edit_objects)) rc = yh_update_objects(ctx, 0, (int)flat.objects.size(), flat.objects.data());
     if (rc == YH_E_INVALID) refused = true, rc = YH_OK;
     return rc;
   });
@@ -522,11 +538,12 @@ inline void init_state(state* st, const scene* sc, const camera* cam, const trac
   // The reference reads its scene structs at every sample, so whatever a caller set since the last init_state is in force from here on
   // (apps/ysceneitraces/ysceneitraces.cpp:392-410: the camera's frame, then reset_display). The contexts hold a flattened copy: compare.
   // Nothing changed: nothing to do. Only what the yh_update_* calls accept (camera fields, material fields, the environments' frames
-  // and emission): those calls, which keep every tree. Anything else — an object's frame, a shape's arrays, a texture, an emission
-  // turned on or off, init_bvh / init_lights called again — is the whole upload.
+  // and emission; with set_object_edits, the objects' frames and materials): those calls, which keep every shape's tree. Anything else
+  // — an object's frame without the opt-in, a shape's arrays, a texture, an emission turned on or off, init_bvh / init_lights called
+  // again — is the whole upload.
   {
     auto     flat = flatten_scene(sc, cam);
-    unsigned kind = sc->uploaded_for ? detail::classify_edit(sc->uploaded, flat) : (unsigned)detail::edit_upload;
+    unsigned kind = sc->uploaded_for ? detail::classify_edit(sc->uploaded, flat, sc->object_edits) : (unsigned)detail::edit_upload;
     if (kind != detail::edit_none && !(kind & detail::edit_upload)) {
       if (update_scene(sc, cam, std::move(flat), kind)) sc->edits++;
       else kind = detail::edit_upload, flat = flatten_scene(sc, cam);

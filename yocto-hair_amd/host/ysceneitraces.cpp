@@ -53,6 +53,7 @@ int main(int argc, const char* argv[]) {
   auto        params = ptr::trace_params{};
   std::string camera_name, imagename = "out.hdr", preview_name, filename, shader = "path";
   int         stop_after_ms = -1, gpus = 1, first_device = 0, turntable = 0;
+  bool        turn_objects = false;
   std::string device_list;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -63,7 +64,7 @@ int main(int argc, const char* argv[]) {
     if (a == "--help" || a == "-h") {
       printf("usage: ysceneitraces [--camera NAME] [--resolution,-r N] [--samples,-s N] [--shader,-t naive|path|eyelight|normal]\n"
              "                     [--bounces,-b N] [--clamp F] [--output,-o FILE] [--pratio N] [--preview-image FILE]\n"
-             "                     [--stop-after-ms N] [--seed N] [--device N] [--gpus N] [--devices A,B,..] [--turntable STEPS] scene\n"
+             "                     [--stop-after-ms N] [--seed N] [--device N] [--gpus N] [--devices A,B,..] [--turntable STEPS [--turntable-objects]] scene\n"
              "Progressive path tracing of hair scenes on MI355X (headless: preview pass, then samples until done or stopped)\n");
       return 0;
     } else if (a == "--camera") camera_name = next();
@@ -81,10 +82,12 @@ int main(int argc, const char* argv[]) {
     else if (a == "--gpus") gpus = std::max(1, atoi(next().c_str()));
     else if (a == "--devices") device_list = next();
     else if (a == "--turntable") turntable = std::max(1, atoi(next().c_str()));
+    else if (a == "--turntable-objects") turn_objects = true;
     else if (!a.empty() && a[0] == '-') print_fatal("unknown option " + a);
     else filename = a;
   }
   if (filename.empty()) print_fatal("missing scene");
+  if (turn_objects && turntable <= 0) print_fatal("--turntable-objects needs --turntable STEPS");
   yh_set_trial_cache_dir(yh_default_trial_cache_dir());  // the command line keeps its kernel-trial record on disk (include/yhair.h); a library caller has to ask
   set_devices(first_device, gpus, device_list);
   bool known = false;
@@ -127,7 +130,7 @@ int main(int argc, const char* argv[]) {
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
     if (orbit)
       printf("edit to preview: %.1f ms (%s)\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_edit).count(),
-          scene->uploads > uploads0 ? "the scene was uploaded again" : "the camera alone was passed on");
+          scene->uploads > uploads0 ? "the scene was uploaded again" : turn_objects ? "the objects alone were passed on" : "the camera alone was passed on");
     if (!preview_name.empty() && yh_save_image(preview_name.c_str(), W, H, (const float*)render.data(), error, sizeof(error)) != YH_OK)
       print_fatal(error);
     // start render
@@ -158,8 +161,21 @@ int main(int argc, const char* argv[]) {
       const size_t slash = imagename.find_last_of('/'), dot = imagename.find_last_of('.');
       const bool   ext   = dot != std::string::npos && (slash == std::string::npos || dot > slash);
       const std::string stem = ext ? imagename.substr(0, dot) : imagename, suffix = ext ? imagename.substr(dot) : "";
+      std::vector<std::pair<ptr::object*, frame3f>> turning;  // --turntable-objects: what turns, with its loaded frame
+      if (turn_objects) {
+        ptr::set_object_edits(scene.get(), true);
+        for (auto& o : scene->objects) {
+          const auto& e = o->material_->emission;
+          if (e.x == 0 && e.y == 0 && e.z == 0) turning.push_back({o.get(), o->frame});
+        }
+      }
       for (int k = 0; k < turntable; k++) {
-        if (k > 0) {
+        if (k > 0 && turn_objects) {
+          t_edit = std::chrono::steady_clock::now();
+          const float a = 2 * (float)3.14159265358979323846 * k / turntable, c = std::cos(a), s = std::sin(a);
+          auto turn = [&](const vec3f& v) { return vec3f{c * v.x + s * v.z, v.y, c * v.z - s * v.x}; };  // about the world's y axis
+          for (auto& [o, f] : turning) ptr::set_frame(o, frame3f{turn(f.x), turn(f.y), turn(f.z), turn(f.o)});
+        } else if (k > 0) {
           t_edit = std::chrono::steady_clock::now();
           update_turntable(camera->frame, camera->focus, {2 * (float)3.14159265358979323846 / turntable, 0});
         }

@@ -142,6 +142,7 @@ _SIGS = {
     "yh_update_camera": (C.c_int, [C.c_void_p, C.POINTER(Camera)]),
     "yh_update_materials": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Material)]),
     "yh_update_environments": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Environment)]),
+    "yh_update_objects": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Object)]),
     "yh_download_display": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     "yh_init_state": (C.c_int, [C.c_void_p, C.POINTER(TraceParams)]),
     "yh_image_size": (C.c_int, [C.c_void_p, c_int_p, c_int_p]),
@@ -303,7 +304,7 @@ class Context:
         else:
             self._chk(self.lib.yh_upload_scene_maps(self.h, desc, C.cast(maps, C.POINTER(MaterialMaps))))
 
-    # edits of the uploaded scene that keep its trees (include/yhair.h): the image state is gone afterwards, call init_state again
+    # edits of the uploaded scene that keep its shapes' trees (include/yhair.h): the image state is gone afterwards, call init_state again
     def update_camera(self, camera):
         """yh_update_camera: `camera` is a Camera (e.g. a copy of desc.contents.camera with fields changed)."""
         self._chk(self.lib.yh_update_camera(self.h, C.byref(camera) if camera is not None else None))
@@ -314,6 +315,13 @@ class Context:
         if materials is not None and not isinstance(materials, C.Array):
             materials = (Material * len(materials))(*materials)
         self._chk(self.lib.yh_update_materials(self.h, first, len(materials) if materials is not None else 0, materials))
+
+    def update_objects(self, first, objects):
+        """yh_update_objects: rows [first, first + len(objects)) of the object list (frame and material; the shape stays); `objects`
+        is a ctypes array of Object, or a list of them."""
+        if objects is not None and not isinstance(objects, C.Array):
+            objects = (Object * len(objects))(*objects)
+        self._chk(self.lib.yh_update_objects(self.h, first, len(objects) if objects is not None else 0, objects))
 
     def update_environments(self, environments):
         """yh_update_environments: frame and emission of every environment (a ctypes array of Environment, or a list)."""
