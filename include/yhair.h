@@ -246,7 +246,8 @@ int yh_upload_scene(yh_context* ctx, const yh_scene_desc* scene);
  * outside [0, num_textures] is YH_E_INVALID and leaves the context's previous scene as it was.                     */
 int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* scene, const yh_material_maps* maps);
 
-/* EDITS OF THE UPLOADED SCENE that leave every shape's acceleration structure as it is. The reference reads its scene structs live: its
+/* EDITS OF THE UPLOADED SCENE that leave every shape's acceleration structure as it is (yh_update_shape, further down, builds ONE
+ * shape's again). The reference reads its scene structs live: its
  * interactive caller edits app->camera->frame in place and the next sample uses it (apps/ysceneitraces/ysceneitraces.cpp:392-410).
  * Here the description was flattened by yh_upload_scene, so an edit is a call:
  *   yh_update_camera        set_frame / set_lens / set_focus on a camera (yocto_pathtrace.h:97-104): the whole yh_camera;
@@ -281,12 +282,49 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* scene, const yh_m
  * scene of about 45 objects can cross the 10 KB line by moving them): room for wide scene nodes exists only where the upload put it,
  * and the answer is a new upload. The materials' maps (yh_material_maps) are not editable. A HIP error once an edit has begun to
  * write returns YH_E_DEVICE and leaves the context without a scene, as a failed upload does.
- * OUT OF SCOPE, for all of which the answer stays a new upload: changing an object's shape, adding or removing objects, geometry
- * (vertex edits), textures and maps, turning emission on or off.                                                                  */
+ * OUT OF SCOPE, for all of which the answer stays a new upload: changing an object's shape, adding or removing objects or shapes,
+ * changing a shape's counts, the geometry of an emitter, textures and maps, turning emission on or off. (Vertex edits that keep a
+ * shape's counts: yh_update_shape, below.)                                                                                        */
 int yh_update_camera(yh_context* ctx, const yh_camera* camera);
 int yh_update_materials(yh_context* ctx, int first, int count, const yh_material* materials);
 int yh_update_environments(yh_context* ctx, int count, const yh_environment* environments);
 int yh_update_objects(yh_context* ctx, int first, int count, const yh_object* objects);
+
+/* VERTEX EDITS OF ONE SHAPE: set_positions / set_normals / set_radius on a shape followed by init_bvh (yocto_pathtrace.h:154-157) —
+ * a groom being combed, a simulation step, a strand-width sweep. `now` is the whole shape `shape` of the uploaded list, borrowed
+ * for the call: num_vertices, num_lines and num_triangles must equal the uploaded shape's; normals and texcoords must be present or
+ * absent as at the upload; radius may be given or NULL, as at an upload (NULL: 0.001); the index array is read again, so another
+ * topology with the same counts is an edit too.
+ *   yh_update_shape         the arrays are HOST arrays;
+ *   yh_update_shape_device  every non-NULL pointer of `now` is a DEVICE pointer on the context's GPU (e.g. the data_ptr() of a
+ *                           contiguous float32 / int32 torch tensor): the vertices of a GPU simulation never visit the host. The
+ *                           call runs on the context's own non-blocking stream and returns when done: earlier writes to the arrays
+ *                           from other streams (e.g. a torch kernel that deforms them) must have completed before.
+ * The CONTRACT above holds for both: afterwards pixels, RNG states, yh_lights_batch, yh_intersect_batch, yh_intersect_plain_batch,
+ * yh_scene_once and the kernel-trial fingerprint are those of a context that got yh_upload_scene_maps of the edited description, and
+ * the image state is gone. The edited shape's bounds, the reference's tree, its leaf and test records, its 4- / 8- / 16-wide nodes
+ * and its per-vertex rows are made again with the upload's own code — on the device for shapes of 32 768 primitives and more (and
+ * always in the device form), on the host for smaller ones, the upload's rule — and from its new root box the world boxes of the
+ * objects that name it and the scene level, as after yh_update_objects. Work and allocation are proportional to the edited shape and
+ * to the number of objects: no other shape's records or nodes, no texture, environment cdf or light table is touched.
+ * ROOM. The number of a shape's wide nodes depends on its positions. An upload gives every shape exactly the room its nodes take.
+ * An edit whose 4-, 8- and 16-wide nodes fit the shape's room writes them in place (the unused rest is zero). A width that does not
+ * fit gets a new region behind the end of the traversal array, on a multiple of 4 units, with room for count + count / 8 nodes; the
+ * array is allocated again and its bytes copied device to device, unchanged; the vacated region is zeroed and NOT reused: a fresh
+ * upload reclaims it. No other shape moves. The 30-bit unit limit of yh_upload_scene holds for the grown array, and the one-lane
+ * kernels' 4 GB candidacy follows it (their 32-bit offsets must reach the furthest 4-wide region).
+ * REFUSED with YH_E_INVALID, a message that names the entry point, and the context exactly as it was: a NULL `now`; `shape` outside
+ * the uploaded list; a count that differs; lines against triangles; normals or texcoords present where the upload had none or the
+ * reverse; NULL positions; a vertex index outside [0, num_vertices) (found by a kernel before anything follows an index, in both
+ * forms); a shape named by an object whose material emits (the light cdf and the kernels' light table are made from it); a tree too
+ * deep for the traversal stack; yh_update_objects' two refusals (the scene level changes its form, or needs more wide scene nodes
+ * than the upload left room for); the 30-bit limit. YH_E_STATE before an upload. A HIP error once the edit has begun to write
+ * returns YH_E_DEVICE and leaves the context without a scene.                                                                      */
+int yh_update_shape(yh_context* ctx, int shape, const yh_shape* now);
+int yh_update_shape_device(yh_context* ctx, int shape, const yh_shape* now);
+/* A diagnostic: where shape `shape`'s 4-, 8- and 16-wide nodes sit in the traversal array (offset, in 32-byte units), how many
+ * nodes it has of each width (count) and how many its region has room for (room). YH_E_STATE before an upload.                    */
+int yh_shape_nodes(const yh_context* ctx, int shape, int64_t offset[3], int count[3], int room[3]);
 
 /* init_state (yocto_pathtrace.cpp:1931-1946): image size from the camera film
  * and params->resolution, zeroed accumulators, per-pixel PCG32 streams

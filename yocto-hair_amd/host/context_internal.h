@@ -8,8 +8,8 @@
 //   trace_launch.cpp   yh_init_state (pt.cpp:1931-1946) and the launches: yh_trace_samples and friends
 //   gather.cpp         tile packing and the one collective (yh_gather_framebuffer: RCCL or peer copies)
 //   batch_api.cpp      the unit-level batch entry points (hair BSDF, intersection, BVH build, curves, self-tests)
-//   scene_edit.cpp     edits of an uploaded scene that leave its shapes' trees alone (yh_update_camera / _materials / _environments /
-//                      _objects: the last one builds the scene-level tree again) and yh_download_display
+//   scene_edit.cpp     edits of an uploaded scene (yh_update_camera / _materials / _environments / _objects: the last one builds the
+//                      scene-level tree again; yh_update_shape / _device: one shape's tree too) and yh_download_display
 #ifndef YH_CONTEXT_INTERNAL_H_
 #define YH_CONTEXT_INTERNAL_H_
 #include <hip/hip_runtime_api.h>
@@ -89,6 +89,13 @@ int yhk_display(const yhd_state*, int samples, float exposure, int filmic, int s
 // unit/objects.hip (yh_update_objects): a lane per row of `rows` (yh_object, device memory); root6 = per shape its root box, 6 floats; writes
 // frame, inv_frame, material and the padded world box into objects[0 .. count) unless NULL, and the world box proper, 6 floats per row, to boxes6
 int yhk_object_rows(int count, const void* rows, const float* root6, void* objects, float* boxes6, hipStream_t);
+// unit/shapes.hip (yh_update_shape), all pointers DEVICE pointers: whether one of n indices lies outside [0, num_vertices) (*bad on the
+// host; synchronises); a shape's rows of the per-vertex arrays — vpos {p.xyz, radius or 0.001 for lines, 0 for triangles}, vtex (zeros
+// without texcoords), elems — written at the shape's bases; and the three lane roots in the rows of the objects that name `shape`
+int yhk_index_check(int n, const int* idx, int num_vertices, unsigned int* flag, int* bad, hipStream_t);
+int yhk_vertex_rows(int lines, int num_vertices, int num_elems, const float* pos, const float* radius, const float* texcoords, const int* idx, void* vpos, float* vtex,
+    void* elems, hipStream_t);
+int yhk_object_lane_roots(int count, const void* rows, int shape, int root4, int root8, int root16, void* objects, hipStream_t);
 }
 
 // A device allocation owned by the context.
@@ -216,6 +223,12 @@ struct yh_context {
   DevBuf                        d_shape_roots;
   int                           max_shape_depth = 0, max_shape_depth8 = 0, max_shape_depth16 = 0;
   int                           scene_wide_room = 0;
+  // ... and what yh_update_shape needs of every shape: what its counts and arrays were, where its per-vertex rows sit (per_vertex: it has
+  // some), the depths of its tree as 4- / 8- / 16-wide nodes (the maxima above are made from them again), how many nodes of each width it
+  // has and how many its region of the traversal array has room for (equal after an upload), and where its first and last 256 positions
+  // sit in key_geometry
+  struct ShapeState { int num_vertices, has_normals, has_texcoords, per_vertex, vert_base, elem_base, depth, depth8, depth16, count[3], room[3]; size_t key_positions; };
+  std::vector<ShapeState>       shape_states;
   // state
   bool             have_state = false;
   yhd_state        state{};
@@ -334,6 +347,23 @@ void forget_image_of_scene(yh_context* ctx);
 // scene_upload.cpp, shared with yh_update_objects: the levels of a host-built tree as the device builder reports them (false: more than 128);
 // whether a scene level of that size is walked as 4-wide nodes out of the lane blob (and the float4 count of its LDS table otherwise); what
 // the scene level adds to every traversal stack; and the three stack needs with the check every scene has to pass
+// ... and with yh_update_shape: one shape's binary tree on the device until its collapses are made, with the index of its wide nodes;
+// the upload's rule for where a shape is built; the build itself (bounds, the reference's tree, leaf-ordered records to d_recs), the
+// index of its wide nodes and their collapse with the shape's test records into a traversal array
+struct ShapeTree {
+  int      kind = 0, num_prims = 0;
+  yhh::Box root{};
+  int      num_nodes = 0, levels = 1;  // the binary tree on the device: node count, levels, first node of every level
+  int      level_first[130] = {0};
+  int      wide_count[3] = {0, 0, 0};  // its 4- / 8- / 16-wide nodes
+  int      depth = 0, depth8 = 0, depth16 = 0;  // depths of the same tree collapsed two / three / four levels at a time
+  DevBuf   d_tree, d_wflag[3], d_widx[3];       // binary nodes (8 floats each); per width the flag and index of every binary node
+  std::vector<yhd_float4> host_prims;  // SMALL shapes: their leaf records on the host too (the LDS light table is made from them)
+};
+bool shape_builds_on_device(int num_prims);
+int build_shape_tree(yh_context* ctx, const char* who, int si, const yh_shape& s, bool arrays_on_device, bool on_device, yhd_float4* d_recs, ShapeTree& T);
+int index_shape_tree(yh_context* ctx, const char* who, ShapeTree& T);
+int collapse_shape_tree(yh_context* ctx, const char* who, const ShapeTree& T, const yh_context::LaneShape& L, void* blob);
 bool tree_levels(const yhh::Tree& tree, int& levels, int* level_first);
 bool scene_level_is_wide(int num_objects, int num_scene_nodes, int* lds_scene_f4);
 struct StackNeeds { int need, need8, need16; };

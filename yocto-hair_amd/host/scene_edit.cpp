@@ -1,9 +1,10 @@
-// scene_edit.cpp — edits of an uploaded scene that leave every shape's acceleration structure as it is: the camera, rows of the material
-// table, the environments' frames and emission, and rows of the object list (yh_update_objects, at the end: the one edit that builds
-// something, the scene-level tree over the objects' world boxes). The reference reads its scene structs live (an interactive caller edits app->camera->frame and traces
-// on, apps/ysceneitraces/ysceneitraces.cpp:392-410); here the description was flattened at yh_upload_scene, so an edit is a call of its own
+// scene_edit.cpp — edits of an uploaded scene: the camera, rows of the material table, the environments' frames and emission, rows of the
+// object list (yh_update_objects: it builds the scene-level tree over the objects' world boxes again) and, at the end, one shape's vertices
+// (yh_update_shape / _device: that shape's tree, records and nodes again, then the scene level; no other shape is touched). The reference
+// reads its scene structs live (an interactive caller edits app->camera->frame and traces on,
+// apps/ysceneitraces/ysceneitraces.cpp:392-410); here the description was flattened at yh_upload_scene, so an edit is a call of its own
 // that leaves the context as an upload of the edited description would: the scene table, the material rows on the device, the kernel
-// variant, the once-per-ray form, the fingerprint and the launch planning. Nothing the geometry sizes is read, written or allocated.
+// variant, the once-per-ray form, the fingerprint and the launch planning. Only a shape edit reads, writes or allocates anything the geometry sizes, and then the edited shape's alone.
 // Also yh_download_display, the tone-mapped bytes of the image (unit/display.hip).
 #include "context_internal.h"
 
@@ -104,6 +105,91 @@ static int stage_alloc(yh_context* ctx, DevBuf& buf, size_t bytes) {
   return YH_OK;
 }
 
+// ---- the scene level again: what yh_update_objects and yh_update_shape share. Everything that can refuse is staged by stage_scene_level;
+// commit_scene_level queues the copies, the memset and the collapse on the context's stream; settle_scene_level, once they are done,
+// brings the host's side of the scene table in line ----
+namespace {
+struct SceneLevelStage {
+  yhh::Tree  tree;
+  int        nn = 0, lds_scene_f4 = 0, wide_count = 0, wide_depth = 0;
+  bool       scene_wide = false, general_rows = false;
+  DevBuf     d_stree, d_sflag, d_sidx, d_nodes_grown, d_prims_grown;
+  StackNeeds needs{};
+  std::vector<yhd_float4> scene_nodes;
+  std::vector<int>        scene_prims;
+};
+}  // namespace
+
+// boxes: every object's world box; depth4 / 8 / 16: the deepest shape tree as 4- / 8- / 16-wide nodes
+static int stage_scene_level(yh_context* ctx, const char* entry, const std::vector<yhh::Box>& boxes, int depth4, int depth8, int depth16, SceneLevelStage& S) {
+  const int total = ctx->scene.num_objects, num_materials = (int)ctx->h_materials.size();
+  // ---- the scene-level tree, as the upload builds it, and what the upload derives from it ----
+  yhh::Tree& tree = S.tree;
+  yhh::build_bvh(tree, boxes);
+  const int nn = S.nn = (int)tree.nodes.size();
+  const bool scene_wide = S.scene_wide = scene_level_is_wide(total, nn, &S.lds_scene_f4), was_wide = ctx->scene.scene_wide_root >= 0;
+  if (scene_wide != was_wide)
+    return fail(ctx, YH_E_INVALID, "%s: the scene tree of the moved objects has %d nodes and its scene level %s: room for wide scene nodes exists only where the upload put it, upload the scene",
+        entry, nn, scene_wide ? "no longer fits the kernels' table (it would be walked as 4-wide nodes)" : "fits the kernels' table again (it was uploaded as 4-wide nodes)");
+  if (scene_wide) {
+    int levels = 1, level_first[130] = {0};
+    if (!tree_levels(tree, levels, level_first)) return fail(ctx, YH_E_INVALID, "%s: scene tree of %d levels", entry, levels);
+    if (int rc = stage_alloc(ctx, S.d_stree, (size_t)nn * 32)) return rc;
+    if (int rc = stage_alloc(ctx, S.d_sflag, ((size_t)nn + 1) * 4)) return rc;
+    if (int rc = stage_alloc(ctx, S.d_sidx, ((size_t)nn + 1) * 4)) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(S.d_stree.p, tree.nodes.data(), (size_t)nn * 32, hipMemcpyHostToDevice, ctx->stream));
+    int e = yhk_wide_index(nn, (const float*)S.d_stree.p, levels, level_first, 2, (unsigned int*)S.d_sflag.p, (unsigned int*)S.d_sidx.p, &S.wide_count, ctx->stream);
+    if (e) return fail(ctx, YH_E_DEVICE, "wide-node index of the scene tree: %s", hipGetErrorString((hipError_t)e));
+    S.wide_depth = 1 + std::max(0, levels - 2) / 2;
+    if (S.wide_count > ctx->scene_wide_room)
+      return fail(ctx, YH_E_INVALID, "%s: %d wide scene nodes, the upload left room for %d: upload the scene", entry, S.wide_count, ctx->scene_wide_room);
+  }
+  S.needs = stack_needs(scene_wide, S.wide_depth, tree.max_depth, depth4, depth8, depth16);
+  if (S.needs.need > yhk_stack_entries())
+    return fail(ctx, YH_E_INVALID, "%s: BVH too deep for the traversal stack (%d > %d)", entry, S.needs.need, yhk_stack_entries());
+  for (auto& n : tree.nodes) S.scene_nodes.push_back(node_lo(n)), S.scene_nodes.push_back(node_hi(n));
+  S.scene_prims = tree.primitives;
+  S.scene_prims.resize((S.scene_prims.size() + 3) / 4 * 4, 0);  // staged to LDS as float4
+  // (a tree over the same objects has up to 2 n - 1 nodes: more than the uploaded one may have had)
+  if (ctx->d_scene_nodes.bytes < S.scene_nodes.size() * 16)
+    if (int rc = stage_alloc(ctx, S.d_nodes_grown, (size_t)(2 * total) * 32)) return rc;
+  if (ctx->d_scene_prims.bytes < S.scene_prims.size() * 4)
+    if (int rc = stage_alloc(ctx, S.d_prims_grown, S.scene_prims.size() * 4)) return rc;
+  S.general_rows = [&] {  // (the material table's verdict, as the upload and yh_update_materials reach it)
+    const bool                mapped = !ctx->h_maps.empty();
+    std::vector<yhd_material> rows((size_t)num_materials);
+    std::vector<yhd_maps>     dmaps(mapped ? (size_t)num_materials : 0);
+    return make_material_rows(ctx->h_materials.data(), mapped ? ctx->h_maps.data() : nullptr, num_materials, rows.data(), dmaps.data());
+  }();
+  return YH_OK;
+}
+
+static int commit_scene_level(yh_context* ctx, SceneLevelStage& S) {
+  if (S.d_nodes_grown.p) std::swap(ctx->d_scene_nodes.p, S.d_nodes_grown.p), std::swap(ctx->d_scene_nodes.bytes, S.d_nodes_grown.bytes);
+  if (S.d_prims_grown.p) std::swap(ctx->d_scene_prims.p, S.d_prims_grown.p), std::swap(ctx->d_scene_prims.bytes, S.d_prims_grown.bytes);
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d_scene_nodes.p, S.scene_nodes.data(), S.scene_nodes.size() * 16, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(ctx->d_scene_prims.p, S.scene_prims.data(), S.scene_prims.size() * 4, hipMemcpyHostToDevice, ctx->stream));
+  if (S.scene_wide) {  // the reserved front of the blob: zero as the upload leaves what it does not use, then the new nodes
+    HIPCHK(ctx, hipMemsetAsync(ctx->d_lane_blob.p, 0, (size_t)ctx->scene_wide_room * 128, ctx->stream));
+    int e = yhk_wide_collapse(2, S.nn, (const float*)S.d_stree.p, (const unsigned int*)S.d_sflag.p, (const unsigned int*)S.d_sidx.p, 1, 0, 0, ctx->d_lane_blob.p, ctx->stream);
+    if (e) return fail(ctx, YH_E_DEVICE, "wide collapse of the scene tree: %s", hipGetErrorString((hipError_t)e));
+  }
+  return YH_OK;
+}
+
+static void settle_scene_level(yh_context* ctx, const SceneLevelStage& S) {
+  ctx->stack_need = S.needs.need, ctx->stack_need8 = S.needs.need8, ctx->stack_need16 = S.needs.need16;
+  yhd_scene& sc = ctx->scene;
+  sc.scene_nodes = (const yhd_float4*)ctx->d_scene_nodes.p, sc.scene_prims = (const int*)ctx->d_scene_prims.p;
+  sc.num_scene_nodes = S.nn;
+  sc.lds_scene_f4    = S.scene_wide ? 0 : S.lds_scene_f4;
+  sc.scene_wide_root = S.scene_wide ? 0 : -1;
+  sc.stack_entries   = std::max(8, (S.needs.need + 7) / 8 * 8);
+  sc.stack_entries8  = std::max(8, (S.needs.need8 + 7) / 8 * 8);
+  sc.stack_entries16 = std::max(8, (S.needs.need16 + 7) / 8 * 8);
+  settle_scene_variant(ctx, sc, S.general_rows);
+}
+
 int yh_update_objects(yh_context* ctx, int first, int count, const yh_object* objects) {
   if (!ctx) return YH_E_INVALID;
   if (!objects && count != 0) return fail(ctx, YH_E_INVALID, "yh_update_objects: objects is NULL");
@@ -138,78 +224,211 @@ int yh_update_objects(yh_context* ctx, int first, int count, const yh_object* ob
     HIPCHK(ctx, hipMemcpyAsync(boxes.data() + first, d_boxes.p, sizeof(yhh::Box) * (size_t)count, hipMemcpyDeviceToHost, ctx->stream));
     YH_WAIT(ctx);
   }
-  // ---- the scene-level tree, as the upload builds it, and what the upload derives from it ----
-  yhh::Tree tree;
-  yhh::build_bvh(tree, boxes);
-  const int  nn = (int)tree.nodes.size();
-  int        lds_scene_f4 = 0;
-  const bool scene_wide = scene_level_is_wide(total, nn, &lds_scene_f4), was_wide = ctx->scene.scene_wide_root >= 0;
-  if (scene_wide != was_wide)
-    return fail(ctx, YH_E_INVALID, "yh_update_objects: the scene tree of the moved objects has %d nodes and its scene level %s: room for wide scene nodes exists only where the upload put it, upload the scene",
-        nn, scene_wide ? "no longer fits the kernels' table (it would be walked as 4-wide nodes)" : "fits the kernels' table again (it was uploaded as 4-wide nodes)");
-  DevBuf d_stree, d_sflag, d_sidx;
-  int    wide_count = 0, wide_depth = 0;
-  if (scene_wide) {
-    int levels = 1, level_first[130] = {0};
-    if (!tree_levels(tree, levels, level_first)) return fail(ctx, YH_E_INVALID, "yh_update_objects: scene tree of %d levels", levels);
-    if (int rc = stage_alloc(ctx, d_stree, (size_t)nn * 32)) return rc;
-    if (int rc = stage_alloc(ctx, d_sflag, ((size_t)nn + 1) * 4)) return rc;
-    if (int rc = stage_alloc(ctx, d_sidx, ((size_t)nn + 1) * 4)) return rc;
-    HIPCHK(ctx, hipMemcpyAsync(d_stree.p, tree.nodes.data(), (size_t)nn * 32, hipMemcpyHostToDevice, ctx->stream));
-    int e = yhk_wide_index(nn, (const float*)d_stree.p, levels, level_first, 2, (unsigned int*)d_sflag.p, (unsigned int*)d_sidx.p, &wide_count, ctx->stream);
-    if (e) return fail(ctx, YH_E_DEVICE, "wide-node index of the scene tree: %s", hipGetErrorString((hipError_t)e));
-    wide_depth = 1 + std::max(0, levels - 2) / 2;
-    if (wide_count > ctx->scene_wide_room)
-      return fail(ctx, YH_E_INVALID, "yh_update_objects: %d wide scene nodes, the upload left room for %d: upload the scene", wide_count, ctx->scene_wide_room);
-  }
-  const StackNeeds needs = stack_needs(scene_wide, wide_depth, tree.max_depth, ctx->max_shape_depth, ctx->max_shape_depth8, ctx->max_shape_depth16);
-  if (needs.need > yhk_stack_entries())
-    return fail(ctx, YH_E_INVALID, "yh_update_objects: BVH too deep for the traversal stack (%d > %d)", needs.need, yhk_stack_entries());
-  std::vector<yhd_float4> scene_nodes;
-  for (auto& n : tree.nodes) scene_nodes.push_back(node_lo(n)), scene_nodes.push_back(node_hi(n));
-  std::vector<int> scene_prims = tree.primitives;
-  scene_prims.resize((scene_prims.size() + 3) / 4 * 4, 0);  // staged to LDS as float4
-  DevBuf d_nodes_grown, d_prims_grown;  // (a tree over the same objects has up to 2 n - 1 nodes: more than the uploaded one may have had)
-  if (ctx->d_scene_nodes.bytes < scene_nodes.size() * 16)
-    if (int rc = stage_alloc(ctx, d_nodes_grown, (size_t)(2 * total) * 32)) return rc;
-  if (ctx->d_scene_prims.bytes < scene_prims.size() * 4)
-    if (int rc = stage_alloc(ctx, d_prims_grown, scene_prims.size() * 4)) return rc;
-  const bool general_rows = [&] {  // (the material table's verdict, as the upload and yh_update_materials reach it)
-    const bool                mapped = !ctx->h_maps.empty();
-    std::vector<yhd_material> rows((size_t)num_materials);
-    std::vector<yhd_maps>     dmaps(mapped ? (size_t)num_materials : 0);
-    return make_material_rows(ctx->h_materials.data(), mapped ? ctx->h_maps.data() : nullptr, num_materials, rows.data(), dmaps.data());
-  }();
+  SceneLevelStage S;
+  if (int rc = stage_scene_level(ctx, "yh_update_objects", boxes, ctx->max_shape_depth, ctx->max_shape_depth8, ctx->max_shape_depth16, S)) return rc;
   // ---- COMMIT ----
   ctx->have_scene = false;
-  if (d_nodes_grown.p) std::swap(ctx->d_scene_nodes.p, d_nodes_grown.p), std::swap(ctx->d_scene_nodes.bytes, d_nodes_grown.bytes);
-  if (d_prims_grown.p) std::swap(ctx->d_scene_prims.p, d_prims_grown.p), std::swap(ctx->d_scene_prims.bytes, d_prims_grown.bytes);
   if (count > 0) {
     int e = yhk_object_rows(count, d_rows.p, (const float*)ctx->d_shape_roots.p, (yhd_object*)ctx->d_objects.p + first, (float*)d_boxes.p, ctx->stream);
     if (e) return fail(ctx, YH_E_DEVICE, "object rows: %s", hipGetErrorString((hipError_t)e));
   }
-  HIPCHK(ctx, hipMemcpyAsync(ctx->d_scene_nodes.p, scene_nodes.data(), scene_nodes.size() * 16, hipMemcpyHostToDevice, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(ctx->d_scene_prims.p, scene_prims.data(), scene_prims.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (scene_wide) {  // the reserved front of the blob: zero as the upload leaves what it does not use, then the new nodes
-    HIPCHK(ctx, hipMemsetAsync(ctx->d_lane_blob.p, 0, (size_t)ctx->scene_wide_room * 128, ctx->stream));
-    int e = yhk_wide_collapse(2, nn, (const float*)d_stree.p, (const unsigned int*)d_sflag.p, (const unsigned int*)d_sidx.p, 1, 0, 0, ctx->d_lane_blob.p, ctx->stream);
-    if (e) return fail(ctx, YH_E_DEVICE, "wide collapse of the scene tree: %s", hipGetErrorString((hipError_t)e));
-  }
+  if (int rc = commit_scene_level(ctx, S)) return rc;
   YH_WAIT(ctx);
   if (count > 0) memcpy(ctx->key_geometry.data() + sizeof(yh_object) * (size_t)first, objects, sizeof(yh_object) * (size_t)count);
   ctx->h_obj_boxes.swap(boxes);
-  ctx->stack_need = needs.need, ctx->stack_need8 = needs.need8, ctx->stack_need16 = needs.need16;
-  yhd_scene& sc = ctx->scene;
-  sc.scene_nodes = (const yhd_float4*)ctx->d_scene_nodes.p, sc.scene_prims = (const int*)ctx->d_scene_prims.p;
-  sc.num_scene_nodes = nn;
-  sc.lds_scene_f4    = scene_wide ? 0 : lds_scene_f4;
-  sc.scene_wide_root = scene_wide ? 0 : -1;
-  sc.stack_entries   = std::max(8, (needs.need + 7) / 8 * 8);
-  sc.stack_entries8  = std::max(8, (needs.need8 + 7) / 8 * 8);
-  sc.stack_entries16 = std::max(8, (needs.need16 + 7) / 8 * 8);
-  settle_scene_variant(ctx, sc, general_rows);
+  settle_scene_level(ctx, S);
   ctx->have_scene = true;
   edit_end(ctx);
+  return YH_OK;
+}
+
+// ---- yh_update_shape / yh_update_shape_device: set_positions / set_normals / set_radius on a shape, then init_bvh -------------------------
+// (yocto_pathtrace.h:154-157). One shape's leaf records, test records, 4- / 8- / 16-wide nodes and per-vertex rows are made again with the
+// upload's own code (scene_upload.cpp: build_shape_tree, index_shape_tree, collapse_shape_tree) and unit/shapes.hip; its root box moves the
+// world boxes of the objects that name it, so the scene level follows as after yh_update_objects. The node counts depend on the
+// positions: a width whose new count exceeds the room of the shape's region gets a new region behind the end of the traversal array
+// (count + count / 8 nodes, on a multiple of 4 units), the array is reallocated and the old bytes copied device to device, the vacated
+// region is zeroed and stays unused until an upload. No other shape moves: the collapse writes absolute references.
+static int update_shape(yh_context* ctx, const char* entry, int shape, const yh_shape* now, bool device) {
+  if (!ctx) return YH_E_INVALID;
+  if (!now) return fail(ctx, YH_E_INVALID, "%s: now is NULL", entry);
+  if (int rc = edit_begin(ctx, entry)) return rc;
+  const int num_shapes = (int)ctx->shape_states.size(), total = ctx->scene.num_objects;
+  if (shape < 0 || shape >= num_shapes) return fail(ctx, YH_E_INVALID, "%s: shape %d is outside the uploaded list of %d shapes", entry, shape, num_shapes);
+  const yh_context::ShapeState& E = ctx->shape_states[(size_t)shape];
+  const yh_context::LaneShape&  L = ctx->lane_shapes[(size_t)shape];
+  const bool lines = L.kind == YH_KIND_LINES;
+  int was_counts[3];  // (key_geometry holds the counts as they were passed in, in front of the shape's positions)
+  memcpy(was_counts, ctx->key_geometry.data() + E.key_positions - sizeof(was_counts), sizeof(was_counts));
+  if ((now->num_lines > 0) != lines)
+    return fail(ctx, YH_E_INVALID, "%s: shape %d was uploaded as %s and is now %s: upload the scene", entry, shape, lines ? "lines" : "triangles", lines ? "triangles" : "lines");
+  if (now->num_vertices != was_counts[0] || now->num_lines != was_counts[1] || now->num_triangles != was_counts[2])
+    return fail(ctx, YH_E_INVALID, "%s: shape %d has %d vertices, %d lines, %d triangles; the uploaded one has %d, %d, %d: upload the scene", entry, shape, now->num_vertices,
+        now->num_lines, now->num_triangles, was_counts[0], was_counts[1], was_counts[2]);
+  if (!now->positions) return fail(ctx, YH_E_INVALID, "%s: shape %d has no positions", entry, shape);
+  const int* idx_in = lines ? now->lines : now->triangles;
+  if (!idx_in) return fail(ctx, YH_E_INVALID, "%s: shape %d has no index array", entry, shape);
+  if ((now->normals != nullptr) != (E.has_normals != 0))
+    return fail(ctx, YH_E_INVALID, "%s: shape %d %s normals, the uploaded one %s: upload the scene", entry, shape, now->normals ? "has" : "has no", E.has_normals ? "had them" : "had none");
+  if ((now->texcoords != nullptr) != (E.has_texcoords != 0))
+    return fail(ctx, YH_E_INVALID, "%s: shape %d %s texcoords, the uploaded one %s: upload the scene", entry, shape, now->texcoords ? "has" : "has no", E.has_texcoords ? "had them" : "had none");
+  // the light cdf and the LDS light table (init_lights, pt.cpp:1695-1740) were made from the shape of every object whose material emits
+  std::vector<yh_object> rows((size_t)total);  // (key_geometry begins with the object rows as they were passed in)
+  memcpy(rows.data(), ctx->key_geometry.data(), sizeof(yh_object) * (size_t)total);
+  for (int i = 0; i < total; i++)
+    if (rows[(size_t)i].shape == shape && !is_black(ctx->h_materials[(size_t)rows[(size_t)i].material].emission))
+      return fail(ctx, YH_E_INVALID, "%s: shape %d is the shape of object %d, whose material emits: the light tables are made from it, upload the scene", entry, shape, i);
+  const std::string who_s = std::string(entry) + ": ";
+  const char*       who   = who_s.c_str();
+  // ---- staging: the arrays on the device (the host form copies them there), the index check before anything follows an index ----
+  const size_t nv = (size_t)now->num_vertices, nel = (size_t)L.num_prims, nidx = nel * (lines ? 2 : 3), per = lines ? 4 : 6;
+  DevBuf   d_pos, d_nrm, d_rad, d_idx, d_tex, d_flag;
+  yh_shape dev = *now;  // the same shape, its arrays in device memory
+  if (!device) {
+    auto h2d = [&](DevBuf& buf, const void* src, size_t bytes, const void** to) -> int {
+      if (!src) return YH_OK;
+      if (int rc = stage_alloc(ctx, buf, bytes)) return rc;
+      HIPCHK(ctx, hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+      *to = buf.p;
+      return YH_OK;
+    };
+    if (int rc = h2d(d_idx, idx_in, nidx * 4, (const void**)(lines ? &dev.lines : &dev.triangles))) return rc;
+    if (int rc = h2d(d_pos, now->positions, nv * 12, (const void**)&dev.positions)) return rc;
+    if (int rc = h2d(d_rad, now->radius, nv * 4, (const void**)&dev.radius)) return rc;
+    if (int rc = h2d(d_nrm, now->normals, nv * 12, (const void**)&dev.normals)) return rc;
+    if (int rc = h2d(d_tex, now->texcoords, nv * 8, (const void**)&dev.texcoords)) return rc;
+  }
+  const int* d_index = lines ? dev.lines : dev.triangles;
+  if (int rc = stage_alloc(ctx, d_flag, 4)) return rc;
+  {
+    int bad = 0, e = yhk_index_check((int)nidx, d_index, now->num_vertices, (unsigned int*)d_flag.p, &bad, ctx->stream);
+    if (e) return fail(ctx, YH_E_DEVICE, "%sindex check: %s", who, hipGetErrorString((hipError_t)e));
+    if (bad) return fail(ctx, YH_E_INVALID, "%sshape %d: vertex index out of range", who, shape);
+  }
+  // ---- the tree, the records and the index of the wide nodes: the upload's rule for where, the upload's code ----
+  const bool on_device = device || shape_builds_on_device((int)nel);
+  ShapeTree  T;
+  DevBuf     d_recs;
+  if (int rc = stage_alloc(ctx, d_recs, nel * per * 16)) return rc;
+  if (int rc = build_shape_tree(ctx, who, shape, on_device ? dev : *now, on_device, on_device, (yhd_float4*)d_recs.p, T)) return rc;
+  if (int rc = index_shape_tree(ctx, who, T)) return rc;
+  // ---- where the wide nodes go ----
+  yh_context::LaneShape  Lnew = L;
+  yh_context::ShapeState Enew = E;
+  const long long old_units = ctx->scene.lane_blob_units, width[3] = {4, 8, 16}, old_off[3] = {L.node_off, L.node_off8, L.node_off16};
+  long long       end = old_units, off[3] = {old_off[0], old_off[1], old_off[2]};
+  for (int w = 0; w < 3; w++) {
+    Enew.count[w] = T.wide_count[w];
+    if (T.wide_count[w] <= E.room[w]) continue;
+    off[w]       = (end + 3) / 4 * 4;
+    Enew.room[w] = T.wide_count[w] + T.wide_count[w] / 8;
+    end          = off[w] + width[w] * Enew.room[w] + 4;  // (four units of slack behind the last node, as the upload leaves)
+  }
+  if (end >= (1ll << 30)) return fail(ctx, YH_E_INVALID, "%sscene too large for 30-bit node offsets (%lld units): upload the scene", who, end);
+  Lnew.num_nodes = T.wide_count[0], Lnew.node_off = off[0], Lnew.node_off8 = off[1], Lnew.node_off16 = off[2];
+  Enew.depth = T.depth, Enew.depth8 = T.depth8, Enew.depth16 = T.depth16;
+  DevBuf d_blob_grown;
+  if (end > old_units)
+    if (int rc = stage_alloc(ctx, d_blob_grown, (size_t)end * 32)) return rc;
+  int depth4 = 0, depth8 = 0, depth16 = 0;
+  for (int s = 0; s < num_shapes; s++) {
+    const yh_context::ShapeState& D = s == shape ? Enew : ctx->shape_states[(size_t)s];
+    depth4 = std::max(depth4, D.depth), depth8 = std::max(depth8, D.depth8), depth16 = std::max(depth16, D.depth16);
+  }
+  // ---- the world boxes of the objects that name the shape, from its new root box; the scene level over all boxes ----
+  std::vector<yhh::Box> boxes = ctx->h_obj_boxes;
+  std::vector<int>      named;
+  for (int i = 0; i < total; i++)
+    if (rows[(size_t)i].shape == shape) named.push_back(i);
+  DevBuf d_rows, d_boxes, d_named, d_root;
+  if (int rc = stage_alloc(ctx, d_rows, sizeof(yh_object) * (size_t)total)) return rc;
+  if (int rc = stage_alloc(ctx, d_boxes, sizeof(yhh::Box) * (size_t)total)) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(d_rows.p, rows.data(), sizeof(yh_object) * (size_t)total, hipMemcpyHostToDevice, ctx->stream));
+  std::vector<yh_object> named_rows;  // (their shape is row 0 of a table of one root box: the context's table changes at COMMIT only)
+  std::vector<yhh::Box>  named_boxes(named.size());
+  for (int i : named) named_rows.push_back(rows[(size_t)i]), named_rows.back().shape = 0;
+  if (!named.empty()) {
+    if (int rc = stage_alloc(ctx, d_named, sizeof(yh_object) * named.size())) return rc;
+    if (int rc = stage_alloc(ctx, d_root, sizeof(yhh::Box))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(d_named.p, named_rows.data(), sizeof(yh_object) * named.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_root.p, &T.root, sizeof(yhh::Box), hipMemcpyHostToDevice, ctx->stream));
+    int e = yhk_object_rows((int)named.size(), d_named.p, (const float*)d_root.p, nullptr, (float*)d_boxes.p, ctx->stream);
+    if (e) return fail(ctx, YH_E_DEVICE, "%sobject rows: %s", who, hipGetErrorString((hipError_t)e));
+    HIPCHK(ctx, hipMemcpyAsync(named_boxes.data(), d_boxes.p, sizeof(yhh::Box) * named.size(), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  // the fingerprint's bytes of the shape: its first and last 256 positions (the device form fetches them)
+  const size_t take = std::min<size_t>(nv, 256);
+  std::vector<unsigned char> key_bytes(2 * take * 12);
+  if (device) {
+    HIPCHK(ctx, hipMemcpyAsync(key_bytes.data(), dev.positions, take * 12, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(key_bytes.data() + take * 12, dev.positions + 3 * (nv - take), take * 12, hipMemcpyDeviceToHost, ctx->stream));
+  } else {
+    memcpy(key_bytes.data(), now->positions, take * 12), memcpy(key_bytes.data() + take * 12, now->positions + 3 * (nv - take), take * 12);
+  }
+  YH_WAIT(ctx);
+  for (size_t k = 0; k < named.size(); k++) boxes[(size_t)named[k]] = named_boxes[k];
+  SceneLevelStage S;
+  if (int rc = stage_scene_level(ctx, entry, boxes, depth4, depth8, depth16, S)) return rc;
+  // ---- COMMIT: from here on kernels, copies and memsets only ----
+  ctx->have_scene = false;
+  if (d_blob_grown.p) {  // the old array's bytes as they are, zeros behind them (what alloc_zero leaves)
+    HIPCHK(ctx, hipMemcpyAsync(d_blob_grown.p, ctx->d_lane_blob.p, (size_t)old_units * 32, hipMemcpyDeviceToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemsetAsync((char*)d_blob_grown.p + (size_t)old_units * 32, 0, (size_t)(end - old_units) * 32, ctx->stream));
+    std::swap(ctx->d_lane_blob.p, d_blob_grown.p), std::swap(ctx->d_lane_blob.bytes, d_blob_grown.bytes);
+    ctx->scene.lane_blob = nullptr;
+  }
+  for (int w = 0; w < 3; w++)  // the shape's regions as they were: vacated, or written again with the unused rest zero
+    if (E.room[w] > 0) HIPCHK(ctx, hipMemsetAsync((char*)ctx->d_lane_blob.p + (size_t)old_off[w] * 32, 0, (size_t)(width[w] * E.room[w]) * 32, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync((yhd_float4*)ctx->d_prims.p + L.prim_base, d_recs.p, nel * per * 16, hipMemcpyDeviceToDevice, ctx->stream));
+  if (int rc = collapse_shape_tree(ctx, who, T, Lnew, ctx->d_lane_blob.p)) return rc;
+  if (E.per_vertex) {
+    int e = yhk_vertex_rows(lines ? 1 : 0, (int)nv, (int)nel, dev.positions, dev.radius, dev.texcoords, d_index, (yhd_float4*)ctx->d_vpos.p + E.vert_base,
+        (float*)ctx->d_vtex.p + 2 * (size_t)E.vert_base, (yhd_int4*)ctx->d_elems.p + E.elem_base, ctx->stream);
+    if (e) return fail(ctx, YH_E_DEVICE, "%svertex rows: %s", who, hipGetErrorString((hipError_t)e));
+  }
+  HIPCHK(ctx, hipMemcpyAsync((yhh::Box*)ctx->d_shape_roots.p + shape, &T.root, sizeof(yhh::Box), hipMemcpyHostToDevice, ctx->stream));
+  {  // the rows of the objects that name the shape, run by run of consecutive ones (no other object's row is written), then the lane roots
+    int e = 0;
+    for (size_t k = 0; k < named.size() && !e;) {
+      size_t end_k = k + 1;
+      while (end_k < named.size() && named[end_k] == named[end_k - 1] + 1) end_k++;
+      const int first = named[k], run = (int)(end_k - k);
+      e = yhk_object_rows(run, (const yh_object*)d_rows.p + first, (const float*)ctx->d_shape_roots.p, (yhd_object*)ctx->d_objects.p + first, (float*)d_boxes.p + 6 * (size_t)first, ctx->stream);
+      k = end_k;
+    }
+    if (!e) e = yhk_object_lane_roots(total, d_rows.p, shape, (int)Lnew.node_off, (int)Lnew.node_off8, (int)Lnew.node_off16, ctx->d_objects.p, ctx->stream);
+    if (e) return fail(ctx, YH_E_DEVICE, "%sobject rows: %s", who, hipGetErrorString((hipError_t)e));
+  }
+  if (int rc = commit_scene_level(ctx, S)) return rc;
+  YH_WAIT(ctx);
+  memcpy(ctx->key_geometry.data() + E.key_positions, key_bytes.data(), key_bytes.size());
+  ctx->scene.num_nodes_total += T.wide_count[0] - E.count[0];
+  ctx->lane_shapes[(size_t)shape]  = Lnew;
+  ctx->shape_states[(size_t)shape] = Enew;  // (E and L are these: not read below)
+  ctx->lane_units = 0;
+  for (int s = 0; s < num_shapes; s++)  // the end of the furthest 4-wide region: what the one-lane kernels address
+    ctx->lane_units = std::max(ctx->lane_units, ctx->lane_shapes[(size_t)s].node_off + 4ll * ctx->shape_states[(size_t)s].room[0] + 4);
+  ctx->scene.lane_blob = (const yhd_float4*)ctx->d_lane_blob.p, ctx->scene.lane_blob_units = end;
+  ctx->h_shape_roots[(size_t)shape] = T.root;
+  ctx->h_obj_boxes.swap(boxes);
+  ctx->max_shape_depth = depth4, ctx->max_shape_depth8 = depth8, ctx->max_shape_depth16 = depth16;
+  settle_scene_level(ctx, S);
+  ctx->have_scene = true;
+  edit_end(ctx);
+  return YH_OK;
+}
+
+int yh_update_shape(yh_context* ctx, int shape, const yh_shape* now) { return update_shape(ctx, "yh_update_shape", shape, now, false); }
+int yh_update_shape_device(yh_context* ctx, int shape, const yh_shape* now) { return update_shape(ctx, "yh_update_shape_device", shape, now, true); }
+
+int yh_shape_nodes(const yh_context* ctx, int shape, int64_t offset[3], int count[3], int room[3]) {
+  if (!ctx) return YH_E_INVALID;
+  if (!ctx->have_scene) return YH_E_STATE;
+  if (shape < 0 || shape >= (int)ctx->shape_states.size() || !offset || !count || !room) return YH_E_INVALID;
+  const yh_context::LaneShape&  L = ctx->lane_shapes[(size_t)shape];
+  const yh_context::ShapeState& E = ctx->shape_states[(size_t)shape];
+  offset[0] = L.node_off, offset[1] = L.node_off8, offset[2] = L.node_off16;
+  for (int w = 0; w < 3; w++) count[w] = E.count[w], room[w] = E.room[w];
   return YH_OK;
 }
 

@@ -185,6 +185,141 @@ StackNeeds stack_needs(bool scene_wide, int scene_wide_depth, int scene_tree_dep
   return {scene_need + 3 * depth4 + 2, scene_need + 7 * depth8 + 2, scene_need + 15 * depth16 + 2};
 }
 
+// ---- one shape's tree and leaf-ordered records: what the upload runs per shape and yh_update_shape for the one it edits ----------------
+// BIG shapes (>= 32 768 primitives: the hair) never leave the device (round 6): their vertex arrays cross PCIe once, as they are, and
+// bounds, the reference's tree (csrc/bvh_gpu.hip), the leaf-ordered records and the wide collapses are made there. SMALL shapes
+// (the configs' sphere and lights: 10 ms together) are built on the host and their trees and records uploaded into the same arrays;
+// the collapses are the device's for both. YHAIR_BVH=host: every shape the small way; YHAIR_BVH=device: every shape on the device.
+bool shape_builds_on_device(int num_prims) {
+  const char* bvh_env   = getenv("YHAIR_BVH");  // developer switch, read per call
+  const bool  host_only = bvh_env && !strcmp(bvh_env, "host"), device_all = bvh_env && !strcmp(bvh_env, "device");
+  return (num_prims >= 32768 || device_all) && !host_only;
+}
+
+// `s`: the shape, its indices checked; its arrays on the host, or (arrays_on_device, which needs on_device) in device memory. The records
+// go to d_recs (device: 4 float4 per segment, 6 per triangle), the binary tree to T.d_tree; `who` begins every message ("" for the upload).
+int build_shape_tree(yh_context* ctx, const char* who, int si, const yh_shape& s, bool arrays_on_device, bool on_device, yhd_float4* d_recs, ShapeTree& T) {
+  const bool lines = s.num_lines > 0;
+  const int  nel   = lines ? s.num_lines : s.num_triangles;
+  const int* idx   = lines ? s.lines : s.triangles;
+  int        rc;
+  T.kind = lines ? YH_KIND_LINES : YH_KIND_TRIANGLES, T.num_prims = nel;
+  T.host_prims.clear();
+  if (on_device) {
+    // ---- on the device ----
+    const size_t nv = (size_t)s.num_vertices;
+    DevBuf d_pos, d_nrm, d_rad, d_idx, d_boxes, d_pid;
+    const void *p_pos = s.positions, *p_nrm = s.normals, *p_rad = s.radius, *p_idx = idx;
+    auto h2d = [&](DevBuf& buf, const void*& src, size_t bytes) -> int {
+      if (arrays_on_device) return YH_OK;
+      if (int arc = dev_alloc(ctx, buf, bytes)) return arc;
+      HIPCHK(ctx, hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+      src = buf.p;
+      return YH_OK;
+    };
+    if ((rc = h2d(d_pos, p_pos, nv * 12))) return rc;
+    if (s.radius && (rc = h2d(d_rad, p_rad, nv * 4))) return rc;
+    if ((rc = h2d(d_idx, p_idx, (size_t)nel * (lines ? 8 : 12)))) return rc;
+    if ((rc = dev_alloc(ctx, d_boxes, (size_t)nel * 24))) return rc;
+    if ((rc = dev_alloc(ctx, d_pid, (size_t)nel * 4))) return rc;
+    if ((rc = dev_alloc(ctx, T.d_tree, ((size_t)2 * nel + 1) * 32))) return rc;
+    int e = yhk_prim_boxes(lines ? 1 : 0, nel, (const float*)p_pos, (const float*)p_rad, (const int*)p_idx, (float*)d_boxes.p, ctx->stream);
+    if (e) return fail(ctx, YH_E_DEVICE, "%sprimitive bounds: %s", who, hipGetErrorString((hipError_t)e));
+    // (the normals' copy is queued behind the kernels that do not need it: it travels while the tree is built)
+    if (s.normals && (rc = h2d(d_nrm, p_nrm, nv * 12))) return rc;
+    e = yhk_bvh_build_resident(nel, (const float*)d_boxes.p, (float*)T.d_tree.p, (int*)d_pid.p, &T.num_nodes, &T.levels, T.level_first, ctx->stream);
+    if (e) return fail(ctx, YH_E_DEVICE, "%sdevice BVH build: %s", who, hipGetErrorString((hipError_t)e));
+    e = yhk_leaf_records(lines ? 1 : 0, nel, (const int*)d_pid.p, (const float*)p_pos, (const float*)p_nrm, (const float*)p_rad, (const int*)p_idx, d_recs, ctx->stream);
+    if (e) return fail(ctx, YH_E_DEVICE, "%sleaf records: %s", who, hipGetErrorString((hipError_t)e));
+    float root8[8];
+    HIPCHK(ctx, hipMemcpyAsync(root8, T.d_tree.p, 32, hipMemcpyDeviceToHost, ctx->stream));
+    YH_WAIT(ctx);  // (the vertex arrays go out of scope)
+    memcpy(T.root.min, root8, 12), memcpy(T.root.max, root8 + 3, 12);
+  } else {
+    // ---- on the host (small shapes) ----
+    auto pos = [&](int v) { return ld3(s.positions + 3 * (size_t)v); };
+    auto rad = [&](int v) { return s.radius ? s.radius[v] : 0.001f; };  // add_radius, sceneio.cpp:390
+    std::vector<yhh::Box> boxes(nel);
+    parallel_for(nel, [&](int e) {
+      if (lines) {  // line_bounds (math.h:3037-3040)
+        int a = idx[2 * e], b = idx[2 * e + 1];
+        F3  p0 = pos(a), p1 = pos(b);
+        float r0 = rad(a), r1 = rad(b);
+        float lo0[3] = {p0.x - r0, p0.y - r0, p0.z - r0}, lo1[3] = {p1.x - r1, p1.y - r1, p1.z - r1};
+        float hi0[3] = {p0.x + r0, p0.y + r0, p0.z + r0}, hi1[3] = {p1.x + r1, p1.y + r1, p1.z + r1};
+        for (int k = 0; k < 3; k++) boxes[e].min[k] = fmin_(lo0[k], lo1[k]), boxes[e].max[k] = fmax_(hi0[k], hi1[k]);
+      } else {  // triangle_bounds (math.h:3041-3044)
+        const float* p0 = s.positions + 3 * (size_t)idx[3 * e];
+        const float* p1 = s.positions + 3 * (size_t)idx[3 * e + 1];
+        const float* p2 = s.positions + 3 * (size_t)idx[3 * e + 2];
+        for (int k = 0; k < 3; k++) {
+          boxes[e].min[k] = fmin_(p0[k], fmin_(p1[k], p2[k]));
+          boxes[e].max[k] = fmax_(p0[k], fmax_(p1[k], p2[k]));
+        }
+      }
+    });
+    yhh::Tree tree;
+    yhh::build_bvh(tree, boxes);
+    // the tree as the device builder leaves it: 8 floats per node (yhh::Node has that layout byte for byte), the first node of every level
+    static_assert(sizeof(yhh::Node) == 32 && offsetof(yhh::Node, start) == 24 && offsetof(yhh::Node, num) == 28 && offsetof(yhh::Node, internal) == 30 && offsetof(yhh::Node, axis) == 31,
+        "yhh::Node is the device's node record");
+    T.num_nodes = (int)tree.nodes.size();
+    if (!tree_levels(tree, T.levels, T.level_first)) return fail(ctx, YH_E_INVALID, "%sshape %d: tree of %d levels", who, si, T.levels);
+    if ((rc = upload(ctx, T.d_tree, tree.nodes.data(), tree.nodes.size() * 32))) return rc;
+    T.root = tree.nodes[0].bbox;
+    auto nrm = [&](int v) { return s.normals ? ld3(s.normals + 3 * (size_t)v) : F3{0, 0, 0}; };
+    const size_t per = lines ? 4 : 6;
+    T.host_prims.resize(per * (size_t)nel);
+    yhd_float4* out = T.host_prims.data();
+    parallel_for(nel, [&](int slot) {
+      int   e = tree.primitives[slot];
+      float ew;
+      memcpy(&ew, &e, 4);
+      yhd_float4* r = out + per * (size_t)slot;
+      if (lines) {
+        int a = idx[2 * e], b = idx[2 * e + 1];
+        F3  p0 = pos(a), p1 = pos(b), t0 = nrm(a), t1 = nrm(b);
+        r[0] = {p0.x, p0.y, p0.z, rad(a)}, r[1] = {p1.x, p1.y, p1.z, rad(b)};
+        r[2] = {t0.x, t0.y, t0.z, ew}, r[3] = {t1.x, t1.y, t1.z, 0};
+      } else {
+        int a = idx[3 * e], b = idx[3 * e + 1], cc = idx[3 * e + 2];
+        F3  p0 = pos(a), p1 = pos(b), p2 = pos(cc), n0 = nrm(a), n1 = nrm(b), n2 = nrm(cc);
+        r[0] = {p0.x, p0.y, p0.z, ew}, r[1] = {p1.x, p1.y, p1.z, 0}, r[2] = {p2.x, p2.y, p2.z, 0};
+        r[3] = {n0.x, n0.y, n0.z, 0}, r[4] = {n1.x, n1.y, n1.z, 0}, r[5] = {n2.x, n2.y, n2.z, 0};
+      }
+    });
+    HIPCHK(ctx, hipMemcpy(d_recs, T.host_prims.data(), T.host_prims.size() * 16, hipMemcpyHostToDevice));
+  }
+  {  // depths of the wide trees: a W-wide node stands for every internal binary node at a level that is a multiple of log2 W, so the wide
+     // depth is 1 + deepest internal level / log2 W (what collapse_wide / _wide8 / _wide16 return). The last level holds leaves only.
+    const int deepest = std::max(0, T.levels - 2);
+    T.depth = 1 + deepest / 2, T.depth8 = 1 + deepest / 3, T.depth16 = 1 + deepest / 4;
+  }
+  return YH_OK;
+}
+
+// The index of every 4- / 8- / 16-wide node of a built tree (one flag pass + one scan per width) and their counts.
+int index_shape_tree(yh_context* ctx, const char* who, ShapeTree& T) {
+  for (int w = 0; w < 3; w++) {
+    if (int rc = dev_alloc(ctx, T.d_wflag[w], ((size_t)T.num_nodes + 1) * 4)) return rc;
+    if (int rc = dev_alloc(ctx, T.d_widx[w], ((size_t)T.num_nodes + 1) * 4)) return rc;
+    int e = yhk_wide_index(T.num_nodes, (const float*)T.d_tree.p, T.levels, T.level_first, 2 + w, (unsigned int*)T.d_wflag[w].p, (unsigned int*)T.d_widx[w].p, &T.wide_count[w], ctx->stream);
+    if (e) return fail(ctx, YH_E_DEVICE, "%swide-node index: %s", who, hipGetErrorString((hipError_t)e));
+  }
+  return YH_OK;
+}
+
+// ... and the nodes themselves with the shape's test records, into the traversal array `blob` (the context's, or the grown copy an edit swaps in)
+int collapse_shape_tree(yh_context* ctx, const char* who, const ShapeTree& T, const yh_context::LaneShape& L, void* blob) {
+  int e = yhk_lane_tests((const yhd_float4*)ctx->d_prims.p, (yhd_float4*)blob, L.kind, L.prim_base, L.num_prims, L.test_off, ctx->stream);
+  const long long offs[3] = {L.node_off, L.node_off8, L.node_off16};
+  for (int w = 0; w < 3 && !e; w++)
+    e = yhk_wide_collapse(2 + w, T.num_nodes, (const float*)T.d_tree.p, (const unsigned int*)T.d_wflag[w].p, (const unsigned int*)T.d_widx[w].p,
+        L.kind == YH_KIND_LINES ? 1 : 0, offs[w], L.test_off, blob, ctx->stream);
+  if (e) return fail(ctx, YH_E_DEVICE, "%swide collapse: %s", who, hipGetErrorString((hipError_t)e));
+  return YH_OK;
+}
+
 int yh_upload_scene(yh_context* ctx, const yh_scene_desc* sd) { return yh_upload_scene_maps(ctx, sd, nullptr); }
 
 int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_material_maps* maps) {
@@ -214,22 +349,11 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
     t_last = now;
   };
   // ---- per-shape BVHs and leaf-ordered records ---------------------------------------------------------------------------
-  // BIG shapes (>= 32 768 primitives: the hair) never leave the device (round 6): their vertex arrays cross PCIe once, as they are, and
-  // bounds, the reference's tree (csrc/bvh_gpu.hip), the leaf-ordered records and — below — the wide collapses are made there. SMALL shapes
-  // (the configs' sphere and lights: 10 ms together) are built on the host as before and their trees and records uploaded into the same arrays;
-  // the collapses are the device's for both. YHAIR_BVH=host: every shape the small way.
-  struct ShapeInfo {
-    int kind, prim_base, vert_base, elem_base, has_normals, depth;
-    int depth8, depth16;  // depths of the same tree collapsed three / four levels at a time
-    yhh::Box root;
-    int num_prims;
-    int num_nodes = 0, levels = 1;   // the binary tree on the device: node count, levels, first node of every level
-    int level_first[130] = {0};
-    int wide_count[3] = {0, 0, 0};   // its 4- / 8- / 16-wide nodes
-    std::vector<yhd_float4> host_prims;  // SMALL shapes: their leaf records on the host too (the LDS light table is made from them)
+  // (build_shape_tree above: big shapes on the device, small ones on the host, the collapses the device's for both)
+  struct ShapeInfo : ShapeTree {
+    int prim_base, vert_base, elem_base, has_normals;
   };
   std::vector<ShapeInfo>  info(sd->num_shapes);
-  std::vector<DevBuf>     d_tree(sd->num_shapes);  // binary nodes per shape (8 floats each), until the collapses are made
   std::vector<yhd_float4> vpos;
   std::vector<float>      vtex;  // 2 per vertex, zeros for shapes without texture coordinates
   std::vector<yhd_int4>   elems;
@@ -255,8 +379,6 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
   ctx->d_prims.reset(), ctx->d_lane_blob.reset();  // (nothing of this context is running: waited for above)
   if ((rc = dev_alloc(ctx, ctx->d_prims, total_prim_f4 * 16))) return rc;
   lap("validation, record array");
-  const char* bvh_env   = getenv("YHAIR_BVH");  // developer switch, read per upload: "host" = every shape the small way, "device" = every shape on the device
-  const bool  host_only = bvh_env && !strcmp(bvh_env, "host"), device_all = bvh_env && !strcmp(bvh_env, "device");
   for (int si = 0; si < sd->num_shapes; si++) {
     auto&      s     = sd->shapes[si];
     auto&      I     = info[si];
@@ -271,97 +393,8 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
       if (bad) return fail(ctx, YH_E_INVALID, "shape %d: vertex index out of range", si);
     }
     I.vert_base = (int)vpos.size(), I.elem_base = (int)elems.size();
-    yhd_float4* d_recs = (yhd_float4*)ctx->d_prims.p + I.prim_base;
-    if ((nel >= 32768 || device_all) && !host_only) {
-      // ---- on the device ----
-      const size_t nv = (size_t)s.num_vertices;
-      DevBuf d_pos, d_nrm, d_rad, d_idx, d_boxes, d_pid;
-      auto h2d = [&](DevBuf& buf, const void* src, size_t bytes) -> int {
-        if (int arc = dev_alloc(ctx, buf, bytes)) return arc;
-        HIPCHK(ctx, hipMemcpyAsync(buf.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-        return YH_OK;
-      };
-      if ((rc = h2d(d_pos, s.positions, nv * 12))) return rc;
-      if (s.radius && (rc = h2d(d_rad, s.radius, nv * 4))) return rc;
-      if ((rc = h2d(d_idx, idx, (size_t)nel * (lines ? 8 : 12)))) return rc;
-      if ((rc = dev_alloc(ctx, d_boxes, (size_t)nel * 24))) return rc;
-      if ((rc = dev_alloc(ctx, d_pid, (size_t)nel * 4))) return rc;
-      if ((rc = dev_alloc(ctx, d_tree[si], ((size_t)2 * nel + 1) * 32))) return rc;
-      int e = yhk_prim_boxes(lines ? 1 : 0, nel, (const float*)d_pos.p, (const float*)d_rad.p, (const int*)d_idx.p, (float*)d_boxes.p, ctx->stream);
-      if (e) return fail(ctx, YH_E_DEVICE, "primitive bounds: %s", hipGetErrorString((hipError_t)e));
-      // (the normals' copy is queued behind the kernels that do not need it: it travels while the tree is built)
-      if (s.normals && (rc = h2d(d_nrm, s.normals, nv * 12))) return rc;
-      e = yhk_bvh_build_resident(nel, (const float*)d_boxes.p, (float*)d_tree[si].p, (int*)d_pid.p, &I.num_nodes, &I.levels, I.level_first, ctx->stream);
-      if (e) return fail(ctx, YH_E_DEVICE, "device BVH build: %s", hipGetErrorString((hipError_t)e));
-      lap("device: bounds + reference tree");
-      e = yhk_leaf_records(lines ? 1 : 0, nel, (const int*)d_pid.p, (const float*)d_pos.p, (const float*)d_nrm.p, (const float*)d_rad.p, (const int*)d_idx.p, d_recs, ctx->stream);
-      if (e) return fail(ctx, YH_E_DEVICE, "leaf records: %s", hipGetErrorString((hipError_t)e));
-      float root8[8];
-      HIPCHK(ctx, hipMemcpyAsync(root8, d_tree[si].p, 32, hipMemcpyDeviceToHost, ctx->stream));
-      YH_WAIT(ctx);  // (the vertex arrays go out of scope)
-      memcpy(I.root.min, root8, 12), memcpy(I.root.max, root8 + 3, 12);
-      lap("device: leaf records");
-    } else {
-      // ---- on the host (small shapes) ----
-      auto pos = [&](int v) { return ld3(s.positions + 3 * (size_t)v); };
-      auto rad = [&](int v) { return s.radius ? s.radius[v] : 0.001f; };  // add_radius, sceneio.cpp:390
-      std::vector<yhh::Box> boxes(nel);
-      parallel_for(nel, [&](int e) {
-        if (lines) {  // line_bounds (math.h:3037-3040)
-          int a = idx[2 * e], b = idx[2 * e + 1];
-          F3  p0 = pos(a), p1 = pos(b);
-          float r0 = rad(a), r1 = rad(b);
-          float lo0[3] = {p0.x - r0, p0.y - r0, p0.z - r0}, lo1[3] = {p1.x - r1, p1.y - r1, p1.z - r1};
-          float hi0[3] = {p0.x + r0, p0.y + r0, p0.z + r0}, hi1[3] = {p1.x + r1, p1.y + r1, p1.z + r1};
-          for (int k = 0; k < 3; k++) boxes[e].min[k] = fmin_(lo0[k], lo1[k]), boxes[e].max[k] = fmax_(hi0[k], hi1[k]);
-        } else {  // triangle_bounds (math.h:3041-3044)
-          const float* p0 = s.positions + 3 * (size_t)idx[3 * e];
-          const float* p1 = s.positions + 3 * (size_t)idx[3 * e + 1];
-          const float* p2 = s.positions + 3 * (size_t)idx[3 * e + 2];
-          for (int k = 0; k < 3; k++) {
-            boxes[e].min[k] = fmin_(p0[k], fmin_(p1[k], p2[k]));
-            boxes[e].max[k] = fmax_(p0[k], fmax_(p1[k], p2[k]));
-          }
-        }
-      });
-      yhh::Tree tree;
-      yhh::build_bvh(tree, boxes);
-      // the tree as the device builder leaves it: 8 floats per node (yhh::Node has that layout byte for byte), the first node of every level
-      static_assert(sizeof(yhh::Node) == 32 && offsetof(yhh::Node, start) == 24 && offsetof(yhh::Node, num) == 28 && offsetof(yhh::Node, internal) == 30 && offsetof(yhh::Node, axis) == 31,
-          "yhh::Node is the device's node record");
-      I.num_nodes = (int)tree.nodes.size();
-      if (!tree_levels(tree, I.levels, I.level_first)) return fail(ctx, YH_E_INVALID, "shape %d: tree of %d levels", si, I.levels);
-      if ((rc = upload(ctx, d_tree[si], tree.nodes.data(), tree.nodes.size() * 32))) return rc;
-      I.root = tree.nodes[0].bbox;
-      auto nrm = [&](int v) { return s.normals ? ld3(s.normals + 3 * (size_t)v) : F3{0, 0, 0}; };
-      const size_t per = lines ? 4 : 6;
-      I.host_prims.resize(per * (size_t)nel);
-      yhd_float4* out = I.host_prims.data();
-      parallel_for(nel, [&](int slot) {
-        int   e = tree.primitives[slot];
-        float ew;
-        memcpy(&ew, &e, 4);
-        yhd_float4* r = out + per * (size_t)slot;
-        if (lines) {
-          int a = idx[2 * e], b = idx[2 * e + 1];
-          F3  p0 = pos(a), p1 = pos(b), t0 = nrm(a), t1 = nrm(b);
-          r[0] = {p0.x, p0.y, p0.z, rad(a)}, r[1] = {p1.x, p1.y, p1.z, rad(b)};
-          r[2] = {t0.x, t0.y, t0.z, ew}, r[3] = {t1.x, t1.y, t1.z, 0};
-        } else {
-          int a = idx[3 * e], b = idx[3 * e + 1], cc = idx[3 * e + 2];
-          F3  p0 = pos(a), p1 = pos(b), p2 = pos(cc), n0 = nrm(a), n1 = nrm(b), n2 = nrm(cc);
-          r[0] = {p0.x, p0.y, p0.z, ew}, r[1] = {p1.x, p1.y, p1.z, 0}, r[2] = {p2.x, p2.y, p2.z, 0};
-          r[3] = {n0.x, n0.y, n0.z, 0}, r[4] = {n1.x, n1.y, n1.z, 0}, r[5] = {n2.x, n2.y, n2.z, 0};
-        }
-      });
-      HIPCHK(ctx, hipMemcpy(d_recs, I.host_prims.data(), I.host_prims.size() * 16, hipMemcpyHostToDevice));
-      lap("host: small shape");
-    }
-    {  // depths of the wide trees: a W-wide node stands for every internal binary node at a level that is a multiple of log2 W, so the wide
-       // depth is 1 + deepest internal level / log2 W (what collapse_wide / _wide8 / _wide16 return). The last level holds leaves only.
-      const int deepest = std::max(0, I.levels - 2);
-      I.depth = 1 + deepest / 2, I.depth8 = 1 + deepest / 3, I.depth16 = 1 + deepest / 4;
-    }
+    if ((rc = build_shape_tree(ctx, "", si, s, false, shape_builds_on_device(nel), (yhd_float4*)ctx->d_prims.p + I.prim_base, I))) return rc;
+    lap(I.host_prims.empty() ? "device: bounds, tree, leaf records" : "host: small shape");
     {
       // Per-vertex positions and per-element indices are read on the device only to sample a point
       // on an area light (triangles, pt.cpp:1287-1292) and to interpolate texture coordinates; the
@@ -418,16 +451,8 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
   }
   // ---- the wide collapses: the index of every wide node (one flag pass + one scan per width), then the layout of the ONE array the traversal
   // kernels read (yh_device.h: lane_blob, 32-byte units): [4-wide nodes of the scene tree, if any][test records of every shape][4-wide nodes][8-wide nodes][16-wide nodes] ----
-  std::vector<DevBuf> d_wflag((size_t)sd->num_shapes * 3), d_widx((size_t)sd->num_shapes * 3);
   for (int si = 0; si < sd->num_shapes; si++)
-    for (int w = 0; w < 3; w++) {
-      auto&  I = info[si];
-      DevBuf &f = d_wflag[(size_t)si * 3 + w], &x = d_widx[(size_t)si * 3 + w];
-      if ((rc = dev_alloc(ctx, f, ((size_t)I.num_nodes + 1) * 4))) return rc;
-      if ((rc = dev_alloc(ctx, x, ((size_t)I.num_nodes + 1) * 4))) return rc;
-      int e = yhk_wide_index(I.num_nodes, (const float*)d_tree[si].p, I.levels, I.level_first, 2 + w, (unsigned int*)f.p, (unsigned int*)x.p, &I.wide_count[w], ctx->stream);
-      if (e) return fail(ctx, YH_E_DEVICE, "wide-node index: %s", hipGetErrorString((hipError_t)e));
-    }
+    if ((rc = index_shape_tree(ctx, "", info[si]))) return rc;
   ctx->lane_shapes.assign((size_t)sd->num_shapes, yh_context::LaneShape{});
   long long U8 = 0, U16 = 0, blob_units = 0;
   {
@@ -453,22 +478,18 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
     (void)U16;
   }
   if ((rc = alloc_zero(ctx, ctx->d_lane_blob, (size_t)blob_units * 32))) return rc;
-  for (int si = 0; si < sd->num_shapes; si++) {
-    auto& L = ctx->lane_shapes[(size_t)si];
-    auto& I = info[si];
-    int e = yhk_lane_tests((const yhd_float4*)ctx->d_prims.p, (yhd_float4*)ctx->d_lane_blob.p, L.kind, L.prim_base, L.num_prims, L.test_off, ctx->stream);
-    const long long offs[3] = {L.node_off, L.node_off8, L.node_off16};
-    for (int w = 0; w < 3 && !e; w++)
-      e = yhk_wide_collapse(2 + w, I.num_nodes, (const float*)d_tree[si].p, (const unsigned int*)d_wflag[(size_t)si * 3 + w].p, (const unsigned int*)d_widx[(size_t)si * 3 + w].p,
-          L.kind == YH_KIND_LINES ? 1 : 0, offs[w], L.test_off, ctx->d_lane_blob.p, ctx->stream);
-    if (e) return fail(ctx, YH_E_DEVICE, "wide collapse: %s", hipGetErrorString((hipError_t)e));
-  }
+  for (int si = 0; si < sd->num_shapes; si++)
+    if ((rc = collapse_shape_tree(ctx, "", info[si], ctx->lane_shapes[(size_t)si], ctx->d_lane_blob.p))) return rc;
   if (scene_wide) {  // leaf references as of a line shape whose test records start at 0: count << 27 | first scene primitive
     int e = yhk_wide_collapse(2, (int)scene_tree.nodes.size(), (const float*)d_stree.p, (const unsigned int*)d_sflag.p, (const unsigned int*)d_sidx.p, 1, 0, 0, ctx->d_lane_blob.p, ctx->stream);
     if (e) return fail(ctx, YH_E_DEVICE, "wide collapse of the scene tree: %s", hipGetErrorString((hipError_t)e));
   }
   YH_WAIT(ctx);
-  d_tree.clear(), d_wflag.clear(), d_widx.clear(), d_stree.reset(), d_sflag.reset(), d_sidx.reset();
+  for (auto& I : info) {
+    I.d_tree.reset();
+    for (int w = 0; w < 3; w++) I.d_wflag[w].reset(), I.d_widx[w].reset();
+  }
+  d_stree.reset(), d_sflag.reset(), d_sidx.reset();
   lap("device: wide collapses, blob");
   // ---- objects ------------------------------------------------------------
   std::vector<yhd_object> objects(sd->num_objects);
@@ -705,11 +726,21 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
     ctx->key_camera = sd->camera;
     ctx->h_materials.assign(sd->materials, sd->materials + sd->num_materials);
     ctx->key_geometry.clear(), ctx->key_envs.clear();
+    ctx->shape_states.assign((size_t)sd->num_shapes, yh_context::ShapeState{});
     bytes(ctx->key_geometry, sd->objects, sizeof(yh_object) * (size_t)sd->num_objects);
     for (int i = 0; i < sd->num_shapes; i++) {
       const yh_shape& sh = sd->shapes[i];
       int counts[3] = {sh.num_vertices, sh.num_lines, sh.num_triangles};
       bytes(ctx->key_geometry, counts, sizeof(counts));
+      {  // what yh_update_shape needs of this shape (context_internal.h); at an upload every width has room for exactly its nodes
+        auto& E = ctx->shape_states[(size_t)i];
+        auto& I = info[(size_t)i];
+        E.num_vertices = sh.num_vertices, E.has_normals = sh.normals != nullptr, E.has_texcoords = sh.texcoords != nullptr;
+        E.per_vertex = sh.num_lines <= 0 || sh.texcoords != nullptr, E.vert_base = I.vert_base, E.elem_base = I.elem_base;
+        E.depth = I.depth, E.depth8 = I.depth8, E.depth16 = I.depth16;
+        for (int w = 0; w < 3; w++) E.count[w] = E.room[w] = I.wide_count[w];
+        E.key_positions = ctx->key_geometry.size();
+      }
       if (sh.positions && sh.num_vertices > 0) {
         const size_t n = (size_t)sh.num_vertices, take = std::min<size_t>(n, 256);
         bytes(ctx->key_geometry, sh.positions, take * 12), bytes(ctx->key_geometry, sh.positions + 3 * (n - take), take * 12);

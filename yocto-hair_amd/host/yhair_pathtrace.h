@@ -94,6 +94,7 @@ struct flat_scene {
   std::vector<yh_object>        objects;
   std::vector<yh_environment>   environments;
   std::vector<yh_texture>       textures;
+  std::vector<unsigned>         shape_vertex_edits;  // per shape how often a vertex setter ran (shape::vertex_edits); empty: all 0
   yh_camera                     camera{};
   yh_scene_desc desc() const {
     yh_scene_desc d{};
@@ -112,23 +113,44 @@ struct flat_scene {
 // texture, a map, the number of anything, a material's texture ids, an emission that turns on or off. No device, no context.
 // objects_too (EXTENSION, see set_object_edits): objects that differ in frame or material only are edit_objects, what
 // yh_update_objects accepts, unless the new material turns the object's emission on or off; an object's shape stays edit_upload.
-enum : unsigned { edit_none = 0, edit_camera = 1, edit_materials = 2, edit_environments = 4, edit_upload = 8, edit_objects = 16 };
-inline unsigned classify_edit(const flat_scene& was, const flat_scene& now, bool objects_too) {
+// shapes_too (EXTENSION, see set_shape_edits): a shape whose counts and index arrays are the uploaded ones and which differs in
+// positions, normals, radius or texcoords only — by their pointers, or by a vertex setter having run since the upload, which writes
+// into the same storage when the sizes agree — is edit_shapes, what yh_update_shape accepts, unless normals or texcoords appear or
+// vanish or an object that names it emits (its light tables were made from it). Without it nothing of this is looked at.
+enum : unsigned { edit_none = 0, edit_camera = 1, edit_materials = 2, edit_environments = 4, edit_upload = 8, edit_objects = 16, edit_shapes = 32 };
+// whether shape i differs in its vertex arrays alone (the counts and the index arrays being equal is the caller's business)
+inline bool shape_vertices_differ(const flat_scene& was, const flat_scene& now, size_t i) {
+  const yh_shape &a = was.shapes[i], &b = now.shapes[i];
+  auto edits = [i](const flat_scene& f) { return i < f.shape_vertex_edits.size() ? f.shape_vertex_edits[i] : 0u; };
+  return a.positions != b.positions || a.normals != b.normals || a.radius != b.radius || a.texcoords != b.texcoords || edits(was) != edits(now);
+}
+inline unsigned classify_edit(const flat_scene& was, const flat_scene& now, bool objects_too, bool shapes_too = false) {
   auto black = [](const float* e) { return e[0] == 0 && e[1] == 0 && e[2] == 0; };
   if (was.shapes.size() != now.shapes.size() || was.materials.size() != now.materials.size() || was.maps.size() != now.maps.size() ||
       was.objects.size() != now.objects.size() || was.environments.size() != now.environments.size() || was.textures.size() != now.textures.size())
     return edit_upload;
+  unsigned shape_kind = edit_none;
   for (size_t i = 0; i < now.shapes.size(); i++) {
     const yh_shape &a = was.shapes[i], &b = now.shapes[i];
-    if (a.num_vertices != b.num_vertices || a.positions != b.positions || a.normals != b.normals || a.radius != b.radius || a.num_lines != b.num_lines ||
-        a.lines != b.lines || a.num_triangles != b.num_triangles || a.triangles != b.triangles || a.texcoords != b.texcoords)
+    if (a.num_vertices != b.num_vertices || a.num_lines != b.num_lines || a.lines != b.lines || a.num_triangles != b.num_triangles || a.triangles != b.triangles)
       return edit_upload;
+    if (!shapes_too) {
+      if (a.positions != b.positions || a.normals != b.normals || a.radius != b.radius || a.texcoords != b.texcoords) return edit_upload;
+      continue;
+    }
+    if (!shape_vertices_differ(was, now, i)) continue;
+    if (!b.positions || (a.normals != nullptr) != (b.normals != nullptr) || (a.texcoords != nullptr) != (b.texcoords != nullptr)) return edit_upload;
+    for (size_t o = 0; o < now.objects.size(); o++) {  // an emitter's geometry: the light list was made from it
+      const yh_object& ob = now.objects[o];
+      if ((size_t)ob.shape == i && ob.material >= 0 && (size_t)ob.material < now.materials.size() && !black(now.materials[(size_t)ob.material].emission)) return edit_upload;
+    }
+    shape_kind = edit_shapes;
   }
   for (size_t i = 0; i < now.textures.size(); i++) {
     const yh_texture &a = was.textures[i], &b = now.textures[i];
     if (a.width != b.width || a.height != b.height || a.is_byte != b.is_byte || a.pixels != b.pixels) return edit_upload;
   }
-  unsigned kind = edit_none;
+  unsigned kind = shape_kind;
   for (size_t i = 0; i < now.objects.size(); i++) {
     const yh_object &a = was.objects[i], &b = now.objects[i];
     if (a.shape != b.shape) return edit_upload;
@@ -281,6 +303,7 @@ struct shape {  // pt.h:335-366
   std::vector<vec3f> positions, normals;
   std::vector<vec2f> texcoords;
   std::vector<float> radius;
+  unsigned           vertex_edits = 0;  // EXTENSION: how often set_positions / _normals / _radius / _texcoords ran (see set_shape_edits)
 };
 struct object {
   frame3f   frame;
@@ -309,6 +332,7 @@ struct scene {
   mutable detail::flat_scene uploaded;
   mutable int                uploads = 0, edits = 0;
   bool                       object_edits = false;  // EXTENSION (set_object_edits): object frames and materials go through yh_update_objects
+  bool                       shape_edits  = false;  // EXTENSION (set_shape_edits): vertex edits of a shape go through yh_update_shape
 };
 struct state {  // pt.h:426-429; `render` is refreshed by trace_samples
   int                width = 0, height = 0, samples = 0;
@@ -371,7 +395,7 @@ inline void set_texture(texture* t, int width, int height, const std::vector<uns
 }
 inline void set_emission(material* m, const vec3f& e, texture* tex = nullptr) { m->emission = e, m->emission_tex = tex; }
 inline void set_color(material* m, const vec3f& c, texture* tex = nullptr) { m->color = c, m->color_tex = tex; }
-inline void set_texcoords(shape* s, const std::vector<vec2f>& v) { s->texcoords = v; }
+inline void set_texcoords(shape* s, const std::vector<vec2f>& v) { s->texcoords = v, s->vertex_edits++; }
 inline void set_specular(material* m, float v = 1, texture* tex = nullptr) { m->specular = v, m->specular_tex = tex; }
 inline void set_ior(material* m, float v) { m->ior = v; }
 inline void set_metallic(material* m, float v, texture* tex = nullptr) { m->metallic = v, m->metallic_tex = tex; }
@@ -387,21 +411,26 @@ inline void set_normalmap(material* m, texture* tex) { m->normal_tex = tex; }
 inline void set_thin(material* m, bool thin) { m->thin = thin; }
 inline void set_lines(shape* s, const std::vector<vec2i>& v) { s->lines = v; }
 inline void set_triangles(shape* s, const std::vector<vec3i>& v) { s->triangles = v; }
-inline void set_positions(shape* s, const std::vector<vec3f>& v) { s->positions = v; }
-inline void set_normals(shape* s, const std::vector<vec3f>& v) { s->normals = v; }
-inline void set_radius(shape* s, const std::vector<float>& v) { s->radius = v; }
+inline void set_positions(shape* s, const std::vector<vec3f>& v) { s->positions = v, s->vertex_edits++; }
+inline void set_normals(shape* s, const std::vector<vec3f>& v) { s->normals = v, s->vertex_edits++; }
+inline void set_radius(shape* s, const std::vector<float>& v) { s->radius = v, s->vertex_edits++; }
 // (the same taking a temporary: the reference's signatures copy; a caller that hands over a vector it no longer needs — a loader — moves it: 60 MB for a hair model)
 inline void set_lines(shape* s, std::vector<vec2i>&& v) { s->lines = std::move(v); }
 inline void set_triangles(shape* s, std::vector<vec3i>&& v) { s->triangles = std::move(v); }
-inline void set_positions(shape* s, std::vector<vec3f>&& v) { s->positions = std::move(v); }
-inline void set_normals(shape* s, std::vector<vec3f>&& v) { s->normals = std::move(v); }
-inline void set_radius(shape* s, std::vector<float>&& v) { s->radius = std::move(v); }
+inline void set_positions(shape* s, std::vector<vec3f>&& v) { s->positions = std::move(v), s->vertex_edits++; }
+inline void set_normals(shape* s, std::vector<vec3f>&& v) { s->normals = std::move(v), s->vertex_edits++; }
+inline void set_radius(shape* s, std::vector<float>&& v) { s->radius = std::move(v), s->vertex_edits++; }
 inline void set_frame(environment* e, const frame3f& f) { e->frame = f; }
 // EXTENSION (no reference counterpart: the reference reads every struct live and has nothing to opt into). By default an object whose
 // frame or material changed since the last init_state costs the whole upload at the next one; with `on`, such objects are passed on
 // through yh_update_objects, which keeps every shape's tree and builds the scene-level tree again (include/yhair.h). What that call
 // refuses — an object's shape, emission on or off, a tree too deep, a scene level that changes its form — falls back to the upload.
 inline void set_object_edits(scene* s, bool on) { s->object_edits = on; }
+// EXTENSION, off by default like the one above. With `on`, a shape whose positions, normals (the hair tangents), radius or texcoords were
+// set since the last init_state — its counts and its lines / triangles being the uploaded ones — is passed on through yh_update_shape:
+// that shape's tree, records and nodes are made again, no other shape, texture or light table is touched (include/yhair.h). What that
+// call refuses — an emitter's geometry, a tree too deep, a scene level that changes its form — falls back to the upload.
+inline void set_shape_edits(scene* s, bool on) { s->shape_edits = on; }
 inline void set_emission(environment* e, const vec3f& em, texture* tex = nullptr) { e->emission = em, e->emission_tex = tex; }
 
 // Flattens the scene graph into a yh_scene_desc and uploads it; the C ABI builds
@@ -449,6 +478,7 @@ inline detail::flat_scene flatten_scene(const scene* sc, const camera* cam) {
     o.triangles     = o.num_triangles ? (const int*)s->triangles.data() : nullptr;
     o.texcoords     = s->texcoords.size() == s->positions.size() && !s->texcoords.empty() ? (const float*)s->texcoords.data() : nullptr;
     shapes.push_back(o);
+    flat.shape_vertex_edits.push_back(s->vertex_edits);
   }
   for (auto& m : sc->materials) {
     yh_material o{};
@@ -511,6 +541,9 @@ inline bool update_scene(const scene* sc, const camera* cam, detail::flat_scene&
     if (!rc && (kind & detail::edit_materials)) rc = yh_update_materials(ctx, 0, (int)flat.materials.size(), flat.materials.data());
     if (!rc && (kind & detail::edit_environments)) rc = yh_update_environments(ctx, (int)flat.environments.size(), flat.environments.data());
     if (!rc && (kind & detail::edit_objects)) rc = yh_update_objects(ctx, 0, (int)flat.objects.size(), flat.objects.data());
+    if (kind & detail::edit_shapes)
+      for (size_t i = 0; i < flat.shapes.size() && !rc; i++)
+        if (detail::shape_vertices_differ(sc->uploaded, flat, i)) rc = yh_update_shape(ctx, (int)i, &flat.shapes[i]);
     if (rc == YH_E_INVALID) refused = true, rc = YH_OK;
     return rc;
   });
@@ -538,12 +571,13 @@ inline void init_state(state* st, const scene* sc, const camera* cam, const trac
   // The reference reads its scene structs at every sample, so whatever a caller set since the last init_state is in force from here on
   // (apps/ysceneitraces/ysceneitraces.cpp:392-410: the camera's frame, then reset_display). The contexts hold a flattened copy: compare.
   // Nothing changed: nothing to do. Only what the yh_update_* calls accept (camera fields, material fields, the environments' frames
-  // and emission; with set_object_edits, the objects' frames and materials): those calls, which keep every shape's tree. Anything else
+  // and emission; with set_object_edits, the objects' frames and materials; with set_shape_edits, a shape's vertex arrays): those calls,
+  // which keep every shape's tree but an edited shape's own. Anything else
   // — an object's frame without the opt-in, a shape's arrays, a texture, an emission turned on or off, init_bvh / init_lights called
   // again — is the whole upload.
   {
     auto     flat = flatten_scene(sc, cam);
-    unsigned kind = sc->uploaded_for ? detail::classify_edit(sc->uploaded, flat, sc->object_edits) : (unsigned)detail::edit_upload;
+    unsigned kind = sc->uploaded_for ? detail::classify_edit(sc->uploaded, flat, sc->object_edits, sc->shape_edits) : (unsigned)detail::edit_upload;
     if (kind != detail::edit_none && !(kind & detail::edit_upload)) {
       if (update_scene(sc, cam, std::move(flat), kind)) sc->edits++;
       else kind = detail::edit_upload, flat = flatten_scene(sc, cam);

@@ -143,6 +143,9 @@ _SIGS = {
     "yh_update_materials": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Material)]),
     "yh_update_environments": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Environment)]),
     "yh_update_objects": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Object)]),
+    "yh_update_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Shape)]),
+    "yh_update_shape_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Shape)]),
+    "yh_shape_nodes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), c_int_p, c_int_p]),
     "yh_download_display": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     "yh_init_state": (C.c_int, [C.c_void_p, C.POINTER(TraceParams)]),
     "yh_image_size": (C.c_int, [C.c_void_p, c_int_p, c_int_p]),
@@ -322,6 +325,48 @@ class Context:
         if objects is not None and not isinstance(objects, C.Array):
             objects = (Object * len(objects))(*objects)
         self._chk(self.lib.yh_update_objects(self.h, first, len(objects) if objects is not None else 0, objects))
+
+    # vertex edits of one shape: its tree, records and nodes are made again, and the scene level; no other shape is touched
+    def update_shape(self, index, shape):
+        """yh_update_shape: `shape` is a Shape with HOST arrays and the uploaded shape's counts (e.g. a copy of
+        desc.contents.shapes[index] with its pointers set to edited float32 / int32 numpy arrays, which the caller keeps alive)."""
+        self._chk(self.lib.yh_update_shape(self.h, index, C.byref(shape) if shape is not None else None))
+
+    def update_shape_device(self, index, positions, normals=None, radius=None, lines=None, triangles=None, texcoords=None):
+        """yh_update_shape_device: contiguous torch tensors on the context's device — positions (n, 3), normals (n, 3), radius (n,),
+        texcoords (n, 2) float32; lines (m, 2) or triangles (m, 3) int32. The current torch stream is synchronised before the call,
+        which runs on the context's own stream."""
+        import torch
+
+        def ptr(t, dtype, cols, what):
+            if t is None:
+                return None
+            if not isinstance(t, torch.Tensor):
+                raise YhError(f"update_shape_device: {what} must be a torch tensor, not {type(t).__name__}")
+            if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (cols and (t.dim() != 2 or t.shape[1] != cols)) or (not cols and t.dim() != 1):
+                raise YhError(f"update_shape_device: {what} must be a contiguous {dtype} tensor on the GPU" + (f" of shape (n, {cols})" if cols else " of shape (n,)"))
+            return t.data_ptr()
+
+        if positions is None:
+            raise YhError("update_shape_device: positions is None")
+        s = Shape()
+        s.positions = C.cast(ptr(positions, torch.float32, 3, "positions"), c_float_p)
+        s.num_vertices = int(positions.shape[0])
+        s.normals = C.cast(ptr(normals, torch.float32, 3, "normals"), c_float_p)
+        s.radius = C.cast(ptr(radius, torch.float32, 0, "radius"), c_float_p)
+        s.texcoords = C.cast(ptr(texcoords, torch.float32, 2, "texcoords"), c_float_p)
+        s.lines = C.cast(ptr(lines, torch.int32, 2, "lines"), c_int_p)
+        s.num_lines = int(lines.shape[0]) if lines is not None else 0
+        s.triangles = C.cast(ptr(triangles, torch.int32, 3, "triangles"), c_int_p)
+        s.num_triangles = int(triangles.shape[0]) if triangles is not None else 0
+        torch.cuda.current_stream(positions.device).synchronize()
+        self._chk(self.lib.yh_update_shape_device(self.h, index, C.byref(s)))
+
+    def shape_nodes(self, index):
+        """yh_shape_nodes: (offsets, counts, room) of the shape's 4-, 8- and 16-wide nodes in the traversal array (32-byte units)."""
+        off, cnt, room = (C.c_int64 * 3)(), (C.c_int * 3)(), (C.c_int * 3)()
+        self._chk(self.lib.yh_shape_nodes(self.h, index, off, cnt, room))
+        return list(off), list(cnt), list(room)
 
     def update_environments(self, environments):
         """yh_update_environments: frame and emission of every environment (a ctypes array of Environment, or a list)."""
