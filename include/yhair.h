@@ -322,6 +322,34 @@ int yh_update_objects(yh_context* ctx, int first, int count, const yh_object* ob
  * returns YH_E_DEVICE and leaves the context without a scene.                                                                      */
 int yh_update_shape(yh_context* ctx, int shape, const yh_shape* now);
 int yh_update_shape_device(yh_context* ctx, int shape, const yh_shape* now);
+/* REFIT: the same vertex edit, kept in the tree the shape HAS — a simulation step, a comb stroke, a sway, in which strands move a
+ * fraction of their length. Arguments, borrowing, stream rules and refusals are those of yh_update_shape / _device (the whole yh_shape:
+ * the index array is read again, records are made from idx[element], and any primitives are valid under recomputed boxes). Nothing is
+ * built: every leaf slot keeps its element (the record in it holds the element id) and is written again from the new arrays, the
+ * bits the upload's leaf records have; the test records are made from them; the boxes of the shape's 4-, 8- and 16-wide nodes are
+ * recomputed bottom-up in place — a leaf slot's the union of its primitives' line_bounds / triangle_bounds (radius 0.001 where the
+ * shape has none), an internal slot's the union of the child node's slots, an empty slot's stays; references, axes and occupied bits
+ * are not written — one kernel launch per level of each wide tree, deepest first (no boxes pass between workgroups inside a launch);
+ * the per-vertex rows are written again; the root box, the rows and world boxes of the objects that name the shape and the scene
+ * level follow as after yh_update_shape (the reference's scene-level tree is built exactly: it is cheap). The traversal array neither
+ * grows nor moves (yh_shape_nodes reports the same offsets, counts and room), the stack depths stay, no other shape's bytes are
+ * touched, and the only scratch the shape sizes is its primitive boxes in leaf order (24 bytes each) and the host form's staged arrays.
+ * Everything that can refuse — the checks, the index check by kernel, the new root box (a min / max reduction, exact and order-free)
+ * and the scene level's two refusals — runs before the first write: a refused call leaves the context exactly as it was.
+ * CONTRACT. After yh_refit_shape the context holds a valid tree over the edited description with the topology of the shape's last
+ * BUILD (the upload, or the last yh_update_shape). Closest hits are those of a fresh upload: the distance of every ray is the same
+ * bits; object, element and uv are the same except where two primitives lie at bit-equal closest distance — the winner of such a
+ * tie follows the visiting order, which is the old topology's. Images are therefore those of a fresh upload except on paths that
+ * meet such a tie. Where the edited description has the same reference tree as the last build (a uniform scale by two, an edit of
+ * tangents, radii or texcoords that moves no centre across a split), EVERYTHING is the same bits as after a fresh upload. Render
+ * speed after large deformations degrades, because boxes overlap: the caller's trade. yh_update_shape with the same arrays restores
+ * the reference's tree, and with it bit-for-bit identity with a fresh upload in every case.
+ * yh_shape_refit_growth is the number to make that trade with: per width (4, 8, 16) the sum of the half-areas of all occupied slot
+ * boxes of the shape's nodes NOW over the same sum at the shape's last build, summed on the device in double in a fixed order:
+ * exactly 1.0f after an upload, after yh_update_shape and after a refit that reproduces the boxes. YH_E_STATE before an upload.     */
+int yh_refit_shape(yh_context* ctx, int shape, const yh_shape* now);
+int yh_refit_shape_device(yh_context* ctx, int shape, const yh_shape* now);
+int yh_shape_refit_growth(const yh_context* ctx, int shape, float growth[3]);
 /* A diagnostic: where shape `shape`'s 4-, 8- and 16-wide nodes sit in the traversal array (offset, in 32-byte units), how many
  * nodes it has of each width (count) and how many its region has room for (room). YH_E_STATE before an upload.                    */
 int yh_shape_nodes(const yh_context* ctx, int shape, int64_t offset[3], int count[3], int room[3]);
@@ -517,6 +545,17 @@ int yh_bvh_build_gpu(yh_context* ctx, int n, const float* boxes, float* nodes, i
  * traversal kernels read: a child's ref is the index of its FIRST SLOT (width x the child node's index), and for width 4 bits 8-11 of `axes`
  * hold the occupied slots.                                                                                                              */
 int yh_bvh_build_wide_gpu(yh_context* ctx, int n, const float* boxes, int width, float* slots);
+/* REFIT of such a tree (what yh_refit_shape runs per width): `slots`, in and out, holds a `width`-wide tree over n primitives in the
+ * form of yh_bvh_build_wide_gpu; `boxes` are the primitives' NEW boxes, in primitive order; `primitives` is the leaf order of
+ * yh_bvh_build / yh_bvh_build_gpu. Every occupied slot's box is formed again bottom-up; ref and axes are not written. Returns the
+ * node count. `slots` MUST hold every node its references name: the count is not an argument, so the call finds the nodes by walking
+ * the references from node 0, level by level, and checks as it goes — an internal reference must name the next node in breadth-first
+ * order (width x its index) and no node past the n-th, a leaf must lie inside the n primitives, `primitives` must be indices below
+ * n — before any box is read or written; what fails a check is YH_E_INVALID and leaves `slots` as it was. It cannot tell a buffer that
+ * is shorter than the tree it describes. yh_bvh_refit_wide is the host restatement (no GPU, no context) that yh_bvh_refit_wide_gpu —
+ * the kernel of yh_refit_shape, one launch per level — is compared with.                                                              */
+int yh_bvh_refit_wide(int n, const float* boxes, const int* primitives, int width, float* slots);
+int yh_bvh_refit_wide_gpu(yh_context* ctx, int n, const float* boxes, const int* primitives, int width, float* slots);
 
 /* One surface lobe (kind = YH_LOBE_*) of yocto_math.h:1513-1620 (implementation
  * 4427-4755): eval_* (value times |cos|), sample_*_pdf and sample_* in one

@@ -160,6 +160,46 @@ int yh_bvh_build_wide(int n, const float* boxes, int width, float* slots) {
   return (int)count;
 }
 
+// what both refits check before a reference is followed, and the boxes in leaf order
+static int refit_wide_args(int n, const float* boxes, const int* primitives, int width, const float* slots, std::vector<yhh::Box>& leaf_boxes, std::vector<int>& first) {
+  if (n < 1 || !boxes || !primitives || !slots || (width != 4 && width != 8 && width != 16)) return YH_E_INVALID;
+  static_assert(sizeof(yhh::WideSlot) == 32 && sizeof(yhh::Box) == 24, "slots and boxes are passed as floats");
+  leaf_boxes.resize((size_t)n);
+  for (int i = 0; i < n; i++) {
+    if (primitives[i] < 0 || primitives[i] >= n) return YH_E_INVALID;
+    memcpy(&leaf_boxes[(size_t)i], boxes + 6 * (size_t)primitives[i], 24);
+  }
+  const int count = yhh::wide_levels(width, n, (const yhh::WideSlot*)slots, n, first);
+  return count < 1 ? YH_E_INVALID : count;
+}
+
+int yh_bvh_refit_wide(int n, const float* boxes, const int* primitives, int width, float* slots) {
+  std::vector<yhh::Box> leaf_boxes;
+  std::vector<int>      first;
+  const int             count = refit_wide_args(n, boxes, primitives, width, slots, leaf_boxes, first);
+  if (count < 1) return count;
+  yhh::refit_wide(width, leaf_boxes.data(), count, (yhh::WideSlot*)slots);
+  return count;
+}
+
+int yh_bvh_refit_wide_gpu(yh_context* ctx, int n, const float* boxes, const int* primitives, int width, float* slots) {
+  if (!ctx) return YH_E_INVALID;
+  std::vector<yhh::Box> leaf_boxes;
+  std::vector<int>      first;
+  const int             count = refit_wide_args(n, boxes, primitives, width, slots, leaf_boxes, first);
+  if (count < 1) return count < 0 ? fail(ctx, count, "yh_bvh_refit_wide_gpu: n, boxes, primitives, width or slots: no %d-wide tree over %d primitives in the device form", width, n) : count;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  YH_WAIT(ctx);
+  DevBuf d_boxes, d_slots;
+  int    rc;
+  if ((rc = upload(ctx, d_boxes, leaf_boxes.data(), (size_t)n * 24)) || (rc = upload(ctx, d_slots, slots, (size_t)count * width * 32))) return rc;
+  int e = yhk_refit_wide(width == 4 ? 2 : width == 8 ? 3 : 4, d_slots.p, 0, 0, 1, (int)first.size() - 1, first.data(), (const float*)d_boxes.p, ctx->stream);
+  if (e) return fail(ctx, YH_E_DEVICE, "yh_bvh_refit_wide_gpu: refit: %s", hipGetErrorString((hipError_t)e));
+  YH_WAIT(ctx);
+  HIPCHK(ctx, hipMemcpy(slots, d_slots.p, (size_t)count * width * 32, hipMemcpyDeviceToHost));
+  return count;
+}
+
 int yh_bvh_build(int n, const float* boxes, float* nodes, int* primitives) {
   if (n < 0 || (n && !boxes)) return YH_E_INVALID;
   std::vector<yhh::Box> b((size_t)n);

@@ -279,4 +279,61 @@ int collapse_wide16(const Tree& tree, std::vector<WideNode16>& out) {
   return max_depth;
 }
 
+int wide_levels(int width, int n, const WideSlot* slots, int max_nodes, std::vector<int>& first) {
+  first.assign(1, 0);
+  if (max_nodes < 1) return -1;
+  int level_end = 1, next = 1;  // the current level is [first.back(), level_end); `next`: the child the next internal slot must name
+  for (int node = 0; node < level_end; node++) {
+    for (int s = 0; s < width; s++) {
+      const unsigned ref = slots[(size_t)node * width + s].ref;
+      if (ref == 0xFFFFFFFFu) continue;
+      if (ref & 0x80000000u) {
+        const long long start = ref & 0x07FFFFFFu, num = (ref >> 27) & 7u;
+        if (!(ref & 0x40000000u) || start + num > n) return -1;
+      } else {
+        if (ref != (unsigned)width * (unsigned)next || next >= max_nodes) return -1;
+        next++;
+      }
+    }
+    if (node + 1 == level_end && next > level_end) first.push_back(level_end), level_end = next;
+  }
+  first.push_back(level_end);
+  return level_end;
+}
+
+void refit_wide(int width, const Box* leaf_boxes, int num_nodes, WideSlot* slots) {
+  const float inf = std::numeric_limits<float>::infinity();
+  auto unite = [](const Box& a, const Box& b) {
+    Box r;
+    for (int k = 0; k < 3; k++) r.min[k] = fmin_(a.min[k], b.min[k]), r.max[k] = fmax_(a.max[k], b.max[k]);
+    return r;
+  };
+  for (int node = num_nodes; node-- > 0;)  // children have larger indices than their parent
+    for (int s = 0; s < width; s++) {
+      WideSlot&      slot = slots[(size_t)node * width + s];
+      const unsigned ref  = slot.ref;
+      if (ref == 0xFFFFFFFFu) continue;
+      Box box;
+      if (ref & 0x80000000u) {
+        const int start = (int)(ref & 0x07FFFFFFu), num = (int)((ref >> 27) & 7u);
+        for (int k = 0; k < 3; k++) box.min[k] = flt_max, box.max[k] = flt_min;
+        for (int i = start; i < start + num; i++) box = unite(box, leaf_boxes[i]);
+      } else {
+        const WideSlot* child = slots + ref;
+        Box             part[16];
+        for (int c = 0; c < width; c++) {
+          if (child[c].ref == 0xFFFFFFFFu) {
+            for (int k = 0; k < 3; k++) part[c].min[k] = inf, part[c].max[k] = -inf;
+          } else {
+            for (int k = 0; k < 3; k++) part[c].min[k] = child[c].bmin[k], part[c].max[k] = child[c].bmax[k];
+          }
+        }
+        for (int step = 1; step < width; step *= 2)
+          for (int c = 0; c < width; c += 2 * step) part[c] = unite(part[c], part[c + step]);
+        box = part[0];
+      }
+      for (int k = 0; k < 3; k++) slot.bmin[k] = box.min[k], slot.bmax[k] = box.max[k];
+    }
+}
+
 }  // namespace yhh

@@ -78,5 +78,17 @@ struct WideNode16 {
 static_assert(sizeof(WideNode16) == 512, "16-wide node is 512 bytes");
 int collapse_wide16(const Tree& tree, std::vector<WideNode16>& out);
 
+// REFIT of a wide tree in the DEVICE form (what the device's collapse writes and the kernels read: an internal slot's ref is the
+// child node's first slot, width x its index; a leaf's low 27 bits are its first leaf slot): the topology stays, every occupied slot's
+// box is formed again bottom-up from `leaf_boxes`, the n primitive boxes in LEAF order — a leaf slot's from its primitives, an
+// internal slot's from the child node's slots, united pairwise as the binary levels they stand for unite their children, so the
+// boxes are the bits a build over the same leaf order forms. ref and axes are not written. The restatement unit/refit.hip's
+// k_refit_wide is compared with.
+// wide_levels: checks the form first — node 0 is the root, the children of a level's nodes are the next level's nodes, consecutive in
+// the order of their parents, leaves lie inside [0, n) — and returns the node count with the first node of every level in `first`
+// (then the count), or -1 for slots that are no such tree (nothing may follow their references).
+int  wide_levels(int width, int n, const WideSlot* slots, int max_nodes, std::vector<int>& first);
+void refit_wide(int width, const Box* leaf_boxes, int num_nodes, WideSlot* slots);
+
 }  // namespace yhh
 #endif

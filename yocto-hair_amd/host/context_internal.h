@@ -9,7 +9,8 @@
 //   gather.cpp         tile packing and the one collective (yh_gather_framebuffer: RCCL or peer copies)
 //   batch_api.cpp      the unit-level batch entry points (hair BSDF, intersection, BVH build, curves, self-tests)
 //   scene_edit.cpp     edits of an uploaded scene (yh_update_camera / _materials / _environments / _objects: the last one builds the
-//                      scene-level tree again; yh_update_shape / _device: one shape's tree too) and yh_download_display
+//                      scene-level tree again; yh_update_shape / _device: one shape's tree too; yh_refit_shape / _device: that tree's boxes
+//                      only, unit/refit.hip) and yh_download_display
 #ifndef YH_CONTEXT_INTERNAL_H_
 #define YH_CONTEXT_INTERNAL_H_
 #include <hip/hip_runtime_api.h>
@@ -96,6 +97,21 @@ int yhk_index_check(int n, const int* idx, int num_vertices, unsigned int* flag,
 int yhk_vertex_rows(int lines, int num_vertices, int num_elems, const float* pos, const float* radius, const float* texcoords, const int* idx, void* vpos, float* vtex,
     void* elems, hipStream_t);
 int yhk_object_lane_roots(int count, const void* rows, int shape, int root4, int root8, int root16, void* objects, hipStream_t);
+// unit/refit.hip (yh_refit_shape, yh_bvh_refit_wide_gpu), all pointers DEVICE pointers unless said otherwise: the primitive boxes of a
+// shape's leaf slots from new arrays (the element id is read from the record in the slot), their union as yhk_refit_partials(n) partial
+// boxes, the records again in place, the boxes of one width's wide nodes level by level (level_first: HOST, levels + 1 entries; units:
+// test records per primitive), and the half-area sum of a width's occupied slots as yhk_refit_partials(count) partial sums
+// ... and, at a build, the levels of the three wide trees and the first wide node of each level, from the indices yhk_wide_index made
+// (levels, level_first: the binary tree's, HOST; d_widx[w]: width 4 << w; d_out: 3 x 66 words of device memory; wide_levels, wide_first:
+// HOST, wide_first[w][wide_levels[w]] = the count; one launch and one copy for the three widths; synchronises)
+int yhk_wide_level_firsts(int num_nodes, int levels, const int* level_first, const unsigned int* const d_widx[3], unsigned int* d_out, int wide_levels[3], int wide_first[3][66],
+    hipStream_t);
+int yhk_refit_partials(int n);
+int yhk_refit_boxes(int lines, int n, const void* recs, const float* pos, const float* radius, const int* idx, float* boxes, hipStream_t);
+int yhk_box_partials(int n, const float* boxes, float* partial, hipStream_t);
+int yhk_refit_records(int lines, int n, const float* pos, const float* nrm, const float* radius, const int* idx, void* recs, hipStream_t);
+int yhk_refit_wide(int L, void* blob, long long node_off, long long test_off, int units, int levels, const int* level_first, const float* lboxes, hipStream_t);
+int yhk_area_partials(int width, const void* blob, long long node_off, int count, double* partial, hipStream_t);
 }
 
 // A device allocation owned by the context.
@@ -227,7 +243,16 @@ struct yh_context {
   // some), the depths of its tree as 4- / 8- / 16-wide nodes (the maxima above are made from them again), how many nodes of each width it
   // has and how many its region of the traversal array has room for (equal after an upload), and where its first and last 256 positions
   // sit in key_geometry
-  struct ShapeState { int num_vertices, has_normals, has_texcoords, per_vertex, vert_base, elem_base, depth, depth8, depth16, count[3], room[3]; size_t key_positions; };
+  // ... and what yh_refit_shape needs of the shape's last BUILD (the upload or the last yh_update_shape): per width the levels of its wide
+  // tree and the first node of each (wide_first[w][wide_levels[w]] = count[w]; children sit one level below their parent, so a refit
+  // recomputes boxes one level per launch), and the half-area sums of the occupied slot boxes then (area_build) and now (area_now):
+  // yh_shape_refit_growth is their ratio
+  struct ShapeState {
+    int    num_vertices, has_normals, has_texcoords, per_vertex, vert_base, elem_base, depth, depth8, depth16, count[3], room[3];
+    size_t key_positions;
+    int    wide_levels[3], wide_first[3][66];
+    double area_build[3], area_now[3];
+  };
   std::vector<ShapeState>       shape_states;
   // state
   bool             have_state = false;
@@ -356,6 +381,7 @@ struct ShapeTree {
   int      num_nodes = 0, levels = 1;  // the binary tree on the device: node count, levels, first node of every level
   int      level_first[130] = {0};
   int      wide_count[3] = {0, 0, 0};  // its 4- / 8- / 16-wide nodes
+  int      wide_levels[3] = {1, 1, 1}, wide_first[3][66] = {};  // ... the levels of each wide tree and the first node of every level (then the count)
   int      depth = 0, depth8 = 0, depth16 = 0;  // depths of the same tree collapsed two / three / four levels at a time
   DevBuf   d_tree, d_wflag[3], d_widx[3];       // binary nodes (8 floats each); per width the flag and index of every binary node
   std::vector<yhd_float4> host_prims;  // SMALL shapes: their leaf records on the host too (the LDS light table is made from them)
@@ -364,6 +390,10 @@ bool shape_builds_on_device(int num_prims);
 int build_shape_tree(yh_context* ctx, const char* who, int si, const yh_shape& s, bool arrays_on_device, bool on_device, yhd_float4* d_recs, ShapeTree& T);
 int index_shape_tree(yh_context* ctx, const char* who, ShapeTree& T);
 int collapse_shape_tree(yh_context* ctx, const char* who, const ShapeTree& T, const yh_context::LaneShape& L, void* blob);
+// scene_edit.cpp: for each of `n` shapes (L[i], count[i]) per width the sum of the half-areas of the occupied slot boxes of its nodes in `blob`,
+// in double and in a fixed order, to area[3 * i + w] — one allocation, 3 n kernels, one copy and one wait for all of them; what a build
+// stores in ShapeState and a refit compares with
+int shape_slot_areas(yh_context* ctx, const char* who, int n, const yh_context::LaneShape* L, const int (*count)[3], const void* blob, double* area);
 bool tree_levels(const yhh::Tree& tree, int& levels, int* level_first);
 bool scene_level_is_wide(int num_objects, int num_scene_nodes, int* lds_scene_f4);
 struct StackNeeds { int need, need8, need16; };

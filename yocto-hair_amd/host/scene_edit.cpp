@@ -1,6 +1,7 @@
 // scene_edit.cpp — edits of an uploaded scene: the camera, rows of the material table, the environments' frames and emission, rows of the
 // object list (yh_update_objects: it builds the scene-level tree over the objects' world boxes again) and, at the end, one shape's vertices
-// (yh_update_shape / _device: that shape's tree, records and nodes again, then the scene level; no other shape is touched). The reference
+// (yh_update_shape / _device: that shape's tree, records and nodes again, then the scene level; no other shape is touched; yh_refit_shape /
+// _device: the same edit in the tree the shape has, its records and boxes only). The reference
 // reads its scene structs live (an interactive caller edits app->camera->frame and traces on,
 // apps/ysceneitraces/ysceneitraces.cpp:392-410); here the description was flattened at yh_upload_scene, so an edit is a call of its own
 // that leaves the context as an upload of the edited description would: the scene table, the material rows on the device, the kernel
@@ -249,8 +250,8 @@ int yh_update_objects(yh_context* ctx, int first, int count, const yh_object* ob
 // positions: a width whose new count exceeds the room of the shape's region gets a new region behind the end of the traversal array
 // (count + count / 8 nodes, on a multiple of 4 units), the array is reallocated and the old bytes copied device to device, the vacated
 // region is zeroed and stays unused until an upload. No other shape moves: the collapse writes absolute references.
-static int update_shape(yh_context* ctx, const char* entry, int shape, const yh_shape* now, bool device) {
-  if (!ctx) return YH_E_INVALID;
+// what yh_update_shape and yh_refit_shape check of their arguments before anything is staged, and `rows`: the object list as it was passed in
+static int check_shape_edit(yh_context* ctx, const char* entry, int shape, const yh_shape* now, std::vector<yh_object>& rows) {
   if (!now) return fail(ctx, YH_E_INVALID, "%s: now is NULL", entry);
   if (int rc = edit_begin(ctx, entry)) return rc;
   const int num_shapes = (int)ctx->shape_states.size(), total = ctx->scene.num_objects;
@@ -266,24 +267,32 @@ static int update_shape(yh_context* ctx, const char* entry, int shape, const yh_
     return fail(ctx, YH_E_INVALID, "%s: shape %d has %d vertices, %d lines, %d triangles; the uploaded one has %d, %d, %d: upload the scene", entry, shape, now->num_vertices,
         now->num_lines, now->num_triangles, was_counts[0], was_counts[1], was_counts[2]);
   if (!now->positions) return fail(ctx, YH_E_INVALID, "%s: shape %d has no positions", entry, shape);
-  const int* idx_in = lines ? now->lines : now->triangles;
-  if (!idx_in) return fail(ctx, YH_E_INVALID, "%s: shape %d has no index array", entry, shape);
+  if (!(lines ? now->lines : now->triangles)) return fail(ctx, YH_E_INVALID, "%s: shape %d has no index array", entry, shape);
   if ((now->normals != nullptr) != (E.has_normals != 0))
     return fail(ctx, YH_E_INVALID, "%s: shape %d %s normals, the uploaded one %s: upload the scene", entry, shape, now->normals ? "has" : "has no", E.has_normals ? "had them" : "had none");
   if ((now->texcoords != nullptr) != (E.has_texcoords != 0))
     return fail(ctx, YH_E_INVALID, "%s: shape %d %s texcoords, the uploaded one %s: upload the scene", entry, shape, now->texcoords ? "has" : "has no", E.has_texcoords ? "had them" : "had none");
   // the light cdf and the LDS light table (init_lights, pt.cpp:1695-1740) were made from the shape of every object whose material emits
-  std::vector<yh_object> rows((size_t)total);  // (key_geometry begins with the object rows as they were passed in)
+  rows.resize((size_t)total);  // (key_geometry begins with the object rows as they were passed in)
   memcpy(rows.data(), ctx->key_geometry.data(), sizeof(yh_object) * (size_t)total);
   for (int i = 0; i < total; i++)
     if (rows[(size_t)i].shape == shape && !is_black(ctx->h_materials[(size_t)rows[(size_t)i].material].emission))
       return fail(ctx, YH_E_INVALID, "%s: shape %d is the shape of object %d, whose material emits: the light tables are made from it, upload the scene", entry, shape, i);
-  const std::string who_s = std::string(entry) + ": ";
-  const char*       who   = who_s.c_str();
-  // ---- staging: the arrays on the device (the host form copies them there), the index check before anything follows an index ----
-  const size_t nv = (size_t)now->num_vertices, nel = (size_t)L.num_prims, nidx = nel * (lines ? 2 : 3), per = lines ? 4 : 6;
+  return YH_OK;
+}
+
+// ... and their staging: the arrays on the device (the host form copies them there: `dev` is the same shape with its arrays in device
+// memory), the index check before anything follows an index
+namespace {
+struct ShapeArrays {
   DevBuf   d_pos, d_nrm, d_rad, d_idx, d_tex, d_flag;
-  yh_shape dev = *now;  // the same shape, its arrays in device memory
+  yh_shape dev{};
+};
+}  // namespace
+static int stage_shape_arrays(yh_context* ctx, const char* who, int shape, const yh_shape* now, bool device, bool lines, size_t nv, size_t nidx, ShapeArrays& A) {
+  const int* idx_in = lines ? now->lines : now->triangles;
+  yh_shape&  dev    = A.dev;
+  dev = *now;
   if (!device) {
     auto h2d = [&](DevBuf& buf, const void* src, size_t bytes, const void** to) -> int {
       if (!src) return YH_OK;
@@ -292,19 +301,57 @@ static int update_shape(yh_context* ctx, const char* entry, int shape, const yh_
       *to = buf.p;
       return YH_OK;
     };
-    if (int rc = h2d(d_idx, idx_in, nidx * 4, (const void**)(lines ? &dev.lines : &dev.triangles))) return rc;
-    if (int rc = h2d(d_pos, now->positions, nv * 12, (const void**)&dev.positions)) return rc;
-    if (int rc = h2d(d_rad, now->radius, nv * 4, (const void**)&dev.radius)) return rc;
-    if (int rc = h2d(d_nrm, now->normals, nv * 12, (const void**)&dev.normals)) return rc;
-    if (int rc = h2d(d_tex, now->texcoords, nv * 8, (const void**)&dev.texcoords)) return rc;
+    if (int rc = h2d(A.d_idx, idx_in, nidx * 4, (const void**)(lines ? &dev.lines : &dev.triangles))) return rc;
+    if (int rc = h2d(A.d_pos, now->positions, nv * 12, (const void**)&dev.positions)) return rc;
+    if (int rc = h2d(A.d_rad, now->radius, nv * 4, (const void**)&dev.radius)) return rc;
+    if (int rc = h2d(A.d_nrm, now->normals, nv * 12, (const void**)&dev.normals)) return rc;
+    if (int rc = h2d(A.d_tex, now->texcoords, nv * 8, (const void**)&dev.texcoords)) return rc;
   }
-  const int* d_index = lines ? dev.lines : dev.triangles;
-  if (int rc = stage_alloc(ctx, d_flag, 4)) return rc;
-  {
-    int bad = 0, e = yhk_index_check((int)nidx, d_index, now->num_vertices, (unsigned int*)d_flag.p, &bad, ctx->stream);
-    if (e) return fail(ctx, YH_E_DEVICE, "%sindex check: %s", who, hipGetErrorString((hipError_t)e));
-    if (bad) return fail(ctx, YH_E_INVALID, "%sshape %d: vertex index out of range", who, shape);
+  if (int rc = stage_alloc(ctx, A.d_flag, 4)) return rc;
+  int bad = 0, e = yhk_index_check((int)nidx, lines ? dev.lines : dev.triangles, now->num_vertices, (unsigned int*)A.d_flag.p, &bad, ctx->stream);
+  if (e) return fail(ctx, YH_E_DEVICE, "%sindex check: %s", who, hipGetErrorString((hipError_t)e));
+  if (bad) return fail(ctx, YH_E_INVALID, "%sshape %d: vertex index out of range", who, shape);
+  return YH_OK;
+}
+
+int shape_slot_areas(yh_context* ctx, const char* who, int n, const yh_context::LaneShape* L, const int (*count)[3], const void* blob, double* area) {
+  std::vector<int> at(3 * (size_t)n + 1, 0);  // where every (shape, width)'s partial sums begin
+  for (int i = 0; i < n; i++)
+    for (int w = 0; w < 3; w++) at[3 * (size_t)i + w + 1] = at[3 * (size_t)i + w] + yhk_refit_partials(count[i][w]);
+  DevBuf d_part;
+  if (int rc = stage_alloc(ctx, d_part, sizeof(double) * (size_t)at.back())) return rc;
+  for (int i = 0; i < n; i++) {
+    const long long off[3] = {L[i].node_off, L[i].node_off8, L[i].node_off16};
+    for (int w = 0; w < 3; w++) {
+      int e = yhk_area_partials(4 << w, blob, off[w], count[i][w], (double*)d_part.p + at[3 * (size_t)i + w], ctx->stream);
+      if (e) return fail(ctx, YH_E_DEVICE, "%sslot areas: %s", who, hipGetErrorString((hipError_t)e));
+    }
   }
+  std::vector<double> part((size_t)at.back());
+  HIPCHK(ctx, hipMemcpyAsync(part.data(), d_part.p, sizeof(double) * part.size(), hipMemcpyDeviceToHost, ctx->stream));
+  YH_WAIT(ctx);
+  for (size_t j = 0; j < 3 * (size_t)n; j++) {  // the partials in index order: the same sum from run to run
+    area[j] = 0;
+    for (int k = at[j]; k < at[j + 1]; k++) area[j] += part[(size_t)k];
+  }
+  return YH_OK;
+}
+
+static int update_shape(yh_context* ctx, const char* entry, int shape, const yh_shape* now, bool device) {
+  if (!ctx) return YH_E_INVALID;
+  std::vector<yh_object> rows;
+  if (int rc = check_shape_edit(ctx, entry, shape, now, rows)) return rc;
+  const int num_shapes = (int)ctx->shape_states.size(), total = ctx->scene.num_objects;
+  const yh_context::ShapeState& E = ctx->shape_states[(size_t)shape];
+  const yh_context::LaneShape&  L = ctx->lane_shapes[(size_t)shape];
+  const bool lines = L.kind == YH_KIND_LINES;
+  const std::string who_s = std::string(entry) + ": ";
+  const char*       who   = who_s.c_str();
+  const size_t nv = (size_t)now->num_vertices, nel = (size_t)L.num_prims, nidx = nel * (lines ? 2 : 3), per = lines ? 4 : 6;
+  ShapeArrays A;
+  if (int rc = stage_shape_arrays(ctx, who, shape, now, device, lines, nv, nidx, A)) return rc;
+  const yh_shape& dev     = A.dev;
+  const int*      d_index = lines ? dev.lines : dev.triangles;
   // ---- the tree, the records and the index of the wide nodes: the upload's rule for where, the upload's code ----
   const bool on_device = device || shape_builds_on_device((int)nel);
   ShapeTree  T;
@@ -403,6 +450,12 @@ static int update_shape(yh_context* ctx, const char* entry, int shape, const yh_
   YH_WAIT(ctx);
   memcpy(ctx->key_geometry.data() + E.key_positions, key_bytes.data(), key_bytes.size());
   ctx->scene.num_nodes_total += T.wide_count[0] - E.count[0];
+  for (int w = 0; w < 3; w++) {
+    Enew.wide_levels[w] = T.wide_levels[w];
+    memcpy(Enew.wide_first[w], T.wide_first[w], sizeof(Enew.wide_first[w]));
+  }
+  if (int rc = shape_slot_areas(ctx, who, 1, &Lnew, &Enew.count, ctx->d_lane_blob.p, Enew.area_build)) return rc;
+  memcpy(Enew.area_now, Enew.area_build, sizeof(Enew.area_now));
   ctx->lane_shapes[(size_t)shape]  = Lnew;
   ctx->shape_states[(size_t)shape] = Enew;  // (E and L are these: not read below)
   ctx->lane_units = 0;
@@ -420,6 +473,124 @@ static int update_shape(yh_context* ctx, const char* entry, int shape, const yh_
 
 int yh_update_shape(yh_context* ctx, int shape, const yh_shape* now) { return update_shape(ctx, "yh_update_shape", shape, now, false); }
 int yh_update_shape_device(yh_context* ctx, int shape, const yh_shape* now) { return update_shape(ctx, "yh_update_shape_device", shape, now, true); }
+
+// ---- yh_refit_shape / yh_refit_shape_device: the same edit, kept in the tree the shape's last build left (unit/refit.hip) ------------------
+// Nothing is built: the leaf slots keep their elements (a record holds its element id), so the records are written again where they are,
+// the test records made from them, and the boxes of the 4- / 8- / 16-wide nodes recomputed bottom-up in place, one launch per level of
+// each wide tree (ShapeState::wide_first). The traversal array neither grows nor moves, the depths stay. What can refuse runs first: the
+// checks, the index check, the new root box (a min / max reduction over the primitive boxes) and the scene level over the world boxes
+// that follow from it. The only scratch the shape sizes: its primitive boxes in leaf order, and the host form's staged arrays.
+static int refit_shape(yh_context* ctx, const char* entry, int shape, const yh_shape* now, bool device) {
+  if (!ctx) return YH_E_INVALID;
+  std::vector<yh_object> rows;
+  if (int rc = check_shape_edit(ctx, entry, shape, now, rows)) return rc;
+  const int total = ctx->scene.num_objects;
+  yh_context::ShapeState&      E = ctx->shape_states[(size_t)shape];
+  const yh_context::LaneShape& L = ctx->lane_shapes[(size_t)shape];
+  const bool lines = L.kind == YH_KIND_LINES;
+  const std::string who_s = std::string(entry) + ": ";
+  const char*       who   = who_s.c_str();
+  const size_t nv = (size_t)now->num_vertices, nel = (size_t)L.num_prims, nidx = nel * (lines ? 2 : 3);
+  ShapeArrays A;
+  if (int rc = stage_shape_arrays(ctx, who, shape, now, device, lines, nv, nidx, A)) return rc;
+  const yh_shape& dev     = A.dev;
+  const int*      d_index = lines ? dev.lines : dev.triangles;
+  yhd_float4*     d_recs  = (yhd_float4*)ctx->d_prims.p + L.prim_base;
+  // ---- the primitive boxes in leaf order and their union, the shape's new root box ----
+  const int parts = yhk_refit_partials((int)nel);
+  DevBuf    d_lboxes, d_part;
+  if (int rc = stage_alloc(ctx, d_lboxes, nel * sizeof(yhh::Box))) return rc;
+  if (int rc = stage_alloc(ctx, d_part, sizeof(yhh::Box) * (size_t)parts)) return rc;
+  int e = yhk_refit_boxes(lines ? 1 : 0, (int)nel, d_recs, dev.positions, dev.radius, d_index, (float*)d_lboxes.p, ctx->stream);
+  if (!e) e = yhk_box_partials((int)nel, (const float*)d_lboxes.p, (float*)d_part.p, ctx->stream);
+  if (e) return fail(ctx, YH_E_DEVICE, "%sprimitive bounds: %s", who, hipGetErrorString((hipError_t)e));
+  std::vector<yhh::Box> part((size_t)parts);
+  HIPCHK(ctx, hipMemcpyAsync(part.data(), d_part.p, sizeof(yhh::Box) * part.size(), hipMemcpyDeviceToHost, ctx->stream));
+  // the fingerprint's bytes of the shape: its first and last 256 positions (the device form fetches them)
+  const size_t take = std::min<size_t>(nv, 256);
+  std::vector<unsigned char> key_bytes(2 * take * 12);
+  if (device) {
+    HIPCHK(ctx, hipMemcpyAsync(key_bytes.data(), dev.positions, take * 12, hipMemcpyDeviceToHost, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(key_bytes.data() + take * 12, dev.positions + 3 * (nv - take), take * 12, hipMemcpyDeviceToHost, ctx->stream));
+  } else {
+    memcpy(key_bytes.data(), now->positions, take * 12), memcpy(key_bytes.data() + take * 12, now->positions + 3 * (nv - take), take * 12);
+  }
+  YH_WAIT(ctx);
+  yhh::Box root = part[0];
+  for (int k = 1; k < parts; k++)
+    for (int c = 0; c < 3; c++) root.min[c] = fmin_(root.min[c], part[(size_t)k].min[c]), root.max[c] = fmax_(root.max[c], part[(size_t)k].max[c]);
+  // ---- the world boxes of the objects that name the shape, from its new root box; the scene level over all boxes ----
+  std::vector<yhh::Box> boxes = ctx->h_obj_boxes;
+  std::vector<int>      named;
+  for (int i = 0; i < total; i++)
+    if (rows[(size_t)i].shape == shape) named.push_back(i);
+  DevBuf d_rows, d_boxes, d_named, d_root;
+  if (int rc = stage_alloc(ctx, d_rows, sizeof(yh_object) * (size_t)total)) return rc;
+  if (int rc = stage_alloc(ctx, d_boxes, sizeof(yhh::Box) * (size_t)total)) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(d_rows.p, rows.data(), sizeof(yh_object) * (size_t)total, hipMemcpyHostToDevice, ctx->stream));
+  std::vector<yh_object> named_rows;  // (their shape is row 0 of a table of one root box: the context's table changes at COMMIT only)
+  std::vector<yhh::Box>  named_boxes(named.size());
+  for (int i : named) named_rows.push_back(rows[(size_t)i]), named_rows.back().shape = 0;
+  if (!named.empty()) {
+    if (int rc = stage_alloc(ctx, d_named, sizeof(yh_object) * named.size())) return rc;
+    if (int rc = stage_alloc(ctx, d_root, sizeof(yhh::Box))) return rc;
+    HIPCHK(ctx, hipMemcpyAsync(d_named.p, named_rows.data(), sizeof(yh_object) * named.size(), hipMemcpyHostToDevice, ctx->stream));
+    HIPCHK(ctx, hipMemcpyAsync(d_root.p, &root, sizeof(yhh::Box), hipMemcpyHostToDevice, ctx->stream));
+    e = yhk_object_rows((int)named.size(), d_named.p, (const float*)d_root.p, nullptr, (float*)d_boxes.p, ctx->stream);
+    if (e) return fail(ctx, YH_E_DEVICE, "%sobject rows: %s", who, hipGetErrorString((hipError_t)e));
+    HIPCHK(ctx, hipMemcpyAsync(named_boxes.data(), d_boxes.p, sizeof(yhh::Box) * named.size(), hipMemcpyDeviceToHost, ctx->stream));
+    YH_WAIT(ctx);
+  }
+  for (size_t k = 0; k < named.size(); k++) boxes[(size_t)named[k]] = named_boxes[k];
+  SceneLevelStage S;
+  if (int rc = stage_scene_level(ctx, entry, boxes, ctx->max_shape_depth, ctx->max_shape_depth8, ctx->max_shape_depth16, S)) return rc;
+  // ---- COMMIT: from here on kernels and copies only ----
+  ctx->have_scene = false;
+  e = yhk_refit_records(lines ? 1 : 0, (int)nel, dev.positions, dev.normals, dev.radius, d_index, d_recs, ctx->stream);
+  if (!e) e = yhk_lane_tests((const yhd_float4*)ctx->d_prims.p, (yhd_float4*)ctx->d_lane_blob.p, L.kind, L.prim_base, L.num_prims, L.test_off, ctx->stream);
+  const long long offs[3] = {L.node_off, L.node_off8, L.node_off16};
+  for (int w = 0; w < 3 && !e; w++)
+    e = yhk_refit_wide(2 + w, ctx->d_lane_blob.p, offs[w], L.test_off, lines ? 1 : 2, E.wide_levels[w], E.wide_first[w], (const float*)d_lboxes.p, ctx->stream);
+  if (e) return fail(ctx, YH_E_DEVICE, "%srefit: %s", who, hipGetErrorString((hipError_t)e));
+  if (E.per_vertex) {
+    e = yhk_vertex_rows(lines ? 1 : 0, (int)nv, (int)nel, dev.positions, dev.radius, dev.texcoords, d_index, (yhd_float4*)ctx->d_vpos.p + E.vert_base,
+        (float*)ctx->d_vtex.p + 2 * (size_t)E.vert_base, (yhd_int4*)ctx->d_elems.p + E.elem_base, ctx->stream);
+    if (e) return fail(ctx, YH_E_DEVICE, "%svertex rows: %s", who, hipGetErrorString((hipError_t)e));
+  }
+  HIPCHK(ctx, hipMemcpyAsync((yhh::Box*)ctx->d_shape_roots.p + shape, &root, sizeof(yhh::Box), hipMemcpyHostToDevice, ctx->stream));
+  e = 0;  // the rows of the objects that name the shape, run by run of consecutive ones (their lane roots stay: nothing moved)
+  for (size_t k = 0; k < named.size() && !e;) {
+    size_t end_k = k + 1;
+    while (end_k < named.size() && named[end_k] == named[end_k - 1] + 1) end_k++;
+    const int first = named[k], run = (int)(end_k - k);
+    e = yhk_object_rows(run, (const yh_object*)d_rows.p + first, (const float*)ctx->d_shape_roots.p, (yhd_object*)ctx->d_objects.p + first, (float*)d_boxes.p + 6 * (size_t)first, ctx->stream);
+    k = end_k;
+  }
+  if (e) return fail(ctx, YH_E_DEVICE, "%sobject rows: %s", who, hipGetErrorString((hipError_t)e));
+  if (int rc = commit_scene_level(ctx, S)) return rc;
+  double area[3];
+  if (int rc = shape_slot_areas(ctx, who, 1, &L, &E.count, ctx->d_lane_blob.p, area)) return rc;  // (waits for the stream)
+  memcpy(E.area_now, area, sizeof(area));
+  memcpy(ctx->key_geometry.data() + E.key_positions, key_bytes.data(), key_bytes.size());
+  ctx->h_shape_roots[(size_t)shape] = root;
+  ctx->h_obj_boxes.swap(boxes);
+  settle_scene_level(ctx, S);
+  ctx->have_scene = true;
+  edit_end(ctx);
+  return YH_OK;
+}
+
+int yh_refit_shape(yh_context* ctx, int shape, const yh_shape* now) { return refit_shape(ctx, "yh_refit_shape", shape, now, false); }
+int yh_refit_shape_device(yh_context* ctx, int shape, const yh_shape* now) { return refit_shape(ctx, "yh_refit_shape_device", shape, now, true); }
+
+int yh_shape_refit_growth(const yh_context* ctx, int shape, float growth[3]) {
+  if (!ctx) return YH_E_INVALID;
+  if (!ctx->have_scene) return YH_E_STATE;
+  if (shape < 0 || shape >= (int)ctx->shape_states.size() || !growth) return YH_E_INVALID;
+  const yh_context::ShapeState& E = ctx->shape_states[(size_t)shape];
+  for (int w = 0; w < 3; w++) growth[w] = E.area_now[w] == E.area_build[w] ? 1.0f : (float)(E.area_now[w] / E.area_build[w]);
+  return YH_OK;
+}
 
 int yh_shape_nodes(const yh_context* ctx, int shape, int64_t offset[3], int count[3], int room[3]) {
   if (!ctx) return YH_E_INVALID;

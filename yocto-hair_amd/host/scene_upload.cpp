@@ -306,6 +306,12 @@ int index_shape_tree(yh_context* ctx, const char* who, ShapeTree& T) {
     int e = yhk_wide_index(T.num_nodes, (const float*)T.d_tree.p, T.levels, T.level_first, 2 + w, (unsigned int*)T.d_wflag[w].p, (unsigned int*)T.d_widx[w].p, &T.wide_count[w], ctx->stream);
     if (e) return fail(ctx, YH_E_DEVICE, "%swide-node index: %s", who, hipGetErrorString((hipError_t)e));
   }
+  // the first wide node of every level of the three wide trees, for a later refit (unit/refit.hip): the scans' values at the levels' first nodes
+  DevBuf d_firsts;
+  if (int rc = dev_alloc(ctx, d_firsts, 3 * 66 * 4)) return rc;
+  const unsigned int* widx[3] = {(const unsigned int*)T.d_widx[0].p, (const unsigned int*)T.d_widx[1].p, (const unsigned int*)T.d_widx[2].p};
+  int e = yhk_wide_level_firsts(T.num_nodes, T.levels, T.level_first, widx, (unsigned int*)d_firsts.p, T.wide_levels, T.wide_first, ctx->stream);
+  if (e) return fail(ctx, YH_E_DEVICE, "%swide-node levels: %s", who, hipGetErrorString((hipError_t)e));
   return YH_OK;
 }
 
@@ -483,6 +489,13 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
   if (scene_wide) {  // leaf references as of a line shape whose test records start at 0: count << 27 | first scene primitive
     int e = yhk_wide_collapse(2, (int)scene_tree.nodes.size(), (const float*)d_stree.p, (const unsigned int*)d_sflag.p, (const unsigned int*)d_sidx.p, 1, 0, 0, ctx->d_lane_blob.p, ctx->stream);
     if (e) return fail(ctx, YH_E_DEVICE, "wide collapse of the scene tree: %s", hipGetErrorString((hipError_t)e));
+  }
+  // the half-area sums of every shape's slot boxes as built: what yh_shape_refit_growth compares a refitted tree with
+  std::vector<double> slot_areas(3 * (size_t)sd->num_shapes);
+  {
+    std::vector<int> counts(3 * (size_t)sd->num_shapes);
+    for (int si = 0; si < sd->num_shapes; si++) memcpy(&counts[3 * (size_t)si], info[si].wide_count, sizeof(info[si].wide_count));
+    if ((rc = shape_slot_areas(ctx, "", sd->num_shapes, ctx->lane_shapes.data(), (const int(*)[3])counts.data(), ctx->d_lane_blob.p, slot_areas.data()))) return rc;
   }
   YH_WAIT(ctx);
   for (auto& I : info) {
@@ -738,7 +751,12 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
         E.num_vertices = sh.num_vertices, E.has_normals = sh.normals != nullptr, E.has_texcoords = sh.texcoords != nullptr;
         E.per_vertex = sh.num_lines <= 0 || sh.texcoords != nullptr, E.vert_base = I.vert_base, E.elem_base = I.elem_base;
         E.depth = I.depth, E.depth8 = I.depth8, E.depth16 = I.depth16;
-        for (int w = 0; w < 3; w++) E.count[w] = E.room[w] = I.wide_count[w];
+        for (int w = 0; w < 3; w++) {
+          E.count[w] = E.room[w] = I.wide_count[w];
+          E.wide_levels[w] = I.wide_levels[w];
+          memcpy(E.wide_first[w], I.wide_first[w], sizeof(E.wide_first[w]));
+          E.area_build[w] = E.area_now[w] = slot_areas[3 * (size_t)i + w];
+        }
         E.key_positions = ctx->key_geometry.size();
       }
       if (sh.positions && sh.num_vertices > 0) {

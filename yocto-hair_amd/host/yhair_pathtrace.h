@@ -333,6 +333,7 @@ struct scene {
   mutable int                uploads = 0, edits = 0;
   bool                       object_edits = false;  // EXTENSION (set_object_edits): object frames and materials go through yh_update_objects
   bool                       shape_edits  = false;  // EXTENSION (set_shape_edits): vertex edits of a shape go through yh_update_shape
+  bool                       shape_refit  = false;  // EXTENSION (set_shape_refit): ... through yh_refit_shape instead
 };
 struct state {  // pt.h:426-429; `render` is refreshed by trace_samples
   int                width = 0, height = 0, samples = 0;
@@ -431,6 +432,11 @@ inline void set_object_edits(scene* s, bool on) { s->object_edits = on; }
 // that shape's tree, records and nodes are made again, no other shape, texture or light table is touched (include/yhair.h). What that
 // call refuses — an emitter's geometry, a tree too deep, a scene level that changes its form — falls back to the upload.
 inline void set_shape_edits(scene* s, bool on) { s->shape_edits = on; }
+// EXTENSION, off by default, with effect only together with set_shape_edits(s, true): the vertex edits that opt-in passes on — counts and
+// index arrays being the uploaded ones — go through yh_refit_shape instead of yh_update_shape: the shape keeps the tree of its last
+// build and gets its records and boxes again (include/yhair.h: REFIT; closest hits those of a build, ties apart; yh_shape_refit_growth
+// tells what the boxes grew by). How an edit is classified does not change, nor what falls back to the upload.
+inline void set_shape_refit(scene* s, bool on) { s->shape_refit = on; }
 inline void set_emission(environment* e, const vec3f& em, texture* tex = nullptr) { e->emission = em, e->emission_tex = tex; }
 
 // Flattens the scene graph into a yh_scene_desc and uploads it; the C ABI builds
@@ -543,7 +549,7 @@ inline bool update_scene(const scene* sc, const camera* cam, detail::flat_scene&
     if (!rc && (kind & detail::edit_objects)) rc = yh_update_objects(ctx, 0, (int)flat.objects.size(), flat.objects.data());
     if (kind & detail::edit_shapes)
       for (size_t i = 0; i < flat.shapes.size() && !rc; i++)
-        if (detail::shape_vertices_differ(sc->uploaded, flat, i)) rc = yh_update_shape(ctx, (int)i, &flat.shapes[i]);
+        if (detail::shape_vertices_differ(sc->uploaded, flat, i)) rc = (sc->shape_refit ? yh_refit_shape : yh_update_shape)(ctx, (int)i, &flat.shapes[i]);
     if (rc == YH_E_INVALID) refused = true, rc = YH_OK;
     return rc;
   });
@@ -571,7 +577,7 @@ inline void init_state(state* st, const scene* sc, const camera* cam, const trac
   // The reference reads its scene structs at every sample, so whatever a caller set since the last init_state is in force from here on
   // (apps/ysceneitraces/ysceneitraces.cpp:392-410: the camera's frame, then reset_display). The contexts hold a flattened copy: compare.
   // Nothing changed: nothing to do. Only what the yh_update_* calls accept (camera fields, material fields, the environments' frames
-  // and emission; with set_object_edits, the objects' frames and materials; with set_shape_edits, a shape's vertex arrays): those calls,
+  // and emission; with set_object_edits, the objects' frames and materials; with set_shape_edits, a shape's vertex arrays — through yh_refit_shape with set_shape_refit): those calls,
   // which keep every shape's tree but an edited shape's own. Anything else
   // — an object's frame without the opt-in, a shape's arrays, a texture, an emission turned on or off, init_bvh / init_lights called
   // again — is the whole upload.

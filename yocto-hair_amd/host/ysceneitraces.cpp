@@ -9,7 +9,8 @@
 //
 // Same flags as the app (ysceneitraces.cpp:313-327): --camera, --resolution,-r, --samples,-s, --shader,-t,
 // --bounces,-b, --clamp, --output,-o, positional scene. Extensions: --pratio (trace_params::pratio, default
-// 8), --preview-image FILE, --stop-after-ms N, --seed, --device, --gpus / --devices, and --turntable STEPS: the app's one gesture, the
+// 8), --preview-image FILE, --stop-after-ms N, --seed, --device, --gpus / --devices, --sway STEPS [--sway-refit] (the vertex edit's gesture: the first
+// line shape displaced step by step, passed on through yh_update_shape or, with --sway-refit, yh_refit_shape) and --turntable STEPS: the app's one gesture, the
 // camera orbit (ysceneitraces.cpp:392-410: update_turntable on app->camera->frame, then reset_display), headless — after the first
 // reset_display, STEPS - 1 times a rotation by 2 pi / STEPS followed by reset_display again; step k is saved as <stem>-<kkk><ext>.
 #include <atomic>
@@ -53,7 +54,8 @@ int main(int argc, const char* argv[]) {
   auto        params = ptr::trace_params{};
   std::string camera_name, imagename = "out.hdr", preview_name, filename, shader = "path";
   int         stop_after_ms = -1, gpus = 1, first_device = 0, turntable = 0;
-  bool        turn_objects = false;
+  bool        turn_objects = false, sway_refit = false;
+  int         sway = 0;
   std::string device_list;
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -64,7 +66,8 @@ int main(int argc, const char* argv[]) {
     if (a == "--help" || a == "-h") {
       printf("usage: ysceneitraces [--camera NAME] [--resolution,-r N] [--samples,-s N] [--shader,-t naive|path|eyelight|normal]\n"
              "                     [--bounces,-b N] [--clamp F] [--output,-o FILE] [--pratio N] [--preview-image FILE]\n"
-             "                     [--stop-after-ms N] [--seed N] [--device N] [--gpus N] [--devices A,B,..] [--turntable STEPS [--turntable-objects]] scene\n"
+             "                     [--stop-after-ms N] [--seed N] [--device N] [--gpus N] [--devices A,B,..] [--turntable STEPS [--turntable-objects]]\n"
+             "                     [--sway STEPS [--sway-refit]] scene\n"
              "Progressive path tracing of hair scenes on MI355X (headless: preview pass, then samples until done or stopped)\n");
       return 0;
     } else if (a == "--camera") camera_name = next();
@@ -83,11 +86,15 @@ int main(int argc, const char* argv[]) {
     else if (a == "--devices") device_list = next();
     else if (a == "--turntable") turntable = std::max(1, atoi(next().c_str()));
     else if (a == "--turntable-objects") turn_objects = true;
+    else if (a == "--sway") sway = std::max(1, atoi(next().c_str()));
+    else if (a == "--sway-refit") sway_refit = true;
     else if (!a.empty() && a[0] == '-') print_fatal("unknown option " + a);
     else filename = a;
   }
   if (filename.empty()) print_fatal("missing scene");
   if (turn_objects && turntable <= 0) print_fatal("--turntable-objects needs --turntable STEPS");
+  if (sway_refit && sway <= 0) print_fatal("--sway-refit needs --sway STEPS");
+  if (sway > 0 && turntable > 0) print_fatal("--sway and --turntable are gestures of their own");
   yh_set_trial_cache_dir(yh_default_trial_cache_dir());  // the command line keeps its kernel-trial record on disk (include/yhair.h); a library caller has to ask
   set_devices(first_device, gpus, device_list);
   bool known = false;
@@ -128,7 +135,10 @@ int main(int argc, const char* argv[]) {
       }
     printf("preview: %dx%d at 1 spp upscaled to %dx%d, %.1f ms\n", pstate->width, pstate->height, W, H,
         std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count());
-    if (orbit)
+    if (orbit && sway > 0)
+      printf("sway step, edit to preview: %.1f ms (%s)\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_edit).count(),
+          scene->uploads > uploads0 ? "the scene was uploaded again" : sway_refit ? "the hair alone was passed on, as a refit" : "the hair alone was passed on, its tree built again");
+    else if (orbit)
       printf("edit to preview: %.1f ms (%s)\n", std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t_edit).count(),
           scene->uploads > uploads0 ? "the scene was uploaded again" : turn_objects ? "the objects alone were passed on" : "the camera alone was passed on");
     if (!preview_name.empty() && yh_save_image(preview_name.c_str(), W, H, (const float*)render.data(), error, sizeof(error)) != YH_OK)
@@ -155,7 +165,39 @@ int main(int argc, const char* argv[]) {
     if (yh_save_image(imagename.c_str(), W, H, (const float*)render.data(), error, sizeof(error)) != YH_OK) print_fatal(error);
     printf("save image: %s\n", imagename.c_str());
     };
-    if (turntable <= 0) {
+    if (sway > 0) {  // the vertex edit's gesture: step k displaces the first line shape by x += a_k y^2, a_k = 0.1 k / STEPS, tangents recomputed
+      const size_t slash = imagename.find_last_of('/'), dot = imagename.find_last_of('.');
+      const bool   ext   = dot != std::string::npos && (slash == std::string::npos || dot > slash);
+      const std::string stem = ext ? imagename.substr(0, dot) : imagename, suffix = ext ? imagename.substr(dot) : "";
+      ptr::shape* hair = nullptr;
+      for (auto& s : scene->shapes)
+        if (!hair && !s->lines.empty()) hair = s.get();
+      if (!hair) print_fatal("--sway: the scene has no line shape");
+      ptr::set_shape_edits(scene.get(), true);
+      ptr::set_shape_refit(scene.get(), sway_refit);
+      const std::vector<vec3f> loaded = hair->positions;
+      for (int k = 0; k <= sway; k++) {
+        if (k > 0) {
+          t_edit = std::chrono::steady_clock::now();
+          const float a = 0.1f * k / sway;
+          std::vector<vec3f> positions = loaded, tangents(loaded.size(), vec3f{0, 0, 0});
+          for (auto& p : positions) p.x += a * p.y * p.y;
+          for (auto& l : hair->lines) {  // a vertex's tangent: the normalised sum of the directions of the segments at it
+            const vec3f &p0 = positions[(size_t)l.x], &p1 = positions[(size_t)l.y], d = {p1.x - p0.x, p1.y - p0.y, p1.z - p0.z};
+            for (int v : {l.x, l.y}) tangents[(size_t)v] = {tangents[(size_t)v].x + d.x, tangents[(size_t)v].y + d.y, tangents[(size_t)v].z + d.z};
+          }
+          for (auto& t : tangents) {
+            const float len = std::sqrt(t.x * t.x + t.y * t.y + t.z * t.z);
+            if (len > 0) t = {t.x / len, t.y / len, t.z / len};
+          }
+          ptr::set_positions(hair, positions);
+          if (!hair->normals.empty()) ptr::set_normals(hair, tangents);
+        }
+        char number[16];
+        snprintf(number, sizeof(number), "-%03d", k);
+        reset_display(stem + number + suffix, k > 0);
+      }
+    } else if (turntable <= 0) {
       reset_display(imagename, false);
     } else {  // the orbit: one turn in `turntable` steps, step k saved as <stem>-<kkk><ext>
       const size_t slash = imagename.find_last_of('/'), dot = imagename.find_last_of('.');

@@ -145,6 +145,9 @@ _SIGS = {
     "yh_update_objects": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(Object)]),
     "yh_update_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Shape)]),
     "yh_update_shape_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Shape)]),
+    "yh_refit_shape": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Shape)]),
+    "yh_refit_shape_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Shape)]),
+    "yh_shape_refit_growth": (C.c_int, [C.c_void_p, C.c_int, c_float_p]),
     "yh_shape_nodes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), c_int_p, c_int_p]),
     "yh_download_display": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     "yh_init_state": (C.c_int, [C.c_void_p, C.POINTER(TraceParams)]),
@@ -176,6 +179,8 @@ _SIGS = {
     "yh_bvh_build": (C.c_int, [C.c_int, c_float_p, c_float_p, c_int_p]),
     "yh_bvh_build_wide": (C.c_int, [C.c_int, c_float_p, C.c_int, c_float_p]),
     "yh_bvh_build_wide_gpu": (C.c_int, [C.c_void_p, C.c_int, c_float_p, C.c_int, c_float_p]),
+    "yh_bvh_refit_wide": (C.c_int, [C.c_int, c_float_p, c_int_p, C.c_int, c_float_p]),
+    "yh_bvh_refit_wide_gpu": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_int_p, C.c_int, c_float_p]),
     "yh_surface_lobe_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p,
                                         c_float_p, c_float_p]),
     "yh_surface_bsdf_batch": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Material), c_float_p, c_float_p, c_float_p,
@@ -225,6 +230,20 @@ def load(path=None):
 
 class YhError(RuntimeError):
     pass
+
+
+def _refit_args(boxes, primitives, slots):
+    return (np.ascontiguousarray(boxes, np.float32).reshape(-1, 6), np.ascontiguousarray(primitives, np.int32),
+            np.array(slots, np.float32, copy=True, order="C"))
+
+
+def bvh_refit_wide(boxes, primitives, width, slots):
+    """yh_bvh_refit_wide (host, no GPU): arguments and result as Context.bvh_refit_wide_gpu."""
+    boxes, primitives, out = _refit_args(boxes, primitives, slots)
+    n = load().yh_bvh_refit_wide(len(boxes), fptr(boxes), iptr(primitives), width, fptr(out))
+    if n < 0:
+        raise YhError(f"yhair error {n}: yh_bvh_refit_wide")
+    return n, out
 
 
 def set_trial_cache_dir(path=None, default=False):
@@ -332,23 +351,23 @@ class Context:
         desc.contents.shapes[index] with its pointers set to edited float32 / int32 numpy arrays, which the caller keeps alive)."""
         self._chk(self.lib.yh_update_shape(self.h, index, C.byref(shape) if shape is not None else None))
 
-    def update_shape_device(self, index, positions, normals=None, radius=None, lines=None, triangles=None, texcoords=None):
-        """yh_update_shape_device: contiguous torch tensors on the context's device — positions (n, 3), normals (n, 3), radius (n,),
-        texcoords (n, 2) float32; lines (m, 2) or triangles (m, 3) int32. The current torch stream is synchronised before the call,
-        which runs on the context's own stream."""
+    @staticmethod
+    def _device_shape(who, positions, normals, radius, lines, triangles, texcoords):
+        """The Shape of the device forms: contiguous torch tensors on the context's device, checked; the current torch stream is
+        synchronised, since the calls run on the context's own stream."""
         import torch
 
         def ptr(t, dtype, cols, what):
             if t is None:
                 return None
             if not isinstance(t, torch.Tensor):
-                raise YhError(f"update_shape_device: {what} must be a torch tensor, not {type(t).__name__}")
+                raise YhError(f"{who}: {what} must be a torch tensor, not {type(t).__name__}")
             if not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or (cols and (t.dim() != 2 or t.shape[1] != cols)) or (not cols and t.dim() != 1):
-                raise YhError(f"update_shape_device: {what} must be a contiguous {dtype} tensor on the GPU" + (f" of shape (n, {cols})" if cols else " of shape (n,)"))
+                raise YhError(f"{who}: {what} must be a contiguous {dtype} tensor on the GPU" + (f" of shape (n, {cols})" if cols else " of shape (n,)"))
             return t.data_ptr()
 
         if positions is None:
-            raise YhError("update_shape_device: positions is None")
+            raise YhError(f"{who}: positions is None")
         s = Shape()
         s.positions = C.cast(ptr(positions, torch.float32, 3, "positions"), c_float_p)
         s.num_vertices = int(positions.shape[0])
@@ -360,7 +379,33 @@ class Context:
         s.triangles = C.cast(ptr(triangles, torch.int32, 3, "triangles"), c_int_p)
         s.num_triangles = int(triangles.shape[0]) if triangles is not None else 0
         torch.cuda.current_stream(positions.device).synchronize()
+        return s
+
+    def update_shape_device(self, index, positions, normals=None, radius=None, lines=None, triangles=None, texcoords=None):
+        """yh_update_shape_device: contiguous torch tensors on the context's device — positions (n, 3), normals (n, 3), radius (n,),
+        texcoords (n, 2) float32; lines (m, 2) or triangles (m, 3) int32. The current torch stream is synchronised before the call,
+        which runs on the context's own stream."""
+        s = self._device_shape("update_shape_device", positions, normals, radius, lines, triangles, texcoords)
         self._chk(self.lib.yh_update_shape_device(self.h, index, C.byref(s)))
+
+    # the same edits kept in the tree the shape has: records and boxes again, nothing built (include/yhair.h: REFIT)
+    def refit_shape(self, index, shape):
+        """yh_refit_shape: arguments as update_shape."""
+        self._chk(self.lib.yh_refit_shape(self.h, index, C.byref(shape) if shape is not None else None))
+
+    def refit_shape_device(self, index, positions, normals=None, radius=None, lines=None, triangles=None, texcoords=None):
+        """yh_refit_shape_device: arguments as update_shape_device."""
+        s = self._device_shape("refit_shape_device", positions, normals, radius, lines, triangles, texcoords)
+        self._chk(self.lib.yh_refit_shape_device(self.h, index, C.byref(s)))
+
+    def shape_refit_growth(self, index):
+        """yh_shape_refit_growth: for the 4-, 8- and 16-wide nodes of the shape, the half-area sum of their slot boxes now over the
+        sum at the shape's last build (exactly 1.0 after an upload, an update and a refit that reproduces the boxes)."""
+        g = (C.c_float * 3)()
+        rc = self.lib.yh_shape_refit_growth(self.h, index, g)
+        if rc != YH_OK:
+            raise YhError(f"yhair error {rc}: yh_shape_refit_growth")
+        return [float(v) for v in g]
 
     def shape_nodes(self, index):
         """yh_shape_nodes: (offsets, counts, room) of the shape's 4-, 8- and 16-wide nodes in the traversal array (32-byte units)."""
@@ -516,6 +561,15 @@ class Context:
         out = np.zeros((len(a[0]), SURFACE_BSDF_FLOATS), np.float32)
         self._chk(self.lib.yh_surface_bsdf_batch(self.h, len(a[0]), materials, *(fptr(x) for x in a), fptr(out)))
         return out
+
+    def bvh_refit_wide_gpu(self, boxes, primitives, width, slots):
+        """yh_bvh_refit_wide_gpu: the refitted copy of `slots` (device form, as from yh_bvh_build_wide_gpu) under the new `boxes`
+        (primitive order); `primitives` is the leaf order. Returns (node count, slots)."""
+        boxes, primitives, out = _refit_args(boxes, primitives, slots)
+        n = self.lib.yh_bvh_refit_wide_gpu(self.h, len(boxes), fptr(boxes), iptr(primitives), width, fptr(out))
+        if n < 0:
+            self._chk(n)
+        return n, out
 
     def intersect(self, rays):
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
