@@ -284,7 +284,8 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* scene, const yh_m
  * write returns YH_E_DEVICE and leaves the context without a scene, as a failed upload does.
  * OUT OF SCOPE, for all of which the answer stays a new upload: changing an object's shape, adding or removing objects or shapes,
  * changing a shape's counts, the geometry of an emitter, textures and maps, turning emission on or off. (Vertex edits that keep a
- * shape's counts: yh_update_shape, below.)                                                                                        */
+ * shape's counts: yh_update_shape, below. What changes the light list — emission on or off, an emitter's geometry — is an edit after
+ * yh_set_light_edits: LIGHT EDITS, below.)                                                                                         */
 int yh_update_camera(yh_context* ctx, const yh_camera* camera);
 int yh_update_materials(yh_context* ctx, int first, int count, const yh_material* materials);
 int yh_update_environments(yh_context* ctx, int count, const yh_environment* environments);
@@ -353,6 +354,45 @@ int yh_shape_refit_growth(const yh_context* ctx, int shape, float growth[3]);
 /* A diagnostic: where shape `shape`'s 4-, 8- and 16-wide nodes sit in the traversal array (offset, in 32-byte units), how many
  * nodes it has of each width (count) and how many its region has room for (room). YH_E_STATE before an upload.                    */
 int yh_shape_nodes(const yh_context* ctx, int shape, int64_t offset[3], int count[3], int room[3]);
+
+/* LIGHT EDITS: muting or soloing a light, handing an object an emitter's material, reshaping an emitting mesh. Off by default: every
+ * paragraph above holds as written. yh_set_light_edits(ctx, 1) — any time, before or after an upload; YH_OK — REPLACES, in seven entry
+ * points, the refusal of an edit merely because it changes the light list (init_lights, yocto_pathtrace.cpp:1695-1740):
+ *   yh_update_materials, yh_update_environments   "turns its emission on / off: the light list changes";
+ *   yh_update_objects                             "object turns its emission on / off with material";
+ *   yh_update_shape, yh_update_shape_device,
+ *   yh_refit_shape, yh_refit_shape_device         "is the shape of object, whose material emits: the light tables are made from it".
+ * Such an edit makes the light list again by the upload's rule: objects first, in order — an object is a light when its material's
+ * emission is not all zero and its shape has triangles (a line shape never is one; every instance of an emitter is a light of its own)
+ * — then the environments, in order; every light has its segment of the light cdf; a light of at most 4 triangles has its record in the
+ * kernels' LDS light table, a larger one is read through memory and selects the GENERAL kernel variant; the first textured environment
+ * light of at least 4096 texels gets the coarse index of its cdf. A light that appears in the middle shifts every later light's index.
+ * The CONTRACT of the edits holds unchanged: pixels, RNG states, yh_lights_batch, yh_intersect_batch, yh_intersect_plain_batch,
+ * yh_scene_once, the kernel variant and the kernel-trial fingerprint are those of a context that got yh_upload_scene_maps of the edited
+ * description (after a REFIT: ties apart, as above — the cdf is by element and does not depend on the tree), and the image state is gone.
+ * The list is made where its data is (unit/light_list.hip), from the vertex and index rows, leaf records and root boxes the context
+ * keeps on the device: a triangle's area is the upload's arithmetic, the cdf ONE float chain in element order inside one wavefront per
+ * light (no reordered sum gives the upload's bits), all lights in one launch. After a vertex edit of an emitter's shape the cdf and the
+ * record of every light that names it are written again where they are, from the new arrays as they sit on the device: nothing is read
+ * back, no other light, shape or environment cdf is touched, and the work is proportional to that emitter's triangles. A textured environment's texel cdf uses the host's sine and is never computed on
+ * the device: a light that exists keeps its segment (a device-to-device copy); one that did not emit at the upload gets its cdf when
+ * it first turns on, made by the upload's own loop from the texels the device kept (the caller passes none), and the context keeps it:
+ * off and on again costs a copy.
+ * STILL REFUSED with YH_E_INVALID, a message that names the entry point, and the context exactly as it was: an edit that would make
+ * more than 16 lights (the message names the object); one that would leave the scene without a light; a changed emission_tex,
+ * color_tex or scattering_tex; and every argument, count, depth and scene-level refusal of the entry points above. Everything that can
+ * refuse runs before the first write; a HIP error after it returns YH_E_DEVICE and leaves the context without a scene. Another
+ * environment texture, textures and maps, counts and new objects stay an upload.                                                     */
+int yh_set_light_edits(yh_context* ctx, int on);
+/* A diagnostic: lights[] of the uploaded scene in the kernels' order: per light the object (-1: an environment), the environment (-1:
+ * an object), the cdf entries, and whether its record is in the LDS light table. Returns the number of lights and fills at most
+ * `capacity` entries of every non-NULL array. YH_E_STATE before an upload.                                                           */
+int yh_light_list(const yh_context* ctx, int* object, int* environment, int* cdf_count, int* in_lds, int capacity);
+/* init_lights' area cdf of one triangle shape (yocto_pathtrace.cpp:1695-1740): cdf[t] = area[t] + cdf[t - 1], one float chain in
+ * element order. yh_triangle_cdf: the host's restatement (no GPU, no context); yh_triangle_cdf_gpu: the kernel of the light edits.
+ * Same bits. YH_E_INVALID: a NULL array, no vertices or triangles, an index outside the vertices.                                     */
+int yh_triangle_cdf(int num_vertices, const float* positions, int num_triangles, const int* triangles, float* cdf);
+int yh_triangle_cdf_gpu(yh_context* ctx, int num_vertices, const float* positions, int num_triangles, const int* triangles, float* cdf);
 
 /* init_state (yocto_pathtrace.cpp:1931-1946): image size from the camera film
  * and params->resolution, zeroed accumulators, per-pixel PCG32 streams

@@ -10,7 +10,7 @@
 //   batch_api.cpp      the unit-level batch entry points (hair BSDF, intersection, BVH build, curves, self-tests)
 //   scene_edit.cpp     edits of an uploaded scene (yh_update_camera / _materials / _environments / _objects: the last one builds the
 //                      scene-level tree again; yh_update_shape / _device: one shape's tree too; yh_refit_shape / _device: that tree's boxes
-//                      only, unit/refit.hip) and yh_download_display
+//                      only, unit/refit.hip; yh_set_light_edits: the light list again, unit/light_list.hip) and yh_download_display
 #ifndef YH_CONTEXT_INTERNAL_H_
 #define YH_CONTEXT_INTERNAL_H_
 #include <hip/hip_runtime_api.h>
@@ -39,6 +39,8 @@
 
 #include "../csrc/yh_device.h"
 #include "../unit/object_math.h"  // F3 and its helpers, inverse_frame, transform_point, transform_bbox, padded_world_box: shared with the device
+#include "../unit/light_math.h"   // triangle_area: an area light's cdf entry, shared with the device
+#include "../unit/light_list.h"   // yhk_light_job
 #include "bvh_build.h"
 #include "deadline.h"
 #include "yhair.h"
@@ -112,6 +114,13 @@ int yhk_box_partials(int n, const float* boxes, float* partial, hipStream_t);
 int yhk_refit_records(int lines, int n, const float* pos, const float* nrm, const float* radius, const int* idx, void* recs, hipStream_t);
 int yhk_refit_wide(int L, void* blob, long long node_off, long long test_off, int units, int levels, const int* level_first, const float* lboxes, hipStream_t);
 int yhk_area_partials(int width, const void* blob, long long node_off, int count, double* partial, hipStream_t);
+// unit/light_list.hip (yh_set_light_edits, yh_triangle_cdf_gpu), all pointers DEVICE pointers: the area cdf of every job's light from the
+// scene's rows (one wave per light, the additions one float chain in element order) or of ONE job from raw positions / triangles; the
+// records of the small lights among the jobs (root6: 6 floats per shape; prims: the leaf records); the coarse index of a texel cdf
+int yhk_light_cdfs(int num_jobs, const void* jobs, const void* vpos, const void* elems, float* cdf, hipStream_t);
+int yhk_triangle_cdf_raw(const void* job, const float* pos, const int* tri, float* cdf, hipStream_t);
+int yhk_small_records(int num_jobs, const void* jobs, const float* root6, const void* prims, const float* cdf, void* table, hipStream_t);
+int yhk_env_tab(int K, int S, int n, const float* cdf, float* tab, hipStream_t);
 }
 
 // A device allocation owned by the context.
@@ -230,6 +239,10 @@ struct yh_context {
   std::vector<yh_material_maps> h_maps;
   std::vector<yhd_maps>         h_dmaps;
   bool                          big_lights = false;
+  // yh_set_light_edits: the edits make the light list again instead of refusing what changes it; and the texel cdf of every textured
+  // environment that has been a light since the upload, kept on the device (made with the host's sine: off and on again costs a copy)
+  bool                          light_edits = false;
+  DevBuf                        d_env_cdf[YH_MAX_ENVS];
   yh_camera                     key_camera{};
   std::vector<unsigned char>    key_geometry, key_envs;
   // ... and what yh_update_objects needs of the upload: every shape's root box (on the device too, 6 floats per shape: unit/objects.hip
@@ -367,6 +380,9 @@ void make_material(const yh_material& m, yhd_material& d);  // scene_upload.cpp
 // fingerprint of the description the context keeps; and what a new scene does to the image state and the launch planning
 bool make_material_rows(const yh_material* materials, const yh_material_maps* maps, int count, yhd_material* rows, yhd_maps* dmaps);
 void settle_scene_variant(const yh_context* ctx, yhd_scene& sc, bool general_rows);
+// scene_upload.cpp, shared with the light edits: the texel cdf of a textured environment (pt.cpp:1720-1734, the host's sine), `stride` floats
+// per texel, appended to `cdf` as one float chain
+void append_env_cdf(const float* texels, int stride, int width, int height, std::vector<float>& cdf);
 uint64_t scene_fingerprint(const yh_context* ctx);
 void forget_image_of_scene(yh_context* ctx);
 // scene_upload.cpp, shared with yh_update_objects: the levels of a host-built tree as the device builder reports them (false: more than 128);

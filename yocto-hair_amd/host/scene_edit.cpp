@@ -6,6 +6,9 @@
 // apps/ysceneitraces/ysceneitraces.cpp:392-410); here the description was flattened at yh_upload_scene, so an edit is a call of its own
 // that leaves the context as an upload of the edited description would: the scene table, the material rows on the device, the kernel
 // variant, the once-per-ray form, the fingerprint and the launch planning. Only a shape edit reads, writes or allocates anything the geometry sizes, and then the edited shape's alone.
+// yh_set_light_edits (off by default): the seven edits that would change the light list make it again by the upload's rule instead of
+// refusing (stage_lights / commit_lights below, unit/light_list.hip): the area cdfs, the small lights' records and the coarse index of a
+// texel cdf on the device, from the rows the context keeps there.
 // Also yh_download_display, the tone-mapped bytes of the image (unit/display.hip).
 #include "context_internal.h"
 
@@ -23,6 +26,176 @@ static int edit_begin(yh_context* ctx, const char* entry) {
 static void edit_end(yh_context* ctx) {
   ctx->scene_key = scene_fingerprint(ctx);
   forget_image_of_scene(ctx);
+}
+
+// a device allocation of an edit's staging
+static int stage_alloc(yh_context* ctx, DevBuf& buf, size_t bytes) {
+  buf.reset();
+  HIPCHK(ctx, hipMalloc(&buf.p, std::max<size_t>(bytes, 16)));
+  buf.bytes = std::max<size_t>(bytes, 16);
+  return YH_OK;
+}
+
+// ---- the light list again (yh_set_light_edits): init_lights' rule as the upload runs it (scene_upload.cpp), over the description the context
+// keeps and the edit at hand. stage_lights walks the objects and the environments in order, refuses what the upload refuses (more than
+// YH_MAX_LIGHTS lights, none at all), lays out the new light_cdf and light table, allocates them and sees to it that every textured
+// environment of the new list has its texel cdf on the device (ctx->d_env_cdf: saved from the light_cdf in force, or made with the
+// upload's loop from the texels read back from d_env_texels — the host's sine, scene_upload.cpp: append_env_cdf). Nothing the kernels
+// read is written. commit_lights queues the kernels and copies into the NEW arrays on the context's stream and brings the scene table
+// in line; the old arrays go when the stage does, after the caller's wait. (A vertex edit of an emitter's shape moves no light:
+// stage_lights_of_shape / commit_lights_of_shape below write the entries of that shape's lights where they are.) ----
+namespace {
+struct LightStage {
+  int       num_lights = 0;
+  yhd_light lights[YH_MAX_LIGHTS] = {};
+  bool      big_lights = false;
+  int       table_f4 = 0, env_tab_light = -1, env_tab_k = 0, env_tab_stride = 0;
+  size_t    cdf_total = 0;
+  std::vector<yhk_light_job> jobs;  // the area lights, in list order
+  DevBuf    d_jobs, d_cdf, d_table, d_tab;
+};
+}  // namespace
+
+// materials: the whole table as the edit leaves it; rows: every object row; emission: 3 floats per environment
+static int stage_lights(yh_context* ctx, const char* entry, const yh_material* materials, const yh_object* rows, const float* emission, LightStage& S) {
+  const yhd_scene& sc = ctx->scene;
+  for (int oi = 0; oi < sc.num_objects; oi++) {
+    const yh_object& o = rows[oi];
+    if (is_black(materials[o.material].emission)) continue;
+    const yh_context::LaneShape&  L = ctx->lane_shapes[(size_t)o.shape];
+    const yh_context::ShapeState& E = ctx->shape_states[(size_t)o.shape];
+    if (L.kind == YH_KIND_LINES || L.num_prims <= 0) continue;  // a line shape never becomes a light
+    if (S.num_lights >= YH_MAX_LIGHTS)
+      return fail(ctx, YH_E_INVALID, "%s: more than %d lights: object %d of %d is emissive too (each instance of an emitter counts)", entry, YH_MAX_LIGHTS, oi, sc.num_objects);
+    yhd_light& l = S.lights[S.num_lights++];
+    l.object = oi, l.environment = -1, l.cdf_base = (int)S.cdf_total, l.cdf_count = L.num_prims, l.small_base = -1;
+    if (L.num_prims <= YH_SMALL_LIGHT_TRIS) l.small_base = S.table_f4, S.table_f4 += YH_SMALL_LIGHT_F4;
+    else S.big_lights = true;
+    S.jobs.push_back({E.elem_base, E.vert_base, L.num_prims, l.cdf_base, L.prim_base, o.shape, l.small_base, 0});
+    S.cdf_total += (size_t)L.num_prims;
+  }
+  for (int ei = 0; ei < sc.num_environments; ei++) {
+    if (is_black(emission + 3 * ei)) continue;
+    if (S.num_lights >= YH_MAX_LIGHTS) return fail(ctx, YH_E_INVALID, "%s: more than %d lights: environment %d is one too", entry, YH_MAX_LIGHTS, ei);
+    yhd_light& l = S.lights[S.num_lights++];
+    l.object = -1, l.environment = ei, l.cdf_base = (int)S.cdf_total, l.small_base = -1;
+    l.cdf_count = sc.environments[ei].tex_w * sc.environments[ei].tex_h;  // (0 x 0 for a constant one: no cdf)
+    S.cdf_total += (size_t)l.cdf_count;
+  }
+  if (S.num_lights == 0) return fail(ctx, YH_E_INVALID, "%s: the edit leaves the scene without a light (the path sampler needs at least one): upload the scene", entry);
+  if (S.cdf_total > (size_t)std::numeric_limits<int>::max()) return fail(ctx, YH_E_INVALID, "%s: light cdf of %zu entries", entry, S.cdf_total);
+  for (int li = 0; li < S.num_lights && S.env_tab_light < 0; li++) {  // the first textured environment light of at least 4096 texels
+    const yhd_light& l = S.lights[li];
+    if (l.environment < 0 || l.cdf_count < 4096) continue;
+    const int n = l.cdf_count, stride = (n + 2047) / 2048;
+    S.env_tab_light = li, S.env_tab_k = (n + stride - 1) / stride, S.env_tab_stride = stride;
+  }
+  // the texel cdf of every textured environment that is a light now or will be one: kept on the device from here on. (A cache that no
+  // entry point shows and whose content depends on the texels alone: a call refused further down leaves it filled, and is still
+  // "the context exactly as it was" for everything a caller can observe.)
+  auto kept = [&](int ei, int count, const float* d_segment) -> int {
+    DevBuf& buf = ctx->d_env_cdf[ei];
+    if (buf.p || count <= 0) return YH_OK;
+    DevBuf made;
+    if (int rc = stage_alloc(ctx, made, (size_t)count * 4)) return rc;
+    if (d_segment) {
+      HIPCHK(ctx, hipMemcpyAsync(made.p, d_segment, (size_t)count * 4, hipMemcpyDeviceToDevice, ctx->stream));  // (commit_lights copies from it on the same stream)
+    } else {  // its first turn as a light: the upload's loop over the floats the upload was given
+      const yhd_environment& e = sc.environments[ei];
+      std::vector<yhd_float4> texels((size_t)count);
+      std::vector<float>      cdf;
+      HIPCHK(ctx, hipMemcpy(texels.data(), (const yhd_float4*)ctx->d_env_texels.p + e.texel_base, texels.size() * 16, hipMemcpyDeviceToHost));
+      cdf.reserve(texels.size());
+      append_env_cdf(&texels[0].x, 4, e.tex_w, e.tex_h, cdf);
+      HIPCHK(ctx, hipMemcpy(made.p, cdf.data(), cdf.size() * 4, hipMemcpyHostToDevice));
+    }
+    std::swap(buf.p, made.p), std::swap(buf.bytes, made.bytes);
+    return YH_OK;
+  };
+  for (int li = 0; li < sc.num_lights; li++)
+    if (sc.lights[li].environment >= 0)
+      if (int rc = kept(sc.lights[li].environment, sc.lights[li].cdf_count, (const float*)ctx->d_light_cdf.p + sc.lights[li].cdf_base)) return rc;
+  for (int li = 0; li < S.num_lights; li++)
+    if (S.lights[li].environment >= 0)
+      if (int rc = kept(S.lights[li].environment, S.lights[li].cdf_count, nullptr)) return rc;
+  if (int rc = stage_alloc(ctx, S.d_cdf, S.cdf_total * 4)) return rc;
+  if (int rc = stage_alloc(ctx, S.d_table, (size_t)S.table_f4 * 16)) return rc;
+  if (int rc = stage_alloc(ctx, S.d_tab, (size_t)S.env_tab_k * 4)) return rc;
+  if (int rc = stage_alloc(ctx, S.d_jobs, S.jobs.size() * sizeof(yhk_light_job))) return rc;
+  return YH_OK;
+}
+
+static int commit_lights(yh_context* ctx, const char* entry, LightStage& S) {
+  const int nj = (int)S.jobs.size();
+  if (nj > 0) HIPCHK(ctx, hipMemcpyAsync(S.d_jobs.p, S.jobs.data(), S.jobs.size() * sizeof(yhk_light_job), hipMemcpyHostToDevice, ctx->stream));
+  int e = yhk_light_cdfs(nj, S.d_jobs.p, ctx->d_vpos.p, ctx->d_elems.p, (float*)S.d_cdf.p, ctx->stream);
+  if (!e) e = yhk_small_records(nj, S.d_jobs.p, (const float*)ctx->d_shape_roots.p, ctx->d_prims.p, (const float*)S.d_cdf.p, S.d_table.p, ctx->stream);
+  if (e) return fail(ctx, YH_E_DEVICE, "%s: light list: %s", entry, hipGetErrorString((hipError_t)e));
+  for (int li = 0; li < S.num_lights; li++) {  // an environment light's segment: a copy of the cdf the context keeps
+    const yhd_light& l = S.lights[li];
+    if (l.environment >= 0 && l.cdf_count > 0)
+      HIPCHK(ctx, hipMemcpyAsync((float*)S.d_cdf.p + l.cdf_base, ctx->d_env_cdf[l.environment].p, (size_t)l.cdf_count * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  if (S.env_tab_light >= 0) {
+    const yhd_light& l = S.lights[S.env_tab_light];
+    e = yhk_env_tab(S.env_tab_k, S.env_tab_stride, l.cdf_count, (const float*)S.d_cdf.p + l.cdf_base, (float*)S.d_tab.p, ctx->stream);
+    if (e) return fail(ctx, YH_E_DEVICE, "%s: coarse index of the environment cdf: %s", entry, hipGetErrorString((hipError_t)e));
+  }
+  auto take = [](DevBuf& mine, DevBuf& staged) { std::swap(mine.p, staged.p), std::swap(mine.bytes, staged.bytes); };
+  take(ctx->d_light_cdf, S.d_cdf), take(ctx->d_light_table, S.d_table), take(ctx->d_env_tab, S.d_tab);
+  yhd_scene& sc = ctx->scene;
+  sc.num_lights = S.num_lights;
+  memcpy(sc.lights, S.lights, sizeof(sc.lights));
+  sc.light_cdf = (const float*)ctx->d_light_cdf.p;
+  sc.light_table = (const yhd_float4*)ctx->d_light_table.p, sc.light_table_f4 = S.table_f4;
+  sc.env_tab = (const float*)ctx->d_env_tab.p;
+  sc.env_tab_light = S.env_tab_light, sc.env_tab_k = S.env_tab_k, sc.env_tab_stride = S.env_tab_stride;
+  ctx->big_lights = S.big_lights;  // (settle_scene_variant reads it: the caller runs that next)
+  return YH_OK;
+}
+
+// A VERTEX edit of an emitter's shape changes no light's place: the list, every offset, the kernel variant and every other light's
+// entries stay. Only the lights that name `shape` get their cdf segment and their small record again, written where they are, from the
+// rows, records and root box the edit has queued on the stream before. rows: every object row.
+static int stage_lights_of_shape(yh_context* ctx, int shape, const yh_object* rows, LightStage& S) {
+  const yhd_scene& sc = ctx->scene;
+  for (int li = 0; li < sc.num_lights; li++) {
+    const yhd_light& l = sc.lights[li];
+    if (l.object < 0 || rows[l.object].shape != shape) continue;
+    const yh_context::LaneShape&  L = ctx->lane_shapes[(size_t)shape];
+    const yh_context::ShapeState& E = ctx->shape_states[(size_t)shape];
+    S.jobs.push_back({E.elem_base, E.vert_base, l.cdf_count, l.cdf_base, L.prim_base, shape, l.small_base, 0});
+  }
+  return stage_alloc(ctx, S.d_jobs, S.jobs.size() * sizeof(yhk_light_job));
+}
+static int commit_lights_of_shape(yh_context* ctx, const char* entry, LightStage& S) {
+  const int nj = (int)S.jobs.size();
+  if (nj == 0) return YH_OK;
+  HIPCHK(ctx, hipMemcpyAsync(S.d_jobs.p, S.jobs.data(), S.jobs.size() * sizeof(yhk_light_job), hipMemcpyHostToDevice, ctx->stream));
+  int e = yhk_light_cdfs(nj, S.d_jobs.p, ctx->d_vpos.p, ctx->d_elems.p, (float*)ctx->d_light_cdf.p, ctx->stream);
+  if (!e) e = yhk_small_records(nj, S.d_jobs.p, (const float*)ctx->d_shape_roots.p, ctx->d_prims.p, (const float*)ctx->d_light_cdf.p, ctx->d_light_table.p, ctx->stream);
+  if (e) return fail(ctx, YH_E_DEVICE, "%s: light list: %s", entry, hipGetErrorString((hipError_t)e));
+  return YH_OK;
+}
+
+// the material table's verdict, as the upload and yh_update_materials reach it
+static bool general_rows_in_force(const yh_context* ctx) {
+  const bool                mapped = !ctx->h_maps.empty();
+  const int                 n      = (int)ctx->h_materials.size();
+  std::vector<yhd_material> rows((size_t)n);
+  std::vector<yhd_maps>     dmaps(mapped ? (size_t)n : 0);
+  return make_material_rows(ctx->h_materials.data(), mapped ? ctx->h_maps.data() : nullptr, n, rows.data(), dmaps.data());
+}
+// every object row as it was passed in (key_geometry begins with them), and the environments' emission in force
+static std::vector<yh_object> uploaded_rows(const yh_context* ctx) {
+  std::vector<yh_object> rows((size_t)ctx->scene.num_objects);
+  memcpy(rows.data(), ctx->key_geometry.data(), sizeof(yh_object) * rows.size());
+  return rows;
+}
+static std::vector<float> emission_in_force(const yh_context* ctx) {
+  std::vector<float> em(3 * YH_MAX_ENVS, 0.0f);
+  for (int i = 0; i < ctx->scene.num_environments; i++) memcpy(&em[3 * (size_t)i], ctx->scene.environments[i].emission, 12);
+  return em;
 }
 
 int yh_update_camera(yh_context* ctx, const yh_camera* camera) {
@@ -45,10 +218,14 @@ int yh_update_materials(yh_context* ctx, int first, int count, const yh_material
   const int total = (int)ctx->h_materials.size();
   if (first < 0 || count < 0 || first > total || count > total - first)
     return fail(ctx, YH_E_INVALID, "yh_update_materials: rows [%d, %d + %d) are outside the uploaded table of %d materials", first, first, count, total);
+  bool lights_change = false;
   for (int i = 0; i < count; i++) {
     const yh_material &was = ctx->h_materials[(size_t)first + i], &now = materials[i];
-    // the light list (init_lights, pt.cpp:1695-1740) was made from the shapes' host arrays, which were borrowed for the upload only
-    if (is_black(was.emission) != is_black(now.emission))
+    // the light list (init_lights, pt.cpp:1695-1740) was made from the shapes' host arrays, which were borrowed for the upload only:
+    // with yh_set_light_edits it is made again from the rows the device keeps
+    const bool toggles = is_black(was.emission) != is_black(now.emission);
+    lights_change = lights_change || toggles;
+    if (toggles && !ctx->light_edits)
       return fail(ctx, YH_E_INVALID, "yh_update_materials: material %d turns its emission %s: the light list changes, upload the scene", first + i, is_black(now.emission) ? "off" : "on");
     // which texel copies exist (sRGB-decoded, linear) was decided at the upload
     if (was.emission_tex != now.emission_tex || was.color_tex != now.color_tex || was.scattering_tex != now.scattering_tex)
@@ -61,13 +238,22 @@ int yh_update_materials(yh_context* ctx, int first, int count, const yh_material
   std::vector<yhd_material> rows((size_t)total);
   std::vector<yhd_maps>     dmaps(mapped ? (size_t)total : 0);
   const bool general_rows = make_material_rows(all.data(), mapped ? ctx->h_maps.data() : nullptr, total, rows.data(), dmaps.data());
+  LightStage LS;
+  if (lights_change)
+    if (int rc = stage_lights(ctx, "yh_update_materials", all.data(), uploaded_rows(ctx).data(), emission_in_force(ctx).data(), LS)) return rc;
+  if (lights_change) ctx->have_scene = false;  // (from here on an error leaves the context without a scene)
   if (count > 0)
     HIPCHK(ctx, hipMemcpy((yhd_material*)ctx->d_materials.p + first, rows.data() + first, sizeof(yhd_material) * (size_t)count, hipMemcpyHostToDevice));
   if (mapped && count > 0)  // (a map's record carries the material's opacity before its snap)
     HIPCHK(ctx, hipMemcpy((yhd_maps*)ctx->d_maps.p + first, dmaps.data() + first, sizeof(yhd_maps) * (size_t)count, hipMemcpyHostToDevice));
+  if (lights_change) {
+    if (int rc = commit_lights(ctx, "yh_update_materials", LS)) return rc;
+    YH_WAIT(ctx);
+  }
   ctx->h_materials.swap(all);
   if (mapped) ctx->h_dmaps.swap(dmaps);
   settle_scene_variant(ctx, ctx->scene, general_rows);
+  ctx->have_scene = true;
   edit_end(ctx);
   return YH_OK;
 }
@@ -78,9 +264,24 @@ int yh_update_environments(yh_context* ctx, int count, const yh_environment* env
   if (int rc = edit_begin(ctx, "yh_update_environments")) return rc;
   if (count != ctx->scene.num_environments)
     return fail(ctx, YH_E_INVALID, "yh_update_environments: %d environments, the uploaded scene has %d", count, ctx->scene.num_environments);
-  for (int i = 0; i < count; i++)
-    if (is_black(ctx->scene.environments[i].emission) != is_black(environments[i].emission))
+  bool lights_change = false;
+  for (int i = 0; i < count; i++) {
+    const bool toggles = is_black(ctx->scene.environments[i].emission) != is_black(environments[i].emission);
+    lights_change = lights_change || toggles;
+    if (toggles && !ctx->light_edits)
       return fail(ctx, YH_E_INVALID, "yh_update_environments: environment %d turns its emission %s: the light list changes, upload the scene", i, is_black(environments[i].emission) ? "off" : "on");
+  }
+  LightStage LS;
+  if (lights_change) {
+    std::vector<float> em(3 * YH_MAX_ENVS, 0.0f);
+    for (int i = 0; i < count; i++) memcpy(&em[3 * (size_t)i], environments[i].emission, 12);
+    if (int rc = stage_lights(ctx, "yh_update_environments", ctx->h_materials.data(), uploaded_rows(ctx).data(), em.data(), LS)) return rc;
+    ctx->have_scene = false;  // (from here on an error leaves the context without a scene)
+    if (int rc = commit_lights(ctx, "yh_update_environments", LS)) return rc;
+    YH_WAIT(ctx);
+    settle_scene_variant(ctx, ctx->scene, general_rows_in_force(ctx));  // (the index of a texel cdf is one of the kernels' LDS tables)
+    ctx->have_scene = true;
+  }
   const size_t head = offsetof(yh_environment, texels), edited = offsetof(yh_environment, tex_width);  // frame and emission
   for (int i = 0; i < count; i++) {
     auto& d = ctx->scene.environments[i];
@@ -99,13 +300,6 @@ int yh_update_environments(yh_context* ctx, int count, const yh_environment* env
 // stack needs, the kernel variant. The per-object arithmetic runs on the device (unit/objects.hip), the tree is built as the upload
 // builds it (yhh::build_bvh on the host, the device's collapse). Everything that can refuse is computed into staging first; from COMMIT
 // on only copies, a memset and two kernels run, and an error there leaves the context without a scene, as a failed upload does.
-static int stage_alloc(yh_context* ctx, DevBuf& buf, size_t bytes) {
-  buf.reset();
-  HIPCHK(ctx, hipMalloc(&buf.p, std::max<size_t>(bytes, 16)));
-  buf.bytes = std::max<size_t>(bytes, 16);
-  return YH_OK;
-}
-
 // ---- the scene level again: what yh_update_objects and yh_update_shape share. Everything that can refuse is staged by stage_scene_level;
 // commit_scene_level queues the copies, the memset and the collapse on the context's stream; settle_scene_level, once they are done,
 // brings the host's side of the scene table in line ----
@@ -123,7 +317,7 @@ struct SceneLevelStage {
 
 // boxes: every object's world box; depth4 / 8 / 16: the deepest shape tree as 4- / 8- / 16-wide nodes
 static int stage_scene_level(yh_context* ctx, const char* entry, const std::vector<yhh::Box>& boxes, int depth4, int depth8, int depth16, SceneLevelStage& S) {
-  const int total = ctx->scene.num_objects, num_materials = (int)ctx->h_materials.size();
+  const int total = ctx->scene.num_objects;
   // ---- the scene-level tree, as the upload builds it, and what the upload derives from it ----
   yhh::Tree& tree = S.tree;
   yhh::build_bvh(tree, boxes);
@@ -156,12 +350,7 @@ static int stage_scene_level(yh_context* ctx, const char* entry, const std::vect
     if (int rc = stage_alloc(ctx, S.d_nodes_grown, (size_t)(2 * total) * 32)) return rc;
   if (ctx->d_scene_prims.bytes < S.scene_prims.size() * 4)
     if (int rc = stage_alloc(ctx, S.d_prims_grown, S.scene_prims.size() * 4)) return rc;
-  S.general_rows = [&] {  // (the material table's verdict, as the upload and yh_update_materials reach it)
-    const bool                mapped = !ctx->h_maps.empty();
-    std::vector<yhd_material> rows((size_t)num_materials);
-    std::vector<yhd_maps>     dmaps(mapped ? (size_t)num_materials : 0);
-    return make_material_rows(ctx->h_materials.data(), mapped ? ctx->h_maps.data() : nullptr, num_materials, rows.data(), dmaps.data());
-  }();
+  S.general_rows = general_rows_in_force(ctx);
   return YH_OK;
 }
 
@@ -199,6 +388,7 @@ int yh_update_objects(yh_context* ctx, int first, int count, const yh_object* ob
   if (first < 0 || count < 0 || first > total || count > total - first)
     return fail(ctx, YH_E_INVALID, "yh_update_objects: rows [%d, %d + %d) are outside the uploaded list of %d objects", first, first, count, total);
   static_assert(sizeof(yh_object) == 56, "the fingerprint's object bytes are the rows themselves");
+  bool                   lights_change = false;
   std::vector<yh_object> was((size_t)count);  // (key_geometry begins with the object rows as they were passed in)
   if (count > 0) memcpy(was.data(), ctx->key_geometry.data() + sizeof(yh_object) * (size_t)first, sizeof(yh_object) * (size_t)count);
   for (int i = 0; i < count; i++) {
@@ -209,7 +399,9 @@ int yh_update_objects(yh_context* ctx, int first, int count, const yh_object* ob
       return fail(ctx, YH_E_INVALID, "yh_update_objects: object %d names material %d of %d", first + i, now.material, num_materials);
     // the light list (init_lights, pt.cpp:1695-1740) holds the objects whose material emits: the rule of yh_update_materials
     const bool black = is_black(ctx->h_materials[(size_t)now.material].emission);
-    if (black != is_black(ctx->h_materials[(size_t)was[(size_t)i].material].emission))
+    const bool toggles = black != is_black(ctx->h_materials[(size_t)was[(size_t)i].material].emission);
+    lights_change = lights_change || toggles;
+    if (toggles && !ctx->light_edits)
       return fail(ctx, YH_E_INVALID, "yh_update_objects: object %d turns its emission %s with material %d: the light list changes, upload the scene", first + i, black ? "off" : "on", now.material);
   }
   // ---- staging: the world boxes of the edited rows, from the device ----
@@ -227,6 +419,12 @@ int yh_update_objects(yh_context* ctx, int first, int count, const yh_object* ob
   }
   SceneLevelStage S;
   if (int rc = stage_scene_level(ctx, "yh_update_objects", boxes, ctx->max_shape_depth, ctx->max_shape_depth8, ctx->max_shape_depth16, S)) return rc;
+  LightStage LS;
+  if (lights_change) {  // the light list over the edited rows
+    std::vector<yh_object> rows = uploaded_rows(ctx);
+    std::copy(objects, objects + count, rows.begin() + first);
+    if (int rc = stage_lights(ctx, "yh_update_objects", ctx->h_materials.data(), rows.data(), emission_in_force(ctx).data(), LS)) return rc;
+  }
   // ---- COMMIT ----
   ctx->have_scene = false;
   if (count > 0) {
@@ -234,6 +432,8 @@ int yh_update_objects(yh_context* ctx, int first, int count, const yh_object* ob
     if (e) return fail(ctx, YH_E_DEVICE, "object rows: %s", hipGetErrorString((hipError_t)e));
   }
   if (int rc = commit_scene_level(ctx, S)) return rc;
+  if (lights_change)
+    if (int rc = commit_lights(ctx, "yh_update_objects", LS)) return rc;
   YH_WAIT(ctx);
   if (count > 0) memcpy(ctx->key_geometry.data() + sizeof(yh_object) * (size_t)first, objects, sizeof(yh_object) * (size_t)count);
   ctx->h_obj_boxes.swap(boxes);
@@ -251,7 +451,8 @@ int yh_update_objects(yh_context* ctx, int first, int count, const yh_object* ob
 // (count + count / 8 nodes, on a multiple of 4 units), the array is reallocated and the old bytes copied device to device, the vacated
 // region is zeroed and stays unused until an upload. No other shape moves: the collapse writes absolute references.
 // what yh_update_shape and yh_refit_shape check of their arguments before anything is staged, and `rows`: the object list as it was passed in
-static int check_shape_edit(yh_context* ctx, const char* entry, int shape, const yh_shape* now, std::vector<yh_object>& rows) {
+// (emits: an object that names the shape is a light — refused without yh_set_light_edits, else the light list follows the edit)
+static int check_shape_edit(yh_context* ctx, const char* entry, int shape, const yh_shape* now, std::vector<yh_object>& rows, bool& emits) {
   if (!now) return fail(ctx, YH_E_INVALID, "%s: now is NULL", entry);
   if (int rc = edit_begin(ctx, entry)) return rc;
   const int num_shapes = (int)ctx->shape_states.size(), total = ctx->scene.num_objects;
@@ -275,9 +476,13 @@ static int check_shape_edit(yh_context* ctx, const char* entry, int shape, const
   // the light cdf and the LDS light table (init_lights, pt.cpp:1695-1740) were made from the shape of every object whose material emits
   rows.resize((size_t)total);  // (key_geometry begins with the object rows as they were passed in)
   memcpy(rows.data(), ctx->key_geometry.data(), sizeof(yh_object) * (size_t)total);
-  for (int i = 0; i < total; i++)
-    if (rows[(size_t)i].shape == shape && !is_black(ctx->h_materials[(size_t)rows[(size_t)i].material].emission))
+  emits = false;
+  for (int i = 0; i < total; i++) {
+    if (rows[(size_t)i].shape != shape || is_black(ctx->h_materials[(size_t)rows[(size_t)i].material].emission)) continue;
+    emits = !lines;  // (a line shape never is a light)
+    if (!ctx->light_edits)
       return fail(ctx, YH_E_INVALID, "%s: shape %d is the shape of object %d, whose material emits: the light tables are made from it, upload the scene", entry, shape, i);
+  }
   return YH_OK;
 }
 
@@ -340,7 +545,8 @@ int shape_slot_areas(yh_context* ctx, const char* who, int n, const yh_context::
 static int update_shape(yh_context* ctx, const char* entry, int shape, const yh_shape* now, bool device) {
   if (!ctx) return YH_E_INVALID;
   std::vector<yh_object> rows;
-  if (int rc = check_shape_edit(ctx, entry, shape, now, rows)) return rc;
+  bool                   emits = false;
+  if (int rc = check_shape_edit(ctx, entry, shape, now, rows, emits)) return rc;
   const int num_shapes = (int)ctx->shape_states.size(), total = ctx->scene.num_objects;
   const yh_context::ShapeState& E = ctx->shape_states[(size_t)shape];
   const yh_context::LaneShape&  L = ctx->lane_shapes[(size_t)shape];
@@ -416,6 +622,9 @@ static int update_shape(yh_context* ctx, const char* entry, int shape, const yh_
   for (size_t k = 0; k < named.size(); k++) boxes[(size_t)named[k]] = named_boxes[k];
   SceneLevelStage S;
   if (int rc = stage_scene_level(ctx, entry, boxes, depth4, depth8, depth16, S)) return rc;
+  LightStage LS;  // an emitter's shape: the cdf and the record of the lights that name it, made once the new arrays sit in the context's rows
+  if (emits)
+    if (int rc = stage_lights_of_shape(ctx, shape, rows.data(), LS)) return rc;
   // ---- COMMIT: from here on kernels, copies and memsets only ----
   ctx->have_scene = false;
   if (d_blob_grown.p) {  // the old array's bytes as they are, zeros behind them (what alloc_zero leaves)
@@ -447,6 +656,8 @@ static int update_shape(yh_context* ctx, const char* entry, int shape, const yh_
     if (e) return fail(ctx, YH_E_DEVICE, "%sobject rows: %s", who, hipGetErrorString((hipError_t)e));
   }
   if (int rc = commit_scene_level(ctx, S)) return rc;
+  if (emits)
+    if (int rc = commit_lights_of_shape(ctx, entry, LS)) return rc;
   YH_WAIT(ctx);
   memcpy(ctx->key_geometry.data() + E.key_positions, key_bytes.data(), key_bytes.size());
   ctx->scene.num_nodes_total += T.wide_count[0] - E.count[0];
@@ -483,7 +694,8 @@ int yh_update_shape_device(yh_context* ctx, int shape, const yh_shape* now) { re
 static int refit_shape(yh_context* ctx, const char* entry, int shape, const yh_shape* now, bool device) {
   if (!ctx) return YH_E_INVALID;
   std::vector<yh_object> rows;
-  if (int rc = check_shape_edit(ctx, entry, shape, now, rows)) return rc;
+  bool                   emits = false;
+  if (int rc = check_shape_edit(ctx, entry, shape, now, rows, emits)) return rc;
   const int total = ctx->scene.num_objects;
   yh_context::ShapeState&      E = ctx->shape_states[(size_t)shape];
   const yh_context::LaneShape& L = ctx->lane_shapes[(size_t)shape];
@@ -544,6 +756,9 @@ static int refit_shape(yh_context* ctx, const char* entry, int shape, const yh_s
   for (size_t k = 0; k < named.size(); k++) boxes[(size_t)named[k]] = named_boxes[k];
   SceneLevelStage S;
   if (int rc = stage_scene_level(ctx, entry, boxes, ctx->max_shape_depth, ctx->max_shape_depth8, ctx->max_shape_depth16, S)) return rc;
+  LightStage LS;  // an emitter's shape: the cdf and the record of the lights that name it (the cdf is by element: it does not depend on the tree)
+  if (emits)
+    if (int rc = stage_lights_of_shape(ctx, shape, rows.data(), LS)) return rc;
   // ---- COMMIT: from here on kernels and copies only ----
   ctx->have_scene = false;
   e = yhk_refit_records(lines ? 1 : 0, (int)nel, dev.positions, dev.normals, dev.radius, d_index, d_recs, ctx->stream);
@@ -568,6 +783,8 @@ static int refit_shape(yh_context* ctx, const char* entry, int shape, const yh_s
   }
   if (e) return fail(ctx, YH_E_DEVICE, "%sobject rows: %s", who, hipGetErrorString((hipError_t)e));
   if (int rc = commit_scene_level(ctx, S)) return rc;
+  if (emits)
+    if (int rc = commit_lights_of_shape(ctx, entry, LS)) return rc;
   double area[3];
   if (int rc = shape_slot_areas(ctx, who, 1, &L, &E.count, ctx->d_lane_blob.p, area)) return rc;  // (waits for the stream)
   memcpy(E.area_now, area, sizeof(area));
@@ -582,6 +799,66 @@ static int refit_shape(yh_context* ctx, const char* entry, int shape, const yh_s
 
 int yh_refit_shape(yh_context* ctx, int shape, const yh_shape* now) { return refit_shape(ctx, "yh_refit_shape", shape, now, false); }
 int yh_refit_shape_device(yh_context* ctx, int shape, const yh_shape* now) { return refit_shape(ctx, "yh_refit_shape_device", shape, now, true); }
+
+int yh_set_light_edits(yh_context* ctx, int on) {
+  if (!ctx) return YH_E_INVALID;
+  ctx->light_edits = on != 0;
+  return YH_OK;
+}
+
+int yh_light_list(const yh_context* ctx, int* object, int* environment, int* cdf_count, int* in_lds, int capacity) {
+  if (!ctx) return YH_E_INVALID;
+  if (!ctx->have_scene) return YH_E_STATE;
+  const yhd_scene& sc = ctx->scene;
+  for (int i = 0; i < sc.num_lights && i < capacity; i++) {
+    if (object) object[i] = sc.lights[i].object;
+    if (environment) environment[i] = sc.lights[i].environment;
+    if (cdf_count) cdf_count[i] = sc.lights[i].cdf_count;
+    if (in_lds) in_lds[i] = sc.lights[i].small_base >= 0;
+  }
+  return sc.num_lights;
+}
+
+// init_lights' area cdf of one triangle shape (pt.cpp:1695-1740): the upload's loop restated, and the kernel of the edit
+static bool triangle_cdf_args(int num_vertices, const float* positions, int num_triangles, const int* triangles, const float* cdf) {
+  if (num_vertices <= 0 || num_triangles <= 0 || !positions || !triangles || !cdf) return false;
+  for (size_t k = 0; k < 3 * (size_t)num_triangles; k++)
+    if (triangles[k] < 0 || triangles[k] >= num_vertices) return false;
+  return true;
+}
+
+int yh_triangle_cdf(int num_vertices, const float* positions, int num_triangles, const int* triangles, float* cdf) {
+  if (!triangle_cdf_args(num_vertices, positions, num_triangles, triangles, cdf)) return YH_E_INVALID;
+  for (int t = 0; t < num_triangles; t++) {
+    float area = triangle_area(ld3(positions + 3 * (size_t)triangles[3 * t]), ld3(positions + 3 * (size_t)triangles[3 * t + 1]), ld3(positions + 3 * (size_t)triangles[3 * t + 2]));
+    if (t) area += cdf[t - 1];
+    cdf[t] = area;
+  }
+  return YH_OK;
+}
+
+int yh_triangle_cdf_gpu(yh_context* ctx, int num_vertices, const float* positions, int num_triangles, const int* triangles, float* cdf) {
+  if (!ctx) return YH_E_INVALID;
+  if (!triangle_cdf_args(num_vertices, positions, num_triangles, triangles, cdf))
+    return fail(ctx, YH_E_INVALID, "yh_triangle_cdf_gpu: a NULL array, an empty shape or a vertex index outside [0, %d)", num_vertices);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  if (ctx->poisoned) return fail(ctx, YH_E_DEVICE, "a launch of this context exceeded its deadline: the context refuses further work, destroy it");
+  YH_WAIT(ctx);
+  const yhk_light_job job{0, 0, num_triangles, 0, 0, 0, -1, 0};
+  DevBuf d_job, d_pos, d_tri, d_cdf;
+  if (int rc = stage_alloc(ctx, d_job, sizeof(job))) return rc;
+  if (int rc = stage_alloc(ctx, d_pos, (size_t)num_vertices * 12)) return rc;
+  if (int rc = stage_alloc(ctx, d_tri, (size_t)num_triangles * 12)) return rc;
+  if (int rc = stage_alloc(ctx, d_cdf, (size_t)num_triangles * 4)) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(d_job.p, &job, sizeof(job), hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(d_pos.p, positions, (size_t)num_vertices * 12, hipMemcpyHostToDevice, ctx->stream));
+  HIPCHK(ctx, hipMemcpyAsync(d_tri.p, triangles, (size_t)num_triangles * 12, hipMemcpyHostToDevice, ctx->stream));
+  int e = yhk_triangle_cdf_raw(d_job.p, (const float*)d_pos.p, (const int*)d_tri.p, (float*)d_cdf.p, ctx->stream);
+  if (e) return fail(ctx, YH_E_DEVICE, "yh_triangle_cdf_gpu: %s", hipGetErrorString((hipError_t)e));
+  HIPCHK(ctx, hipMemcpyAsync(cdf, d_cdf.p, (size_t)num_triangles * 4, hipMemcpyDeviceToHost, ctx->stream));
+  YH_WAIT(ctx);
+  return YH_OK;
+}
 
 int yh_shape_refit_growth(const yh_context* ctx, int shape, float growth[3]) {
   if (!ctx) return YH_E_INVALID;

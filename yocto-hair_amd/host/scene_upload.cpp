@@ -326,6 +326,18 @@ int collapse_shape_tree(yh_context* ctx, const char* who, const ShapeTree& T, co
   return YH_OK;
 }
 
+void append_env_cdf(const float* texels, int stride, int width, int height, std::vector<float>& cdf) {
+  const size_t n = (size_t)width * height, at = cdf.size();
+  for (size_t i = 0; i < n; i++) {
+    int   iy    = (int)(i / width);
+    float th    = (iy + 0.5f) * pif / height;
+    float mx    = fmax_(fmax_(texels[stride * i], texels[stride * i + 1]), texels[stride * i + 2]);
+    float value = mx * std::sin(th);
+    if (i) value += cdf[at + i - 1];
+    cdf.push_back(value);
+  }
+}
+
 int yh_upload_scene(yh_context* ctx, const yh_scene_desc* sd) { return yh_upload_scene_maps(ctx, sd, nullptr); }
 
 int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_material_maps* maps) {
@@ -383,6 +395,7 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
   ctx->have_scene = false, ctx->have_state = false;
   ctx->scene.lane_blob = nullptr, ctx->scene.prims = nullptr;
   ctx->d_prims.reset(), ctx->d_lane_blob.reset();  // (nothing of this context is running: waited for above)
+  for (DevBuf& kept : ctx->d_env_cdf) kept.reset();  // (the texel cdfs a light edit kept: another scene's)
   if ((rc = dev_alloc(ctx, ctx->d_prims, total_prim_f4 * 16))) return rc;
   lap("validation, record array");
   for (int si = 0; si < sd->num_shapes; si++) {
@@ -553,10 +566,8 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
     if (s.num_triangles <= YH_SMALL_LIGHT_TRIS) small_lights.push_back(sc.num_lights - 1);  // its record is made below, once the cdf exists
     else big_lights = true;  // a light sampled and intersected through memory: the general kernel variant (settle_scene_variant)
     for (int t = 0; t < s.num_triangles; t++) {
-      F3 p0 = ld3(s.positions + 3 * (size_t)s.triangles[3 * t]), p1 = ld3(s.positions + 3 * (size_t)s.triangles[3 * t + 1]),
-         p2 = ld3(s.positions + 3 * (size_t)s.triangles[3 * t + 2]);
-      F3    c    = cross(p1 - p0, p2 - p0);
-      float area = std::sqrt(dot(c, c)) / 2;  // triangle_area (math.h:3306)
+      float area = triangle_area(ld3(s.positions + 3 * (size_t)s.triangles[3 * t]), ld3(s.positions + 3 * (size_t)s.triangles[3 * t + 1]),
+          ld3(s.positions + 3 * (size_t)s.triangles[3 * t + 2]));  // (unit/light_math.h: triangle_area, math.h:3306)
       if (t) area += light_cdf.back();
       light_cdf.push_back(area);
     }
@@ -578,16 +589,8 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
     auto& L = sc.lights[sc.num_lights++];
     L.object = -1, L.environment = ei, L.cdf_base = (int)light_cdf.size(), L.cdf_count = 0, L.small_base = -1;
     if (e.texels) {
-      size_t n    = (size_t)e.tex_width * e.tex_height;
-      L.cdf_count = (int)n;
-      for (size_t i = 0; i < n; i++) {
-        int   iy    = (int)(i / e.tex_width);
-        float th    = (iy + 0.5f) * pif / e.tex_height;
-        float mx    = fmax_(fmax_(e.texels[3 * i], e.texels[3 * i + 1]), e.texels[3 * i + 2]);
-        float value = mx * std::sin(th);
-        if (i) value += light_cdf.back();
-        light_cdf.push_back(value);
-      }
+      L.cdf_count = (int)((size_t)e.tex_width * e.tex_height);
+      append_env_cdf(e.texels, 3, e.tex_width, e.tex_height, light_cdf);
     }
   }
   if (sc.num_lights == 0) return fail(ctx, YH_E_INVALID, "scene has no lights (the path sampler needs at least one)");

@@ -117,6 +117,9 @@ struct flat_scene {
 // positions, normals, radius or texcoords only — by their pointers, or by a vertex setter having run since the upload, which writes
 // into the same storage when the sizes agree — is edit_shapes, what yh_update_shape accepts, unless normals or texcoords appear or
 // vanish or an object that names it emits (its light tables were made from it). Without it nothing of this is looked at.
+// lights_too (EXTENSION, see set_light_edits): what changes the light list no longer makes an edit an upload — a material or an
+// environment whose emission turns on or off, an object whose new material does, the vertex arrays of an emitter's shape (with
+// shapes_too) — since yh_set_light_edits makes the yh_update_* calls take them. The default classification is unchanged.
 enum : unsigned { edit_none = 0, edit_camera = 1, edit_materials = 2, edit_environments = 4, edit_upload = 8, edit_objects = 16, edit_shapes = 32 };
 // whether shape i differs in its vertex arrays alone (the counts and the index arrays being equal is the caller's business)
 inline bool shape_vertices_differ(const flat_scene& was, const flat_scene& now, size_t i) {
@@ -124,7 +127,7 @@ inline bool shape_vertices_differ(const flat_scene& was, const flat_scene& now, 
   auto edits = [i](const flat_scene& f) { return i < f.shape_vertex_edits.size() ? f.shape_vertex_edits[i] : 0u; };
   return a.positions != b.positions || a.normals != b.normals || a.radius != b.radius || a.texcoords != b.texcoords || edits(was) != edits(now);
 }
-inline unsigned classify_edit(const flat_scene& was, const flat_scene& now, bool objects_too, bool shapes_too = false) {
+inline unsigned classify_edit(const flat_scene& was, const flat_scene& now, bool objects_too, bool shapes_too = false, bool lights_too = false) {
   auto black = [](const float* e) { return e[0] == 0 && e[1] == 0 && e[2] == 0; };
   if (was.shapes.size() != now.shapes.size() || was.materials.size() != now.materials.size() || was.maps.size() != now.maps.size() ||
       was.objects.size() != now.objects.size() || was.environments.size() != now.environments.size() || was.textures.size() != now.textures.size())
@@ -140,7 +143,7 @@ inline unsigned classify_edit(const flat_scene& was, const flat_scene& now, bool
     }
     if (!shape_vertices_differ(was, now, i)) continue;
     if (!b.positions || (a.normals != nullptr) != (b.normals != nullptr) || (a.texcoords != nullptr) != (b.texcoords != nullptr)) return edit_upload;
-    for (size_t o = 0; o < now.objects.size(); o++) {  // an emitter's geometry: the light list was made from it
+    for (size_t o = 0; o < now.objects.size() && !lights_too; o++) {  // an emitter's geometry: the light list was made from it
       const yh_object& ob = now.objects[o];
       if ((size_t)ob.shape == i && ob.material >= 0 && (size_t)ob.material < now.materials.size() && !black(now.materials[(size_t)ob.material].emission)) return edit_upload;
     }
@@ -158,7 +161,7 @@ inline unsigned classify_edit(const flat_scene& was, const flat_scene& now, bool
     if (!objects_too) return edit_upload;
     const size_t nm = now.materials.size();
     if (a.material < 0 || b.material < 0 || (size_t)a.material >= nm || (size_t)b.material >= nm) return edit_upload;
-    if (black(was.materials[(size_t)a.material].emission) != black(now.materials[(size_t)b.material].emission)) return edit_upload;  // the light list changes
+    if (!lights_too && black(was.materials[(size_t)a.material].emission) != black(now.materials[(size_t)b.material].emission)) return edit_upload;  // the light list changes
     kind |= edit_objects;
   }
   static_assert(sizeof(yh_material_maps) == 6 * sizeof(int) && sizeof(yh_material) == 30 * 4 && sizeof(yh_camera) == 17 * 4, "compared as bytes: no padding");
@@ -166,12 +169,12 @@ inline unsigned classify_edit(const flat_scene& was, const flat_scene& now, bool
   for (size_t i = 0; i < now.materials.size(); i++) {
     const yh_material &a = was.materials[i], &b = now.materials[i];
     if (!memcmp(&a, &b, sizeof(a))) continue;
-    if (black(a.emission) != black(b.emission) || a.emission_tex != b.emission_tex || a.color_tex != b.color_tex || a.scattering_tex != b.scattering_tex) return edit_upload;
+    if ((!lights_too && black(a.emission) != black(b.emission)) || a.emission_tex != b.emission_tex || a.color_tex != b.color_tex || a.scattering_tex != b.scattering_tex) return edit_upload;
     kind |= edit_materials;
   }
   for (size_t i = 0; i < now.environments.size(); i++) {
     const yh_environment &a = was.environments[i], &b = now.environments[i];
-    if (a.tex_width != b.tex_width || a.tex_height != b.tex_height || a.texels != b.texels || black(a.emission) != black(b.emission)) return edit_upload;
+    if (a.tex_width != b.tex_width || a.tex_height != b.tex_height || a.texels != b.texels || (!lights_too && black(a.emission) != black(b.emission))) return edit_upload;
     if (memcmp(a.frame, b.frame, 48) || memcmp(a.emission, b.emission, 12)) kind |= edit_environments;
   }
   if (memcmp(&was.camera, &now.camera, sizeof(yh_camera))) kind |= edit_camera;
@@ -334,6 +337,7 @@ struct scene {
   bool                       object_edits = false;  // EXTENSION (set_object_edits): object frames and materials go through yh_update_objects
   bool                       shape_edits  = false;  // EXTENSION (set_shape_edits): vertex edits of a shape go through yh_update_shape
   bool                       shape_refit  = false;  // EXTENSION (set_shape_refit): ... through yh_refit_shape instead
+  bool                       light_edits  = false;  // EXTENSION (set_light_edits): what changes the light list is an edit too (yh_set_light_edits)
 };
 struct state {  // pt.h:426-429; `render` is refreshed by trace_samples
   int                width = 0, height = 0, samples = 0;
@@ -437,6 +441,12 @@ inline void set_shape_edits(scene* s, bool on) { s->shape_edits = on; }
 // build and gets its records and boxes again (include/yhair.h: REFIT; closest hits those of a build, ties apart; yh_shape_refit_growth
 // tells what the boxes grew by). How an edit is classified does not change, nor what falls back to the upload.
 inline void set_shape_refit(scene* s, bool on) { s->shape_refit = on; }
+// EXTENSION, off by default. With `on`, init_state passes on as an edit what changes the LIGHT LIST (include/yhair.h: LIGHT EDITS): an
+// emission turned on or off by a material setter or by set_emission on an environment, set_material on an object under
+// set_object_edits, and a vertex edit of an emitter's shape under set_shape_edits / set_shape_refit. The contexts make the light list
+// again on the device. What they still refuse — a 17th light, no light left (also in between: the materials are passed on before the
+// environments), another texture — falls back to the upload.
+inline void set_light_edits(scene* s, bool on) { s->light_edits = on; }
 inline void set_emission(environment* e, const vec3f& em, texture* tex = nullptr) { e->emission = em, e->emission_tex = tex; }
 
 // Flattens the scene graph into a yh_scene_desc and uploads it; the C ABI builds
@@ -542,7 +552,7 @@ inline void upload_scene(const scene* sc, const camera* cam) { upload_scene(sc, 
 inline bool update_scene(const scene* sc, const camera* cam, detail::flat_scene&& flat, unsigned kind) {
   std::atomic<bool> refused{false};  // (every context from a thread of its own)
   detail::for_each_context([&](yh_context* ctx, int) {
-    int rc = YH_OK;
+    int rc = yh_set_light_edits(ctx, sc->light_edits ? 1 : 0);
     if (!rc && (kind & detail::edit_camera)) rc = yh_update_camera(ctx, &flat.camera);
     if (!rc && (kind & detail::edit_materials)) rc = yh_update_materials(ctx, 0, (int)flat.materials.size(), flat.materials.data());
     if (!rc && (kind & detail::edit_environments)) rc = yh_update_environments(ctx, (int)flat.environments.size(), flat.environments.data());
@@ -579,11 +589,11 @@ inline void init_state(state* st, const scene* sc, const camera* cam, const trac
   // Nothing changed: nothing to do. Only what the yh_update_* calls accept (camera fields, material fields, the environments' frames
   // and emission; with set_object_edits, the objects' frames and materials; with set_shape_edits, a shape's vertex arrays — through yh_refit_shape with set_shape_refit): those calls,
   // which keep every shape's tree but an edited shape's own. Anything else
-  // — an object's frame without the opt-in, a shape's arrays, a texture, an emission turned on or off, init_bvh / init_lights called
-  // again — is the whole upload.
+  // — an object's frame without the opt-in, a shape's arrays, a texture, an emission turned on or off (without set_light_edits),
+  // init_bvh / init_lights called again — is the whole upload.
   {
     auto     flat = flatten_scene(sc, cam);
-    unsigned kind = sc->uploaded_for ? detail::classify_edit(sc->uploaded, flat, sc->object_edits, sc->shape_edits) : (unsigned)detail::edit_upload;
+    unsigned kind = sc->uploaded_for ? detail::classify_edit(sc->uploaded, flat, sc->object_edits, sc->shape_edits, sc->light_edits) : (unsigned)detail::edit_upload;
     if (kind != detail::edit_none && !(kind & detail::edit_upload)) {
       if (update_scene(sc, cam, std::move(flat), kind)) sc->edits++;
       else kind = detail::edit_upload, flat = flatten_scene(sc, cam);

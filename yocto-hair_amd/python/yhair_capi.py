@@ -149,6 +149,10 @@ _SIGS = {
     "yh_refit_shape_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(Shape)]),
     "yh_shape_refit_growth": (C.c_int, [C.c_void_p, C.c_int, c_float_p]),
     "yh_shape_nodes": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int64), c_int_p, c_int_p]),
+    "yh_set_light_edits": (C.c_int, [C.c_void_p, C.c_int]),
+    "yh_light_list": (C.c_int, [C.c_void_p, c_int_p, c_int_p, c_int_p, c_int_p, C.c_int]),
+    "yh_triangle_cdf": (C.c_int, [C.c_int, c_float_p, C.c_int, c_int_p, c_float_p]),
+    "yh_triangle_cdf_gpu": (C.c_int, [C.c_void_p, C.c_int, c_float_p, C.c_int, c_int_p, c_float_p]),
     "yh_download_display": (C.c_int, [C.c_void_p, C.c_float, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
     "yh_init_state": (C.c_int, [C.c_void_p, C.POINTER(TraceParams)]),
     "yh_image_size": (C.c_int, [C.c_void_p, c_int_p, c_int_p]),
@@ -244,6 +248,21 @@ def bvh_refit_wide(boxes, primitives, width, slots):
     if n < 0:
         raise YhError(f"yhair error {n}: yh_bvh_refit_wide")
     return n, out
+
+
+def _cdf_args(positions, triangles):
+    positions = np.ascontiguousarray(positions, np.float32).reshape(-1, 3)
+    triangles = np.ascontiguousarray(triangles, np.int32).reshape(-1, 3)
+    return positions, triangles, np.zeros(len(triangles), np.float32)
+
+
+def triangle_cdf(positions, triangles):
+    """yh_triangle_cdf (host, no GPU): the area cdf of a triangle shape, one float32 chain in element order."""
+    positions, triangles, out = _cdf_args(positions, triangles)
+    rc = load().yh_triangle_cdf(len(positions), fptr(positions), len(triangles), iptr(triangles), fptr(out))
+    if rc != YH_OK:
+        raise YhError(f"yhair error {rc}: yh_triangle_cdf")
+    return out
 
 
 def set_trial_cache_dir(path=None, default=False):
@@ -412,6 +431,25 @@ class Context:
         off, cnt, room = (C.c_int64 * 3)(), (C.c_int * 3)(), (C.c_int * 3)()
         self._chk(self.lib.yh_shape_nodes(self.h, index, off, cnt, room))
         return list(off), list(cnt), list(room)
+
+    # light edits (include/yhair.h: LIGHT EDITS): with the opt-in, the edits above make the light list again instead of refusing
+    def set_light_edits(self, on=True):
+        """yh_set_light_edits: emission toggles, an emitter's material on another object and vertex edits of an emitter's shape go
+        through the update / refit calls (off by default)."""
+        self._chk(self.lib.yh_set_light_edits(self.h, int(bool(on))))
+
+    def light_list(self):
+        """yh_light_list: [(object or -1, environment or -1, cdf entries, in the LDS light table)] in the kernels' order."""
+        a = [(C.c_int * 16)() for _ in range(4)]
+        n = self.lib.yh_light_list(self.h, *a, 16)
+        self._chk(min(n, 0))
+        return [(a[0][i], a[1][i], a[2][i], bool(a[3][i])) for i in range(n)]
+
+    def triangle_cdf_gpu(self, positions, triangles):
+        """yh_triangle_cdf_gpu: triangle_cdf by the kernel of the light edits (one wave, the sums one chain in element order)."""
+        positions, triangles, out = _cdf_args(positions, triangles)
+        self._chk(self.lib.yh_triangle_cdf_gpu(self.h, len(positions), fptr(positions), len(triangles), iptr(triangles), fptr(out)))
+        return out
 
     def update_environments(self, environments):
         """yh_update_environments: frame and emission of every environment (a ctypes array of Environment, or a list)."""
