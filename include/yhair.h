@@ -458,6 +458,50 @@ int yh_gather_framebuffer(yh_context** contexts, int n, float* rgba);
  * rng state words (2 x u64 per pixel) and sample count.                      */
 int yh_download_rng(yh_context* ctx, uint64_t* state_inc);
 
+/* FIRST-HIT FEATURE PASS (an extension: the reference has no counterpart). Per pixel of the image of yh_init_state, the camera
+ * ray's first intersection (intersect_scene_bvh, as yh_intersect_batch) and what the `normal` shader evaluates at it (trace_normal,
+ * yocto_pathtrace.cpp:1644-1658: eval_position, eval_normal with the normal map, the orthonormalised normal of a line and the flip of
+ * a thin material; no opacity pass-through). One plane per quantity, row-major top row first, one entry per pixel; a NULL plane is
+ * skipped with, where possible, the work behind it; at least one must be given.
+ *   plane               type     hit                                                            miss
+ *   object, element     int      the hit's object and element                                   -1
+ *   material            int      the object's material                                          -1
+ *   uv                  float2   element uv of the hit                                          0
+ *   distance            float    ray distance                                                   0
+ *   position            float3   eval_position (a strand: on its axis)                          0
+ *   normal              float3   the shading normal described above                             0
+ *   tangent             float3   eval_normal of a line hit (strand direction); 0 on triangles   0
+ *   texcoord            float2   eval_texcoord                                                  0
+ *   albedo              float3   material colour x colour texture (:411-412), hair included      0
+ *   ray                 6 float  origin, direction of the traced ray                            the same
+ * mode YH_GBUFFER_CENTRE: the pinhole ray through the pixel centre (sample_camera at uv + 0.5 with the lens point at zero whatever
+ * the aperture): guides that depend neither on depth of field nor on the render's progress. YH_GBUFFER_NEXT_SAMPLE: the ray the
+ * pixel's NEXT sample will take, drawn from a copy of its stream (nothing is written back): with the `normal` shader the next
+ * yh_trace_samples(1) adds exactly normal * 0.5 + 0.5 to a hit pixel.
+ * The pass covers the WHOLE image on every context, whatever yh_set_shard says, so a multi-GPU caller runs it on one context and needs
+ * no gather; it costs about one sample of the `normal` shader. It changes no accumulator, stream, sample count, trial record or launch
+ * shape: a render interleaved with it has the bits it has without it. Blocking; yh_last_trace_ms reports the kernel's event time.
+ * yh_trace_gbuffer takes HOST pointers, yh_trace_gbuffer_device DEVICE pointers (written on the context's own stream, nothing copied).
+ * YH_E_STATE before yh_upload_scene / yh_init_state or with an asynchronous launch pending; YH_E_INVALID for an unknown mode, a NULL
+ * `out`, no plane at all, or a scene whose trees exceed the one-lane kernels' 32-bit offsets (4 GB).                                   */
+#define YH_GBUFFER_CENTRE 0
+#define YH_GBUFFER_NEXT_SAMPLE 1
+typedef struct yh_gbuffer {
+  int*   object;
+  int*   element;
+  int*   material;
+  float* uv;
+  float* distance;
+  float* position;
+  float* normal;
+  float* tangent;
+  float* texcoord;
+  float* albedo;
+  float* ray;
+} yh_gbuffer;
+int yh_trace_gbuffer(yh_context* ctx, int mode, const yh_gbuffer* out);
+int yh_trace_gbuffer_device(yh_context* ctx, int mode, const yh_gbuffer* out);
+
 /* Work counters of the launches since the last reset (instrumented build of
  * the same kernel; 0 = ok).                                                  */
 int yh_trace_samples_counted(yh_context* ctx, int nsamples, yh_workcounts* out);

@@ -8,6 +8,7 @@
 //   trace_launch.cpp   yh_init_state (pt.cpp:1931-1946) and the launches: yh_trace_samples and friends
 //   gather.cpp         tile packing and the one collective (yh_gather_framebuffer: RCCL or peer copies)
 //   batch_api.cpp      the unit-level batch entry points (hair BSDF, intersection, BVH build, curves, self-tests)
+//   gbuffer.cpp        yh_trace_gbuffer / _device: the first-hit feature pass over the state's image (unit/gbuffer.hip)
 //   scene_edit.cpp     edits of an uploaded scene (yh_update_camera / _materials / _environments / _objects: the last one builds the
 //                      scene-level tree again; yh_update_shape / _device: one shape's tree too; yh_refit_shape / _device: that tree's boxes
 //                      only, unit/refit.hip; yh_set_light_edits: the light list again, unit/light_list.hip) and yh_download_display

@@ -648,5 +648,41 @@ inline void trace_samples(state* st, const scene* sc, const camera* cam, const t
   if (stop && *stop) return;
   download(st);
 }
+
+// EXTENSION (no reference counterpart): the first-hit feature pass over the image of `st` (include/yhair.h: yh_trace_gbuffer) — per pixel
+// what the camera ray meets first and what the `normal` shader evaluates there, for denoising guides, masks and picking. Every plane has
+// the state's size, row-major, top row first; misses hold -1 in the id planes and 0 elsewhere. Context 0 alone runs the pass, over the
+// whole image however many devices render; the state's samples and `render` are untouched.
+template <typename T>
+struct image {
+  int            width = 0, height = 0;
+  std::vector<T> pixels;
+  const T& operator[](vec2i ij) const { return pixels[(size_t)ij.y * width + ij.x]; }
+};
+struct ray6f { vec3f o, d; };
+enum struct gbuffer_mode { centre = YH_GBUFFER_CENTRE, next_sample = YH_GBUFFER_NEXT_SAMPLE };
+struct gbuffer {
+  image<int>   object, element, material;
+  image<vec2f> uv;
+  image<float> distance;
+  image<vec3f> position, normal, tangent;
+  image<vec2f> texcoord;
+  image<vec3f> albedo;
+  image<ray6f> ray;
+};
+inline gbuffer trace_gbuffer(state* st, const scene*, const camera*, const trace_params&, gbuffer_mode mode = gbuffer_mode::centre) {
+  bind_state(st);
+  gbuffer g;
+  auto    size = [&](auto& im) { im.width = st->width, im.height = st->height, im.pixels.resize((size_t)st->width * st->height); };
+  size(g.object), size(g.element), size(g.material), size(g.uv), size(g.distance), size(g.position), size(g.normal), size(g.tangent);
+  size(g.texcoord), size(g.albedo), size(g.ray);
+  static_assert(sizeof(vec2f) == 8 && sizeof(vec3f) == 12 && sizeof(ray6f) == 24, "the planes are packed floats");
+  yh_gbuffer out{g.object.pixels.data(), g.element.pixels.data(), g.material.pixels.data(), (float*)g.uv.pixels.data(),
+      g.distance.pixels.data(), (float*)g.position.pixels.data(), (float*)g.normal.pixels.data(), (float*)g.tangent.pixels.data(),
+      (float*)g.texcoord.pixels.data(), (float*)g.albedo.pixels.data(), (float*)g.ray.pixels.data()};
+  auto ctx = detail::require_context();
+  detail::check(yh_trace_gbuffer(ctx, (int)mode, &out), ctx);
+  return g;
+}
 }  // namespace yhair::pathtrace
 #endif

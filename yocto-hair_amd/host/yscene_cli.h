@@ -7,6 +7,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string>
+#include <vector>
 
 #include "yhair_pathtrace.h"
 
@@ -124,5 +125,41 @@ inline void set_devices(int first, int gpus, const std::string& list) {
   } else {
     for (int i = 0; i < (gpus < 1 ? 1 : gpus); i++) devs.push_back(first + i);
   }
+}
+
+// "--features PREFIX [--features-mode centre|next]" (an extension of both command lines): the first-hit feature pass over the state's image
+// (ptr::trace_gbuffer; context 0 alone runs it, whatever --gpus says) as four images — PREFIX.normal.hdr = normal * 0.5 + 0.5 as the `normal`
+// shader shows it, PREFIX.albedo.hdr, PREFIX.depth.hdr = the distance in all three channels, PREFIX.ids.hdr = object, element, material as
+// floats; a pixel that hits nothing is 0 in all four (RGBE holds no negative value). The ids file is a picture of the masks, not a table: RGBE
+// keeps eight bits of a pixel's largest channel, so a large element id rounds the object and material ids next to it; exact ids come from
+// the C ABI or the mirror
+inline ptr::gbuffer_mode features_mode(const std::string& name) {
+  if (name == "centre") return ptr::gbuffer_mode::centre;
+  if (name == "next") return ptr::gbuffer_mode::next_sample;
+  print_fatal("unknown features mode " + name);
+}
+inline void save_features(ptr::state* state, const ptr::scene* scene, const ptr::camera* camera, const ptr::trace_params& params, const std::string& prefix,
+    ptr::gbuffer_mode mode) {
+  const auto g = ptr::trace_gbuffer(state, scene, camera, params, mode);
+  const size_t n = (size_t)state->width * state->height;
+  std::vector<yhair::math::vec4f> img(n);
+  char error[512];
+  auto save = [&](const char* what) {
+    const std::string name = prefix + "." + what + ".hdr";
+    if (yh_save_image(name.c_str(), state->width, state->height, (const float*)img.data(), error, sizeof(error)) != YH_OK) print_fatal(error);
+    printf("save features: %s\n", name.c_str());
+  };
+  for (size_t i = 0; i < n; i++) {
+    const auto& v = g.normal.pixels[i];
+    const bool  hit = g.object.pixels[i] >= 0;
+    img[i] = hit ? yhair::math::vec4f{v.x * 0.5f + 0.5f, v.y * 0.5f + 0.5f, v.z * 0.5f + 0.5f, 1} : yhair::math::vec4f{0, 0, 0, 1};
+  }
+  save("normal");
+  for (size_t i = 0; i < n; i++) img[i] = {g.albedo.pixels[i].x, g.albedo.pixels[i].y, g.albedo.pixels[i].z, 1};
+  save("albedo");
+  for (size_t i = 0; i < n; i++) img[i] = {g.distance.pixels[i], g.distance.pixels[i], g.distance.pixels[i], 1};
+  save("depth");
+  for (size_t i = 0; i < n; i++) img[i] = {(float)g.object.pixels[i], (float)g.element.pixels[i], (float)g.material.pixels[i], 1};
+  save("ids");
 }
 #endif

@@ -6,7 +6,8 @@
 // --save-batch, --output-image,-o out.hdr, positional scene. Extensions:
 // --seed, --exact-bsdf, --device, --spp-per-launch, --timing (one "timing: {json}" line with the wall-clock of every phase: what
 // bench.py's config.end_to_end reads), --gpus N / --devices A,B,.. (tile-sharded over
-// the GPUs of one node, one RCCL gather of the float4 framebuffer at the end). Same flow: load scene -> convert through
+// the GPUs of one node, one RCCL gather of the float4 framebuffer at the end), --features PREFIX [--features-mode centre|next] (the first-hit
+// feature pass after the render: yscene_cli.h, save_features). Same flow: load scene -> convert through
 // the add_* / set_* API -> init_bvh -> init_lights -> init_state -> sample loop
 // -> save_image. Errors print and exit(1) like print_fatal
 // (yocto_commonio.h:258-261).
@@ -25,14 +26,17 @@ int main(int argc, const char* argv[]) {
   auto save_batch = false, timing = false;
   std::string camera_name, imfilename = "out.hdr", filename, shader = "path";
   int  spp_per_launch = 256, gpus = 1, first_device = 0;  // (every launch waits for its unluckiest pixel: C1 0.2375 ms per sample at 64 per launch, 0.228 at 256, 0.2226 in one launch of 1536)
-  std::string device_list;
+  std::string device_list, features, features_mode_name = "centre";
 
   auto usage = [&]() {
     printf("usage: yscenetrace [--camera NAME] [--resolution,-r N] [--samples,-s N] [--shader,-t naive|path|eyelight|normal]\n"
            "                   [--bounces,-b N] [--clamp F] [--save-batch] [--output-image,-o FILE]\n"
-           "                   [--seed N] [--exact-bsdf] [--device N] [--gpus N] [--devices A,B,..] [--spp-per-launch N] [--timing] scene\n"
+           "                   [--seed N] [--exact-bsdf] [--device N] [--gpus N] [--devices A,B,..] [--spp-per-launch N] [--timing]\n"
+           "                   [--features PREFIX] [--features-mode centre|next] scene\n"
            "Offline path tracing of hair scenes on MI355X. --gpus N: the image's 8x8 tiles are dealt round-robin to N\n"
-           "GPUs of this node (devices --device .. --device + N - 1, or --devices), one RCCL gather at the end.\n");
+           "GPUs of this node (devices --device .. --device + N - 1, or --devices), one RCCL gather at the end.\n"
+           "--features PREFIX: after the render, the first hit of every pixel as PREFIX.normal.hdr, .albedo.hdr, .depth.hdr and .ids.hdr\n"
+           "(centre: the ray through the pixel centre without depth of field; next: the ray of the pixel's next sample).\n");
   };
   for (int i = 1; i < argc; i++) {
     std::string a = argv[i];
@@ -55,6 +59,8 @@ int main(int argc, const char* argv[]) {
     else if (a == "--device") first_device = atoi(next().c_str());
     else if (a == "--gpus") gpus = std::max(1, atoi(next().c_str()));
     else if (a == "--devices") device_list = next();
+    else if (a == "--features") features = next();
+    else if (a == "--features-mode") features_mode_name = next();
     else if (a == "--spp-per-launch") spp_per_launch = std::max(1, atoi(next().c_str()));
     else if (!a.empty() && a[0] == '-') print_fatal("unknown option " + a);
     else filename = a;
@@ -66,6 +72,7 @@ int main(int argc, const char* argv[]) {
   for (size_t i = 0; i < ptr::shader_names.size(); i++)
     if (ptr::shader_names[i] == shader) params.shader = (ptr::shader_type)i, known = true;
   if (!known) print_fatal("unknown shader " + shader);
+  const auto feature_mode = features_mode(features_mode_name);
 
   try {
     char error[512];
@@ -145,6 +152,7 @@ int main(int argc, const char* argv[]) {
              "\"total_s\": %.4f, \"width\": %d, \"height\": %d, \"samples\": %d, \"gpus\": %d}\n",
           ph_load, ph_convert, ph_bvh, ph_lights, ph_state, ph_render, kernel_ms / 1e3, launches, requests, ph_download, ph_save, secs(), state->width, state->height,
           params.samples, (int)yhair::detail::devices().size());
+    if (!features.empty()) save_features(state.get(), scene.get(), camera, params, features, feature_mode);
   } catch (const std::exception& e) {
     print_fatal(e.what());
   }

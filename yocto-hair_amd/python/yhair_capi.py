@@ -86,6 +86,18 @@ class TraceParams(C.Structure):
                            1 if hair_exact else 0)
 
 
+GBUFFER_CENTRE, GBUFFER_NEXT_SAMPLE = 0, 1
+GBUFFER_MODES = {"centre": GBUFFER_CENTRE, "next": GBUFFER_NEXT_SAMPLE}
+# the planes of yh_gbuffer in the struct's order: name, numpy dtype, components per pixel
+GBUFFER_PLANES = (("object", np.int32, 1), ("element", np.int32, 1), ("material", np.int32, 1), ("uv", np.float32, 2),
+                  ("distance", np.float32, 1), ("position", np.float32, 3), ("normal", np.float32, 3), ("tangent", np.float32, 3),
+                  ("texcoord", np.float32, 2), ("albedo", np.float32, 3), ("ray", np.float32, 6))
+
+
+class GBuffer(C.Structure):
+    _fields_ = [(n, c_int_p if t is np.int32 else c_float_p) for n, t, _ in GBUFFER_PLANES]
+
+
 class WorkCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "nodes", "seg_tests", "tri_tests",
                                           "hair_shades", "surf_shades", "env_lookups",
@@ -166,6 +178,8 @@ _SIGS = {
     "yh_gather_framebuffer": (C.c_int, [C.POINTER(C.c_void_p), C.c_int, c_float_p]),
     "yh_shard_pixels": (C.c_int64, [C.c_void_p, C.c_int, C.c_int]),
     "yh_download_rng": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
+    "yh_trace_gbuffer": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(GBuffer)]),
+    "yh_trace_gbuffer_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(GBuffer)]),
     "yh_trace_samples_counted": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(WorkCounts)]),
     "yh_last_trace_ms": (C.c_int, [C.c_void_p, c_float_p, c_int_p]),
     "yh_launch_shape": (C.c_int, [C.c_void_p]),
@@ -533,6 +547,47 @@ class Context:
         rng = np.zeros((self.height * self.width, 2), np.uint64)
         self._chk(self.lib.yh_download_rng(self.h, rng.ctypes.data_as(C.POINTER(C.c_uint64))))
         return rng
+
+    # the first-hit feature pass (include/yhair.h: yh_trace_gbuffer)
+    def trace_gbuffer(self, mode=GBUFFER_CENTRE, planes=None):
+        """yh_trace_gbuffer: a dict of numpy arrays, (H, W) or (H, W, components), for the planes named in `planes` (default: all of
+        GBUFFER_PLANES). mode: GBUFFER_CENTRE / GBUFFER_NEXT_SAMPLE, or "centre" / "next"."""
+        mode = GBUFFER_MODES.get(mode, mode)
+        names = [n for n, _, _ in GBUFFER_PLANES] if planes is None else list(planes)
+        g, out = GBuffer(), {}
+        h, w = getattr(self, "height", 0), getattr(self, "width", 0)  # (before init_state: the call itself refuses)
+        for n, t, c in GBUFFER_PLANES:
+            if n in names:
+                out[n] = np.zeros((h, w) + ((c,) if c > 1 else ()), t)
+                setattr(g, n, iptr(out[n]) if t is np.int32 else fptr(out[n]))
+        if len(out) != len(names):
+            raise YhError("trace_gbuffer: unknown plane among " + ", ".join(names))
+        self._chk(self.lib.yh_trace_gbuffer(self.h, mode, C.byref(g)))
+        return out
+
+    def trace_gbuffer_device(self, mode=GBUFFER_CENTRE, **planes):
+        """yh_trace_gbuffer_device: writes the planes given by name (GBUFFER_PLANES) into contiguous torch tensors on the context's
+        device, int32 / float32 with at least height x width x components elements; nothing is copied. The current torch stream is
+        synchronised before the call, which runs on the context's own stream and returns when the planes are written."""
+        import torch
+        mode = GBUFFER_MODES.get(mode, mode)
+        kinds = {n: (t, c) for n, t, c in GBUFFER_PLANES}
+        g, device = GBuffer(), None
+        for n, t in planes.items():
+            if n not in kinds:
+                raise YhError(f"trace_gbuffer_device: unknown plane {n}")
+            if t is None:
+                continue
+            dtype = torch.int32 if kinds[n][0] is np.int32 else torch.float32
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() \
+                    or t.numel() < self.height * self.width * kinds[n][1]:
+                raise YhError(f"trace_gbuffer_device: {n} must be a contiguous {dtype} tensor on the GPU of at least "
+                              f"{self.height} x {self.width} x {kinds[n][1]} elements")
+            setattr(g, n, C.cast(t.data_ptr(), c_int_p if dtype == torch.int32 else c_float_p))
+            device = t.device
+        if device is not None:
+            torch.cuda.current_stream(device).synchronize()
+        self._chk(self.lib.yh_trace_gbuffer_device(self.h, mode, C.byref(g)))
 
     def shard_pixels(self, rank, world):
         return int(self.lib.yh_shard_pixels(self.h, rank, world))
