@@ -596,6 +596,27 @@ int yh_hair_pdf_batch(yh_context* ctx, int n, const float* brdf,
 int yh_hair_eval_pdf_batch(yh_context* ctx, int n, const float* brdf,
     const float* outgoing, const float* incoming, float* pdf);
 
+/* The hair path of a shaded hit, row by row: what the sample-loop kernels run at
+ * a hair hit (csrc/dev_path.h) — hair_setup, hair_prepare, hair_sample from
+ * that hair_out, then the fused eval + pdf, at `incoming` and at the sampled
+ * direction — on the material row that yh_upload_scene makes of `materials`
+ * (the per-lobe constants computed on the host, not on the device as the
+ * yh_hair_*_batch calls above derive them). form 0: a quad per row, as the
+ * quad kernels run it (the lobe pdfs come from lanes 2-3 of the quad, gamma_t
+ * from lane 0, lobe p is evaluated on lane p); form 1: a lane per row, as the
+ * streaming kernel runs it. exact 0: the default arithmetic of the BSDF;
+ * exact 1: the exact arithmetic (yh_trace_params::hair_exact), form 0 only —
+ * form 1 with exact 1 is YH_E_INVALID, as are a form or exact other than 0 / 1.
+ * materials: n x yh_material (only hair fields read); v: n; normal, tangent,
+ * outgoing, incoming: 3n; rn: 2n. out: YH_HAIR_SHADE_FLOATS per row = f[3] and
+ * pdf at `incoming`, the sampled direction[3], f[3] and pdf at it, the four
+ * lobe pdfs.                                                                 */
+#define YH_HAIR_SHADE_FLOATS 15
+int yh_hair_shade_batch(yh_context* ctx, int form, int exact, int n,
+    const yh_material* materials, const float* v, const float* normal,
+    const float* tangent, const float* outgoing, const float* incoming,
+    const float* rn, float* out);
+
 /* The pbrt `curve` -> hair-line conversion of the reference's pbrt loader
  * (libs/yocto/yocto_pbrt.h:1751-1797): each curve's first four control points
  * become a strand of five vertices (Bezier at u = 0, 1/4, 1/2, 3/4, 1), with

@@ -1936,6 +1936,15 @@ void yo_hair_pdf(int n, const float* brdf, const float* wo, const float* wi, flo
   for (int i = 0; i < n; i++)
     out[i] = sample_hair_scattering_pdf(mkbrdf(brdf + 30 * i), v3(wo + 3 * i), v3(wi + 3 * i));
 }
+// compute_ap_pdf (ext.cpp:365-397) as sample_hair_scattering and sample_hair_scattering_pdf call it: the four lobe pdfs, out 4n
+void yo_hair_lobe_pdfs(int n, const float* brdf, const float* wo, float* out) {
+  for (int i = 0; i < n; i++) {
+    auto b           = mkbrdf(brdf + 30 * i);
+    auto outgoing    = transform_direction(b.world_to_brdf, v3(wo + 3 * i));
+    auto cos_theta_o = safe_sqrt(1 - sqr(outgoing.x));
+    compute_ap_pdf(b, cos_theta_o, out + 4 * i);
+  }
+}
 
 // The four self-tests (ext.cpp:555-693): same seed, loop bounds (float
 // accumulating loop counters included), sample counts and thresholds.

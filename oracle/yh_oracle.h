@@ -42,6 +42,8 @@ void yo_hair_sample(
     int n, const float* brdf, const float* wo, const float* rn, float* out);
 void yo_hair_pdf(
     int n, const float* brdf, const float* wo, const float* wi, float* out);
+/* compute_ap_pdf (ext.cpp:365-397) at the outgoing direction: the four lobe pdfs, out 4n */
+void yo_hair_lobe_pdfs(int n, const float* brdf, const float* wo, float* out);
 /* ext.cpp:555-693: returns 1 = "OK!", 0 = "TEST FAILED!" */
 int yo_selftest(int which, float* worst);
 

@@ -131,6 +131,7 @@ class Oracle(_UnitApi):
         lib = C.CDLL(ORACLE_SO)
         super().__init__(lib, "yo_")
         lib.yo_selftest.argtypes = [C.c_int, fp]
+        lib.yo_hair_lobe_pdfs.argtypes = [C.c_int, fp, fp, fp]
         lib.yo_surface_bsdf.argtypes = [C.c_int, C.POINTER(yh.Material), fp, fp, fp, fp, fp]
         lib.yo_scene_create.restype = C.c_void_p
         lib.yo_scene_create.argtypes = [C.POINTER(yh.SceneDesc)]
@@ -148,6 +149,13 @@ class Oracle(_UnitApi):
         worst = C.c_float()
         ok = self.lib.yo_selftest(which, C.byref(worst))
         return bool(ok), worst.value
+
+    def hair_lobe_pdfs(self, brdf, wo):
+        """compute_ap_pdf (ext.cpp:365-397) at the outgoing direction: (n, 4)."""
+        brdf, wo = _f(brdf), _f(wo)
+        out = np.zeros((len(brdf), 4), np.float32)
+        self.lib.yo_hair_lobe_pdfs(len(brdf), yh.fptr(brdf), yh.fptr(wo), yh.fptr(out))
+        return out
 
     def surface_bsdf(self, materials, normal, wo, wi, rn3):
         """eval_brdf + lobe dispatch (pt.cpp:405-471,1069-1280): (n, YH_SURFACE_BSDF_FLOATS)."""

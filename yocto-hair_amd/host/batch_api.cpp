@@ -70,6 +70,32 @@ int yh_hair_eval_pdf_batch(yh_context* ctx, int n, const float* brdf, const floa
   return yh_hair_pdf_batch(ctx, n, brdf, wo, wi, pdf);
 }
 
+// The hair path of a shaded hit (dev_path.h: hair_setup, hair_prepare, hair_sample, the fused eval + pdf) on the material rows the upload
+// makes: make_material is the upload's own code (scene_upload.cpp), so the kernels read what a render reads.
+int yh_hair_shade_batch(yh_context* ctx, int form, int exact, int n, const yh_material* materials, const float* v, const float* normal,
+    const float* tangent, const float* outgoing, const float* incoming, const float* rn, float* out) {
+  if (!ctx || n < 0 || (form != 0 && form != 1) || (exact != 0 && exact != 1) || (exact && form != 0) ||
+      (n && (!materials || !v || !normal || !tangent || !outgoing || !incoming || !rn || !out)))
+    return YH_E_INVALID;
+  if (n == 0) return YH_OK;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::vector<yhd_material> mats((size_t)n);
+  for (int i = 0; i < n; i++) make_material(materials[i], mats[(size_t)i]);
+  Staged s(ctx);
+  auto   dm = s.in(mats.data(), sizeof(yhd_material) * (size_t)n);
+  auto   dv = (float*)s.in(v, 4 * (size_t)n);
+  auto   dn = (float*)s.in(normal, 12 * (size_t)n);
+  auto   dt = (float*)s.in(tangent, 12 * (size_t)n);
+  auto   da = (float*)s.in(outgoing, 12 * (size_t)n);
+  auto   db = (float*)s.in(incoming, 12 * (size_t)n);
+  auto   dr = (float*)s.in(rn, 8 * (size_t)n);
+  auto   o  = (float*)s.out(4 * YH_HAIR_SHADE_FLOATS * (size_t)n);
+  if (s.rc) return s.rc;
+  int e = exact ? yhk_hair_shade_exact(form, n, dm, dv, dn, dt, da, db, dr, o, ctx->stream)
+                : yhk_hair_shade(form, n, dm, dv, dn, dt, da, db, dr, o, ctx->stream);
+  return finish(ctx, e, out, o, 4 * YH_HAIR_SHADE_FLOATS * (size_t)n);
+}
+
 int yh_curves_to_lines(yh_context* ctx, int n, const float* P, const float* width0, const float* width1,
     int base_vertex, float* positions, float* normals, float* radius, int* lines) {
   if (!ctx || n < 0 || (n && (!P || !width0 || !width1 || !positions || !normals || !radius || !lines))) return YH_E_INVALID;

@@ -88,6 +88,11 @@ int yhk_lights(const yhd_scene*, int, const float*, const float*, const float*, 
 int yhk_intersect_plain(const yhd_scene*, int form, int, const float*, int*, int*, float*, float*, hipStream_t);  // unit/intersect_quad.hip
 int yhk_lights_lanes(const yhd_scene* sc, const yhd_scene* sc_dev, int n, const float* position, const float* direction, const float* rn,
     unsigned int* stack_ovf, int ovf_entries, float* out, hipStream_t stream);
+// unit/hair_shade.hip, unit/hair_shade_exact.hip (yh_hair_shade_batch): mats = n rows of yhd_material; form 0 a quad per row, 1 a lane per row (fast only)
+int yhk_hair_shade(int form, int n, const void* mats, const float* v, const float* normal, const float* tangent, const float* outgoing, const float* incoming,
+    const float* rn, float* out, hipStream_t);
+int yhk_hair_shade_exact(int form, int n, const void* mats, const float* v, const float* normal, const float* tangent, const float* outgoing,
+    const float* incoming, const float* rn, float* out, hipStream_t);
 int yhk_selftest(int, float, float, uint64_t, uint64_t, int, const float*, double*, unsigned int*, hipStream_t);
 int yhk_display(const yhd_state*, int samples, float exposure, int filmic, int srgb, void* rgba8, hipStream_t);  // unit/display.hip
 // unit/objects.hip (yh_update_objects): a lane per row of `rows` (yh_object, device memory); root6 = per shape its root box, 6 floats; writes

@@ -15,6 +15,7 @@ LIB_PATH = os.environ.get("YHAIR_LIB", os.path.join(ROOT, "yocto-hair_amd", "lib
 
 YH_OK, YH_E_INVALID, YH_E_DEVICE, YH_E_STATE, YH_E_IO, YH_E_SELFTEST = 0, -1, -2, -3, -4, -5
 YH_HAIR_BRDF_FLOATS = 30
+HAIR_SHADE_FLOATS = 15
 SURFACE_BSDF_FLOATS = 29
 (LOBE_DIFFUSE, LOBE_SPECULAR, LOBE_METAL, LOBE_TRANSMISSION, LOBE_REFRACTION, LOBE_DELTA_SPECULAR,
  LOBE_DELTA_METAL, LOBE_DELTA_TRANSMISSION, LOBE_DELTA_REFRACTION) = range(9)
@@ -207,6 +208,8 @@ _SIGS = {
     "yh_hair_sample_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),
     "yh_hair_pdf_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),
     "yh_hair_eval_pdf_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),
+    "yh_hair_shade_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Material), c_float_p, c_float_p, c_float_p,
+                                      c_float_p, c_float_p, c_float_p, c_float_p]),
     "yh_intersect_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_int_p, c_int_p, c_float_p, c_float_p]),
     "yh_intersect_plain_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, c_int_p, c_int_p, c_float_p, c_float_p]),
     "yh_scene_once": (C.c_int, [C.c_void_p]),
@@ -629,6 +632,19 @@ class Context:
 
     def hair_pdf(self, brdf, wo, wi):
         return self._wowi(self.lib.yh_hair_pdf_batch, brdf, wo, wi, 1)
+
+    def hair_shade(self, form, exact, materials, v, normal, tangent, wo, wi, rn2):
+        """yh_hair_shade_batch: the hair path of a shaded hit on the upload's material rows (form 0: a quad per row, 1: a lane per
+        row; exact: the exact arithmetic, form 0 only). materials: (n, 12) rows as for hair_brdf, or the ctypes array
+        hair_material_rows makes of them. (n, HAIR_SHADE_FLOATS) = f [3], pdf at wi, the sampled direction [3], f [3], pdf at
+        it, the four lobe pdfs."""
+        mats = materials if isinstance(materials, C.Array) else hair_material_rows(materials)
+        a = [np.ascontiguousarray(x, np.float32) for x in (v, normal, tangent, wo, wi, rn2)]
+        n = len(mats)
+        assert all(len(x) == n for x in a)
+        out = np.zeros((n, HAIR_SHADE_FLOATS), np.float32)
+        self._chk(self.lib.yh_hair_shade_batch(self.h, form, int(exact), n, mats, *(fptr(x) for x in a), fptr(out)))
+        return out
 
     def curves_to_lines(self, P, width0, width1, base_vertex=0):
         """pbrt curves (n, 12) -> positions (5n, 3), tangents (5n, 3), radius (5n), lines (4n, 2)."""
