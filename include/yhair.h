@@ -697,6 +697,20 @@ int yh_intersect_plain_batch(yh_context* ctx, int form, int n, const float* rays
  * node: at most four objects): the number of objects, else 0; YH_E_STATE
  * before yh_upload_scene.                                                    */
 int yh_scene_once(const yh_context* ctx);
+/* 1 when the uploaded scene is plain, none of its environments has a texture
+ * and every light is an environment: light sampling, the light pdf and the
+ * environment lookup of the plain 512-thread kernels (launch shapes 0 and 5)
+ * then take the counts and the emissions from the kernel argument and fetch
+ * nothing; else 0. Follows every edit, as yh_scene_once. YH_E_STATE before
+ * yh_upload_scene.                                                          */
+int yh_lights_const_env(const yh_context* ctx);
+/* Developer diagnostics: the shading pass of the last yh_trace_samples_counted
+ * by REGION of a wave iteration, three numbers per region — the waves' cycles
+ * in it, the trips that ran it, the lanes it ran with — in the order loop head
+ * (path regeneration; outside cyc_shade), miss, fetch (rows, record, normals),
+ * hair set-up, sampling branch, BSDF value and pdf, lights pdf, weight and
+ * continuation, path end. Writes min(capacity, 27) numbers, returns 27.     */
+int yh_shade_regions(const yh_context* ctx, uint64_t* out, int capacity);
 
 /* The light code on the uploaded scene, row by row: sample_lights and
  * sample_lights_pdf (yocto_pathtrace.cpp:1283-1358) and eval_environment

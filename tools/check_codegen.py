@@ -139,13 +139,13 @@ def kernels(src):
 
 if __name__ == "__main__":
     bad = 0
-    for src, pat in (("kernels.hip", r"k_traceILb0ELb[01]E"), ("wide.hip", r"k_trace_sbsILb[01]E"), ("exact.hip", r"k_trace_exact"), ("stream.hip", r"k_streamILb[01]ELi\dELb0")):
+    for src, pat in (("kernels.hip", r"k_traceILb0ELb[01]E|k_trace_cenvILb0E"), ("wide.hip", r"k_trace_sbsILb[01]E|k_trace_sbs_cenvILb[01]E"), ("exact.hip", r"k_trace_exact"), ("stream.hip", r"k_streamILb[01]ELi\dELb0")):
         ks = kernels(src)
         funcs = ks.pop("__functions__", {})
         for name, k in sorted(ks.items()):
             if not re.search(pat, name):
                 continue
-            product = ("k_traceILb0ELb0" in name or "k_trace_sbsILb0" in name or "k_streamILb0" in name or "k_trace_exactILb0" in name)  # the plain variants every BASELINE config runs
+            product = ("k_traceILb0ELb0" in name or "k_trace_sbsILb0" in name or "k_trace_cenvILb0" in name or "k_trace_sbs_cenv" in name or "k_streamILb0" in name or "k_trace_exactILb0" in name)  # the plain variants every BASELINE config runs
             print(f"{name[:64]:64s} vgprs {k['vgprs']:3d} spilled {k['vgpr_spills']:3d} (sgpr {k['sgpr_spills']:3d}) scratch {k['scratch_bytes']:4d} B")
             for h, r in k["trav"].items():
                 flag = ""

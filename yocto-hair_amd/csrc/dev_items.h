@@ -39,7 +39,9 @@ using namespace yhd;
 // except in k_trace_sbs, where two lists share one launch).
 // ONCE (dev_trace.h: trace_ray_loop): the scene level resolved once per ray ahead of the traversal loop, for a scene whose scene
 // level is one leaf node (yhd_scene::scene_once, set at upload): the host selects these variants, nothing in the loop asks.
-template <bool COUNT, bool GENERAL, int BLOCK, int SHADER, int MODE = YH_MODE_QUAD, bool ONCE = false>
+// TRIM, CENV (dev_path.h: path_step): the trimmed shading pass of the plain 512-thread kernels, and its form for a scene whose lights are
+// constant environments (yhd_scene::lights_const_env): as ONCE, the host selects, nothing in the loop asks.
+template <bool COUNT, bool GENERAL, int BLOCK, int SHADER, int MODE = YH_MODE_QUAD, bool ONCE = false, bool TRIM = false, bool CENV = false>
 YH_DEV void trace_items(const yhd_scene& sc, const yhd_state& st, int nsamples, yhd_counters* counters, unsigned int block = blockIdx.x,
     unsigned int blocks = gridDim.x) {
   constexpr int LPP    = YH_IS_HEX(MODE) ? 16 : YH_IS_OCT(MODE) ? 8 : 4;  // lanes per path
@@ -58,8 +60,15 @@ YH_DEV void trace_items(const yhd_scene& sc, const yhd_state& st, int nsamples, 
 
   tc.lds_stack = lds_stack + (threadIdx.x / LPP);
   tc.lds_once  = ONCE ? lds_tabs + YHD_LDS_TABLES_F4(&sc) + (threadIdx.x / LPP) : nullptr;
+  const_env_t ce;
+  if constexpr (CENV) const_environments(sc, ce);
   stats_t stats = {};
   tc.stats = COUNT ? &stats : nullptr;
+  if constexpr (COUNT) {  // the regions of the shading pass: sums per wave in LDS (static, in front of the dynamic carve-out; the instrumented build only)
+    __shared__ unsigned long long region_sums[(BLOCK / 64) * 3 * YH_REGIONS];
+    stats.r = region_sums + (threadIdx.x >> 6) * 3 * YH_REGIONS;
+    if ((threadIdx.x & 63) < 3 * YH_REGIONS) stats.r[threadIdx.x & 63] = 0;
+  }
 
   const int lane = threadIdx.x & 63;
   // The FIRST item of a wave is the list entry at the wave's own position (workgroup x waves per workgroup + wave), the
@@ -100,14 +109,26 @@ YH_DEV void trace_items(const yhd_scene& sc, const yhd_state& st, int nsamples, 
     unsigned long long cyc_trace = 0, cyc_shade = 0;
     unsigned int       w_iters = 0, w_steps = 0, l_steps = 0, l_iters = 0;
     while (true) {
+      YH_REGION_MARK("regen");
       if (!alive && left > 0) {
+        if (COUNT) stats.from = clock64();
         yhd_camera cam;
-        for (int k = 0; k < 12; k++) cam.frame[k] = lds_cam[k];
-        cam.lens = lds_cam[12], cam.film_x = lds_cam[13], cam.film_y = lds_cam[14], cam.focus = lds_cam[15], cam.aperture = lds_cam[16];
+        if constexpr (TRIM) {  // the camera's 17 floats as five 16-byte reads (its place in the tables is a float4 boundary, dev_trace.h: stage_tables)
+          const YH_LDS v4f* c4 = (const YH_LDS v4f*)lds_cam;
+          const v4f a = c4[0], b = c4[1], c = c4[2], d = c4[3];
+          cam.frame[0] = a.x, cam.frame[1] = a.y, cam.frame[2] = a.z, cam.frame[3] = a.w, cam.frame[4] = b.x, cam.frame[5] = b.y;
+          cam.frame[6] = b.z, cam.frame[7] = b.w, cam.frame[8] = c.x, cam.frame[9] = c.y, cam.frame[10] = c.z, cam.frame[11] = c.w;
+          cam.lens = d.x, cam.film_x = d.y, cam.film_y = d.z, cam.focus = d.w, cam.aperture = lds_cam[16];
+        } else {
+          for (int k = 0; k < 12; k++) cam.frame[k] = lds_cam[k];
+          cam.lens = lds_cam[12], cam.film_x = lds_cam[13], cam.film_y = lds_cam[14], cam.focus = lds_cam[15], cam.aperture = lds_cam[16];
+        }
         path_begin(cam, ps, rng, i, j, st.width, st.height);
         left--;
         alive = true;
+        count_region<COUNT>(tc.stats, YH_REGION_REGEN, stats.from);
       }
+      YH_REGION_MARK("trace");
       if (!__any(alive)) break;
       unsigned long long c0 = 0, c1 = 0;
       unsigned int       steps = 0;
@@ -123,14 +144,20 @@ YH_DEV void trace_items(const yhd_scene& sc, const yhd_state& st, int nsamples, 
         for (int off = 32; off > 0; off >>= 1) smax = max(smax, (unsigned int)__shfl_xor((int)smax, off, 64));
         w_steps += smax, l_steps += (lane & 3) == 0 ? steps : 0;
       }
+      YH_REGION_MARK("shade_head");
       if (alive) {
-        if constexpr (SHADER == YH_SHADER_PATH) alive = path_step<COUNT, GROUPS, GENERAL>(tc, ps, isec, rng, st.bounces);
+        if constexpr (CENV) alive = path_step<COUNT, GROUPS, GENERAL, TRIM, CENV>(tc, ps, isec, rng, st.bounces, &ce);
+        else if constexpr (SHADER == YH_SHADER_PATH) alive = path_step<COUNT, GROUPS, GENERAL, TRIM>(tc, ps, isec, rng, st.bounces);
         else alive = shade_step<COUNT, GROUPS, SHADER>(tc, ps, isec, rng, st.bounces);
         if (!alive) {
+          YH_REGION_MARK("end");
+          if (COUNT) stats.from = clock64();
           path_end(ps, st.clamp, acc);
           if (COUNT) count_quad<COUNT>(stats.samples);
+          count_region<COUNT>(tc.stats, YH_REGION_END, stats.from);
         }
       }
+      YH_REGION_MARK("loop_tail");
       if (COUNT) cyc_shade += clock64() - c1;
     }
     if (COUNT) {  // flush this item's counters: one wave reduction, one atomic per counter
@@ -160,7 +187,10 @@ YH_DEV void trace_items(const yhd_scene& sc, const yhd_state& st, int nsamples, 
           if (lane == 0) atomicAdd(&counters->branch[k], (unsigned long long)b[k]);
         }
       }
+      unsigned long long* sums = stats.r;
+      if (lane < 3 * YH_REGIONS) atomicAdd(&counters->region[lane], sums[lane]), sums[lane] = 0;
       stats = stats_t{};
+      stats.r = sums;
     }
     if (owner && (lane & (LPP - 1)) == 0) {
       st.rng_state[pix] = rng.state;
@@ -184,7 +214,13 @@ template <bool COUNT, bool GENERAL, int BLOCK, int WAVES, int MODE = YH_MODE_QUA
 __global__ __launch_bounds__(BLOCK, WAVES) void k_trace(const yhd_scene sc, const yhd_state st,
     int nsamples, yhd_counters* counters) {
   static_assert(!ONCE || !GENERAL, "the prologue form exists for the plain variants");
-  trace_items<COUNT, GENERAL, BLOCK, YH_SHADER_PATH, MODE, ONCE>(sc, st, nsamples, counters);
+  constexpr bool TRIM = !GENERAL && BLOCK == YH_BLOCK && MODE == YH_MODE_QUAD;  // launch shape 0 on a plain scene
+  trace_items<COUNT, GENERAL, BLOCK, YH_SHADER_PATH, MODE, ONCE, TRIM>(sc, st, nsamples, counters);
+}
+// launch shape 0 on a plain scene whose lights are constant environments (yhd_scene::lights_const_env)
+template <bool COUNT, bool ONCE>
+__global__ __launch_bounds__(YH_BLOCK, YH_MIN_WAVES) void k_trace_cenv(const yhd_scene sc, const yhd_state st, int nsamples, yhd_counters* counters) {
+  trace_items<COUNT, false, YH_BLOCK, YH_SHADER_PATH, YH_MODE_QUAD, ONCE, true, true>(sc, st, nsamples, counters);
 }
 // SIDE BY SIDE in one launch (launch shape 5): the first `oct_blocks` workgroups run the octet form over the second part of
 // the work list (`oct_entries` half-quadrant entries behind the `quad_items` quad entries, its own cursor), the others the
@@ -197,11 +233,25 @@ __global__ __launch_bounds__(YH_BLOCK, YH_MIN_WAVES) void k_trace_sbs(const yhd_
   if ((int)blockIdx.x < oct_blocks) {
     yhd_state so   = st;
     so.tiles       = st.tiles + quad_items, so.num_tiles = oct_entries, so.tile_cursor = st.tile_cursor + 16;
-    trace_items<false, GENERAL, YH_BLOCK, YH_SHADER_PATH, YH_MODE_OCT, ONCE>(sc, so, nsamples, nullptr, blockIdx.x, (unsigned)oct_blocks);
+    trace_items<false, GENERAL, YH_BLOCK, YH_SHADER_PATH, YH_MODE_OCT, ONCE, !GENERAL>(sc, so, nsamples, nullptr, blockIdx.x, (unsigned)oct_blocks);
   } else {
     yhd_state sq = st;
     sq.num_tiles = quad_items;
-    trace_items<false, GENERAL, YH_BLOCK, YH_SHADER_PATH, YH_MODE_QUAD, ONCE>(sc, sq, nsamples, nullptr, blockIdx.x - (unsigned)oct_blocks, gridDim.x - (unsigned)oct_blocks);
+    trace_items<false, GENERAL, YH_BLOCK, YH_SHADER_PATH, YH_MODE_QUAD, ONCE, !GENERAL>(sc, sq, nsamples, nullptr, blockIdx.x - (unsigned)oct_blocks, gridDim.x - (unsigned)oct_blocks);
+  }
+}
+// the same on a plain scene whose lights are constant environments (yhd_scene::lights_const_env)
+template <bool ONCE>
+__global__ __launch_bounds__(YH_BLOCK, YH_MIN_WAVES) void k_trace_sbs_cenv(const yhd_scene sc, const yhd_state st, int nsamples, int oct_blocks,
+    int quad_items, int oct_entries) {
+  if ((int)blockIdx.x < oct_blocks) {
+    yhd_state so   = st;
+    so.tiles       = st.tiles + quad_items, so.num_tiles = oct_entries, so.tile_cursor = st.tile_cursor + 16;
+    trace_items<false, false, YH_BLOCK, YH_SHADER_PATH, YH_MODE_OCT, ONCE, true, true>(sc, so, nsamples, nullptr, blockIdx.x, (unsigned)oct_blocks);
+  } else {
+    yhd_state sq = st;
+    sq.num_tiles = quad_items;
+    trace_items<false, false, YH_BLOCK, YH_SHADER_PATH, YH_MODE_QUAD, ONCE, true, true>(sc, sq, nsamples, nullptr, blockIdx.x - (unsigned)oct_blocks, gridDim.x - (unsigned)oct_blocks);
   }
 }
 #endif

@@ -115,6 +115,42 @@ YH_DEV hit_geom eval_hit(const yhd_scene& sc, const yhd_object& o, int slot, flo
   return g;
 }
 
+// The same for the 512-thread plain kernels (path_step, TRIM), where a wave often holds a hair hit and a triangle hit at once: the two
+// branches above then wait for their loads one after the other. Here the record's address and length follow from the object row before
+// any branch, every row is fetched first — four rows whatever the kind (a segment's record has four), a triangle's fifth and sixth under
+// its own mask — and the wave waits once. The arithmetic is eval_hit's, operation for operation.
+YH_DEV hit_geom eval_hit_fetch_first(const yhd_scene& sc, const yhd_object& o, int slot, float u, float v) {
+  const bool        tri = o.kind == YH_KIND_TRIANGLES;
+  const yhd_float4* rec = sc.prims + (size_t)o.prim_base + (size_t)slot * (tri ? 6 : 4);
+  const v4f r0 = ldg4(rec), r1 = ldg4(rec + 1), r2 = ldg4(rec + 2), r3 = ldg4(rec + 3);
+  v4f       r4 = r3, r5 = r3;
+  if (tri) r4 = ldg4(rec + 4), r5 = ldg4(rec + 5);
+  frame    fr = ldframe(o.frame);
+  hit_geom g;
+  if (tri) {
+    f3 p0 = xyz(r0), p1 = xyz(r1), p2 = xyz(r2);
+    g.position       = transform_point(fr, p0 * (1 - u - v) + p1 * u + p2 * v);
+    g.element_normal = quad_transform_normal(fr, quad_normalize(cross(p1 - p0, p2 - p0)));
+    if (o.has_normals) {
+      f3 n0 = xyz(r3), n1 = xyz(r4), n2 = xyz(r5);
+      g.normal = quad_transform_normal(fr, quad_normalize(n0 * (1 - u - v) + n1 * u + n2 * v));
+    } else {
+      g.normal = g.element_normal;
+    }
+  } else {
+    f3 p0 = xyz(r0), p1 = xyz(r1);
+    g.position       = transform_point(fr, p0 * (1 - u) + p1 * u);
+    g.element_normal = quad_transform_normal(fr, quad_normalize(p1 - p0));
+    if (o.has_normals) {
+      f3 n0 = xyz(r2), n1 = xyz(r3);
+      g.normal = quad_transform_normal(fr, quad_normalize(n0 * (1 - u) + n1 * u));
+    } else {
+      g.normal = g.element_normal;
+    }
+  }
+  return g;
+}
+
 // texture lookup of an environment (pt.cpp:167-200), wrap + bilinear
 YH_DEV f3 eval_env_texture(const yhd_scene& sc, const yhd_environment& env, float u_, float v_) {
   if (env.tex_w == 0) return mk3(1.0f);
@@ -132,10 +168,18 @@ YH_DEV f3 eval_env_texture(const yhd_scene& sc, const yhd_environment& env, floa
   return a * (1 - u) * (1 - v) + b * (1 - u) * v + c * u * (1 - v) + d * u * v;
 }
 // eval_environment (pt.cpp:536-547)
-template <bool COUNT>
-YH_DEV f3 eval_environment(const trace_ctx& tc, f3 dir) {
+// CENV (yhd_scene::lights_const_env, the host selects the variant): no environment of the scene has a texture and every light is one of
+// them. The lookup, the light sampling and the light pdf below then need the counts and the emissions only, which are kernel arguments:
+// the same operations in the same order, none of the code of the other kinds of light.
+template <bool COUNT, bool CENV = false>
+YH_DEV f3 eval_environment(const trace_ctx& tc, f3 dir, const const_env_t* ce = nullptr) {
   const yhd_scene& sc = *tc.sc;
   f3 emission = mk3(0.0f);
+  if constexpr (CENV) {  // the sum below, taken once per wave (const_environments): a read of the kernel argument per miss is a memory access on the chain
+    if (COUNT)
+      for (int k = 0; k < sc.num_environments; k++) count_quad<COUNT>(tc.stats->envl);
+    return ld3(ce->env_sum);
+  }
   for (int k = 0; k < sc.num_environments; k++) {
     const yhd_environment& env = sc.environments[k];
     if (COUNT) count_quad<COUNT>(tc.stats->envl);
@@ -150,6 +194,20 @@ YH_DEV f3 eval_environment(const trace_ctx& tc, f3 dir) {
     emission = emission + ld3(env.emission) * eval_env_texture(sc, env, tx, ty);
   }
   return emission;
+}
+
+// CENV: eval_environment's sum and sample_lights_pdf's value for a scene whose lights are constant environments, operation for operation
+// what the loops of those two functions compute — `emission + ld3(env.emission) * {1,1,1}` per environment in order; `pdf += 1 / (4 pi)`
+// per light in order, then `* 1 / n` — made wave-uniform (scalar registers). Once per wave, ahead of the sample loop.
+YH_DEV void const_environments(const yhd_scene& sc, const_env_t& ce) {
+  f3 emission = mk3(0.0f);
+  for (int k = 0; k < sc.num_environments; k++) emission = emission + ld3(sc.environments[k].emission) * mk3(1.0f);
+  float pdf = 0.0f;
+  for (int k = 0; k < sc.num_lights; k++) pdf += 1 / (4 * pif);
+  pdf *= (float)1 / (float)sc.num_lights;
+  auto uniform = [](float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); };
+  ce.env_sum[0] = uniform(emission.x), ce.env_sum[1] = uniform(emission.y), ce.env_sum[2] = uniform(emission.z);
+  ce.lights_pdf = uniform(pdf);
 }
 
 // std::upper_bound (math.h:4960): first index in [lo, lo + len) whose entry is greater than r, lo + len if none
@@ -221,10 +279,16 @@ YH_DEV bool small_light_hit(const YH_LDS v4f* L, const frame& inv, f3 ro, f3 rd,
 // BIG_LIGHTS = false: every area light of the scene is a small one with its record in LDS (the host says so:
 // yhd_scene::general_materials is set otherwise), and the code that samples / intersects a light through memory —
 // with a whole traversal loop inlined into the shading code — is not compiled in.
-template <bool COUNT, bool BIG_LIGHTS>
+template <bool COUNT, bool BIG_LIGHTS, bool CENV = false>
 YH_DEV f3 sample_lights(const trace_ctx& tc, f3 position, float rl, float rel, float ruvx,
     float ruvy) {
   const yhd_scene& sc = *tc.sc;
+  if constexpr (CENV) {  // whichever light rl picks is a constant environment: sample_sphere (math.h:4847-4852)
+    float z   = 2 * ruvy - 1;
+    float r   = sqrtf(fclamp(1 - z * z, 0.0f, 1.0f));
+    float phi = 2 * pif * ruvx;
+    return f3{r * cosf(phi), r * sinf(phi), z};
+  }
   int n        = sc.num_lights;
   int light_id = iclamp((int)(rl * n), 0, n - 1);
   const yhd_light& light = sc.lights[light_id];
@@ -270,10 +334,11 @@ YH_DEV f3 sample_lights(const trace_ctx& tc, f3 position, float rl, float rel, f
 }
 
 // sample_lights_pdf (pt.cpp:1311-1358)
-template <bool COUNT, int STRIDE, bool BIG_LIGHTS>
-YH_DEV float sample_lights_pdf(const trace_ctx& tc, f3 position, f3 direction) {
+template <bool COUNT, int STRIDE, bool BIG_LIGHTS, bool CENV = false>
+YH_DEV float sample_lights_pdf(const trace_ctx& tc, f3 position, f3 direction, const const_env_t* ce = nullptr) {
   const yhd_scene& sc = *tc.sc;
   float pdf = 0.0f;
+  if constexpr (CENV) return ce->lights_pdf;  // (const_environments)
   for (int k = 0; k < sc.num_lights; k++) {
     const yhd_light& light = sc.lights[k];
     if (light.object >= 0 && (!BIG_LIGHTS || (light.small_base >= 0 && tc.lds_lights))) {  // a small light: no memory access
@@ -522,8 +587,13 @@ YH_DEV void medium_crossing(const yhd_scene& sc, path_t& ps, const yhd_material&
 // closest hit of ps.ray. Returns true when the path continues with the new
 // ps.ray, false when it ended (miss, zero / non-finite weight, Russian
 // roulette or the bounce limit).
-template <bool COUNT, int STRIDE, bool GENERAL>
-YH_DEV bool path_step(const trace_ctx& tc, path_t& ps, const hit_t& isec, rng_t& rng, int bounces) {
+// TRIM: the 512-thread plain kernels (launch shape 0 and both halves of k_trace_sbs), whose launch is as long as the sample chain of its
+// most expensive items: the hit's record fetched in one round trip (eval_hit_fetch_first) and the remaining divisions by a common
+// denominator spread over the quad (dev_math.h: quad_div). CENV: eval_environment above. Both render the bits of the other form.
+template <bool COUNT, int STRIDE, bool GENERAL, bool TRIM = false, bool CENV = false>
+YH_DEV bool path_step(const trace_ctx& tc, path_t& ps, const hit_t& isec, rng_t& rng, int bounces, const const_env_t* ce = nullptr) {
+  static_assert(!TRIM || (!GENERAL && !YH_LANE), "the trimmed shading pass exists for the plain quad kernels");
+  static_assert(!CENV || TRIM, "the constant-environment form exists for the trimmed kernels");
   const yhd_scene& sc = *tc.sc;
   unsigned long long k0 = 0, k1 = 0, k2 = 0, k3 = 0;
   if (COUNT) k0 = clock64();
@@ -531,11 +601,18 @@ YH_DEV bool path_step(const trace_ctx& tc, path_t& ps, const hit_t& isec, rng_t&
   if (isec.object < 0) return false;  // (k_stream's shading stages take hits only: a ray that missed goes to its finish stage, which looks the environment up)
 #else
   if (isec.object < 0) {
-    ps.radiance = ps.radiance + ps.weight * eval_environment<COUNT>(tc, ps.ray.d);
+    YH_REGION_MARK("miss");
+    unsigned long long km = 0;
+    if (COUNT) km = clock64();
+    ps.radiance = ps.radiance + ps.weight * eval_environment<COUNT, CENV>(tc, ps.ray.d, ce);
     if (COUNT) tc.stats->c_rest += clock64() - k0;
+    count_region<COUNT>(tc.stats, YH_REGION_MISS, km);
     return false;
   }
 #endif
+  unsigned long long kr = 0;  // COUNT: the wave-level stamps of the regions the lanes with a hit run through together
+  if (COUNT) kr = clock64();
+  YH_REGION_MARK("fetch");
   f3 outgoing = -ps.ray.d;
   if (GENERAL && ps.in_medium) {
 #if YH_LANE
@@ -582,10 +659,12 @@ YH_DEV bool path_step(const trace_ctx& tc, path_t& ps, const hit_t& isec, rng_t&
   // starts with ONE dependent fetch (the leaf record) instead of object -> record and object -> material chains.
   // (not in the 256-thread k_trace shape, STRIDE 64 quads: there the LDS form happens to put spill reloads into
   // the traversal loop, 0.8x on C2 / C4 — tools/check_codegen.py watches for that; k_stream is YH_LANE)
-  constexpr bool from_lds = !GENERAL && (YH_LANE || STRIDE != 64);
+  constexpr bool from_lds = (!GENERAL && (YH_LANE || STRIDE != 64)) || TRIM;
   const yhd_object&   o   = !from_lds ? sc.objects[isec.object] : *(const yhd_object*)(const YH_LDS yhd_object*)(tc.lds_scene + YH_OBJECT_F4 * isec.object);
   const yhd_material& mat = !from_lds ? sc.materials[o.material] : *(const yhd_material*)(const YH_LDS yhd_material*)(tc.lds_mats + YH_MATERIAL_F4 * o.material);
-  hit_geom hg = eval_hit(sc, o, isec.slot, isec.u, isec.v);
+  hit_geom hg;
+  if constexpr (TRIM) hg = eval_hit_fetch_first(sc, o, isec.slot, isec.u, isec.v);
+  else hg = eval_hit(sc, o, isec.slot, isec.u, isec.v);
   f3 position = hg.position;
   f3 nrm      = hg.normal;
   hit_maps hm;  // scalar and normal maps (GENERAL only: a material with maps is never plain)
@@ -637,12 +716,16 @@ YH_DEV bool path_step(const trace_ctx& tc, path_t& ps, const hit_t& isec, rng_t&
     if (COUNT) tc.stats->c_rest += clock64() - k0;
     return path_continue(ps, rng, bounces);
   }
+  count_region<COUNT>(tc.stats, YH_REGION_FETCH, kr);
+  YH_REGION_MARK("hair");
   hair_hit hh;
   hair_out ho;
   if (is_hair) {
     hh = hair_setup<!YH_LANE>(isec.v, normal, nrm);  // tangent = eval_normal (pt.cpp:487)
     ho = hair_prepare<!YH_LANE>(mat, hh, outgoing);  // shared by sample / eval / pdf
   }
+  count_region<COUNT>(tc.stats, YH_REGION_HAIR, kr, is_hair);
+  YH_REGION_MARK("sample");
 
   if (COUNT) k1 = clock64(), tc.stats->c_geom += k1 - k0;
   f3 incoming;
@@ -656,16 +739,18 @@ YH_DEV bool path_step(const trace_ctx& tc, path_t& ps, const hit_t& isec, rng_t&
     } else {  // sample_brdfcos (pt.cpp:1139-1174): only the diffuse lobe
       incoming = mk3(0.0f);
       if (mat.diffuse_pdf != 0 && rnl < 0.0f + mat.diffuse_pdf) {
-        if (!(dot(normal, outgoing) <= 0)) incoming = sample_hemisphere_cos(normal, rnx, rny);
+        if (!(dot(normal, outgoing) <= 0)) incoming = TRIM ? sample_hemisphere_cos_quad(normal, rnx, rny) : sample_hemisphere_cos(normal, rnx, rny);
       }
     }
   } else {
     float ruvx = rand1f(rng), ruvy = rand1f(rng);
     float rel = rand1f(rng);
     float rl  = rand1f(rng);
-    incoming  = sample_lights<COUNT, GENERAL>(tc, position, rl, rel, ruvx, ruvy);
+    incoming  = sample_lights<COUNT, GENERAL, CENV>(tc, position, rl, rel, ruvx, ruvy);
   }
   if (COUNT) k2 = clock64(), tc.stats->c_sample += k2 - k1;
+  count_region<COUNT>(tc.stats, YH_REGION_SAMPLE, kr);
+  YH_REGION_MARK("eval");
   f3    brdfcos;
   float brdf_pdf;
   if (is_hair) {
@@ -695,16 +780,23 @@ YH_DEV bool path_step(const trace_ctx& tc, path_t& ps, const hit_t& isec, rng_t&
     }
   }
   if (COUNT) k3 = clock64(), tc.stats->c_eval += k3 - k2;
+  count_region<COUNT>(tc.stats, YH_REGION_EVAL, kr);
+  YH_REGION_MARK("lights_pdf");
 #if YH_LANE
   float light_pdf = lane_lights_pdf<GENERAL>(tc, position, incoming);
 #else
-  float light_pdf = sample_lights_pdf<COUNT, STRIDE, GENERAL>(tc, position, incoming);
+  float light_pdf = sample_lights_pdf<COUNT, STRIDE, GENERAL, CENV>(tc, position, incoming, ce);
 #endif
-  ps.weight = ps.weight * (brdfcos / (0.5f * brdf_pdf + 0.5f * light_pdf));
+  count_region<COUNT>(tc.stats, YH_REGION_LIGHTS_PDF, kr);
+  YH_REGION_MARK("weight");
+  if constexpr (TRIM) ps.weight = ps.weight * quad_div(brdfcos, 0.5f * brdf_pdf + 0.5f * light_pdf);
+  else ps.weight = ps.weight * (brdfcos / (0.5f * brdf_pdf + 0.5f * light_pdf));
   if (general) medium_crossing(sc, ps, mat, normal, outgoing, incoming, ctex, etex_x, tu, tv);
   ps.ray    = mkray(position, incoming);
   if (COUNT) tc.stats->c_rest += clock64() - k3;
-  return path_continue(ps, rng, bounces);
+  const bool goes_on = path_continue(ps, rng, bounces);
+  count_region<COUNT>(tc.stats, YH_REGION_WEIGHT, kr);
+  return goes_on;
 }
 
 // The reference's other shaders (get_trace_shader_func, pt.cpp:1660-1672), one loop iteration each

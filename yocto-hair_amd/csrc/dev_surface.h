@@ -103,6 +103,20 @@ YH_DEV f3 sample_hemisphere_cos(f3 normal, float rx, float ry) {
   float phi = 2 * pif * rx;
   return from_local_z(normal, f3{r * cosf(phi), r * sinf(phi), z});
 }
+// The same by the four lanes of a quad with identical arguments: the two normalisations' divisions spread over the lanes (dev_math.h)
+YH_DEV f3 sample_hemisphere_cos_quad(f3 normal, float rx, float ry) {
+  float z   = sqrtf(ry);
+  float r   = sqrtf(1 - z * z);
+  float phi = 2 * pif * rx;
+  f3    local = f3{r * cosf(phi), r * sinf(phi), z};
+  f3    zz   = quad_normalize(normal);
+  float sign = copysignf(1.0f, zz.z);
+  float a    = -1.0f / (sign + zz.z);
+  float b    = zz.x * zz.y * a;
+  f3    x    = {1.0f + sign * zz.x * zz.x * a, sign * b, -sign * zz.x};
+  f3    y    = {b, sign + zz.y * zz.y * a, -zz.y};
+  return quad_normalize(x * local.x + y * local.y + zz * local.z);
+}
 YH_DEV bool both_above(f3 normal, f3 outgoing, f3 incoming) {
   return !(dot(normal, incoming) <= 0 || dot(normal, outgoing) <= 0);
 }

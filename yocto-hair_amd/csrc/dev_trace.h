@@ -213,6 +213,11 @@ struct trace_ctx {
                                     // argument itself must not have its address escape: it would be copied to scratch)
   YH_LDS v4f*           lds_once;   // ONCE (trace_ray_loop): this path's column of the per-object ray records, else unused
 };
+// CENV (dev_path.h): what eval_environment and sample_lights_pdf return for a scene whose lights are constant environments — functions of
+// the kernel argument alone, computed once per wave ahead of the sample loop (dev_items.h), wave-uniform
+struct const_env_t {
+  float env_sum[3], lights_pdf;
+};
 // Stages the tables every kernel keeps in LDS — the scene level (objects, scene BVH nodes and primitives; when it
 // fits), the camera, the small area lights and the environment cdf index — at `at` (YHD_LDS_TABLES_F4 float4) and
 // points `tc` at them. All threads of the block call it; a __syncthreads() must follow.
@@ -258,6 +263,8 @@ struct stats_t {
   // divergence profile of the traversal loop: for each kind of step, how many wave trips
   // executed its code (t_*) and how many lanes were active in it (l_*)
   unsigned int t_node, l_node, t_line, l_line, t_tri, l_tri, t_enter, l_enter, t_scene, l_scene;
+  unsigned long long* r;         // this wave's sums by region of the shading pass, in LDS (count_region; dev_items.h flushes them with the item)
+  unsigned long long from;       // ... and where the region at hand began (the sample loop's own regions, dev_items.h)
 };
 // Inside a divergent branch: one count per wave trip + the active lanes of that trip.
 template <bool COUNT>
@@ -265,6 +272,29 @@ YH_DEV void count_branch(unsigned int& trips, unsigned int& lanes) {
   if (COUNT) {
     unsigned long long m = __ballot(1);
     if ((int)__lane_id() == __ffsll((long long)m) - 1) trips++, lanes += (unsigned int)__popcll(m);
+  }
+}
+// -DYH_ISA_MARKS (developer build, never shipped): a comment line in the assembly where a region of the shading pass begins, for the static
+// instruction counts of a budget (tools/isa_blocks.py --marks; profiles/shading_pass/). Without the flag: nothing.
+#ifdef YH_ISA_MARKS
+#define YH_REGION_MARK(name) asm volatile("; YHMARK " name)
+#else
+#define YH_REGION_MARK(name)
+#endif
+// A REGION of the shading pass at wave level (yhd_counters::region, YH_REGION_*): the wave's cycles since `from`, one trip, and the lanes
+// for which `in` holds. Called where the lanes that run the region are together again; the first of them adds — to the wave's own sums in
+// LDS: an atomic on the launch's counters here would sit in front of the next region's loads — and `from` moves on. A trip in which `in`
+// holds for no lane is not counted (its few cycles of stepping around the region stay unnamed).
+template <bool COUNT>
+YH_DEV void count_region(stats_t* s, int region, unsigned long long& from, bool in = true) {
+  if (COUNT) {
+    const unsigned long long now = clock64(), m = __ballot(1), mi = __ballot(in);
+    if (mi && (int)__lane_id() == __ffsll((long long)m) - 1) {
+      s->r[3 * region] += now - from;
+      s->r[3 * region + 1] += 1;
+      s->r[3 * region + 2] += (unsigned long long)__popcll(mi);
+    }
+    from = clock64();
   }
 }
 // one 16-byte load (never split into dwordx3 + dword)

@@ -422,7 +422,8 @@ static_assert(yhd_shapes[YH_SHAPE_QUAD].block_threads == YH_BLOCK && yhd_shapes[
 static int shape_block(int shape) { return yhd_shapes[shape].block_threads; }
 static int shape_groups(int shape) { return shape_block(shape) / yhd_shapes[shape].lanes_per_path; }
 // `once`: the scene takes the form that resolves the scene level once per ray (yhd_scene::scene_once): shape 0's plain variants have it
-static trace_kernel_t trace_kernel(bool counted, bool general, int shape, int shader = YH_SHADER_PATH, bool once = false) {
+// `cenv`: ... and its lights are constant environments (yhd_scene::lights_const_env): shape 0's plain variants have a form for that too
+static trace_kernel_t trace_kernel(bool counted, bool general, int shape, int shader = YH_SHADER_PATH, bool once = false, bool cenv = false) {
   if (shader == YH_SHADER_NAIVE) return k_trace_shader<YH_SHADER_NAIVE>;
   if (shader == YH_SHADER_EYELIGHT) return k_trace_shader<YH_SHADER_EYELIGHT>;
   if (shader == YH_SHADER_NORMAL) return k_trace_shader<YH_SHADER_NORMAL>;
@@ -437,6 +438,8 @@ static trace_kernel_t trace_kernel(bool counted, bool general, int shape, int sh
   if (shape == YH_SHAPE_QUAD_DENSE)
     return counted ? (general ? k_trace<true, true, 256, YH_DENSE_WAVES> : k_trace<true, false, 256, YH_DENSE_WAVES>)
                    : (general ? k_trace<false, true, 256, YH_DENSE_WAVES> : k_trace<false, false, 256, YH_DENSE_WAVES>);
+  if (cenv && !general)
+    return counted ? (once ? k_trace_cenv<true, true> : k_trace_cenv<true, false>) : (once ? k_trace_cenv<false, true> : k_trace_cenv<false, false>);
   if (once && !general) return counted ? k_trace<true, false, YH_BLOCK, YH_MIN_WAVES, YH_MODE_QUAD, true> : k_trace<false, false, YH_BLOCK, YH_MIN_WAVES, YH_MODE_QUAD, true>;
   return counted ? (general ? k_trace<true, true, YH_BLOCK, YH_MIN_WAVES> : k_trace<true, false, YH_BLOCK, YH_MIN_WAVES>)
                  : (general ? k_trace<false, true, YH_BLOCK, YH_MIN_WAVES> : k_trace<false, false, YH_BLOCK, YH_MIN_WAVES>);
@@ -457,7 +460,7 @@ int yhk_trace(const yhd_scene* sc, const yhd_state* st, int nsamples, yhd_counte
   if (!path && counters) return (int)hipErrorInvalidValue;
   if ((unsigned)shape >= YH_SHAPES || yhd_shapes[shape].kind == YH_SHAPE_KIND_STREAM || yhd_shapes[shape].kind == YH_SHAPE_KIND_SBS) return (int)hipErrorInvalidValue;
   size_t    lds   = trace_lds(sc, shape);
-  trace_kernel_t k     = trace_kernel(counters != nullptr, sc->general_materials != 0, shape, st->shader, sc->scene_once > 0);
+  trace_kernel_t k     = trace_kernel(counters != nullptr, sc->general_materials != 0, shape, st->shader, sc->scene_once > 0, sc->lights_const_env != 0);
   if (!k) return (int)hipErrorInvalidValue;
   if (lds > 64 * 1024) {  // above 64 KB the dynamic-LDS limit must be raised explicitly; the attribute is per
                           // device, so it is set for the current device at every such launch (no process-wide cache)

@@ -43,7 +43,8 @@ int yhk_trace_sbs_occupancy(int lds_bytes, int general) {
 int yhk_trace_sbs(const yhd_scene* sc, const yhd_state* st, int nsamples, int oct_blocks, int quad_items, int oct_entries, int grid_blocks,
     hipStream_t stream) {
   const size_t lds = sbs_lds(sc);
-  auto         k   = sc->general_materials ? k_trace_sbs<true> : sc->scene_once > 0 ? k_trace_sbs<false, true> : k_trace_sbs<false>;
+  const bool   once = sc->scene_once > 0;
+  auto         k    = sc->general_materials ? k_trace_sbs<true> : sc->lights_const_env ? (once ? k_trace_sbs_cenv<true> : k_trace_sbs_cenv<false>) : once ? k_trace_sbs<false, true> : k_trace_sbs<false>;
   if (lds > 64 * 1024) {
     hipError_t e = hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return (int)e;

@@ -211,7 +211,11 @@ typedef struct yhd_scene {
   // (host/scene_upload.cpp) for a plain scene whose scene level is ONE leaf node (at most four objects) in LDS, when the records
   // cost those kernels no resident workgroup. (At the end: every other offset is as it was.)
   int               scene_once;
-  int               pad_once;
+  // LIGHTS THAT ARE CONSTANT ENVIRONMENTS ONLY (dev_path.h: CENV): 1 when the scene is plain, no environment has a texture and every
+  // light is an environment — light sampling, the light pdf and the environment lookup then need num_lights, num_environments and the
+  // emissions above, nothing from memory; the plain 512-thread kernels have variants for it, which the host selects. Set wherever the
+  // light list is made (host/scene_upload.cpp: settle_scene_variant, after an upload and after every edit). (It fills what was padding.)
+  int               lights_const_env;
 } yhd_scene;
 // float4 of the per-object ray records of the ONCE form behind the tables, for `groups` paths per workgroup: 4 per (path, object)
 #define YHD_ONCE_F4(sc, groups) (4 * (sc)->scene_once * (groups))
@@ -332,6 +336,22 @@ typedef struct yhd_counters {
   unsigned long long c_geom, c_sample, c_eval, c_rest;  // lane-0 cycles inside path_step: hit geometry, direction sampling, BSDF eval+pdf, the rest
   // traversal divergence: (wave trips, active lanes) for node, line-leaf, triangle-leaf, ENTER, scene-node code
   unsigned long long branch[10];
+  // the regions of a wave iteration's shading pass (dev_path.h: path_step; dev_items.h): per region the wave's cycles, the trips that ran
+  // it and the lanes it ran with, added where the region ends (dev_trace.h: count_region)
+  unsigned long long region[3 * 9];
 } yhd_counters;
+enum yhd_region {
+  YH_REGION_REGEN = 0,   // the loop head: path_begin of the quads that start a sample (outside cyc_shade)
+  YH_REGION_MISS,        // eval_environment of the quads whose ray left the scene
+  YH_REGION_FETCH,       // object and material rows, the hit's record, position and normals, emission
+  YH_REGION_HAIR,        // hair_setup and hair_prepare
+  YH_REGION_SAMPLE,      // the sampling branch: BSDF | lights, with its four draws
+  YH_REGION_EVAL,        // BSDF value and pdf
+  YH_REGION_LIGHTS_PDF,  // sample_lights_pdf
+  YH_REGION_WEIGHT,      // weight update, next ray, path_continue
+  YH_REGION_END,         // path_end of the quads whose path ended
+  YH_REGIONS
+};
+static_assert(YH_REGIONS == 9, "yhd_counters::region");
 
 #endif

@@ -362,6 +362,7 @@ int yh_intersect_plain_batch(yh_context* ctx, int form, int n, const float* rays
 }
 
 int yh_scene_once(const yh_context* ctx) { return !ctx ? YH_E_INVALID : !ctx->have_scene ? YH_E_STATE : ctx->scene.scene_once; }
+int yh_lights_const_env(const yh_context* ctx) { return !ctx ? YH_E_INVALID : !ctx->have_scene ? YH_E_STATE : ctx->scene.lights_const_env; }
 
 int yh_lights_batch(yh_context* ctx, int form, int n, const float* position, const float* direction, const float* rn, float* out) {
   if (!ctx || n < 0 || (form != 0 && form != 1) || (n && (!position || !direction || !rn || !out))) return YH_E_INVALID;

@@ -115,7 +115,7 @@ void settle_scene_variant(const yh_context* ctx, yhd_scene& sc, bool general_row
   sc.general_materials = general_rows || ctx->big_lights || sc.lds_materials == 0 || sc.lds_scene_f4 == 0;
   // THE SCENE LEVEL ONCE PER RAY (csrc/dev_trace.h: ONCE): a plain scene whose scene level is one leaf node. Its records (8 KB per
   // object in the 512-thread quad form) must cost shapes 0 and 5 no resident workgroup, else the scene keeps the in-loop form
-  sc.scene_once = 0, sc.pad_once = 0;
+  sc.scene_once = 0;
   if (!sc.general_materials && sc.num_scene_nodes == 1 && sc.num_objects >= 1 && sc.num_objects <= 4) {
     const int quad0 = yhk_trace_occupancy(yhk_trace_lds_bytes(&sc, YH_SHAPE_QUAD), 0, YH_SHAPE_QUAD);
     const int sbs0  = yhk_trace_sbs_occupancy(yhk_trace_sbs_lds_bytes(&sc), 0);
@@ -123,6 +123,13 @@ void settle_scene_variant(const yh_context* ctx, yhd_scene& sc, bool general_row
     if (yhk_trace_occupancy(yhk_trace_lds_bytes(&sc, YH_SHAPE_QUAD), 0, YH_SHAPE_QUAD) < quad0 || yhk_trace_sbs_occupancy(yhk_trace_sbs_lds_bytes(&sc), 0) < sbs0)
       sc.scene_once = 0;
   }
+  // LIGHTS THAT ARE CONSTANT ENVIRONMENTS ONLY (csrc/dev_path.h: CENV): a plain scene none of whose environments has a texture and none of
+  // whose lights is an object. From the table as it stands: every edit that makes the light list again comes through here afterwards.
+  sc.lights_const_env = sc.general_materials ? 0 : 1;
+  for (int ei = 0; ei < sc.num_environments; ei++)
+    if (sc.environments[ei].tex_w != 0 || sc.environments[ei].tex_h != 0) sc.lights_const_env = 0;
+  for (int li = 0; li < sc.num_lights; li++)
+    if (sc.lights[li].object >= 0 || sc.lights[li].environment < 0) sc.lights_const_env = 0;
 }
 
 // Fingerprint of the scene for the process-wide trial record: counts, camera, materials, objects, a sample of the geometry, environment

@@ -416,5 +416,11 @@ int yh_trace_samples_counted(yh_context* ctx, int nsamples, yh_workcounts* out) 
   out->wave_steps = c.wave_steps, out->lane_steps = c.lane_steps, out->lane_iters = c.lane_iters;
   out->cyc_geom = c.c_geom, out->cyc_sample = c.c_sample, out->cyc_eval = c.c_eval, out->cyc_rest = c.c_rest;
   for (int k = 0; k < 10; k++) out->branch[k] = c.branch[k];
+  for (int k = 0; k < 3 * YH_REGIONS; k++) ctx->last_regions[k] = c.region[k];
   return YH_OK;
+}
+int yh_shade_regions(const yh_context* ctx, uint64_t* out, int capacity) {
+  if (!ctx || !out || capacity < 0) return YH_E_INVALID;
+  for (int k = 0; k < capacity && k < 3 * YH_REGIONS; k++) out[k] = ctx->last_regions[k];
+  return 3 * YH_REGIONS;
 }

@@ -213,6 +213,8 @@ _SIGS = {
     "yh_intersect_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_int_p, c_int_p, c_float_p, c_float_p]),
     "yh_intersect_plain_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, c_int_p, c_int_p, c_float_p, c_float_p]),
     "yh_scene_once": (C.c_int, [C.c_void_p]),
+    "yh_lights_const_env": (C.c_int, [C.c_void_p]),
+    "yh_shade_regions": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
     "yh_lights_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),
     "yh_selftest": (C.c_int, [C.c_void_p, C.c_int, c_float_p]),
     "yh_scene_load": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]),
@@ -704,6 +706,21 @@ class Context:
         if rc < 0:
             self._chk(rc)
         return rc
+
+    def lights_const_env(self):
+        """yh_lights_const_env: 1 when the plain 512-thread kernels take this scene's lights (constant environments only) from the kernel argument."""
+        rc = int(self.lib.yh_lights_const_env(self.h))
+        if rc < 0:
+            self._chk(rc)
+        return rc
+
+    SHADE_REGIONS = ("regen", "miss", "fetch", "hair", "sample", "eval", "lights_pdf", "weight", "end")
+
+    def shade_regions(self):
+        """yh_shade_regions of the last trace_samples_counted: {region: (cycles, trips, lanes)}."""
+        out = (C.c_uint64 * 27)()
+        self.lib.yh_shade_regions(self.h, out, 27)
+        return {nm: (int(out[3 * k]), int(out[3 * k + 1]), int(out[3 * k + 2])) for k, nm in enumerate(self.SHADE_REGIONS)}
 
     def lights(self, form, position, direction, rn4):
         """yh_lights_batch on the uploaded scene (form 0: a quad per row, 1: a lane per row): (n, 8) = sample_lights
