@@ -724,6 +724,42 @@ int yh_shade_regions(const yh_context* ctx, uint64_t* out, int capacity);
 int yh_lights_batch(yh_context* ctx, int form, int n, const float* position,
     const float* direction, const float* rn, float* out);
 
+/* The homogeneous medium of a path, row by row: what the sample-loop kernels
+ * run when a path crosses into a closed transmissive object and flies through
+ * it (csrc/dev_path.h: medium_crossing, the free-flight block of path_step;
+ * csrc/dev_surface.h: eval_transmittance ... sample_scattering_pdf), on the
+ * material row that yh_upload_scene makes of `materials`. Per row:
+ *   1. medium_crossing from outside with `normal`, `outgoing`, `incoming`.
+ *      tex 0: the row's host-made density. tex 1: the row with its colour
+ *      texture set, so that the device derives the density from the row's
+ *      colour x texval[0..2] and its transmission x texval[3].
+ *   2. the free flight for rl, rd and max_distance: distance, the weight
+ *      factor eval_transmittance / sample_transmittance_pdf and that pdf;
+ *   3. the scatter for rx, ry: the sampled direction, eval_scattering and
+ *      sample_scattering_pdf at `incoming` and at the sampled direction.
+ * A row that enters no medium runs 2 and 3 on a zero medium. form 0: a quad
+ * per row, as the quad kernels run it; form 1: a lane per row, as the
+ * streaming kernel runs it (the medium read back from the path's slot).
+ * YH_E_INVALID for n < 1, a NULL pointer, a form or tex other than 0 / 1.
+ * normal, outgoing, incoming: 3n; texval: 4n; rn: 5n (rl, rd, max_distance,
+ * rx, ry). out: YH_VOLUME_FLOATS per row = in_medium (0 / 1), density[3],
+ * scatter[3], anisotropy, distance, weight factor[3], distance pdf, sampled
+ * direction[3], f[3] and pdf at `incoming`, f[3] and pdf at the sampled
+ * direction.                                                                 */
+#define YH_VOLUME_FLOATS 24
+int yh_volume_batch(yh_context* ctx, int form, int tex, int n,
+    const yh_material* materials, const float* normal, const float* outgoing,
+    const float* incoming, const float* texval, const float* rn, float* out);
+/* The quad forms of the trimmed 512-thread kernels next to the plain forms
+ * whose bits they render (csrc/dev_surface.h: sample_hemisphere_cos_quad,
+ * csrc/dev_math.h: quad_div), a quad per row. normal, a: 3n; rn: 2n (rx, ry);
+ * b: n. out: YH_QUAD_FORMS_FLOATS per row = sample_hemisphere_cos_quad[3],
+ * sample_hemisphere_cos[3], quad_div(a, b)[3], a / b [3]. YH_E_INVALID for
+ * n < 1 or a NULL pointer.                                                   */
+#define YH_QUAD_FORMS_FLOATS 12
+int yh_quad_forms_batch(yh_context* ctx, int n, const float* normal,
+    const float* rn, const float* a, const float* b, float* out);
+
 /* The four Monte-Carlo self-tests of yocto_extension.cpp:555-693 on the
  * device: 0 white_furnace, 1 white_furnace_sampled, 2 sampling_weights,
  * 3 sampling_consistency. Same seeds, counts and thresholds. `worst` (may be

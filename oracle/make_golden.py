@@ -118,6 +118,32 @@ def main():
         for kind in range(yh.LOBE_COUNT):
             out[f"lobe_{kind}"] = ref.surface_lobe(kind, p, nn, wo, wi, rn)
         np.savez_compressed(os.path.join(GOLD, "lobes.npz"), **out)
+    # ---- the surface lobes at their edges: the strata of tests/surface_cases.py, which has its own seeds ------------------------
+    if want("lobes_edges.npz"):
+        import surface_cases as sc
+        out = {}
+        for name in sc.STRATA:
+            s = sc.inputs(name)
+            k = sc.GOLDEN_ROWS
+            a = (s.params[:k], s.nrm[:k], s.wo[:k], s.wi[:k], s.rn[:k])
+            for key, v in zip(("params", "normal", "wo", "wi", "rn"), a):
+                out[f"{name}_{key}"] = v
+            out[f"{name}_fresnel"] = ref.fresnel(a[0], a[1], a[2])
+            for kind in range(yh.LOBE_COUNT):
+                out[f"{name}_lobe_{kind}"] = ref.surface_lobe(kind, *a)
+        np.savez_compressed(os.path.join(GOLD, "lobes_edges.npz"), **out)
+    # ---- homogeneous volumes at unit level (math.h:4758-4813): the strata of tests/volume_cases.py, which has its own seeds ------
+    if want("volumes_unit.npz"):
+        import volume_cases as vc
+        oracle = oc.Oracle()
+        out = {}
+        for name, k in vc.GOLDEN_ROWS.items():
+            s = vc.inputs(name)
+            orc = oracle.volume(0, s.mats[:k], s.nrm[:k], s.wo[:k], s.wi[:k], s.tex[:k], s.rn[:k])  # the medium: eval_vsdf, pinned by the images
+            out[f"{name}_density"], out[f"{name}_anisotropy"] = orc[:, 1:4], orc[:, 7]
+            out[f"{name}_wo"], out[f"{name}_wi"], out[f"{name}_rn"] = s.wo[:k], s.wi[:k], s.rn[:k]
+            out[f"{name}_ref"] = ref.volume(orc[:, 1:4], orc[:, 7], s.wo[:k], s.wi[:k], s.rn[:k])
+        np.savez_compressed(os.path.join(GOLD, "volumes_unit.npz"), **out)
     # ---- pbrt curve -> line strands (yocto_pbrt.h:1751-1797) ------------------------------------
     if want("curves.npz"):
         crng = np.random.default_rng(20240610)

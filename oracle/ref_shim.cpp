@@ -162,6 +162,27 @@ void ref_fresnel(int n, const float* params, const float* normal, const float* o
   }
 }
 
+// The public volume functions of yocto_math.h:4758-4813 on a GIVEN medium, in the order a path calls them: density 3n,
+// anisotropy n, outgoing and incoming 3n, rn 5n (rl, rd, max_distance, rx, ry); out 12n: distance, eval_transmittance /
+// sample_transmittance_pdf [3], that pdf, sample_phasefunction [3], eval_phasefunction and sample_phasefunction_pdf at
+// `incoming`, the two at the sampled direction.
+void ref_volume_batch(int n, const float* density, const float* anisotropy, const float* outgoing, const float* incoming,
+    const float* rn, float* out) {
+  for (int i = 0; i < n; i++) {
+    auto d = v3(density + 3 * i), wo = v3(outgoing + 3 * i), wi = v3(incoming + 3 * i);
+    auto g = anisotropy[i];
+    auto q = rn + 5 * i;
+    auto dist = ym::sample_transmittance(d, q[2], q[0], q[1]);
+    auto tpdf = ym::sample_transmittance_pdf(d, dist, q[2]);
+    auto w    = ym::eval_transmittance(d, dist) / tpdf;
+    auto s    = ym::sample_phasefunction(g, wo, ym::vec2f{q[3], q[4]});
+    auto o    = out + 12 * i;
+    o[0] = dist, o[1] = w.x, o[2] = w.y, o[3] = w.z, o[4] = tpdf, o[5] = s.x, o[6] = s.y, o[7] = s.z;
+    o[8] = ym::eval_phasefunction(g, wo, wi), o[9] = ym::sample_phasefunction_pdf(g, wo, wi);
+    o[10] = ym::eval_phasefunction(g, wo, s), o[11] = ym::sample_phasefunction_pdf(g, wo, s);
+  }
+}
+
 // mats: 12 floats per item = sigma_a[3] beta_m beta_n alpha eta color[3]
 // eumelanin pheomelanin (yocto_extension.h:86-95 field order)
 void ref_hair_brdf(int n, const float* mats, const float* v, const float* nrm,

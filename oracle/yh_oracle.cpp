@@ -2203,6 +2203,44 @@ void yo_surface_bsdf(int n, const yh_material* materials, const float* normal,
   }
 }
 
+// The homogeneous medium of a path, row by row, in the row layout of yh_volume_batch: the crossing of pt.cpp:1458-1467 from outside
+// with eval_vsdf (pt.cpp:504-527), the free flight of pt.cpp:1403-1414, the scatter of pt.cpp:1472-1497.
+void yo_volume_batch(int tex, int n, const yh_material* materials, const float* normal, const float* outgoing, const float* incoming,
+    const float* texval, const float* rn, float* out) {
+  for (int i = 0; i < n; i++) {
+    auto&    m = materials[i];
+    Material mt;
+    mt.color = v3(m.color), mt.thin = m.thin != 0, mt.transmission = m.transmission;
+    mt.scattering = v3(m.scattering), mt.scanisotropy = m.scanisotropy, mt.trdepth = m.trdepth;
+    auto nn = v3(normal + 3 * i), wo = v3(outgoing + 3 * i), wi = v3(incoming + 3 * i);
+    auto t  = texval + 4 * i;
+    auto q  = rn + 5 * i;
+    auto rl = q[0], rd = q[1], max_distance = q[2], rx = q[3], ry = q[4];
+    Vsdf vsdf;
+    auto in_medium = false;
+    if (has_volume(mt) && dot(nn, wo) * dot(nn, wi) < 0) {
+      vsdf      = tex ? eval_vsdf(mt, v3(t), t[3], V3{1, 1, 1}) : eval_vsdf(mt, V3{1, 1, 1}, 1.0f, V3{1, 1, 1});
+      in_medium = true;
+    }
+    auto dist    = sample_transmittance(vsdf.density, max_distance, rl, rd);
+    auto tpdf    = sample_transmittance_pdf(vsdf.density, dist, max_distance);
+    auto w       = eval_transmittance(vsdf.density, dist) / tpdf;
+    auto sampled = sample_scattering(vsdf, wo, rx, ry);
+    auto f       = eval_scattering(vsdf, wo, wi);
+    auto pdf     = sample_scattering_pdf(vsdf, wo, wi);
+    auto fs      = eval_scattering(vsdf, wo, sampled);
+    auto pdfs    = sample_scattering_pdf(vsdf, wo, sampled);
+    auto o       = out + YH_VOLUME_FLOATS * i;
+    o[0] = in_medium ? 1.0f : 0.0f;
+    o[1] = vsdf.density.x, o[2] = vsdf.density.y, o[3] = vsdf.density.z;
+    o[4] = vsdf.scatter.x, o[5] = vsdf.scatter.y, o[6] = vsdf.scatter.z, o[7] = vsdf.anisotropy;
+    o[8] = dist, o[9] = w.x, o[10] = w.y, o[11] = w.z, o[12] = tpdf;
+    o[13] = sampled.x, o[14] = sampled.y, o[15] = sampled.z;
+    o[16] = f.x, o[17] = f.y, o[18] = f.z, o[19] = pdf;
+    o[20] = fs.x, o[21] = fs.y, o[22] = fs.z, o[23] = pdfs;
+  }
+}
+
 yo_scene* yo_scene_create(const yh_scene_desc* d) {
   auto sc = new yo_scene{};
   for (int i = 0; i < d->num_textures; i++) {

@@ -62,6 +62,11 @@ void yo_fresnel(int n, const float* params, const float* normal, const float* ou
 void yo_surface_bsdf(int n, const yh_material* materials, const float* normal,
     const float* outgoing, const float* incoming, const float* rn, float* out);
 
+/* The homogeneous medium of a path (pt.cpp:504-527, 1403-1414, 1458-1497; math.h:4758-4813), row by row: the
+ * counterpart of yh_volume_batch, same arguments (without the form) and the same YH_VOLUME_FLOATS per row.    */
+void yo_volume_batch(int tex, int n, const yh_material* materials, const float* normal, const float* outgoing,
+    const float* incoming, const float* texval, const float* rn, float* out);
+
 /* math.h:3426-3505,3544-3554 */
 void yo_intersect_line(int n, const float* rays, const float* p0,
     const float* p1, const float* r0, const float* r1, int* hit, float* uv,

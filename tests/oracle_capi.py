@@ -133,6 +133,7 @@ class Oracle(_UnitApi):
         lib.yo_selftest.argtypes = [C.c_int, fp]
         lib.yo_hair_lobe_pdfs.argtypes = [C.c_int, fp, fp, fp]
         lib.yo_surface_bsdf.argtypes = [C.c_int, C.POINTER(yh.Material), fp, fp, fp, fp, fp]
+        lib.yo_volume_batch.argtypes = [C.c_int, C.c_int, C.POINTER(yh.Material), fp, fp, fp, fp, fp, fp]
         lib.yo_scene_create.restype = C.c_void_p
         lib.yo_scene_create.argtypes = [C.POINTER(yh.SceneDesc)]
         lib.yo_scene_free.argtypes = [C.c_void_p]
@@ -162,6 +163,16 @@ class Oracle(_UnitApi):
         normal, wo, wi, rn3 = _f(normal), _f(wo), _f(wi), _f(rn3)
         out = np.zeros((len(normal), yh.SURFACE_BSDF_FLOATS), np.float32)
         self.lib.yo_surface_bsdf(len(normal), materials, yh.fptr(normal), yh.fptr(wo), yh.fptr(wi), yh.fptr(rn3),
+                                 yh.fptr(out))
+        return out
+
+    def volume(self, tex, materials, normal, wo, wi, texval4, rn5):
+        """The homogeneous medium of a path, the counterpart of yh_volume_batch: (n, VOLUME_FLOATS). materials: (n, 10) rows as
+        for yh.volume_material_rows, or the ctypes array it makes."""
+        mats = materials if isinstance(materials, C.Array) else yh.volume_material_rows(materials)
+        normal, wo, wi, texval4, rn5 = _f(normal), _f(wo), _f(wi), _f(texval4), _f(rn5)
+        out = np.zeros((len(normal), yh.VOLUME_FLOATS), np.float32)
+        self.lib.yo_volume_batch(tex, len(normal), mats, yh.fptr(normal), yh.fptr(wo), yh.fptr(wi), yh.fptr(texval4), yh.fptr(rn5),
                                  yh.fptr(out))
         return out
 
@@ -262,6 +273,19 @@ class Ref(_UnitApi):
         lib.ref_scene_render.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_uint64, C.c_int, C.c_float, C.c_int,
                                          ip, ip, fp, u64p, C.c_int]
         lib.ref_scene_num_lights.argtypes = [C.c_void_p]
+        # (a shim built before ref_volume_batch existed — a prebuilt oracle/_ref where the reference's sources are absent — lacks it)
+        self.has_volume = hasattr(lib, "ref_volume_batch")
+        if self.has_volume:
+            lib.ref_volume_batch.argtypes = [C.c_int, fp, fp, fp, fp, fp, fp]
+
+    def volume(self, density, anisotropy, wo, wi, rn5):
+        """The reference's public volume functions on a given medium (oracle/ref_shim.cpp: ref_volume_batch): (n, 12) =
+        distance, weight factor [3], distance pdf, sampled [3], phase and its pdf at wi, the two at the sampled direction."""
+        density, anisotropy, wo, wi, rn5 = _f(density), _f(anisotropy), _f(wo), _f(wi), _f(rn5)
+        out = np.zeros((len(density), 12), np.float32)
+        self.lib.ref_volume_batch(len(density), yh.fptr(density), yh.fptr(anisotropy), yh.fptr(wo), yh.fptr(wi), yh.fptr(rn5),
+                                  yh.fptr(out))
+        return out
 
     def scene(self, json_path, camera=""):
         return RefScene(self, json_path, camera)

@@ -26,6 +26,12 @@ def test_library_exports_every_declared_symbol(yh):
         assert hasattr(lib, name), f"libyhair.so does not export {name}"
     # and the Python binding covers the same set
     assert sorted(yh.EXPORTS) == declared
+    assert {"yh_volume_batch", "yh_quad_forms_batch"} <= set(declared)
+    # ... and the row widths the binding allocates are the header's
+    header = open(os.path.join(ROOT, "include", "yhair.h")).read()
+    for define, value in (("YH_VOLUME_FLOATS", yh.VOLUME_FLOATS), ("YH_QUAD_FORMS_FLOATS", yh.QUAD_FORMS_FLOATS),
+                          ("YH_HAIR_SHADE_FLOATS", yh.HAIR_SHADE_FLOATS), ("YH_SURFACE_BSDF_FLOATS", yh.SURFACE_BSDF_FLOATS)):
+        assert re.search(rf"#define {define} +{value}\b", header), define
     assert b"gfx950" in lib.yh_version()
 
 

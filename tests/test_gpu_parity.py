@@ -107,15 +107,25 @@ def _lobe_close(got, want):
 def test_surface_lobes_match_reference_vectors(ctx, yh):
     """each lobe of yocto_math.h:4427-4755 on the device vs the reference's
     own outputs. Values and pdfs are + - * / sqrt only: all within 1e-4 (most bit-exact);
-    sampled directions go through device atan/sin/cos: 5e-5 absolute. The refraction lobes pick
-    reflect-or-refract by `rnl < F(sampled halfway)`, so a last-ulp change flips a few rows."""
+    sampled directions go through device atan/sin/cos: 5e-5 absolute. The refraction lobe picks
+    reflect-or-refract by `rnl < F(sampled halfway)`, so a last-place change of F flips a row whose rnl sits on it: only rows
+    whose rnl lies within 1e-5 of the float64 Fresnel value (decided on the inputs, tests/surface_f64.py; at most 2e-4 of the
+    rows) may miss the direction, as in tests/test_surface_unit.py."""
+    import surface_f64 as s64
     g = golden("lobes.npz")
     args = (g["params"], g["normal"], g["wo"], g["wi"], g["rn"])
+    p64, rn64 = g["params"].astype(np.float64), g["rn"].astype(np.float64)
+    fresnel = s64.refraction_fresnel(p64[:, 0], p64[:, 1], g["normal"].astype(np.float64), g["wo"].astype(np.float64), rn64[:, 1], rn64[:, 2])[0]
+    aside = np.abs(rn64[:, 0] - fresnel) <= 1e-5
+    assert aside.mean() <= 2e-4
     for kind in range(yh.LOBE_COUNT):
         got, want = ctx.surface_lobe(kind, *args), g[f"lobe_{kind}"]
         bad, ok_f, ok_w = _lobe_close(got, want)
         assert ok_f.all(), (kind, np.flatnonzero(~ok_f)[:5])
-        assert bad <= (2e-3 if kind == yh.LOBE_REFRACTION else 0.0), (kind, bad)
+        if kind == yh.LOBE_REFRACTION:
+            assert (ok_w | aside).all(), (kind, np.flatnonzero(~(ok_w | aside))[:5])
+        else:
+            assert bad <= 0.0, (kind, bad)
         assert np.mean(got[:, :4] == want[:, :4]) > 0.97, kind
 
 

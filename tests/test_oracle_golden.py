@@ -56,6 +56,22 @@ def test_hair_bsdf_survey_sanity_row(oracle):
     assert np.allclose(g["brdf"][-2][0:3], [0.00143605738, 0.0242141783, 0.258826762], rtol=1e-6)
 
 
+def test_volume_functions_bit_exact(oracle, yh):
+    """The free flight and the scatter in a homogeneous medium (yocto_math.h:4758-4813) on the strata of tests/volume_cases.py:
+    the oracle's rows against the reference's own outputs on the same medium, bit for bit; the committed inputs are the strata's."""
+    import volume_cases as vc
+    g = golden("volumes_unit.npz")
+    for name, k in vc.GOLDEN_ROWS.items():
+        s = vc.inputs(name)
+        orc = oracle.volume(0, s.mats[:k], s.nrm[:k], s.wo[:k], s.wi[:k], s.tex[:k], s.rn[:k])
+        for key, got in (("density", orc[:, 1:4]), ("anisotropy", orc[:, 7]), ("wo", s.wo[:k]), ("wi", s.wi[:k]), ("rn", s.rn[:k])):
+            assert np.array_equal(got, g[f"{name}_{key}"]), (name, key)
+        view, covered = vc.reference_view(orc)
+        assert covered.mean() > (0.05 if name == "g" else 0.7), name
+        differ = np.flatnonzero(~((view == g[f"{name}_ref"]) | (np.isnan(view) & np.isnan(g[f"{name}_ref"]))).all(axis=1) & covered)
+        assert len(differ) == 0, (name, differ[:5], view[differ[:2]], g[f"{name}_ref"][differ[:2]])
+
+
 def test_surface_lobes_bit_exact(oracle, yh):
     """Fresnel terms and the nine surface lobes (yocto_math.h:4215-4755)
     — value * |cos|, pdf and sampled direction — against vectors made by the reference."""
@@ -69,6 +85,22 @@ def test_surface_lobes_bit_exact(oracle, yh):
         assert np.isfinite(want).all()
         assert (want[:, :3] != 0).any(axis=1).mean() > 0.15, kind
         assert (want[:, 4:] != 0).any(axis=1).mean() > 0.4, kind
+
+
+def test_surface_lobes_at_their_edges_bit_exact(oracle, yh):
+    """The Fresnel terms and the nine lobes on the edge strata of tests/surface_cases.py (grazing, a zero halfway vector, the
+    specular peak at roughness 1e-6, the critical angle, degenerate metals, the random numbers' edges) against the reference's own
+    outputs; the committed inputs are the strata's."""
+    import surface_cases as sc
+    g = golden("lobes_edges.npz")
+    for name in sc.STRATA:
+        s, k = sc.inputs(name), sc.GOLDEN_ROWS
+        args = (s.params[:k], s.nrm[:k], s.wo[:k], s.wi[:k], s.rn[:k])
+        for key, got in zip(("params", "normal", "wo", "wi", "rn"), args):
+            assert np.array_equal(got, g[f"{name}_{key}"]), (name, key)
+        assert np.array_equal(oracle.fresnel(*args[:3]), g[f"{name}_fresnel"], equal_nan=True), name
+        for kind in range(yh.LOBE_COUNT):
+            assert np.array_equal(oracle.surface_lobe(kind, *args), g[f"{name}_lobe_{kind}"], equal_nan=True), (name, kind)
 
 
 def test_curve_conversion_bit_exact(oracle):

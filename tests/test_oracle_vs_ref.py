@@ -39,6 +39,39 @@ def test_curve_conversion_random_inputs(oracle, ref):
     _check("curve_conversion_random_inputs", rc.curve_conversion_random_inputs, oracle, ref)
 
 
+@pytest.mark.parametrize("name", list("abcdefg"))
+def test_volume_functions_on_every_stratum(oracle, ref, name):
+    """Every row of the unit-level volume strata (tests/volume_cases.py), both tex forms: the oracle's free flight and scatter against
+    the live reference's public functions on the same medium, bit for bit. Where the reference is not built, the committed rows
+    (tests/golden/volumes_unit.npz, test_oracle_golden.py) are what holds the oracle."""
+    import volume_cases as vc
+    s = vc.inputs(name)
+    for tex in (0, 1):
+        orc = oracle.volume(tex, s.mats, s.nrm, s.wo, s.wi, s.tex, s.rn)
+        view, covered = vc.reference_view(orc)
+        assert covered.any()
+        if ref is not None and ref.has_volume:
+            live = ref.volume(orc[:, 1:4], orc[:, 7], s.wo, s.wi, s.rn)
+            differ = np.flatnonzero(~((view == live) | (np.isnan(view) & np.isnan(live))).all(axis=1) & covered)
+            assert len(differ) == 0, (name, tex, differ[:5], view[differ[:2]], live[differ[:2]])
+
+
+@pytest.mark.parametrize("name", list("abcdefg"))
+def test_surface_lobes_on_every_stratum(oracle, ref, yh, name):
+    """Every row of the unit-level surface strata (tests/surface_cases.py): the oracle's Fresnel terms and nine lobes against the
+    live reference, bit for bit. Where the reference is not built, the committed rows (tests/golden/lobes_edges.npz,
+    test_oracle_golden.py) are what holds the oracle."""
+    import surface_cases as sc
+    s = sc.inputs(name)
+    args = (s.params, s.nrm, s.wo, s.wi, s.rn)
+    got = [oracle.fresnel(*args[:3])] + [oracle.surface_lobe(kind, *args) for kind in range(yh.LOBE_COUNT)]
+    assert all(len(x) == s.n for x in got)
+    if ref is not None:
+        live = [ref.fresnel(*args[:3])] + [ref.surface_lobe(kind, *args) for kind in range(yh.LOBE_COUNT)]
+        for k, (a, b) in enumerate(zip(got, live)):
+            assert np.array_equal(a, b, equal_nan=True), (name, k - 1, np.flatnonzero(~((a == b) | (np.isnan(a) & np.isnan(b))).all(axis=1))[:5])
+
+
 def test_selftests_match_reference(oracle, ref):
     # the reference prints "OK!"; ours returns 1. Only the two cheap ones here (the 300k-sample
     # furnace tests take ~12 s on the reference and are covered by the GPU self-tests).

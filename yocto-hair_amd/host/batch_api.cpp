@@ -388,6 +388,47 @@ int yh_lights_batch(yh_context* ctx, int form, int n, const float* position, con
   return finish(ctx, yhk_lights_lanes(&ctx->scene, (const yhd_scene*)ctx->d_scene_copy.p, n, dp, dd, dr, dovf, ovf_entries, o, ctx->stream), out, o, 32 * (size_t)n);
 }
 
+// The homogeneous-medium code of a path (dev_path.h: medium_crossing, the free flight and the scatter of path_step) on the material rows
+// the upload makes. tex 1: the row with color_tex set, so that the device derives the density from the (textured) colour and transmission.
+int yh_volume_batch(yh_context* ctx, int form, int tex, int n, const yh_material* materials, const float* normal, const float* outgoing,
+    const float* incoming, const float* texval, const float* rn, float* out) {
+  if (!ctx || n < 1 || (form != 0 && form != 1) || (tex != 0 && tex != 1) || !materials || !normal || !outgoing || !incoming || !texval || !rn || !out)
+    return YH_E_INVALID;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  std::vector<yhd_material> mats((size_t)n);
+  for (int i = 0; i < n; i++) {
+    make_material(materials[i], mats[(size_t)i]);
+    mats[(size_t)i].color_tex = tex ? 0 : -1, mats[(size_t)i].emission_tex = -1, mats[(size_t)i].scattering_tex = -1;  // (no texture is looked up: the values are given)
+  }
+  Staged s(ctx);
+  auto   dm = s.in(mats.data(), sizeof(yhd_material) * (size_t)n);
+  auto   dn = (float*)s.in(normal, 12 * (size_t)n);
+  auto   da = (float*)s.in(outgoing, 12 * (size_t)n);
+  auto   db = (float*)s.in(incoming, 12 * (size_t)n);
+  auto   dt = (float*)s.in(texval, 16 * (size_t)n);
+  auto   dr = (float*)s.in(rn, 20 * (size_t)n);
+  auto   ds = s.out(32 * (size_t)n);
+  auto   o  = (float*)s.out(4 * YH_VOLUME_FLOATS * (size_t)n);
+  if (s.rc) return s.rc;
+  static const yhd_scene empty{};
+  int e = form == 0 ? yhk_volume_quads(&empty, n, dm, dn, da, db, dt, dr, ds, o, ctx->stream)
+                    : yhk_volume_lanes(&empty, n, dm, dn, da, db, dt, dr, ds, o, ctx->stream);
+  return finish(ctx, e, out, o, 4 * YH_VOLUME_FLOATS * (size_t)n);
+}
+
+int yh_quad_forms_batch(yh_context* ctx, int n, const float* normal, const float* rn, const float* a, const float* b, float* out) {
+  if (!ctx || n < 1 || !normal || !rn || !a || !b || !out) return YH_E_INVALID;
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  Staged s(ctx);
+  auto   dn = (float*)s.in(normal, 12 * (size_t)n);
+  auto   dr = (float*)s.in(rn, 8 * (size_t)n);
+  auto   da = (float*)s.in(a, 12 * (size_t)n);
+  auto   db = (float*)s.in(b, 4 * (size_t)n);
+  auto   o  = (float*)s.out(4 * YH_QUAD_FORMS_FLOATS * (size_t)n);
+  if (s.rc) return s.rc;
+  return finish(ctx, yhk_quad_forms(n, dn, dr, da, db, o, ctx->stream), out, o, 4 * YH_QUAD_FORMS_FLOATS * (size_t)n);
+}
+
 // ---- the four self-tests (ext.cpp:555-693) ---------------------------------
 // The host replays the reference's serial structure (seed, loop bounds with
 // the accumulating float counters, per-block draw counts) and hands every

@@ -93,6 +93,12 @@ int yhk_hair_shade(int form, int n, const void* mats, const float* v, const floa
     const float* rn, float* out, hipStream_t);
 int yhk_hair_shade_exact(int form, int n, const void* mats, const float* v, const float* normal, const float* tangent, const float* outgoing,
     const float* incoming, const float* rn, float* out, hipStream_t);
+// unit/volume_quad.hip, unit/volume_lane.hip (yh_volume_batch): mats = n rows of yhd_material, texval 4n, rn 5n, slots = 2n float4 (the lane form's medium_mem)
+int yhk_volume_quads(const yhd_scene* sc, int n, const void* mats, const float* normal, const float* outgoing, const float* incoming, const float* texval,
+    const float* rn, void* slots, float* out, hipStream_t);
+int yhk_volume_lanes(const yhd_scene* sc, int n, const void* mats, const float* normal, const float* outgoing, const float* incoming, const float* texval,
+    const float* rn, void* slots, float* out, hipStream_t);
+int yhk_quad_forms(int n, const float* normal, const float* rn, const float* a, const float* b, float* out, hipStream_t);  // unit/volume_quad.hip
 int yhk_selftest(int, float, float, uint64_t, uint64_t, int, const float*, double*, unsigned int*, hipStream_t);
 int yhk_display(const yhd_state*, int samples, float exposure, int filmic, int srgb, void* rgba8, hipStream_t);  // unit/display.hip
 // unit/objects.hip (yh_update_objects): a lane per row of `rows` (yh_object, device memory); root6 = per shape its root box, 6 floats; writes

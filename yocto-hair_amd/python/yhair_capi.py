@@ -17,6 +17,8 @@ YH_OK, YH_E_INVALID, YH_E_DEVICE, YH_E_STATE, YH_E_IO, YH_E_SELFTEST = 0, -1, -2
 YH_HAIR_BRDF_FLOATS = 30
 HAIR_SHADE_FLOATS = 15
 SURFACE_BSDF_FLOATS = 29
+VOLUME_FLOATS = 24
+QUAD_FORMS_FLOATS = 12
 (LOBE_DIFFUSE, LOBE_SPECULAR, LOBE_METAL, LOBE_TRANSMISSION, LOBE_REFRACTION, LOBE_DELTA_SPECULAR,
  LOBE_DELTA_METAL, LOBE_DELTA_TRANSMISSION, LOBE_DELTA_REFRACTION) = range(9)
 LOBE_COUNT = 9
@@ -145,6 +147,21 @@ def hair_material_rows(mats12):
     return arr
 
 
+def volume_material_rows(rows10):
+    """(n, 10) float rows [color3 transmission thin trdepth scattering3 scanisotropy] -> ctypes array of yh_material
+    (a non-hair material otherwise at its defaults: no specular, no metal, roughness 1, opacity 1, ior 1.5)."""
+    rows10 = np.ascontiguousarray(rows10, dtype=np.float32).reshape(-1, 10)
+    arr = (Material * len(rows10))()
+    for i, r in enumerate(rows10):
+        m = arr[i]
+        m.color[:] = r[0:3].tolist()
+        m.transmission, m.thin, m.trdepth = float(r[3]), int(r[4] != 0), float(r[5])
+        m.scattering[:] = r[6:9].tolist()
+        m.scanisotropy = float(r[9])
+        m.opacity, m.ior, m.roughness = 1.0, 1.5, 1.0
+    return arr
+
+
 _SIGS = {
     "yh_create": (C.c_void_p, [C.c_int]),
     "yh_destroy": (None, [C.c_void_p]),
@@ -216,6 +233,9 @@ _SIGS = {
     "yh_lights_const_env": (C.c_int, [C.c_void_p]),
     "yh_shade_regions": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
     "yh_lights_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),
+    "yh_volume_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Material), c_float_p, c_float_p, c_float_p, c_float_p,
+                                  c_float_p, c_float_p]),
+    "yh_quad_forms_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p]),
     "yh_selftest": (C.c_int, [C.c_void_p, C.c_int, c_float_p]),
     "yh_scene_load": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]),
     "yh_scene_get": (C.POINTER(SceneDesc), [C.c_void_p]),
@@ -671,6 +691,30 @@ class Context:
         a = [np.ascontiguousarray(x, np.float32) for x in (normal, wo, wi, rn3)]
         out = np.zeros((len(a[0]), SURFACE_BSDF_FLOATS), np.float32)
         self._chk(self.lib.yh_surface_bsdf_batch(self.h, len(a[0]), materials, *(fptr(x) for x in a), fptr(out)))
+        return out
+
+    def volume(self, form, tex, materials, normal, wo, wi, texval4, rn5):
+        """yh_volume_batch: the homogeneous medium of a path on the upload's material rows (form 0: a quad per row, 1: a lane per
+        row; tex 1: the density derived on the device from colour x texval[:, 0:3] and transmission x texval[:, 3]). materials:
+        (n, 10) rows as for volume_material_rows, or the ctypes array it makes. rn5: rl, rd, max_distance, rx, ry.
+        (n, VOLUME_FLOATS) = in_medium, density [3], scatter [3], anisotropy, distance, weight factor [3], distance pdf, the
+        sampled direction [3], f [3], pdf at wi, f [3], pdf at the sampled direction."""
+        mats = materials if isinstance(materials, C.Array) else volume_material_rows(materials)
+        a = [np.ascontiguousarray(x, np.float32) for x in (normal, wo, wi, texval4, rn5)]
+        n = len(mats)
+        assert all(len(x) == n for x in a)
+        out = np.zeros((n, VOLUME_FLOATS), np.float32)
+        self._chk(self.lib.yh_volume_batch(self.h, form, tex, n, mats, *(fptr(x) for x in a), fptr(out)))
+        return out
+
+    def quad_forms(self, normal, rn2, a, b):
+        """yh_quad_forms_batch: (n, QUAD_FORMS_FLOATS) = sample_hemisphere_cos_quad [3], sample_hemisphere_cos [3],
+        quad_div(a, b) [3], a / b [3]."""
+        x = [np.ascontiguousarray(v, np.float32) for v in (normal, rn2, a, b)]
+        n = len(x[0])
+        assert all(len(v) == n for v in x)
+        out = np.zeros((n, QUAD_FORMS_FLOATS), np.float32)
+        self._chk(self.lib.yh_quad_forms_batch(self.h, n, *(fptr(v) for v in x), fptr(out)))
         return out
 
     def bvh_refit_wide_gpu(self, boxes, primitives, width, slots):
