@@ -16,14 +16,14 @@ wait
 HOSTOBJ="$P/host/*.o"
 if [ -n "${HOSTFLAGS:-}" ]; then
   mkdir -p /tmp/yh_var/host; CXXF=$(sed -n 's/^CXXFLAGS := //p' $P/Makefile | sed 's#\$(ROCM)#/opt/rocm#; s#-I\.\./include#-I'$R'/include#')
-  for f in $P/host/context.cpp $P/host/scene_upload.cpp $P/host/launch_plan.cpp $P/host/trace_launch.cpp $P/host/gather.cpp $P/host/batch_api.cpp $P/host/bvh_build.cpp $P/host/scene_io.cpp; do
-    g++ $CXXF $HOSTFLAGS -I$P/host -c $f -o /tmp/yh_var/host/$(basename ${f%.cpp}).o &
+  for f in $(sed -n 's/^HOSTSRC := //p' $P/Makefile); do
+    g++ $CXXF $HOSTFLAGS -I$P/host -c $P/$f -o /tmp/yh_var/host/$(basename ${f%.cpp}).o &
   done; wait
   HOSTOBJ="/tmp/yh_var/host/*.o"
 fi
 for v in "$@"; do
   name=${v%%:*}
-  others=""; for o in kernels wide exact stream bvh_gpu; do [ "$o" != "$SRC" ] && others="$others $P/csrc/$o.o"; done
+  others=""; for o in $(sed -n 's/^KERNOBJ := //p' $P/Makefile); do [ "$o" != "csrc/$SRC.o" ] && others="$others $P/$o"; done
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o $R/tools/_ab/libyhair_$name.so /tmp/yh_var/${SRC}_$name.o $others \
       $HOSTOBJ -lpthread -lz -ldl
   echo "built tools/_ab/libyhair_$name.so"

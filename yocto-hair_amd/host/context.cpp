@@ -1,5 +1,5 @@
-// context.cpp — the C ABI of include/yhair.h, part 1: the context (create / destroy / errors), shards and downloads; the shared
-// helpers (fail, upload, alloc_zero). There is no CPU fallback: without a GPU yh_create returns NULL. See context_internal.h
+// context.cpp — the C ABI of include/yhair.h, part 1: the context (create / destroy / errors), shards and downloads (the image, its
+// tone-mapped bytes, the rng, the costs); the shared helpers (fail, dev_alloc, upload, alloc_zero). There is no CPU fallback: without a GPU yh_create returns NULL. See context_internal.h
 // for the other translation units.
 #include "context_internal.h"
 
@@ -14,6 +14,15 @@ int fail(yh_context* ctx, int code, const char* fmt, ...) {
   if (ctx) ctx->error = buf;
   else g_create_error = buf;
   return code;
+}
+
+// A plain device allocation owned by `buf`: no wait, no copy, content undefined (scratch and staging; what replaces a buffer the device
+// may still read goes through upload / alloc_zero below).
+int dev_alloc(yh_context* ctx, DevBuf& buf, size_t bytes) {
+  buf.reset();
+  HIPCHK(ctx, hipMalloc(&buf.p, std::max<size_t>(bytes, 16)));
+  buf.bytes = std::max<size_t>(bytes, 16);
+  return YH_OK;
 }
 
 // (Both start with the BOUNDED wait for whatever the context has queued: freeing the old buffer is a device-synchronising hipFree and the copy a
@@ -101,7 +110,7 @@ yh_context* yh_create(int device) {
 
 void yh_destroy(yh_context* ctx) {
   if (!ctx) return;
-  if (ctx->poisoned) return;  // a launch exceeded its deadline (wait_for_launch): the device may still be running it — synchronising or freeing would wait for it; the process is expected to end
+  if (ctx->poisoned) return;  // a launch ran past its deadline (wait_for_launch): the device may still be running it — synchronising or freeing would wait for it; the process is expected to end
   destroy_communicators(ctx);
   (void)hipSetDevice(ctx->device);
   if (ctx->stream && wait_for_launch(ctx) != YH_OK) return;  // (a queued launch that never completes: as above)
@@ -138,6 +147,25 @@ int yh_download(yh_context* ctx, float* rgba) {
   int e = yhk_resolve(&ctx->state, (int)ctx->owned.size(), ctx->state.samples_done, ctx->d_image.p, ctx->stream);
   if (e) return fail(ctx, YH_E_DEVICE, "k_resolve launch: %s", hipGetErrorString((hipError_t)e));
   HIPCHK(ctx, hipMemcpyAsync(rgba, ctx->d_image.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  YH_WAIT(ctx);
+  return YH_OK;
+}
+
+// the tone-mapped bytes of the image (unit/display.hip)
+int yh_download_display(yh_context* ctx, float exposure, int filmic, int srgb, uint8_t* rgba8) {
+  if (!ctx) return YH_E_INVALID;
+  if (!rgba8) return fail(ctx, YH_E_INVALID, "yh_download_display: rgba8 is NULL");
+  if (ctx->poisoned) return refuse_poisoned(ctx);
+  if (!ctx->have_state) return fail(ctx, YH_E_STATE, "yh_download_display before yh_init_state");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t bytes = (size_t)ctx->state.width * ctx->state.height * 4;
+  if (!ctx->d_display.p || ctx->d_display.bytes < bytes) {
+    YH_WAIT(ctx);
+    if (int rc = dev_alloc(ctx, ctx->d_display, bytes)) return rc;
+  }
+  int e = yhk_display(&ctx->state, ctx->state.samples_done, exposure, filmic ? 1 : 0, srgb ? 1 : 0, ctx->d_display.p, ctx->stream);
+  if (e) return fail(ctx, YH_E_DEVICE, "k_display launch: %s", hipGetErrorString((hipError_t)e));
+  HIPCHK(ctx, hipMemcpyAsync(rgba8, ctx->d_display.p, bytes, hipMemcpyDeviceToHost, ctx->stream));
   YH_WAIT(ctx);
   return YH_OK;
 }

@@ -1,7 +1,7 @@
 // context_internal.h — what the translation units of the host library share: the launchers of csrc/*.hip, the context, small
 // host helpers with the reference's operation order, and the internal functions that cross files. Not installed; the public
 // interface is include/yhair.h.
-//   context.cpp        create / destroy, errors, shard, downloads
+//   context.cpp        create / destroy, errors, shard, downloads (yh_download_display: unit/display.hip)
 //   scene_upload.cpp   yh_upload_scene = init_bvh + init_lights (pt.cpp:755-818,1695-1740): reference-identical BVHs, leaf-ordered
 //                      records, inverse frames, per-material hair constants, light CDFs; the wide-node and lane-blob arrays
 //   launch_plan.cpp    which kernel runs (timing trials, their record in memory and on disk) and the hand-out order of the work items
@@ -9,9 +9,13 @@
 //   gather.cpp         tile packing and the one collective (yh_gather_framebuffer: RCCL or peer copies)
 //   batch_api.cpp      the unit-level batch entry points (hair BSDF, intersection, BVH build, curves, self-tests)
 //   gbuffer.cpp        yh_trace_gbuffer / _device: the first-hit feature pass over the state's image (unit/gbuffer.hip)
-//   scene_edit.cpp     edits of an uploaded scene (yh_update_camera / _materials / _environments / _objects: the last one builds the
-//                      scene-level tree again; yh_update_shape / _device: one shape's tree too; yh_refit_shape / _device: that tree's boxes
-//                      only, unit/refit.hip; yh_set_light_edits: the light list again, unit/light_list.hip) and yh_download_display
+//   scene_edit.cpp     edits of an uploaded scene that keep its geometry: yh_update_camera / _materials / _environments / _objects, and the
+//                      scene level again (the tree over the objects' world boxes, which the shape edits move too)
+//   shape_edit.cpp     one shape's vertices: yh_update_shape / _device (its tree again), yh_refit_shape / _device (that tree's boxes only,
+//                      unit/refit.hip); yh_shape_nodes, yh_shape_refit_growth
+//   light_edit.cpp     yh_set_light_edits: the light list again where an edit changes it (unit/light_list.hip; the rule itself:
+//                      light_layout.h, shared with the upload); yh_light_list, yh_triangle_cdf / _gpu
+//   (edit_internal.h: what crosses those three)
 #ifndef YH_CONTEXT_INTERNAL_H_
 #define YH_CONTEXT_INTERNAL_H_
 #include <hip/hip_runtime_api.h>
@@ -148,6 +152,7 @@ struct DevBuf {
     if (p) (void)hipFree(p);
     p = nullptr, bytes = 0;
   }
+  void swap(DevBuf& o) { std::swap(p, o.p), std::swap(bytes, o.bytes); }
 };
 
 namespace {
@@ -243,7 +248,7 @@ struct yh_context {
   std::vector<LaneShape>   lane_shapes;
   long long                lane_units = 0;
   DevBuf                   d_lane_blob;
-  // what an edit of the uploaded scene needs of its description (host/scene_edit.cpp): the material rows as they were passed in, their maps
+  // what an edit of the uploaded scene needs of its description (host/edit_internal.h): the material rows as they were passed in, their maps
   // (empty: no material has an effective map) with the device's records of them, whether some area light is read through memory (one of
   // the inputs of yhd_scene::general_materials), and the bytes the fingerprint mixes in its order — camera, materials, objects and
   // geometry sample, environment heads, maps
@@ -343,6 +348,9 @@ extern std::string g_create_error;  // why yh_create returned NULL
     if (e_ != hipSuccess) return fail(ctx, YH_E_DEVICE, "%s: %s", #call, hipGetErrorString(e_));       \
   } while (0)
 
+// what every entry point answers on a poisoned context (wait_for_launch, trace_launch.cpp)
+#define refuse_poisoned(ctx) fail(ctx, YH_E_DEVICE, "a launch of this context exceeded its deadline: the context refuses further work, destroy it")
+
 // every wait for the context's stream is bounded (wait_for_launch, trace_launch.cpp)
 #define YH_WAIT(ctx)                                      \
   do {                                                    \
@@ -359,6 +367,7 @@ int fail(yh_context* ctx, int code, const char* fmt, ...);
 int upload(yh_context* ctx, DevBuf& buf, const void* src, size_t bytes);
 int upload_keep(yh_context* ctx, DevBuf& buf, const void* src, size_t bytes);  // ... into a buffer that is kept while it is large enough
 int alloc_zero(yh_context* ctx, DevBuf& buf, size_t bytes);
+int dev_alloc(yh_context* ctx, DevBuf& buf, size_t bytes);  // a plain allocation: no wait, no copy, content undefined
 yhd_float4 node_lo(const yhh::Node& n);
 yhd_float4 node_hi(const yhh::Node& n);
 int forced_shape();  // YHAIR_SHAPE, -1 when unset
@@ -388,7 +397,7 @@ int side_by_side_impl(yh_context* ctx, int nsamples, bool sync);
 void destroy_communicators(yh_context* ctx);
 inline int tiles_of(int n) { return (n + YH_TILE - 1) / YH_TILE; }
 void make_material(const yh_material& m, yhd_material& d);  // scene_upload.cpp
-// scene_upload.cpp, shared with scene_edit.cpp: the device rows of `count` materials (`maps` / `dmaps`: theirs, or NULL in a scene without effective
+// scene_upload.cpp, shared with the edits: the device rows of `count` materials (`maps` / `dmaps`: theirs, or NULL in a scene without effective
 // maps), true when one of them is not plain; the kernel variant and the once-per-ray form of a scene table whose materials are known; the
 // fingerprint of the description the context keeps; and what a new scene does to the image state and the launch planning
 bool make_material_rows(const yh_material* materials, const yh_material_maps* maps, int count, yhd_material* rows, yhd_maps* dmaps);
@@ -419,11 +428,15 @@ bool shape_builds_on_device(int num_prims);
 int build_shape_tree(yh_context* ctx, const char* who, int si, const yh_shape& s, bool arrays_on_device, bool on_device, yhd_float4* d_recs, ShapeTree& T);
 int index_shape_tree(yh_context* ctx, const char* who, ShapeTree& T);
 int collapse_shape_tree(yh_context* ctx, const char* who, const ShapeTree& T, const yh_context::LaneShape& L, void* blob);
-// scene_edit.cpp: for each of `n` shapes (L[i], count[i]) per width the sum of the half-areas of the occupied slot boxes of its nodes in `blob`,
+// shape_edit.cpp: for each of `n` shapes (L[i], count[i]) per width the sum of the half-areas of the occupied slot boxes of its nodes in `blob`,
 // in double and in a fixed order, to area[3 * i + w] — one allocation, 3 n kernels, one copy and one wait for all of them; what a build
 // stores in ShapeState and a refit compares with
 int shape_slot_areas(yh_context* ctx, const char* who, int n, const yh_context::LaneShape* L, const int (*count)[3], const void* blob, double* area);
 bool tree_levels(const yhh::Tree& tree, int& levels, int* level_first);
+// scene_upload.cpp, shared with the scene level of an edit: the index of the 4-wide nodes of a scene tree that is walked out of the lane
+// blob — its levels, the three arrays, the nodes' copy and yhk_wide_index (which synchronises: the count comes back); `who` begins the
+// message about the levels ("" for the upload)
+int index_scene_tree(yh_context* ctx, const char* who, const yhh::Tree& tree, DevBuf& d_stree, DevBuf& d_sflag, DevBuf& d_sidx, int* wide_count, int* wide_depth);
 bool scene_level_is_wide(int num_objects, int num_scene_nodes, int* lds_scene_f4);
 struct StackNeeds { int need, need8, need16; };
 StackNeeds stack_needs(bool scene_wide, int scene_wide_depth, int scene_tree_depth, int depth4, int depth8, int depth16);

@@ -1,6 +1,7 @@
 // scene_upload.cpp — yh_upload_scene = init_bvh + init_lights (pt.cpp:755-818,1695-1740): everything a launch reads is made here, big shapes
 // entirely on the device (csrc/bvh_gpu.hip); nothing is deferred to a first launch (rounds 3-5 built the 8- / 16-wide nodes there).
 #include "context_internal.h"
+#include "light_layout.h"
 
 #include <atomic>
 
@@ -8,14 +9,6 @@
 // per-lobe constants the kernels use (dev_hair.h). Same libm as the reference
 // (this runs on the host), so these values are bit-identical to what the
 // reference recomputes at every hit.
-// a plain device allocation owned by `buf`
-static int dev_alloc(yh_context* ctx, DevBuf& buf, size_t bytes) {
-  buf.reset();
-  HIPCHK(ctx, hipMalloc(&buf.p, std::max<size_t>(bytes, 16)));
-  buf.bytes = std::max<size_t>(bytes, 16);
-  return YH_OK;
-}
-
 void make_material(const yh_material& m, yhd_material& d) {
   memset(&d, 0, sizeof(d));
   memcpy(d.emission, m.emission, 12);
@@ -89,7 +82,7 @@ static bool has_effective_map(const yh_material_maps& m) {
 
 static_assert(sizeof(yhd_maps) == 32, "yhd_maps");
 
-// The material section of the upload, which yh_update_materials runs again for the rows it replaces (host/scene_edit.cpp).
+// The material section of the upload, which yh_update_materials runs again for the rows it replaces (scene_edit.cpp).
 bool make_material_rows(const yh_material* materials, const yh_material_maps* maps, int count, yhd_material* rows, yhd_maps* dmaps) {
   bool general = false;
   for (int i = 0; i < count; i++) {
@@ -173,6 +166,22 @@ bool tree_levels(const yhh::Tree& tree, int& levels, int* level_first) {
   for (int l = 0; l <= levels; l++) level_first[l] = num_nodes;
   for (size_t n = tree.nodes.size(); n-- > 0;) level_first[level[n]] = (int)n;
   return true;
+}
+
+// The index of the 4-wide nodes of a scene tree that is walked out of the lane blob (the upload, and every edit that builds the tree
+// again): the binary nodes on the device and, per node, the flag and the index of its wide node, for yhk_wide_collapse.
+int index_scene_tree(yh_context* ctx, const char* who, const yhh::Tree& tree, DevBuf& d_stree, DevBuf& d_sflag, DevBuf& d_sidx, int* wide_count, int* wide_depth) {
+  const int nn = (int)tree.nodes.size();
+  int levels = 1, level_first[130] = {0};
+  if (!tree_levels(tree, levels, level_first)) return fail(ctx, YH_E_INVALID, "%sscene tree of %d levels", who, levels);
+  if (int rc = dev_alloc(ctx, d_stree, (size_t)nn * 32)) return rc;
+  if (int rc = dev_alloc(ctx, d_sflag, ((size_t)nn + 1) * 4)) return rc;
+  if (int rc = dev_alloc(ctx, d_sidx, ((size_t)nn + 1) * 4)) return rc;
+  HIPCHK(ctx, hipMemcpyAsync(d_stree.p, tree.nodes.data(), (size_t)nn * 32, hipMemcpyHostToDevice, ctx->stream));
+  int e = yhk_wide_index(nn, (const float*)d_stree.p, levels, level_first, 2, (unsigned int*)d_sflag.p, (unsigned int*)d_sidx.p, wide_count, ctx->stream);
+  if (e) return fail(ctx, YH_E_DEVICE, "wide-node index of the scene tree: %s", hipGetErrorString((hipError_t)e));
+  *wide_depth = 1 + std::max(0, levels - 2) / 2;
+  return YH_OK;
 }
 
 // scene-level LDS table: objects (YH_OBJECT_F4 = 11 float4 each), scene BVH nodes (2 float4 each), primitive ids; up to 10 KB = 46
@@ -351,7 +360,7 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
   if (!ctx) return YH_E_INVALID;
   if (!sd) return fail(ctx, YH_E_INVALID, "scene is NULL");
   HIPCHK(ctx, hipSetDevice(ctx->device));
-  if (ctx->poisoned) return fail(ctx, YH_E_DEVICE, "a launch of this context exceeded its deadline: the context refuses further work, destroy it");
+  if (ctx->poisoned) return refuse_poisoned(ctx);
   YH_WAIT(ctx);  // (an asynchronous launch may still be reading the scene this call replaces: wait for it, within the deadline)
   if (sd->num_objects <= 0) return fail(ctx, YH_E_INVALID, "scene has no objects");
   if (sd->num_environments > YH_MAX_ENVS) return fail(ctx, YH_E_INVALID, "more than %d environments", YH_MAX_ENVS);
@@ -464,17 +473,7 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
   const bool scene_wide   = scene_level_is_wide(sd->num_objects, (int)scene_tree.nodes.size(), &lds_scene_f4);
   DevBuf d_stree, d_sflag, d_sidx;
   int    scene_wide_count = 0, scene_wide_depth = 0;
-  if (scene_wide) {
-    int levels = 1, level_first[130] = {0};
-    const int nn = (int)scene_tree.nodes.size();
-    if (!tree_levels(scene_tree, levels, level_first)) return fail(ctx, YH_E_INVALID, "scene tree of %d levels", levels);
-    if ((rc = upload(ctx, d_stree, scene_tree.nodes.data(), scene_tree.nodes.size() * 32))) return rc;
-    if ((rc = dev_alloc(ctx, d_sflag, ((size_t)nn + 1) * 4))) return rc;
-    if ((rc = dev_alloc(ctx, d_sidx, ((size_t)nn + 1) * 4))) return rc;
-    int e = yhk_wide_index(nn, (const float*)d_stree.p, levels, level_first, 2, (unsigned int*)d_sflag.p, (unsigned int*)d_sidx.p, &scene_wide_count, ctx->stream);
-    if (e) return fail(ctx, YH_E_DEVICE, "wide-node index of the scene tree: %s", hipGetErrorString((hipError_t)e));
-    scene_wide_depth = 1 + std::max(0, levels - 2) / 2;
-  }
+  if (scene_wide && (rc = index_scene_tree(ctx, "", scene_tree, d_stree, d_sflag, d_sidx, &scene_wide_count, &scene_wide_depth))) return rc;
   // ---- the wide collapses: the index of every wide node (one flag pass + one scan per width), then the layout of the ONE array the traversal
   // kernels read (yh_device.h: lane_blob, 32-byte units): [4-wide nodes of the scene tree, if any][test records of every shape][4-wide nodes][8-wide nodes][16-wide nodes] ----
   for (int si = 0; si < sd->num_shapes; si++)
@@ -554,32 +553,13 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
   std::vector<yhd_material> materials(sd->num_materials);
   std::vector<yhd_maps> mat_maps(any_maps ? (size_t)sd->num_materials : 0);
   const bool general_rows = make_material_rows(sd->materials, any_maps ? maps : nullptr, sd->num_materials, materials.data(), mat_maps.data());
-  bool big_lights = false;
-  // ---- lights (pt.cpp:1695-1740) -----------------------------------------
+  // ---- environments, and the lights (pt.cpp:1695-1740): which they are and where their entries sit is light_layout.h's rule; the cdf
+  // values, the small lights' records and the index entries are computed here, from the arrays the caller lent ----
   yhd_scene sc{};
-  std::vector<float>      light_cdf;
   std::vector<yhd_float4> env_texels;
-  std::vector<int>        small_lights;  // lights whose record goes into the LDS light table
-  for (int oi = 0; oi < sd->num_objects; oi++) {
-    auto& o = sd->objects[oi];
-    auto& m = sd->materials[o.material];
-    if (m.emission[0] == 0 && m.emission[1] == 0 && m.emission[2] == 0) continue;
-    auto& s = sd->shapes[o.shape];
-    if (s.num_lines > 0 || s.num_triangles <= 0) continue;
-    // (every object with an emissive material is a light of its own, so every frame of an instanced emitter is one: init_lights walks objects)
-    if (sc.num_lights >= YH_MAX_LIGHTS) return fail(ctx, YH_E_INVALID, "more than %d lights: object %d of %d is emissive too (each instance of an emitter counts)", YH_MAX_LIGHTS, oi, sd->num_objects);
-    auto& L = sc.lights[sc.num_lights++];
-    L.object = oi, L.environment = -1, L.cdf_base = (int)light_cdf.size(), L.cdf_count = s.num_triangles, L.small_base = -1;
-    if (s.num_triangles <= YH_SMALL_LIGHT_TRIS) small_lights.push_back(sc.num_lights - 1);  // its record is made below, once the cdf exists
-    else big_lights = true;  // a light sampled and intersected through memory: the general kernel variant (settle_scene_variant)
-    for (int t = 0; t < s.num_triangles; t++) {
-      float area = triangle_area(ld3(s.positions + 3 * (size_t)s.triangles[3 * t]), ld3(s.positions + 3 * (size_t)s.triangles[3 * t + 1]),
-          ld3(s.positions + 3 * (size_t)s.triangles[3 * t + 2]));  // (unit/light_math.h: triangle_area, math.h:3306)
-      if (t) area += light_cdf.back();
-      light_cdf.push_back(area);
-    }
-  }
   sc.num_environments = sd->num_environments;
+  float env_emission[3 * YH_MAX_ENVS] = {};
+  int   env_texel_count[YH_MAX_ENVS] = {};
   for (int ei = 0; ei < sd->num_environments; ei++) {
     auto& e = sd->environments[ei];
     auto& d = sc.environments[ei];
@@ -591,28 +571,52 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
     if (e.texels)
       for (size_t t = 0; t < (size_t)e.tex_width * e.tex_height; t++)
         env_texels.push_back({e.texels[3 * t], e.texels[3 * t + 1], e.texels[3 * t + 2], 0});
-    if (e.emission[0] == 0 && e.emission[1] == 0 && e.emission[2] == 0) continue;
-    if (sc.num_lights >= YH_MAX_LIGHTS) return fail(ctx, YH_E_INVALID, "more than %d lights", YH_MAX_LIGHTS);
-    auto& L = sc.lights[sc.num_lights++];
-    L.object = -1, L.environment = ei, L.cdf_base = (int)light_cdf.size(), L.cdf_count = 0, L.small_base = -1;
-    if (e.texels) {
-      L.cdf_count = (int)((size_t)e.tex_width * e.tex_height);
+    memcpy(env_emission + 3 * ei, e.emission, 12);
+    env_texel_count[ei] = e.texels ? (int)((size_t)e.tex_width * e.tex_height) : 0;
+  }
+  LightLayout lights;
+  {
+    std::vector<LightShape> light_shapes;
+    for (auto& I : info) light_shapes.push_back({I.kind == YH_KIND_LINES, I.num_prims});
+    int at = 0;
+    switch (light_layout({sd->num_objects, sd->objects, sd->materials, light_shapes.data(), sd->num_environments, env_emission, env_texel_count}, lights, &at)) {
+      // (every object with an emissive material is a light of its own, so every frame of an instanced emitter is one: init_lights walks objects)
+      case YH_LIGHTS_OBJECT_TOO_MANY:
+        return fail(ctx, YH_E_INVALID, "more than %d lights: object %d of %d is emissive too (each instance of an emitter counts)", YH_MAX_LIGHTS, at, sd->num_objects);
+      case YH_LIGHTS_ENVIRONMENT_TOO_MANY: return fail(ctx, YH_E_INVALID, "more than %d lights", YH_MAX_LIGHTS);
+      case YH_LIGHTS_NONE: return fail(ctx, YH_E_INVALID, "scene has no lights (the path sampler needs at least one)");
+    }
+  }
+  sc.num_lights = lights.num_lights;
+  memcpy(sc.lights, lights.lights, sizeof(sc.lights));
+  std::vector<float> light_cdf;  // every light's segment, in list order: an area cdf by element, or a texel cdf
+  for (int li = 0; li < sc.num_lights; li++) {
+    const yhd_light& L = sc.lights[li];
+    if (L.object >= 0) {
+      auto& s = sd->shapes[sd->objects[L.object].shape];
+      for (int t = 0; t < s.num_triangles; t++) {
+        float area = triangle_area(ld3(s.positions + 3 * (size_t)s.triangles[3 * t]), ld3(s.positions + 3 * (size_t)s.triangles[3 * t + 1]),
+            ld3(s.positions + 3 * (size_t)s.triangles[3 * t + 2]));  // (unit/light_math.h: triangle_area, math.h:3306)
+        if (t) area += light_cdf.back();
+        light_cdf.push_back(area);
+      }
+    } else if (L.cdf_count > 0) {
+      auto& e = sd->environments[L.environment];
       append_env_cdf(e.texels, 3, e.tex_width, e.tex_height, light_cdf);
     }
   }
-  if (sc.num_lights == 0) return fail(ctx, YH_E_INVALID, "scene has no lights (the path sampler needs at least one)");
   // ---- tables the kernels keep in LDS (yh_device.h) -----------------------------------------------------
   // small area lights: root box, leaf-ordered triangles, area cdf — everything sample_lights / sample_lights_pdf read
   std::vector<yhd_float4> light_table;
-  for (int li : small_lights) {
-    auto& L  = sc.lights[li];
+  for (int li = 0; li < sc.num_lights; li++) {
+    const yhd_light& L = sc.lights[li];
+    if (L.small_base < 0) continue;  // (light_table.size() is L.small_base here: the records follow each other in list order)
     auto& I  = info[sd->objects[L.object].shape];
     if (I.host_prims.empty()) {  // (a shape made on the device — YHAIR_BVH=device: a light of <= 4 triangles is otherwise a small shape): its few records back
       I.host_prims.resize((size_t)6 * L.cdf_count);
       HIPCHK(ctx, hipMemcpy(I.host_prims.data(), (const yhd_float4*)ctx->d_prims.p + I.prim_base, I.host_prims.size() * 16, hipMemcpyDeviceToHost));
     }
     const yhd_float4* rec = I.host_prims.data();
-    L.small_base = (int)light_table.size();
     yhd_float4 b0{I.root.min[0], I.root.min[1], I.root.min[2], 0}, b1{I.root.max[0], I.root.max[1], I.root.max[2], light_cdf[(size_t)L.cdf_base + L.cdf_count - 1]};
     memcpy(&b0.w, &L.cdf_count, 4);
     light_table.push_back(b0), light_table.push_back(b1);
@@ -625,14 +629,12 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
   // coarse index of the first textured environment light's cdf: 2048 entries (8 KB) halve the dependent fetches of
   // its 21-step binary search
   std::vector<float> env_tab;
-  sc.env_tab_light = -1, sc.env_tab_k = 0, sc.env_tab_stride = 0;
-  for (int li = 0; li < sc.num_lights && sc.env_tab_light < 0; li++) {
-    auto& L = sc.lights[li];
-    if (L.environment < 0 || L.cdf_count < 4096) continue;
-    const int n = L.cdf_count, S = (n + 2047) / 2048, K = (n + S - 1) / S;
+  sc.env_tab_light = lights.env_tab_light, sc.env_tab_k = lights.env_tab_k, sc.env_tab_stride = lights.env_tab_stride;
+  if (sc.env_tab_light >= 0) {
+    const yhd_light& L = sc.lights[sc.env_tab_light];
+    const int n = L.cdf_count, S = sc.env_tab_stride, K = sc.env_tab_k;
     env_tab.resize((size_t)K);
     for (int k = 0; k < K; k++) env_tab[(size_t)k] = light_cdf[(size_t)L.cdf_base + (size_t)std::min<int64_t>(n, (int64_t)(k + 1) * S) - 1];
-    sc.env_tab_light = li, sc.env_tab_k = K, sc.env_tab_stride = S;
   }
   // ---- material colour textures (lookup_texture's per-texel conversion done once, pt.cpp:147-164) --------
   std::vector<yhd_texture> textures((size_t)std::max(0, sd->num_textures));
@@ -741,10 +743,10 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
   sc.scene_wide_root = scene_wide ? 0 : -1;
   static_assert(sizeof(yhd_material) == 16 * YH_MATERIAL_F4, "yhd_material is staged to LDS as float4");
   sc.lds_materials = sd->num_materials <= 24 ? sd->num_materials : 0;  // the material table in LDS
-  ctx->big_lights  = big_lights;
+  ctx->big_lights  = lights.big_lights;  // (a light sampled and intersected through memory: the general kernel variant, settle_scene_variant)
   settle_scene_variant(ctx, sc, general_rows);
   ctx->scene      = sc;
-  {  // what the edits of this scene start from (host/scene_edit.cpp), and the bytes its fingerprint mixes, in the fingerprint's order
+  {  // what the edits of this scene start from (host/edit_internal.h), and the bytes its fingerprint mixes, in the fingerprint's order
     auto bytes = [](std::vector<unsigned char>& to, const void* p, size_t n) { to.insert(to.end(), (const unsigned char*)p, (const unsigned char*)p + n); };
     ctx->key_camera = sd->camera;
     ctx->h_materials.assign(sd->materials, sd->materials + sd->num_materials);

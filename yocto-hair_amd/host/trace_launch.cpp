@@ -6,7 +6,7 @@
 // completes costs the caller an error, not the process. On expiry the context is POISONED: the device may still be running the kernel
 // (and the worker is still inside the call), so every later call is refused and yh_destroy frees nothing (hipFree would wait too).
 int wait_for_launch(yh_context* ctx) {
-  if (ctx->poisoned) return fail(ctx, YH_E_DEVICE, "a launch of this context exceeded its deadline: the context refuses further work, destroy it");
+  if (ctx->poisoned) return refuse_poisoned(ctx);
   const double timeout = yhh::launch_timeout_s();
   const int    device  = ctx->device;
   hipStream_t  stream  = ctx->stream;
@@ -42,7 +42,7 @@ int wait_for_launch(yh_context* ctx) {
 
 int yh_init_state(yh_context* ctx, const yh_trace_params* params) {
   if (!ctx) return YH_E_INVALID;
-  if (ctx->poisoned) return fail(ctx, YH_E_DEVICE, "a launch of this context exceeded its deadline: the context refuses further work, destroy it");
+  if (ctx->poisoned) return refuse_poisoned(ctx);
   if (!ctx->have_scene) return fail(ctx, YH_E_STATE, "yh_init_state before yh_upload_scene");
   if (!params || params->resolution <= 0 || params->bounces < 0)
     return fail(ctx, YH_E_INVALID, "bad trace params");
