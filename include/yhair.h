@@ -750,6 +750,53 @@ int yh_lights_batch(yh_context* ctx, int form, int n, const float* position,
 int yh_volume_batch(yh_context* ctx, int form, int tex, int n,
     const yh_material* materials, const float* normal, const float* outgoing,
     const float* incoming, const float* texval, const float* rn, float* out);
+/* The shading point of a hit, row by row on the uploaded scene with its maps:
+ * what the sample loops make of a closest hit before the lobes are sampled
+ * (csrc/dev_path.h: eval_hit, eval_hit_fetch_first, eval_texcoord, eval_maps,
+ * eval_normalmap, eval_hit_maps, the shading-normal rule and the head of
+ * path_step / shade_step up to surface_brdf; csrc/dev_surface.h:
+ * eval_texture), the loops' own functions in the order the head of path_step
+ * calls them, then medium_crossing from outside with incoming = -outgoing.
+ * Per row: object, element (the caller's element; a small kernel inverts the
+ * leaf order of the shapes the batch names to find the hit's leaf slot — a
+ * diagnostic, like yh_shape_nodes), uv[2], outgoing[3] (as given: not
+ * normalised). Each form reads its rows where the loop it stands for reads
+ * them:
+ *   form 0  launch shape 0 on this scene, a quad per row. Plain scene: object
+ *           and material rows from LDS, eval_hit_fetch_first, no maps, no
+ *           mixture. General scene: rows from memory, eval_hit +
+ *           eval_hit_maps, the mixture unless the material is plain.
+ *   form 1  the streaming kernel, a lane per row: rows from LDS on a plain
+ *           scene, else from memory; eval_hit (+ eval_hit_maps).
+ *   form 2  the 256-thread shape and shade_step, a quad per row: rows from
+ *           memory whatever the scene, eval_hit + eval_hit_maps, the mixture
+ *           for every material.
+ * out: YH_POINT_FLOATS per row, the columns below. Where the loop computes no
+ * mixture (a plain material on a plain variant) the row reports what its
+ * diffuse-only path works with — the colour as the diffuse weight, roughness
+ * and opacity 1, the pdfs (the row's diffuse_pdf, 0, 0, 0, 0) — which is what
+ * eval_brdf makes of such a material. The texcoord is the one the loop has:
+ * eval_texcoord where the material has a texture or a map, else the element
+ * uv it keeps. YH_E_STATE before an upload; YH_E_INVALID for n < 1, a NULL
+ * pointer, an unknown form, an object outside the scene or an element outside
+ * its shape (found before anything follows the index).                       */
+#define YH_POINT_POSITION        0 /* [3] eval_position                                        */
+#define YH_POINT_NORMAL          3 /* [3] eval_normal                                          */
+#define YH_POINT_SHADING_NORMAL  6 /* [3] eval_shading_normal, the normal map included         */
+#define YH_POINT_TEXCOORD        9 /* [2] eval_texcoord                                        */
+#define YH_POINT_COLOR_TEX      11 /* [3] eval_texture(color_tex)                              */
+#define YH_POINT_EMISSION_TEX   14 /* [3] eval_texture(emission_tex)                           */
+#define YH_POINT_EMISSION_TEX_X 17 /*     eval_texture(emission_tex, linear).x                 */
+#define YH_POINT_SCATTERING_TEX 18 /* [3] eval_texture(scattering_tex)                         */
+#define YH_POINT_EMISSION       21 /* [3] eval_emission                                        */
+#define YH_POINT_BSDF           24 /* [22] the leading floats of YH_SURFACE_BSDF_FLOATS: the
+                                      five lobe weights, roughness, opacity, the five pdfs     */
+#define YH_POINT_DENSITY        46 /* [3] eval_vsdf of the medium entered straight through the */
+#define YH_POINT_SCATTER        49 /* [3] surface (pt.cpp:1458-1467 with incoming = -outgoing) */
+#define YH_POINT_ANISOTROPY     52 /*     for a material with a volume; zero otherwise         */
+#define YH_POINT_FLOATS         53
+int yh_point_batch(yh_context* ctx, int form, int n, const int* object,
+    const int* element, const float* uv, const float* outgoing, float* out);
 /* The quad forms of the trimmed 512-thread kernels next to the plain forms
  * whose bits they render (csrc/dev_surface.h: sample_hemisphere_cos_quad,
  * csrc/dev_math.h: quad_div), a quad per row. normal, a: 3n; rn: 2n (rx, ry);

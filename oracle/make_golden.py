@@ -104,11 +104,31 @@ def lobe_inputs(rng, n):
     return p, nn, wo, wi.astype(np.float32), rn
 
 
+def points_unit():
+    """The oracle's shading points (yo_scene_point_batch) on the strata of tests/point_cases.py, general scene: stratum a whole, GOLDEN_ROWS
+    rows of each edge stratum. The oracle's maps are pinned by the reference's images (maps.npz); these rows pin the oracle's unit-level
+    entry point to what it gave when that held, inputs included. Needs no reference."""
+    import point_cases as pc
+    oracle = oc.Oracle()
+    osc = oracle.scene(*pc.scene(True).desc(yh))
+    out = {}
+    for name in pc.STRATA:
+        s = pc.inputs(name, osc)
+        k = pc.ROWS if name == "a" else pc.GOLDEN_ROWS
+        out[f"{name}_object"], out[f"{name}_element"], out[f"{name}_uv"], out[f"{name}_outgoing"] = s.obj[:k], s.elem[:k], s.uv[:k], s.wo[:k]
+        out[f"{name}_point"] = osc.point(s.obj[:k], s.elem[:k], s.uv[:k], s.wo[:k])
+    np.savez_compressed(os.path.join(GOLD, "points_unit.npz"), **out)
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
-    ref = oc.Ref()
     only = sys.argv[1:]  # e.g. `make_golden.py lobes` regenerates just the fixtures whose name contains "lobes"
     want = lambda tag: not only or any(o in tag for o in only)  # noqa: E731
+    if want("points_unit.npz"):
+        points_unit()
+        if only and all(o in "points_unit.npz" for o in only):
+            return
+    ref = oc.Ref()
 
     # ---- surface lobes (math.h:4215-4755), its own generator so older fixtures never move ------
     if want("lobes.npz"):

@@ -580,6 +580,7 @@ struct Material {
   V3           scattering{0, 0, 0};
   float        scanisotropy = 0, trdepth = 0.01f;
   int          emission_tex = -1, color_tex = -1, scattering_tex = -1;  // index into yo_scene::textures
+  int          specular_tex = -1, metallic_tex = -1, roughness_tex = -1, opacity_tex = -1, normal_tex = -1;  // the maps (pt.h:311-320)
   HairMaterial hair;
   bool         thin;
 };
@@ -906,12 +907,59 @@ V3 eval_normal(const yo_scene& scene, int object, int element, const float uv[2]
   }
   return {0, 0, 0};
 }
+// triangle_tangents_fromuv (math.h:3360-3383)
+void triangle_tangents_fromuv(V3 p0, V3 p1, V3 p2, const float* uv0, const float* uv1, const float* uv2, V3& tu, V3& tv) {
+  auto  p = p1 - p0, q = p2 - p0;
+  float sx = uv1[0] - uv0[0], sy = uv2[0] - uv0[0];
+  float tx = uv1[1] - uv0[1], ty = uv2[1] - uv0[1];
+  auto  div = sx * ty - sy * tx;
+  if (div != 0) {
+    tu = V3{ty * p.x - tx * q.x, ty * p.y - tx * q.y, ty * p.z - tx * q.z} / div;
+    tv = V3{sx * q.x - sy * p.x, sx * q.y - sy * p.y, sx * q.z - sy * p.z} / div;
+  } else {
+    tu = {1, 0, 0}, tv = {0, 1, 0};
+  }
+}
+// eval_element_tangents (pt.cpp:314-327): zero tangents for a shape without texture coordinates
+void eval_element_tangents(const yo_scene& scene, int object, int element, V3& tu, V3& tv) {
+  auto& obj   = scene.objects[object];
+  auto& shape = scene.shapes[obj.shape];
+  tu = {0, 0, 0}, tv = {0, 0, 0};
+  if (shape.ntriangles() && !shape.texcoords.empty()) {
+    auto t = &shape.triangles[3 * element];
+    triangle_tangents_fromuv(shape.positions[t[0]], shape.positions[t[1]], shape.positions[t[2]], &shape.texcoords[2 * t[0]],
+        &shape.texcoords[2 * t[1]], &shape.texcoords[2 * t[2]], tu, tv);
+    tu = transform_direction(obj.frame, tu), tv = transform_direction(obj.frame, tv);
+  }
+}
+// eval_normalmap (pt.cpp:329-347)
+V3 eval_normalmap(const yo_scene& scene, int object, int element, const float uv[2]) {
+  auto& obj        = scene.objects[object];
+  auto& shape      = scene.shapes[obj.shape];
+  auto  normal_tex = texture_of(scene, scene.materials[obj.material].normal_tex);
+  auto  normal     = eval_normal(scene, object, element, uv);
+  float tc[2];
+  eval_texcoord(scene, object, element, uv, tc);
+  if (normal_tex && shape.ntriangles()) {
+    auto normalmap = 2 * eval_texture(normal_tex, tc, true) + (-1.0f);  // -1 + 2 * texture
+    V3   tu, tv;
+    eval_element_tangents(scene, object, element, tu, tv);
+    auto fz = normal;
+    auto fx = orthonormalize(tu, fz);
+    auto fy = normalize(cross(fz, fx));
+    auto flip_v = dot(fy, tv) < 0;
+    normalmap.y *= flip_v ? 1 : -1;  // flip vertical axis
+    normal = normalize(fx * normalmap.x + fy * normalmap.y + fz * normalmap.z);  // transform_normal (math.h:3145-3152)
+  }
+  return normal;
+}
 V3 eval_shading_normal(const yo_scene& scene, int object, int element,
     const float uv[2], V3 outgoing) {  // pt.cpp:350-369
   auto& obj   = scene.objects[object];
   auto& shape = scene.shapes[obj.shape];
   if (shape.ntriangles()) {
     auto normal = eval_normal(scene, object, element, uv);
+    if (scene.materials[obj.material].normal_tex >= 0) normal = eval_normalmap(scene, object, element, uv);
     if (!scene.materials[obj.material].thin) return normal;
     return dot(normal, outgoing) >= 0 ? normal : -normal;
   } else if (shape.nlines()) {
@@ -1200,7 +1248,7 @@ float sample_delta_refraction_pdf(float ior, V3 normal, V3 outgoing, V3 incoming
 
 // ---------------------------------------------------------------------------
 // eval_brdf and the lobe dispatch (pt.cpp:372-394, 405-495, 1069-1280).
-// Textures are out of scope: every eval_texture(nullptr) factor is 1.
+// A missing texture's factor is eval_texture(nullptr) = {1, 1, 1}.
 // ---------------------------------------------------------------------------
 struct Brdf {
   V3       diffuse{0, 0, 0}, specular{0, 0, 0}, metal{0, 0, 0}, transmission{0, 0, 0},
@@ -1213,15 +1261,21 @@ struct Brdf {
   HairBrdf hair_brdf;
 };
 // color_tex = eval_texture(color_tex, texcoord, false); emission_tex_x = eval_texture(emission_tex,
-// texcoord, true).x — the reference multiplies TRANSMISSION by the emission texture (pt.cpp:421-422)
-Brdf surface_brdf(const Material& mat, V3 normal, V3 outgoing, V3 color_tex = {1, 1, 1}, float emission_tex_x = 1.0f) {  // pt.cpp:405-471
+// texcoord, true).x — the reference multiplies TRANSMISSION by the emission texture (pt.cpp:421-422). maps: the .x of the
+// specular, metallic and roughness textures and the opacity texture's value, each looked up linear (pt.cpp:413-424).
+struct MapValues {
+  float specular = 1, metallic = 1, roughness = 1;
+  V3    opacity{1, 1, 1};
+};
+Brdf surface_brdf(const Material& mat, V3 normal, V3 outgoing, V3 color_tex = {1, 1, 1}, float emission_tex_x = 1.0f,
+    const MapValues& maps = MapValues{}) {  // pt.cpp:405-471
   auto base         = mat.color * color_tex;
-  auto specular     = mat.specular * 1.0f;
-  auto metallic     = mat.metallic * 1.0f;
-  auto roughness    = mat.roughness * 1.0f;
+  auto specular     = mat.specular * maps.specular;
+  auto metallic     = mat.metallic * maps.metallic;
+  auto roughness    = mat.roughness * maps.roughness;
   auto ior          = mat.ior;
   auto transmission = mat.transmission * emission_tex_x;
-  auto opacity      = mat.opacity * ((1.0f + 1.0f + 1.0f) / 3);
+  auto opacity      = mat.opacity * ((maps.opacity.x + maps.opacity.y + maps.opacity.z) / 3);  // mean (math.h:2095)
   auto thin         = mat.thin || !mat.transmission;
 
   Brdf brdf;
@@ -1267,8 +1321,13 @@ Brdf eval_brdf(const yo_scene& scene, int object, int element, const float uv[2]
   auto& shape = scene.shapes[obj.shape];
   float tc[2];
   eval_texcoord(scene, object, element, uv, tc);
+  MapValues maps;
+  maps.specular  = eval_texture(texture_of(scene, mat.specular_tex), tc, true).x;
+  maps.metallic  = eval_texture(texture_of(scene, mat.metallic_tex), tc, true).x;
+  maps.roughness = eval_texture(texture_of(scene, mat.roughness_tex), tc, true).x;
+  maps.opacity   = eval_texture(texture_of(scene, mat.opacity_tex), tc, true);
   auto brdf = surface_brdf(mat, normal, outgoing, eval_texture(texture_of(scene, mat.color_tex), tc, false),
-      eval_texture(texture_of(scene, mat.emission_tex), tc, true).x);
+      eval_texture(texture_of(scene, mat.emission_tex), tc, true).x, maps);
   brdf.hair   = shape.nlines() > 0;  // pt.cpp:474
   if (brdf.hair) {
     auto tangent   = eval_normal(scene, object, element, uv);
@@ -2241,7 +2300,8 @@ void yo_volume_batch(int tex, int n, const yh_material* materials, const float* 
   }
 }
 
-yo_scene* yo_scene_create(const yh_scene_desc* d) {
+yo_scene* yo_scene_create(const yh_scene_desc* d) { return yo_scene_create_maps(d, nullptr); }
+yo_scene* yo_scene_create_maps(const yh_scene_desc* d, const yh_material_maps* maps) {
   auto sc = new yo_scene{};
   for (int i = 0; i < d->num_textures; i++) {
     auto&   t = d->textures[i];
@@ -2282,6 +2342,11 @@ yo_scene* yo_scene_create(const yh_scene_desc* d) {
     mt.ior = m.ior, mt.transmission = m.transmission, mt.opacity = m.opacity;
     mt.scattering = v3(m.scattering), mt.scanisotropy = m.scanisotropy, mt.trdepth = m.trdepth;
     mt.emission_tex = m.emission_tex - 1, mt.color_tex = m.color_tex - 1, mt.scattering_tex = m.scattering_tex - 1;
+    if (maps) {  // (transmission_tex is read by no lookup: pt.cpp:421-422 scales transmission by the emission texture)
+      auto& mp = maps[i];
+      mt.specular_tex = mp.specular_tex - 1, mt.metallic_tex = mp.metallic_tex - 1, mt.roughness_tex = mp.roughness_tex - 1;
+      mt.opacity_tex = mp.opacity_tex - 1, mt.normal_tex = mp.normal_tex - 1;
+    }
     mt.hair.sigma_a = v3(m.sigma_a);
     mt.hair.beta_m = m.beta_m, mt.hair.beta_n = m.beta_n;
     mt.hair.alpha = m.alpha, mt.hair.eta = m.eta;
@@ -2330,6 +2395,46 @@ void yo_scene_intersect(const yo_scene* scene, int n, const float* rays, int* ob
     auto  hit = intersect_scene_bvh(*scene, mkray(rays + 8 * i), o, e, u, d);
     object[i] = hit ? o : -1, element[i] = hit ? e : -1;
     uv[2 * i] = u[0], uv[2 * i + 1] = u[1], dist[i] = d;
+  }
+}
+
+// The shading point of a hit as the renderers below make it (pt.cpp:1420-1426: eval_position, eval_shading_normal, eval_emission,
+// eval_brdf) with what they are made of (eval_normal, eval_texcoord, the textures' values) and the medium of pt.cpp:1458-1467 for a
+// path that goes straight through (incoming = -outgoing), row by row in the row layout of yh_point_batch.
+void yo_scene_point_batch(const yo_scene* scene_, int n, const int* object, const int* element, const float* uv, const float* outgoing,
+    float* out) {
+  auto& scene = *scene_;
+  for (int i = 0; i < n; i++) {
+    auto  ob = object[i], el = element[i];
+    auto  u  = uv + 2 * (size_t)i;
+    auto  wo = v3(outgoing + 3 * (size_t)i);
+    auto& mat = scene.materials[scene.objects[ob].material];
+    float tc[2];
+    eval_texcoord(scene, ob, el, u, tc);
+    auto position = eval_position(scene, ob, el, u);
+    auto nrm      = eval_normal(scene, ob, el, u);
+    auto normal   = eval_shading_normal(scene, ob, el, u, wo);
+    auto ctex     = eval_texture(texture_of(scene, mat.color_tex), tc, false);
+    auto etex     = eval_texture(texture_of(scene, mat.emission_tex), tc, false);
+    auto etex_x   = eval_texture(texture_of(scene, mat.emission_tex), tc, true).x;
+    auto stex     = eval_texture(texture_of(scene, mat.scattering_tex), tc, false);
+    auto emission = mat.emission * etex;  // pt.cpp:397-402
+    auto b        = eval_brdf(scene, ob, el, u, normal, wo);
+    Vsdf vsdf;
+    auto incoming = -wo;
+    if (has_volume(mat) && dot(normal, wo) * dot(normal, incoming) < 0) vsdf = eval_vsdf(mat, ctex, etex_x, stex);
+    auto o    = out + YH_POINT_FLOATS * (size_t)i;
+    auto put3 = [&](int at, V3 a) { o[at] = a.x, o[at + 1] = a.y, o[at + 2] = a.z; };
+    put3(YH_POINT_POSITION, position), put3(YH_POINT_NORMAL, nrm), put3(YH_POINT_SHADING_NORMAL, normal);
+    o[YH_POINT_TEXCOORD] = tc[0], o[YH_POINT_TEXCOORD + 1] = tc[1];
+    put3(YH_POINT_COLOR_TEX, ctex), put3(YH_POINT_EMISSION_TEX, etex), o[YH_POINT_EMISSION_TEX_X] = etex_x;
+    put3(YH_POINT_SCATTERING_TEX, stex), put3(YH_POINT_EMISSION, emission);
+    V3 lobes[5] = {b.diffuse, b.specular, b.metal, b.transmission, b.refraction};
+    for (int k = 0; k < 5; k++) put3(YH_POINT_BSDF + 3 * k, lobes[k]);
+    auto q = o + YH_POINT_BSDF;
+    q[15] = b.roughness, q[16] = b.opacity;
+    q[17] = b.diffuse_pdf, q[18] = b.specular_pdf, q[19] = b.metal_pdf, q[20] = b.transmission_pdf, q[21] = b.refraction_pdf;
+    put3(YH_POINT_DENSITY, vsdf.density), put3(YH_POINT_SCATTER, vsdf.scatter), o[YH_POINT_ANISOTROPY] = vsdf.anisotropy;
   }
 }
 

@@ -77,11 +77,23 @@ void yo_intersect_bbox(int n, const float* rays, const float* bbox, int* hit);
 
 /* init_bvh + init_lights (pt.cpp:755-818,1695-1740) on a copy of the scene */
 yo_scene* yo_scene_create(const yh_scene_desc* desc);
+/* The same with the materials' scalar and normal maps (eval_normalmap and eval_element_tangents, pt.cpp:314-347; the
+ * scalar maps of eval_brdf, :413-424; the opacity of :423-424, 453): `maps` holds desc->num_materials entries, or is
+ * NULL (yo_scene_create(desc) is yo_scene_create_maps(desc, NULL)).                                                  */
+yo_scene* yo_scene_create_maps(const yh_scene_desc* desc, const yh_material_maps* maps);
 void      yo_scene_free(yo_scene* scene);
 int       yo_scene_num_lights(const yo_scene* scene);
 /* pt.cpp:1039-1046; element/object -1 on miss */
 void yo_scene_intersect(const yo_scene* scene, int n, const float* rays,
     int* object, int* element, float* uv, float* dist);
+/* The shading point of a hit as yo_render makes it (pt.cpp:232-369, 396-471, 504-527), row by row, the counterpart of
+ * yh_point_batch: object n, element n, uv 2n, outgoing 3n (as given, not normalised); out YH_POINT_FLOATS per row, the
+ * columns of yhair.h (YH_POINT_*): eval_position, eval_normal, eval_shading_normal (normal map included), eval_texcoord,
+ * the colour, emission (and its linear .x) and scattering textures' values, eval_emission, what eval_brdf makes (the
+ * five lobe weights, roughness, opacity, the five pdfs) and eval_vsdf of the medium a path enters that goes straight
+ * through the surface (pt.cpp:1458-1467 with incoming = -outgoing; zero without a volume). Indices are not checked.  */
+void yo_scene_point_batch(const yo_scene* scene, int n, const int* object, const int* element, const float* uv,
+    const float* outgoing, float* out);
 /* Light `light` as init_lights (pt.cpp:1695-1740) made it: its object and environment (-1: none) and its
  * cdf (triangle areas or texel weights, accumulated); returns the cdf's length, -1 when there is no such
  * light. Every pointer may be NULL.                                                                      */

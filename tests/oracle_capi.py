@@ -136,10 +136,13 @@ class Oracle(_UnitApi):
         lib.yo_volume_batch.argtypes = [C.c_int, C.c_int, C.POINTER(yh.Material), fp, fp, fp, fp, fp, fp]
         lib.yo_scene_create.restype = C.c_void_p
         lib.yo_scene_create.argtypes = [C.POINTER(yh.SceneDesc)]
+        lib.yo_scene_create_maps.restype = C.c_void_p
+        lib.yo_scene_create_maps.argtypes = [C.POINTER(yh.SceneDesc), C.POINTER(yh.MaterialMaps)]
         lib.yo_scene_free.argtypes = [C.c_void_p]
         lib.yo_scene_num_lights.argtypes = [C.c_void_p]
         lib.yo_scene_intersect.argtypes = [C.c_void_p, C.c_int, fp, ip, ip, fp, fp]
         lib.yo_scene_intersect_counted.argtypes = [C.c_void_p, C.c_int, fp, ip, ip]
+        lib.yo_scene_point_batch.argtypes = [C.c_void_p, C.c_int, ip, ip, fp, fp, fp]
         lib.yo_scene_light.argtypes = [C.c_void_p, C.c_int, ip, ip, fp]
         lib.yo_scene_lights_batch.argtypes = [C.c_void_p, C.c_int, fp, fp, fp, fp, ip]
         lib.yo_scene_bvh.argtypes = [C.c_void_p, C.c_int, fp, ip]
@@ -176,14 +179,18 @@ class Oracle(_UnitApi):
                                  yh.fptr(out))
         return out
 
-    def scene(self, desc):
-        return OracleScene(self, desc)
+    def scene(self, desc, maps=None):
+        """yo_scene_create, or yo_scene_create_maps with `maps`: one MaterialMaps per material (e.g. SceneFile.maps)."""
+        return OracleScene(self, desc, maps)
 
 
 class OracleScene:
-    def __init__(self, oracle, desc):
+    def __init__(self, oracle, desc, maps=None):
         self.o = oracle
-        self.h = oracle.lib.yo_scene_create(desc)
+        if maps is None:
+            self.h = oracle.lib.yo_scene_create(desc)
+        else:
+            self.h = oracle.lib.yo_scene_create_maps(desc, C.cast(maps, C.POINTER(yh.MaterialMaps)))
 
     def close(self):
         if self.h:
@@ -203,6 +210,17 @@ class OracleScene:
         uv, dist = np.zeros((n, 2), np.float32), np.zeros(n, np.float32)
         self.o.lib.yo_scene_intersect(self.h, n, yh.fptr(rays), yh.iptr(obj), yh.iptr(elem), yh.fptr(uv), yh.fptr(dist))
         return obj, elem, uv, dist
+
+    def point(self, object, element, uv, outgoing):
+        """The shading point of a hit as the oracle's renderer makes it, the counterpart of yh_point_batch: (n, POINT_FLOATS), the
+        columns of yh.POINT_COLUMNS."""
+        object, element = np.ascontiguousarray(object, np.int32), np.ascontiguousarray(element, np.int32)
+        uv, outgoing = _f(uv).reshape(-1, 2), _f(outgoing).reshape(-1, 3)
+        n = len(object)
+        assert len(element) == n and len(uv) == n and len(outgoing) == n
+        out = np.zeros((n, yh.POINT_FLOATS), np.float32)
+        self.o.lib.yo_scene_point_batch(self.h, n, yh.iptr(object), yh.iptr(element), yh.fptr(uv), yh.fptr(outgoing), yh.fptr(out))
+        return out
 
     def light(self, k):
         """Light k as init_lights made it: (object, environment, cdf)."""

@@ -42,6 +42,28 @@ SHADER_CASES = [
 ]
 
 
+# The `maps` scene and its one-map variants (tools/make_scenes.py: make_maps), as tests/golden/maps.npz holds them
+# (tools/make_map_goldens.py): (prefix of the fixture's keys, scene keywords, the fixture's key of the resolution, shaders).
+MAP_KINDS = ["specular", "metallic", "roughness", "opacity", "normal"]
+MAPS_CASES = [("", {}, "res", ["path", "naive", "eyelight", "normal"])] + [
+    (f"only-{kind}/", dict(only=kind), "vres", ["path", "naive", "eyelight"]) for kind in MAP_KINDS]
+
+
+def maps_entries(api, scene_path, g, prefix, kw, res_key, shaders):
+    """What `api` renders for every `*_1`, `*_8` and `*_8_s777` entry of the maps fixture `g` under `prefix`, and `rng_8`."""
+    out = {}
+    for shader in shaders:
+        for suffix, spp, seed in (("_1", 1, None), ("_8", 8, None), ("_8_s777", 8, int(g["seeds"][1]))):
+            key = f"{prefix}{shader}{suffix}"
+            if key not in g.files:
+                continue
+            r = render(api, scene_path, "maps", kw, int(g[res_key]), spp, shader, seed)
+            out[key] = r["image"]
+            if key == "path_8":
+                out["rng_8"] = r["rng"]
+    return out
+
+
 def digest(a):
     """sha256 of an array, with np.array_equal(..., equal_nan=True)'s notion of equality: every NaN alike, -0 == +0."""
     a = np.ascontiguousarray(a)
@@ -103,15 +125,16 @@ def curve_conversion_random_inputs(api):
     return dict(zip(("positions", "normals", "radius", "lines"), api.curves_to_lines(P, w0, w1, 3)))
 
 
-def render(api, scene_path, name, kw, res, spp, shader="path"):
-    """The image and the per-pixel RNG states after `spp` samples of the scene; scene_path(name, **kw) gives its JSON."""
+def render(api, scene_path, name, kw, res, spp, shader="path", seed=None):
+    """The image and the per-pixel RNG states after `spp` samples of the scene; scene_path(name, **kw) gives its JSON. The
+    oracle gets the materials' maps the scene file names, as the reference's loader gives them to the reference."""
     path = scene_path(name, **kw)
-    p = yh.TraceParams.default(resolution=res, shader=shader)
+    p = yh.TraceParams.default(resolution=res, shader=shader) if seed is None else yh.TraceParams.default(resolution=res, shader=shader, seed=seed)
     if isinstance(api, oc.Ref):
         sc, sf = api.scene(path), None
     else:
         sf = yh.SceneFile(path)
-        sc = api.scene(sf.desc)
+        sc = api.scene(sf.desc, sf.maps)
     img, rng = sc.render(p, spp, want_rng=True)
     sc.close()
     if sf is not None:

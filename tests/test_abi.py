@@ -26,12 +26,19 @@ def test_library_exports_every_declared_symbol(yh):
         assert hasattr(lib, name), f"libyhair.so does not export {name}"
     # and the Python binding covers the same set
     assert sorted(yh.EXPORTS) == declared
-    assert {"yh_volume_batch", "yh_quad_forms_batch"} <= set(declared)
+    assert {"yh_volume_batch", "yh_quad_forms_batch", "yh_point_batch"} <= set(declared)
     # ... and the row widths the binding allocates are the header's
     header = open(os.path.join(ROOT, "include", "yhair.h")).read()
-    for define, value in (("YH_VOLUME_FLOATS", yh.VOLUME_FLOATS), ("YH_QUAD_FORMS_FLOATS", yh.QUAD_FORMS_FLOATS),
+    for define, value in (("YH_VOLUME_FLOATS", yh.VOLUME_FLOATS), ("YH_QUAD_FORMS_FLOATS", yh.QUAD_FORMS_FLOATS), ("YH_POINT_FLOATS", yh.POINT_FLOATS),
                           ("YH_HAIR_SHADE_FLOATS", yh.HAIR_SHADE_FLOATS), ("YH_SURFACE_BSDF_FLOATS", yh.SURFACE_BSDF_FLOATS)):
         assert re.search(rf"#define {define} +{value}\b", header), define
+    # ... and the columns of a yh_point_batch row, by name
+    offsets = {m.group(1).lower(): int(m.group(2)) for m in re.finditer(r"#define YH_POINT_([A-Z_]+?) +(\d+)\b", header)}
+    assert offsets.pop("floats") == yh.POINT_FLOATS and sorted(offsets) == sorted(yh.POINT_COLUMNS)
+    order = sorted(offsets, key=offsets.get)
+    for name, nxt in zip(order, order[1:] + [None]):
+        c = yh.POINT_COLUMNS[name]
+        assert (c.start, c.stop) == (offsets[name], offsets[nxt] if nxt else yh.POINT_FLOATS), name
     assert b"gfx950" in lib.yh_version()
 
 

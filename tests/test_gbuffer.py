@@ -17,6 +17,7 @@ from test_scene_edits import Edited
 from test_object_edits import CROWD, HAIRBLOCK, Moved, _compose, _rotation, _translation
 from test_shape_edits import Reshaped, _edited, _sway
 from test_shape_refit import TIE_PIXELS
+from point_f64 import _texture64  # eval_texture in float64 (shared with the shading-point tests)
 from test_instances import GOLDEN_KW as FIELD_KW  # 339 objects: the scene level is walked as 4-wide nodes
 
 F = np.float32
@@ -224,25 +225,6 @@ def test_axis_parallel_centre_ray_takes_the_exact_redo(ctx, oracle, yh, scenes):
 # ---------------------------------------------------------------------------------------------
 # 5. the derived planes against float64 numpy
 # ---------------------------------------------------------------------------------------------
-def _srgb_to_linear(c):
-    return np.where(c <= 0.04045, c / 12.92, ((c + 0.055) / 1.055) ** 2.4)
-
-
-def _texture64(t, tu, tv):
-    """eval_texture (pt.cpp:167-200) of a colour texture, float64: wrap, bilinear, bytes decoded from sRGB."""
-    w, h = t.width, t.height
-    if t.is_byte:
-        px = _srgb_to_linear(np.ctypeslib.as_array(C.cast(t.pixels, C.POINTER(C.c_uint8)), (h, w, 3)).astype(np.float64) / 255)
-    else:
-        px = np.ctypeslib.as_array(C.cast(t.pixels, C.POINTER(C.c_float)), (h, w, 3)).astype(np.float64)
-    s, tt = np.fmod(tu, 1.0) * w, np.fmod(tv, 1.0) * h
-    s, tt = np.where(s < 0, s + w, s), np.where(tt < 0, tt + h, tt)
-    i, j = np.clip(s.astype(np.int64), 0, w - 1), np.clip(tt.astype(np.int64), 0, h - 1)
-    ii, jj = (i + 1) % w, (j + 1) % h
-    u, v = (s - i)[:, None], (tt - j)[:, None]
-    return px[j, i] * (1 - u) * (1 - v) + px[jj, i] * (1 - u) * v + px[j, ii] * u * (1 - v) + px[jj, ii] * u * v
-
-
 def _unit(a):
     return a / np.linalg.norm(a, axis=-1, keepdims=True)
 

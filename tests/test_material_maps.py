@@ -1,5 +1,7 @@
 """Scalar material textures and normal maps (yh_material_maps, yh_upload_scene_maps): the `maps` scene of tools/make_scenes.py
-against the REFERENCE's own images of it (tests/golden/maps.npz, tools/make_map_goldens.py; the CPU oracle does not know maps).
+against the REFERENCE's own images of it (tests/golden/maps.npz, tools/make_map_goldens.py). The CPU oracle knows the maps too
+(yo_scene_create_maps) and renders these very images bit for bit (tests/test_oracle_golden.py::test_material_maps_bit_exact); row by
+row the maps are held to it at unit level in tests/test_point_unit.py.
 
 CPU: the scene reader's keys and indices, the mirror's setters with texture arguments, the fixture against a live render of the
 reference where oracle/_ref is built. GPU: the four shaders against the reference with the bars of the other shader tests, the

@@ -72,6 +72,24 @@ def test_volume_functions_bit_exact(oracle, yh):
         assert len(differ) == 0, (name, differ[:5], view[differ[:2]], g[f"{name}_ref"][differ[:2]])
 
 
+def test_shading_points_bit_exact(oracle, yh):
+    """yo_scene_point_batch on the strata of tests/point_cases.py (general scene: stratum a whole, GOLDEN_ROWS rows of each edge
+    stratum) against the committed rows, bit for bit; the committed inputs are the strata's."""
+    import point_cases as pc
+    g = golden("points_unit.npz")
+    osc = oracle.scene(*pc.scene(True).desc(yh))
+    for name in pc.STRATA:
+        s = pc.inputs(name, osc)
+        k = pc.ROWS if name == "a" else pc.GOLDEN_ROWS
+        for key, got in (("object", s.obj[:k]), ("element", s.elem[:k]), ("uv", s.uv[:k]), ("outgoing", s.wo[:k])):
+            assert np.array_equal(got, g[f"{name}_{key}"]), (name, key)
+        got, want = osc.point(s.obj[:k], s.elem[:k], s.uv[:k], s.wo[:k]), g[f"{name}_point"]
+        assert want.shape == (k, yh.POINT_FLOATS)
+        differ = np.flatnonzero((got.view(np.uint32) != want.view(np.uint32)).any(axis=1))
+        assert len(differ) == 0, (name, differ[:5])
+    osc.close()
+
+
 def test_surface_lobes_bit_exact(oracle, yh):
     """Fresnel terms and the nine surface lobes (yocto_math.h:4215-4755)
     — value * |cos|, pdf and sampled direction — against vectors made by the reference."""
@@ -170,6 +188,29 @@ def test_other_shaders_bit_exact(oracle, yh):
     with pytest.raises(Exception):
         sc.render(yh.TraceParams.default(resolution=16, shader=9), 1)
     sc.close(), sf.close()
+
+
+def _maps_ids():
+    import ref_cases as rc
+    return rc.MAPS_CASES
+
+
+@pytest.mark.parametrize("prefix,kw,res_key,shaders", _maps_ids(), ids=[c[0].strip("/") or "maps" for c in _maps_ids()])
+def test_material_maps_bit_exact(oracle, yh, prefix, kw, res_key, shaders):
+    """The materials' maps (eval_normalmap and eval_element_tangents, pt.cpp:314-347; the scalar maps of eval_brdf, :413-424; the
+    opacity rule): the oracle's renders of the `maps` scene and of its five one-map variants against EVERY `*_1`, `*_8` and
+    `*_8_s777` image the reference rendered of them (tests/golden/maps.npz) — path, naive, eyelight and normal — and the
+    pixels' RNG states after path_8, bit for bit. The reference's eval_* are static, so this fixture is what holds the
+    restatement to it."""
+    import ref_cases as rc
+    g = golden("maps.npz")
+    got = rc.maps_entries(oracle, scene_path, g, prefix, kw, res_key, shaders)
+    want = [k for k in g.files if k.startswith(prefix) and "/" not in k[len(prefix):] and k != "rng_8" and k.split("_")[-1] in ("1", "8", "s777")]
+    assert sorted(k for k in got if k != "rng_8") == sorted(want) and len(want) == (11 if not prefix else 9)
+    for k in want:
+        assert np.array_equal(got[k], g[k], equal_nan=True), (k, int((got[k] != g[k]).any(axis=2).sum()))
+    if not prefix:
+        assert np.array_equal(got["rng_8"], g["rng_8"])
 
 
 REF_SCENE_NAMES = ["sloth", "bold-man", "straight-hair", "curly-hair", "hair-curls", "sphere-hairblock"]

@@ -90,3 +90,18 @@ def test_images_bit_identical_to_reference(oracle, ref, yh, name, kw, res, spp):
 @pytest.mark.parametrize("name,kw,res,spp", rc.SHADER_CASES)
 def test_other_shaders_bit_identical_to_reference(oracle, ref, yh, name, kw, res, spp, shader):
     _check(rc.image_key(name, kw, res, spp, shader), lambda api: rc.render(api, scene_path, name, kw, res, spp, shader), oracle, ref)
+
+
+@pytest.mark.parametrize("prefix,kw,res_key,shaders", rc.MAPS_CASES, ids=[c[0].strip("/") or "maps" for c in rc.MAPS_CASES])
+def test_material_maps_bit_identical_to_reference(oracle, ref, yh, prefix, kw, res_key, shaders):
+    """The `maps` scene and its one-map variants: the oracle's renders against the LIVE reference's, bit for bit, where it is
+    built. Everywhere else the reference's committed images of the same renders (tests/golden/maps.npz,
+    test_oracle_golden.py::test_material_maps_bit_exact) are what holds the oracle."""
+    from conftest import golden
+    g = golden("maps.npz")
+    got = rc.maps_entries(oracle, scene_path, g, prefix, kw, res_key, shaders)
+    assert got
+    if ref is not None:
+        live = rc.maps_entries(ref, scene_path, g, prefix, kw, res_key, shaders)
+        for k in got:
+            assert np.array_equal(got[k], live[k], equal_nan=True), f"{k} differs from the live reference"

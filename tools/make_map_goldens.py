@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Writes tests/golden/maps.npz: the REFERENCE's own images of the `maps` scene (tools/make_scenes.py: make_maps), rendered
-with oracle/_ref/libyh_ref.so (built by `make -C oracle ref`) through tests/oracle_capi.Ref. The CPU oracle does not know
-scalar or normal maps, so the parity of the maps (tests/test_material_maps.py) is checked against these.
+with oracle/_ref/libyh_ref.so (built by `make -C oracle ref`) through tests/oracle_capi.Ref. They are what holds the
+CPU oracle's restatement of the maps to the reference (tests/test_oracle_golden.py renders every entry bit for bit) and what the
+parity of the maps on the device (tests/test_material_maps.py) is checked against.
 
 Entries (float32 (H, W, 4) images unless noted):
   <shader>_<spp>             the whole scene, shader in path / naive / eyelight / normal, spp 1 and 8, seed 961748941, RES^2

@@ -1,5 +1,5 @@
 // batch_api.cpp — the unit-level batch entry points of include/yhair.h (hair BSDF, intersection, BVH build, curves, self-tests).
-#include "context_internal.h"
+#include "edit_internal.h"
 
 // ---- unit-level batches ----------------------------------------------------
 namespace {
@@ -414,6 +414,44 @@ int yh_volume_batch(yh_context* ctx, int form, int tex, int n, const yh_material
   int e = form == 0 ? yhk_volume_quads(&empty, n, dm, dn, da, db, dt, dr, ds, o, ctx->stream)
                     : yhk_volume_lanes(&empty, n, dm, dn, da, db, dt, dr, ds, o, ctx->stream);
   return finish(ctx, e, out, o, 4 * YH_VOLUME_FLOATS * (size_t)n);
+}
+
+// The shading point of a hit (dev_path.h: the head of path_step / shade_step up to surface_brdf) on the uploaded scene. The loops know a hit by
+// its leaf slot, the caller by its element: the leaf order of every shape the batch names is inverted on the device first (unit/point_quad.hip:
+// k_point_slots), work proportional to those shapes.
+int yh_point_batch(yh_context* ctx, int form, int n, const int* object, const int* element, const float* uv, const float* outgoing, float* out) {
+  if (!ctx || n < 1 || form < 0 || form > 2 || !object || !element || !uv || !outgoing || !out) return YH_E_INVALID;
+  if (!ctx->have_scene) return fail(ctx, YH_E_STATE, "yh_point_batch before yh_upload_scene");
+  const std::vector<yh_object> rows = uploaded_rows(ctx);
+  const int num_objects = ctx->scene.num_objects, num_shapes = (int)ctx->lane_shapes.size();
+  std::vector<int> shape_base((size_t)num_shapes, -1), shape_object((size_t)num_shapes, -1), slot_base((size_t)num_objects, 0);
+  int total = 0;
+  for (int i = 0; i < n; i++) {  // every index, before anything follows one
+    if (object[i] < 0 || object[i] >= num_objects) return fail(ctx, YH_E_INVALID, "yh_point_batch: row %d names object %d of %d", i, object[i], num_objects);
+    const int shape = rows[(size_t)object[i]].shape, num = ctx->lane_shapes[(size_t)shape].num_prims;
+    if (element[i] < 0 || element[i] >= num) return fail(ctx, YH_E_INVALID, "yh_point_batch: row %d names element %d of object %d, whose shape has %d", i, element[i], object[i], num);
+    if (shape_base[(size_t)shape] < 0) shape_base[(size_t)shape] = total, shape_object[(size_t)shape] = object[i], total += num;
+  }
+  for (int k = 0; k < num_objects; k++) slot_base[(size_t)k] = std::max(0, shape_base[(size_t)rows[(size_t)k].shape]);
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  Staged s(ctx);
+  auto   dob = (int*)s.in(object, 4 * (size_t)n);
+  auto   del = (int*)s.in(element, 4 * (size_t)n);
+  auto   dsb = (int*)s.in(slot_base.data(), 4 * (size_t)num_objects);
+  auto   duv = (float*)s.in(uv, 8 * (size_t)n);
+  auto   dwo = (float*)s.in(outgoing, 12 * (size_t)n);
+  auto   dso = (int*)s.out(4 * (size_t)total);
+  auto   dsl = s.out(32 * (size_t)n);
+  auto   o   = (float*)s.out(4 * YH_POINT_FLOATS * (size_t)n);
+  if (s.rc) return s.rc;
+  for (int k = 0; k < num_shapes; k++) {
+    if (shape_base[(size_t)k] < 0) continue;
+    int e = yhk_point_slots(&ctx->scene, shape_object[(size_t)k], ctx->lane_shapes[(size_t)k].num_prims, dso + shape_base[(size_t)k], ctx->stream);
+    if (e) return fail(ctx, YH_E_DEVICE, "k_point_slots launch: %s", hipGetErrorString((hipError_t)e));
+  }
+  int e = form == 1 ? yhk_point_lanes(&ctx->scene, form, n, dob, del, dso, dsb, duv, dwo, dsl, o, ctx->stream)
+                    : yhk_point_quads(&ctx->scene, form, n, dob, del, dso, dsb, duv, dwo, dsl, o, ctx->stream);
+  return finish(ctx, e, out, o, 4 * YH_POINT_FLOATS * (size_t)n);
 }
 
 int yh_quad_forms_batch(yh_context* ctx, int n, const float* normal, const float* rn, const float* a, const float* b, float* out) {

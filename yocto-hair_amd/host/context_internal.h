@@ -97,6 +97,13 @@ int yhk_hair_shade(int form, int n, const void* mats, const float* v, const floa
     const float* rn, float* out, hipStream_t);
 int yhk_hair_shade_exact(int form, int n, const void* mats, const float* v, const float* normal, const float* tangent, const float* outgoing,
     const float* incoming, const float* rn, float* out, hipStream_t);
+// unit/point_quad.hip, unit/point_lane.hip (yh_point_batch): slot_of = the leaf slots by element of the shapes the batch names (yhk_point_slots: one shape,
+// through an object that has it), slot_base = per object where its shape's begin there; slots = 2n float4 (the lane form's medium_mem)
+int yhk_point_slots(const yhd_scene* sc, int object, int num, int* slot_of, hipStream_t);
+int yhk_point_quads(const yhd_scene* sc, int form, int n, const int* object, const int* element, const int* slot_of, const int* slot_base, const float* uv,
+    const float* outgoing, void* slots, float* out, hipStream_t);
+int yhk_point_lanes(const yhd_scene* sc, int form, int n, const int* object, const int* element, const int* slot_of, const int* slot_base, const float* uv,
+    const float* outgoing, void* slots, float* out, hipStream_t);
 // unit/volume_quad.hip, unit/volume_lane.hip (yh_volume_batch): mats = n rows of yhd_material, texval 4n, rn 5n, slots = 2n float4 (the lane form's medium_mem)
 int yhk_volume_quads(const yhd_scene* sc, int n, const void* mats, const float* normal, const float* outgoing, const float* incoming, const float* texval,
     const float* rn, void* slots, float* out, hipStream_t);

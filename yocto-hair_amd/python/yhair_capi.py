@@ -19,6 +19,12 @@ HAIR_SHADE_FLOATS = 15
 SURFACE_BSDF_FLOATS = 29
 VOLUME_FLOATS = 24
 QUAD_FORMS_FLOATS = 12
+# yh_point_batch: the columns of a row (include/yhair.h: YH_POINT_*)
+POINT_FLOATS = 53
+POINT_COLUMNS = {"position": slice(0, 3), "normal": slice(3, 6), "shading_normal": slice(6, 9), "texcoord": slice(9, 11),
+                 "color_tex": slice(11, 14), "emission_tex": slice(14, 17), "emission_tex_x": slice(17, 18),
+                 "scattering_tex": slice(18, 21), "emission": slice(21, 24), "bsdf": slice(24, 46), "density": slice(46, 49),
+                 "scatter": slice(49, 52), "anisotropy": slice(52, 53)}
 (LOBE_DIFFUSE, LOBE_SPECULAR, LOBE_METAL, LOBE_TRANSMISSION, LOBE_REFRACTION, LOBE_DELTA_SPECULAR,
  LOBE_DELTA_METAL, LOBE_DELTA_TRANSMISSION, LOBE_DELTA_REFRACTION) = range(9)
 LOBE_COUNT = 9
@@ -235,6 +241,7 @@ _SIGS = {
     "yh_lights_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),
     "yh_volume_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Material), c_float_p, c_float_p, c_float_p, c_float_p,
                                   c_float_p, c_float_p]),
+    "yh_point_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_float_p, c_float_p, c_float_p]),
     "yh_quad_forms_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p]),
     "yh_selftest": (C.c_int, [C.c_void_p, C.c_int, c_float_p]),
     "yh_scene_load": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]),
@@ -705,6 +712,18 @@ class Context:
         assert all(len(x) == n for x in a)
         out = np.zeros((n, VOLUME_FLOATS), np.float32)
         self._chk(self.lib.yh_volume_batch(self.h, form, tex, n, mats, *(fptr(x) for x in a), fptr(out)))
+        return out
+
+    def point(self, form, object, element, uv, outgoing):
+        """yh_point_batch: the shading point of a hit on the uploaded scene with its maps (form 0: launch shape 0 on this scene, a quad
+        per row; 1: the streaming kernel, a lane per row; 2: the 256-thread shape and shade_step). (n, POINT_FLOATS), the columns of
+        POINT_COLUMNS."""
+        object, element = np.ascontiguousarray(object, np.int32), np.ascontiguousarray(element, np.int32)
+        uv, outgoing = np.ascontiguousarray(uv, np.float32).reshape(-1, 2), np.ascontiguousarray(outgoing, np.float32).reshape(-1, 3)
+        n = len(object)
+        assert len(element) == n and len(uv) == n and len(outgoing) == n
+        out = np.zeros((n, POINT_FLOATS), np.float32)
+        self._chk(self.lib.yh_point_batch(self.h, form, n, iptr(object), iptr(element), fptr(uv), fptr(outgoing), fptr(out)))
         return out
 
     def quad_forms(self, normal, rn2, a, b):
