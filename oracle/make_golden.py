@@ -120,14 +120,38 @@ def points_unit():
     np.savez_compressed(os.path.join(GOLD, "points_unit.npz"), **out)
 
 
+HITS_UNIT_VARIANTS = ("four", "six", "far")
+HITS_UNIT_ROWS = 512
+
+
+def hits_unit():
+    """Closest hits of the REFERENCE on the strata of tests/hit_cases.py: the first HITS_UNIT_ROWS rows of every stratum of every
+    variant of the scene hits-unit, inputs included."""
+    import hit_cases as hc
+    ref = oc.Ref()
+    out = {}
+    for v in HITS_UNIT_VARIANTS:
+        sc = ref.scene(make_scenes.ensure_scene("hits-unit", "/tmp/yhair_golden_scenes", variant=v))
+        for name, s in hc.strata(v).items():
+            rays = s.rays[:HITS_UNIT_ROWS]
+            out[f"{v}_{name}_rays"] = rays
+            out[f"{v}_{name}_object"], out[f"{v}_{name}_element"], out[f"{v}_{name}_uv"], out[f"{v}_{name}_distance"] = sc.intersect(rays)
+        sc.close()
+    np.savez_compressed(os.path.join(GOLD, "hits_unit.npz"), **out)
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
+    if sys.argv[1:] == ["hits_unit"]:
+        return hits_unit()
     only = sys.argv[1:]  # e.g. `make_golden.py lobes` regenerates just the fixtures whose name contains "lobes"
     want = lambda tag: not only or any(o in tag for o in only)  # noqa: E731
     if want("points_unit.npz"):
         points_unit()
         if only and all(o in "points_unit.npz" for o in only):
             return
+    if want("hits_unit.npz"):
+        hits_unit()
     ref = oc.Ref()
 
     # ---- surface lobes (math.h:4215-4755), its own generator so older fixtures never move ------

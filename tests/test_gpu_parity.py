@@ -367,6 +367,8 @@ IDS = [f"{n}-{'-'.join(map(str, k.values()))}" for n, k in GOLDEN_SCENES]
 
 @pytest.mark.parametrize("name,kw", GOLDEN_SCENES, ids=IDS)
 def test_closest_hits_bit_exact(ctx, oracle, yh, name, kw):
+    """Camera rays and jittered rays over the rendered scenes. The edges of the segment, triangle and box tests — rays built on a
+    threshold and a float to either side of it — are tests/test_hits_unit.py's."""
     g = golden(f"scene_{scene_tag(name, kw)}.npz")
     sf = yh.SceneFile(scene_path(name, **kw))
     ctx.upload_scene(sf.desc)

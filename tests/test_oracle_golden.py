@@ -90,6 +90,22 @@ def test_shading_points_bit_exact(oracle, yh):
     osc.close()
 
 
+@pytest.mark.parametrize("variant", ("four", "six", "far"))
+def test_hits_unit_bit_exact(oracle, yh, variant):
+    """yo_scene_intersect on the first rows of every stratum of tests/hit_cases.py against the reference's committed closest hits
+    (oracle/make_golden.py: hits_unit), bit for bit; the committed rays are the strata's."""
+    import hit_cases as hc
+    g = golden("hits_unit.npz")
+    got = hc.oracle_hits(variant, yh, oracle, scene_path)[0]
+    for k, name in enumerate(hc.NAMES):
+        rays = g[f"{variant}_{name}_rays"]
+        n = len(rays)
+        assert n == 512 and np.array_equal(rays.view(np.uint32), hc.strata(variant)[name].rays[:n].view(np.uint32)), (variant, name)
+        for what, a in zip(("object", "element", "uv", "distance"), got):
+            a, want = a[k * hc.N:k * hc.N + n], g[f"{variant}_{name}_{what}"]
+            assert np.array_equal(np.ascontiguousarray(a).view(np.uint32), want.view(np.uint32)), (variant, name, what)
+
+
 def test_surface_lobes_bit_exact(oracle, yh):
     """Fresnel terms and the nine surface lobes (yocto_math.h:4215-4755)
     — value * |cos|, pdf and sampled direction — against vectors made by the reference."""

@@ -105,3 +105,49 @@ def test_material_maps_bit_identical_to_reference(oracle, ref, yh, prefix, kw, r
         live = rc.maps_entries(ref, scene_path, g, prefix, kw, res_key, shaders)
         for k in got:
             assert np.array_equal(got[k], live[k], equal_nan=True), f"{k} differs from the live reference"
+
+
+HITS_VARIANTS = ("four", "six", "far", "deep")
+
+
+def _same_bits(a, b):
+    return np.array_equal(np.ascontiguousarray(a).view(np.uint32), np.ascontiguousarray(b).view(np.uint32))
+
+
+@pytest.mark.parametrize("name", list("bcde"))
+def test_primitive_tests_on_the_edge_strata(oracle, ref, name):
+    """The primitive-level form of the closest-hit edge strata (tests/hit_cases.py: the ray and the segment or triangle it was aimed
+    at, the primitive's box and the shape's): yo_intersect_line, _triangle and _bbox against the live reference's, bit for bit. Where
+    the reference is not built, the scene-level rows of tests/golden/hits_unit.npz are what holds the oracle."""
+    import hit_cases as hc
+    if ref is None:
+        pytest.skip("oracle/_ref has not been built")
+    lines, tris, boxes = hc.primitive_form("four", name)
+    for what, args in (("intersect_line", lines), ("intersect_triangle", tris), ("intersect_bbox", boxes)):
+        if len(args[0]) == 0:
+            continue
+        got, want = getattr(oracle, what)(*args), getattr(ref, what)(*args)
+        got, want = (got, want) if isinstance(got, tuple) else ((got,), (want,))
+        hit = want[0] != 0
+        assert (got[0] != 0).tolist() == hit.tolist(), (name, what)
+        for a, b in zip(got[1:], want[1:]):  # (uv and distance are written on a hit only)
+            assert _same_bits(a[hit], b[hit]), (name, what)
+        assert 0 < hit.mean() < 1, (name, what, hit.mean())
+
+
+@pytest.mark.parametrize("variant", HITS_VARIANTS)
+def test_closest_hits_on_every_stratum(oracle, ref, yh, variant):
+    """yo_scene_intersect against the live reference's intersect_scene_bvh on every row of every stratum of tests/hit_cases.py and
+    on the quad-only batch, bit for bit (a NaN uv — an r = 0 tip met exactly — included); on `deep`, on hit_cases.deep_rays."""
+    import hit_cases as hc
+    if ref is None:
+        pytest.skip("oracle/_ref has not been built")
+    rsc = ref.scene(scene_path("hits-unit", variant=variant))
+    batches = (hc.deep_rays(),) if variant == "deep" else (hc.main_batch(variant), hc.quad_only(variant).rays)
+    for rays, got in zip(batches, hc.oracle_hits(variant, yh, oracle, scene_path)):
+        want = rsc.intersect(rays)
+        for what, a, b in zip(("object", "element", "uv", "distance"), got, want):
+            same = (np.ascontiguousarray(a).view(np.uint32) == np.ascontiguousarray(b).view(np.uint32)).reshape(len(a), -1).all(1)
+            bad = np.flatnonzero(~same)
+            assert bad.size == 0, f"{what} differs on {bad.size} rows, first {hc.where(bad[0]) if len(rays) == 65536 else bad[0]}: oracle {a[bad[0]]} reference {b[bad[0]]}"
+    rsc.close()

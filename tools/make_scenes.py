@@ -888,7 +888,158 @@ def make_scene_once(outdir, scale=1.0, name="scene-once", variant="disjoint"):
     return os.path.join(d, name + ".json"), nseg
 
 
+HITS_UNIT_VARIANTS = ("four", "six", "far", "deep")
+HITS_CHAIN_SEGMENTS = 44
+_Q = 1.0 / 1024  # the grid of hits-unit: every coordinate, radius and frame entry is a multiple of 2^-10 below 2^6
+
+
+def _hits_strands():
+    """Shape `strands` of hits-unit: (positions (V, 3), radius (V,), polylines: lists of vertex indices), float64 on the 2^-10 grid.
+    Strand 0 lies along x; 1 and 2 cross at a shared joint; 3 has a segment of zero length; 4 and 5 are the same strand twice; the
+    rest are seeded, 4-8 segments each, their radii tapering, every third to exactly 0 at the tip."""
+    rng = np.random.default_rng(7)
+    pos, rad, lines = [], [], []
+
+    def strand(p, r):
+        lines.append(list(range(len(pos), len(pos) + len(p))))
+        pos.extend(p), rad.extend(r)
+    strand([(-1 + 0.5 * k, 0.25, 0.25) for k in range(5)], [32 * _Q, 28 * _Q, 24 * _Q, 20 * _Q, 16 * _Q])
+    cross = (0.5, -0.5, -0.5)
+    strand([(0.5, -1 + 0.25 * k, -0.5) for k in range(5)], [16 * _Q] * 5)          # along y, `cross` its third vertex
+    strand([(0.5, -0.5, -1 + 0.25 * k) for k in range(5)], [24 * _Q, 20 * _Q, 16 * _Q, 12 * _Q, 8 * _Q])  # along z, `cross` its third vertex
+    assert pos[7] == cross and pos[12] == cross
+    strand([(-0.5, -0.75, 0.5), (-0.5, -0.5, 0.5), (-0.5, -0.5, 0.5), (-0.25, -0.25, 0.5), (-0.25, 0.0, 0.75)], [16 * _Q] * 5)
+    twin = [(-0.75, 0.5, -0.75 + 0.25 * k) for k in range(5)]
+    strand(twin, [20 * _Q, 16 * _Q, 12 * _Q, 8 * _Q, 0.0])
+    strand(twin, [20 * _Q, 16 * _Q, 12 * _Q, 8 * _Q, 0.0])
+    for s in range(26):
+        n = int(rng.integers(4, 9))
+        p = rng.integers(-896, 897, 3).astype(np.float64)
+        step = rng.integers(-192, 193, (n, 3)).astype(np.float64)
+        step[np.abs(step).sum(1) == 0] = (64, 0, 0)
+        pts = np.clip(np.concatenate([[p], p + np.cumsum(step, 0)]), -1024, 1024) * _Q
+        r0 = int(rng.integers(12, 33))
+        r1 = 0 if s % 3 == 0 else int(rng.integers(2, 12))
+        strand([tuple(v) for v in pts], [((r0 * (n - k) + r1 * k) // n) * _Q for k in range(n + 1)])
+    return np.array(pos, np.float64), np.array(rad, np.float64), lines
+
+
+def _hits_tris():
+    """Shape `tris` of hits-unit, in the plane z = 0: an 8 x 8 grid of squares over [-1, 1]^2 (128 triangles, shared edges and
+    vertices), then a triangle without area, a sliver of aspect 2^10 and the grid's triangle 37 once more (a coincident pair)."""
+    verts = [(-1 + 0.25 * i, -1 + 0.25 * j, 0.0) for j in range(9) for i in range(9)]
+    tris = []
+    for j in range(8):
+        for i in range(8):
+            a, b, c, d = 9 * j + i, 9 * j + i + 1, 9 * (j + 1) + i, 9 * (j + 1) + i + 1
+            tris += [(a, b, c), (d, c, b)]
+    k = len(verts)
+    verts += [(0.25, 1.25, 0.0), (0.5, 1.25, 0.0), (0.75, 1.25, 0.0), (-1.0, 1.25, 0.0), (0.0, 1.25, 0.0), (-0.5, 1.25 + _Q, 0.0)]
+    tris += [(k, k + 1, k + 2), (k + 3, k + 4, k + 5), tris[37]]
+    return np.array(verts, np.float64), np.array(tris, np.int32)
+
+
+def _hits_chain(n=HITS_CHAIN_SEGMENTS):
+    """Shape `chain` of hits-unit (variant `deep`): n separate segments along x, the k-th from 0.75 c to 1.25 c with radius c / 8 at
+    both ends, c = 2^k 2^-20 (its centroid). Every box holds a stretch of the x axis, and the middle split of the centroids' range
+    takes the largest one or two away from all the others: the tree is as deep as the shape has segments, nearly."""
+    c = 2.0 ** (np.arange(n) - 20.0)
+    pos = np.zeros((2 * n, 3))
+    pos[0::2, 0], pos[1::2, 0] = 0.75 * c, 1.25 * c
+    return pos, np.repeat(c / 8, 2), [[2 * k, 2 * k + 1] for k in range(n)]
+
+
+def hits_unit_geometry(variant="four"):
+    """The scene hits-unit as arrays, for the tests that aim rays at it: a list of objects in the scene's object order, each a dict
+    of name, shape, frame (12 float32: x, y, z axes and origin), positions (V, 3) and radius (V,) as float32, lines (S, 2) or
+    triangles (T, 3)."""
+    assert variant in HITS_UNIT_VARIANTS, variant
+    sp, sr, sl = _hits_strands()
+    tp, tt = _hits_tris()
+    cp, cr, cl = _hits_chain()
+    shapes = {"strands": dict(positions=sp, radius=sr, lines=np.array([(l[k], l[k + 1]) for l in sl for k in range(len(l) - 1)], np.int32)),
+              "tris": dict(positions=tp, radius=np.zeros(len(tp)), triangles=tt),
+              "chain": dict(positions=cp, radius=cr, lines=np.array(cl, np.int32))}
+    rot = rotation_frame((1, 2, 3), 40)
+    objects = [("a-strands", "strands", IDENT[:9] + [0, 0, 0]),
+               ("b-sheared", "strands", [1.5, 0.25, 0, 0, 0.75, 0.5, 0, 0, 1.25, 3, 0, 0]),
+               ("c-tris", "tris", IDENT[:9] + [0, 0, 0]),  # (through the strands of a-strands: world space is both objects' own)
+               ("d-rotated", "tris", rot[:9] + [3, 0, -1.5])]
+    if variant in ("six", "far"):
+        objects += [("e-mirrored", "strands", [-1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 3, 0]),
+                    ("f-tris2", "tris", [2, 0, 0, 0, 2, 0, 0, 0, 0.5, 3, 3.5, 0.5])]
+    if variant == "deep":  # (first by name: where it shares a leaf of the scene tree, the others are entered after it)
+        objects = [("a-chain", "chain", [2.0 ** -19, 0, 0, 0, 2.0 ** -19, 0, 0, 0, 2.0 ** -19, -8, 0, -0.75])] + objects
+    out = []
+    for k, (name, shape, frame) in enumerate(objects):
+        frame = np.array(frame, np.float64)
+        if variant == "far":
+            frame[9:] += (65536, -2048, 8192) if name == "f-tris2" else (4096, -2048, 8192)
+        sh = shapes[shape]
+        out.append(dict(name=name, shape=shape, frame=frame.astype(np.float32), positions=sh["positions"].astype(np.float32),
+                        radius=sh["radius"].astype(np.float32), **{k2: sh[k2] for k2 in ("lines", "triangles") if k2 in sh}))
+    return out
+
+
+def _write_f32_ply(path, positions, radius=None, polylines=None, triangles=None):
+    """A binary float32 PLY in the reference's layout: lines with tangents and radii, or bare triangles."""
+    positions = np.asarray(positions, "<f4")
+    header = f"ply\nformat binary_little_endian 1.0\ncomment hits-unit (tools/make_scenes.py)\nelement vertex {len(positions)}\nproperty float x\nproperty float y\nproperty float z\n"
+    body = b""
+    if polylines is not None:
+        tang = np.zeros_like(positions)
+        for l in polylines:
+            p = positions[l].astype(np.float64)
+            t = np.gradient(p, axis=0)
+            t[np.linalg.norm(t, axis=1) == 0] = (1, 0, 0)
+            tang[l] = t / np.linalg.norm(t, axis=1, keepdims=True)
+        header += f"property float nx\nproperty float ny\nproperty float nz\nproperty float radius\nelement line {len(polylines)}\nproperty list uchar int vertex_indices\n"
+        verts = np.concatenate([positions, tang, np.asarray(radius, "<f4")[:, None]], axis=1).astype("<f4")
+        body = b"".join(bytes([len(l)]) + np.asarray(l, "<i4").tobytes() for l in polylines)
+    else:
+        header += f"element face {len(triangles)}\nproperty list uchar int vertex_indices\n"
+        verts = positions
+        body = b"".join(b"\x03" + np.asarray(t, "<i4").tobytes() for t in triangles)
+    with open(path, "wb") as f:
+        f.write((header + "end_header\n").encode() + verts.tobytes() + body)
+
+
+def make_hits_unit(outdir, scale=1.0, name="hits-unit", variant="four"):
+    """Closest hits at the edges of segments, triangles and boxes (tests/hit_cases.py aims the rays): geometry on the 2^-10 grid, so
+    that a ray built on an edge is on it exactly in float32. Shapes: `strands` and `tris` (_hits_strands, _hits_tris). `variant`:
+      four   strands | strands in a scaled and sheared frame | tris (an axis-aligned flat box) | tris in a rigid rotation: a scene level of one leaf
+      six    those, strands mirrored and a second, scaled tris: a scene tree of more than one node
+      far    six, every frame moved by (2^12, -2^11, 2^13) and the last object out to x = 2^16
+      deep   a `chain` (_hits_chain, off the grid: powers of two from 2^-21 to 2^24, in a frame that scales them by 2^-19, its small
+             end at (-8, 0, -0.75)) and four: a shape tree deep enough that a ray along it fills the traversal stacks past their LDS
+             windows, on its way to the objects of `four` behind
+    Hair and diffuse materials only: the plain kernel variants take the scenes."""
+    d = _prep(outdir, name)
+    sp, sr, sl = _hits_strands()
+    tp, tt = _hits_tris()
+    _write_f32_ply(os.path.join(d, "shapes", "strands.ply"), sp, sr, polylines=sl)
+    _write_f32_ply(os.path.join(d, "shapes", "tris.ply"), tp, triangles=tt)
+    if variant == "deep":
+        cp, cr, cl = _hits_chain()
+        _write_f32_ply(os.path.join(d, "shapes", "chain.ply"), cp, cr, polylines=cl)
+    geo = hits_unit_geometry(variant)
+    objects = {o["name"]: {"frame": [float(v) for v in o["frame"]], "shape": o["shape"],
+                           "material": "hair" if o["shape"] != "tris" else "diffuse"} for o in geo}
+    shift = geo[0]["frame"][9:].astype(np.float64)
+    eye, at = shift + (1.5, 1.0, 9.0), shift + (1.5, 1.0, 0.0)
+    scene = {
+        "asset": {"copyright": "synthetic (tools/make_scenes.py)"},
+        "cameras": {"default": {"lens": 0.05, "aperture": 0.0, "aspect": 1.0, "lookat": [float(v) for v in (*eye, *at)] + [0, 1, 0]}},
+        "environments": {"sky": {"emission": [1, 1, 1]}},
+        "objects": objects,
+        "materials": {"diffuse": {"color": [0.8, 0.4, 0.05]}, "hair": {"eumelanin": 1.3}},
+    }
+    _dump(scene, os.path.join(d, name + ".json"))
+    return os.path.join(d, name + ".json"), sum(len(o.get("lines", ())) for o in geo)
+
+
 MAKERS = {
+    "hits-unit": make_hits_unit,
     "scene-once": make_scene_once,
     "lights-unit": make_lights_unit,
     "envs-unit": make_envs_unit,

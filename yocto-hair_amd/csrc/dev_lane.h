@@ -346,6 +346,26 @@ YH_DEV bool lane_step(const trace_ctx& tc, lane_trav& t, lane_stack& s, int sp0,
       hm |= box_test(t.lo, t.ldinv, ray_eps, t.tmax, f3{A2.x, A2.y, A2.z}, f3{A2.w, B2.x, B2.y}) ? 4u : 0u;
       hm |= box_test(t.lo, t.ldinv, ray_eps, t.tmax, f3{A3.x, A3.y, A3.z}, f3{A3.w, B3.x, B3.y}) ? 8u : 0u;
       hm &= axes >> 8;
+      if (EXACT) {
+        // The binary nodes this wide node skips — its two halves, and the node it stands for itself (the shape's root is tested nowhere
+        // else) — are the unions of its occupied slots; the reference's NaN-aware test of each must pass too (dev_trace.h: exact_ancestors_pass)
+        const unsigned int occ = (axes >> 8) & 15u;
+        const f3 mn[4] = {f3{A0.x, A0.y, A0.z}, f3{A1.x, A1.y, A1.z}, f3{A2.x, A2.y, A2.z}, f3{A3.x, A3.y, A3.z}};
+        const f3 mx[4] = {f3{A0.w, B0.x, B0.y}, f3{A1.w, B1.x, B1.y}, f3{A2.w, B2.x, B2.y}, f3{A3.w, B3.x, B3.y}};
+        auto passes = [&](unsigned int set) {
+          f3 lo_ = mk3(flt_max), hi_ = mk3(-flt_max);
+#pragma unroll
+          for (int k = 0; k < 4; k++)
+            if ((set & occ) >> k & 1u) {
+              lo_ = f3{fmin_(lo_.x, mn[k].x), fmin_(lo_.y, mn[k].y), fmin_(lo_.z, mn[k].z)};
+              hi_ = f3{fmax_(hi_.x, mx[k].x), fmax_(hi_.y, mx[k].y), fmax_(hi_.z, mx[k].z)};
+            }
+          return intersect_bbox(t.lo, t.ldinv, ray_eps, t.tmax, lo_, hi_);
+        };
+        if (!passes(15u)) hm = 0;
+        if (!passes(3u)) hm &= ~3u;
+        if (!passes(12u)) hm &= ~12u;
+      }
       // Visiting order of the slots (pt.cpp:887-893 at both collapsed levels, dev_trace.h): the pair on the near side of
       // the node's axis first, inside a pair the slot on the near side of that child's axis. The first hit slot in that order
       // becomes `cur`, the others go on the stack so that they pop in order: the k-th visited hit (k >= 1) lands n - 1 - k

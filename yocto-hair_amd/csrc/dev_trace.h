@@ -343,6 +343,30 @@ YH_DEV void count_quad(unsigned int& slot) {
 #define YH_MODE_HEX 3 /* SIXTEEN lanes, 16-wide nodes (four levels, host/bvh_build.h: WideNode16): lane o tests slot o; the four quads hold the same path */
 #define YH_ROW_HALF_MIRROR 0x141 /* DPP: lane i of every eight reads lane 7 - i */
 #define YH_ROW_MIRROR 0x140      /* DPP: lane i of every sixteen reads lane 15 - i */
+
+// The EXACT pass only. The reference tests the box of EVERY binary node on the way down, and in its compare + select test a NaN slab
+// (0 * inf: a zero direction component, the origin exactly on a face) takes part by its position in hmax / hmin: a NaN in y erases
+// the verdict of x, one in z erases both. So a node can reject a ray that boxes further down accept, and the subtree is never seen. A
+// wide node stands for 2 .. 4 levels of the binary tree and holds the boxes of the lowest only; the nodes in between, and the shape's
+// root, are the unions of the slots below them (a node's box is the union of its children's, min and max being exact). Lane o of the
+// group holds slot o; LEVELS = log2 of the width: after step k the lane holds the box of its ancestor k levels up, which must pass as
+// well. An empty slot's box is inverted and changes no union. Tested with the tmax of this step, which is the reference's tmax when it
+// pops the node itself and the near side, and no smaller than the one it pops the far side with: never a cull the reference does not make.
+template <int LEVELS>
+YH_DEV bool exact_ancestors_pass(f3 lo, f3 ldinv, float tmin, float tmax, f3 bmin, f3 bmax, bool occupied) {
+  if (!occupied) bmin = mk3(flt_max), bmax = mk3(-flt_max);
+  bool ok = true;
+#define YH_UNION_STEP(CTRL)                                                                                                          \
+  bmin = f3{fmin_(bmin.x, dpp_f<CTRL>(bmin.x)), fmin_(bmin.y, dpp_f<CTRL>(bmin.y)), fmin_(bmin.z, dpp_f<CTRL>(bmin.z))};             \
+  bmax = f3{fmax_(bmax.x, dpp_f<CTRL>(bmax.x)), fmax_(bmax.y, dpp_f<CTRL>(bmax.y)), fmax_(bmax.z, dpp_f<CTRL>(bmax.z))};             \
+  ok   = intersect_bbox(lo, ldinv, tmin, tmax, bmin, bmax) && ok;
+  YH_UNION_STEP(YH_QUAD_XOR1)
+  YH_UNION_STEP(YH_QUAD_XOR2)
+  if (LEVELS >= 3) { YH_UNION_STEP(YH_ROW_HALF_MIRROR) }
+  if (LEVELS >= 4) { YH_UNION_STEP(YH_ROW_MIRROR) }
+#undef YH_UNION_STEP
+  return ok;
+}
 #define YH_MODE_OCTP 4 /* YH_MODE_OCT with LEAF PAIRS: the octet's two quads test two leaves in one step (leaf groups, below). Bit-identical; 6 % fewer trips and
                           2-6 % slower on C1 (the look at the stack's top and the exchange between the quads cost every leaf step), 17 % FASTER on hair-curls
                           (many leaf steps per ray): its own launch shape, the trials decide (profiles/r03/oct_leaf_pairs_ab.txt, hex_ab.txt) */
@@ -635,7 +659,8 @@ YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_obj
         const unsigned int n3   = (lsign >> ((axes >> (14 + 2 * (o >> 1))) & 3)) & 1;
         const unsigned int rank = (((o >> 3) ^ n0) << 3) | ((((o >> 2) & 1) ^ n1) << 2) | ((((o >> 1) & 1) ^ n2) << 1) | ((o & 1) ^ n3);
         unsigned int ref = __float_as_uint(s1.z);
-        const bool   h   = box_test(lo, ldinv, ray.tmin, tmax, f3{s0.x, s0.y, s0.z}, f3{s0.w, s1.x, s1.y}) && ref != YH_NONE;
+        bool         h   = box_test(lo, ldinv, ray.tmin, tmax, f3{s0.x, s0.y, s0.z}, f3{s0.w, s1.x, s1.y}) && ref != YH_NONE;
+        if constexpr (EXACT) h = exact_ancestors_pass<4>(lo, ldinv, ray.tmin, tmax, f3{s0.x, s0.y, s0.z}, f3{s0.w, s1.x, s1.y}, ref != YH_NONE) && h;
         unsigned int bits = h ? (1u << rank) : 0u;
         unsigned int M    = bits | (unsigned int)dpp_i<YH_QUAD_XOR1>((int)bits);
         M |= (unsigned int)dpp_i<YH_QUAD_XOR2>((int)M);
@@ -665,7 +690,8 @@ YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_obj
         const unsigned int n2   = (lsign >> ((axes >> (6 + 2 * g)) & 3)) & 1;
         const unsigned int rank = ((((g >> 1) ^ n0) << 2) | (((g & 1) ^ n1) << 1)) | ((__lane_id() & 1u) ^ n2);
         const unsigned int ref  = __float_as_uint(s1.z);
-        const bool         h    = box_test(lo, ldinv, ray.tmin, tmax, f3{s0.x, s0.y, s0.z}, f3{s0.w, s1.x, s1.y}) && ref != YH_NONE;
+        bool               h    = box_test(lo, ldinv, ray.tmin, tmax, f3{s0.x, s0.y, s0.z}, f3{s0.w, s1.x, s1.y}) && ref != YH_NONE;
+        if constexpr (EXACT) h = exact_ancestors_pass<3>(lo, ldinv, ray.tmin, tmax, f3{s0.x, s0.y, s0.z}, f3{s0.w, s1.x, s1.y}, ref != YH_NONE) && h;
         unsigned int bits = h ? (1u << rank) : 0u;
         unsigned int M    = bits | (unsigned int)dpp_i<YH_QUAD_XOR1>((int)bits);
         M |= (unsigned int)dpp_i<YH_QUAD_XOR2>((int)M);
@@ -687,6 +713,7 @@ YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_obj
         unsigned int ref  = __float_as_uint(s1.z);
         unsigned int axes = __float_as_uint(s1.w);
         h = h && ref != YH_NONE;  // an empty slot's inverted box still passes the min/max slab test
+        if constexpr (EXACT) h = exact_ancestors_pass<2>(lo, ldinv, ray.tmin, tmax, f3{s0.x, s0.y, s0.z}, f3{s0.w, s1.x, s1.y}, ref != YH_NONE) && h;
         if (!LDS_SCENE && scene_node) ref = (ref & ~YH_TAG_MASK) | YH_TAG_SCENE;  // children of a scene node are scene entries: a node's offset, or count << 27 | first of a leaf
         // Visiting order of the four slots (pt.cpp:887-893 applied at both collapsed
         // levels): the pair on the near side of the node's own axis first, and
