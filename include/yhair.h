@@ -502,6 +502,60 @@ typedef struct yh_gbuffer {
 int yh_trace_gbuffer(yh_context* ctx, int mode, const yh_gbuffer* out);
 int yh_trace_gbuffer_device(yh_context* ctx, int mode, const yh_gbuffer* out);
 
+/* DENOISE (an extension: the reference has no counterpart; the consumer of the feature pass above). An edge-avoiding a-trous wavelet
+ * filter (Dammertz et al. 2010) over the resolved render, guided by the CENTRE-mode planes object, normal, position and albedo.
+ * Per pixel p: colour c (float4), id (-1: a miss), normal n, position x, albedo a.
+ *   effective albedo   per channel (a < 1e-3f) ? 1 : a; 1 when `demodulate` is 0, and 1 on a miss whatever the plane holds
+ *   working colour     u = c.rgb / effective albedo; alpha is never filtered, the output's alpha is the input's
+ *   level l            l = 0 .. iterations - 1, tap spacing s = 2^l, 25 taps q = p + s (dx, dy), dy = -2..2 outer, dx = -2..2 inner;
+ *                      taps outside the image are skipped. h = k[|dx|] k[|dy|], k = {3/8, 1/4, 1/16};
+ *                      w = h / (1 + x + 0.5 x x) — the reciprocal of exp's second-order Taylor polynomial, not exp(-x): + - x / and
+ *                      comparisons only, so that device, host and a float32 restatement give the same bits — with
+ *                      x = |n_p - n_q|^2 / sigma_normal^2 + |x_p - x_q|^2 / sigma_position^2 + |u_p - u_q|^2 / (sigma_color 2^-l)^2,
+ *                      u the level's input; a term whose sigma is <= 0 contributes 0. w = 0 when `match_object` is set and the ids
+ *                      differ, when a channel of u_q is not finite, when x >= 0 does not hold. One float accumulator per channel and
+ *                      one for w, summed in tap order (a tap of weight 0 is not added): u'_p = sum w u_q / sum w, and u'_p = u_p
+ *                      when the sum of w is 0 or u_p is not finite.
+ *   misses             a pixel with id -1 passes every level unchanged: its output has its input's bits
+ *   after the last     out.rgb = u x effective albedo. With iterations = 0 the output is the input.
+ * It changes no accumulator, stream, sample count, item cost, trial record or launch shape. Blocking on the context's stream;
+ * yh_last_trace_ms reports its kernels' event time and launch count (the feature pass included where the call runs it).
+ * YH_E_STATE before yh_upload_scene / yh_init_state where the call needs them (the context entries take the image size from the
+ * state; tracing guides needs the scene), with an asynchronous launch pending, and for rgba_in NULL on a sharded context (yh_set_shard
+ * world > 1: gather first and pass the image). YH_E_INVALID: iterations outside 0 .. YH_DENOISE_MAX_ITERATIONS, a NULL params or
+ * output, a guide plane the parameters need missing (object always; normal / position where their sigma is > 0; albedo where
+ * `demodulate` is set), a device image that is not 16-byte aligned, an unknown form. Every refusal comes before the first write. */
+#define YH_DENOISE_MAX_ITERATIONS 6
+typedef struct yh_denoise_params {
+  int   iterations;
+  float sigma_color, sigma_normal, sigma_position;
+  int   demodulate, match_object;
+} yh_denoise_params;
+/* The defaults: 5 iterations, sigma_color 4, sigma_normal 0.5, sigma_position = 0.05 x the diagonal of the uploaded scene's bounds
+ * (0 = off with ctx NULL or before an upload), demodulate 1, match_object 1. Settled on the CPU with yh_atrous_filter against the
+ * quality condition of tests/test_denoise.py (profiles/denoise/quality.txt).                                                      */
+int yh_denoise_default_params(const yh_context* ctx, yh_denoise_params* p);
+/* Everything a DEVICE pointer: rgba_in / rgba_out float4 images of the state's size (rgba_in NULL: the context's own render, accum /
+ * samples; rgba_out may be rgba_in). guides NULL: the call traces its own centre-mode guides into temporary planes (albedo only
+ * when `demodulate` is set); else the struct's object, normal, position, albedo planes as yh_trace_gbuffer_device writes them.    */
+int yh_denoise_image_device(yh_context* ctx, const yh_denoise_params* p, const void* rgba_in, const yh_gbuffer* guides, void* rgba_out);
+/* The same with HOST pointers, staged as yh_trace_gbuffer stages its planes; the guides are traced by the call. rgba_in may be a
+ * gathered multi-GPU image (yh_gather_framebuffer).                                                                               */
+int yh_denoise(yh_context* ctx, const yh_denoise_params* p, const float* rgba_in, float* rgba_out);
+/* The context's own render, denoised, then the tone map of yh_download_display, as bytes.                                         */
+int yh_denoise_display(yh_context* ctx, const yh_denoise_params* p, float exposure, int filmic, int srgb, uint8_t* rgba8);
+/* The filter at unit level on the caller's arrays (HOST pointers; w x h pixels; rgba 4, normal / position / albedo 3 floats per
+ * pixel, NULL allowed where the parameters do not read them). yh_atrous_filter: the host's form (no GPU, no context), the
+ * restatement the device is compared with. yh_atrous_filter_gpu: the same arrays through the device kernels; form 0: every tap
+ * from memory; form 1: the levels with s <= 4 from a 16 x 16 tile staged with its halo in LDS. Same bits, all three.              */
+int yh_atrous_filter(int w, int h, const yh_denoise_params* p, const float* rgba, const int* object, const float* normal,
+    const float* position, const float* albedo, float* out);
+int yh_atrous_filter_gpu(yh_context* ctx, int form, int w, int h, const yh_denoise_params* p, const float* rgba, const int* object,
+    const float* normal, const float* position, const float* albedo, float* out);
+/* Developer diagnostics: the event times in ms of the last yh_atrous_filter_gpu, kernel by kernel — the pack step, then each
+ * level. Writes min(capacity, 1 + iterations) numbers, returns 1 + iterations of that call (0: none yet).                         */
+int yh_atrous_level_ms(const yh_context* ctx, float* ms, int capacity);
+
 /* Work counters of the launches since the last reset (instrumented build of
  * the same kernel; 0 = ok).                                                  */
 int yh_trace_samples_counted(yh_context* ctx, int nsamples, yh_workcounts* out);

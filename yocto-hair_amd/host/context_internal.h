@@ -9,6 +9,7 @@
 //   gather.cpp         tile packing and the one collective (yh_gather_framebuffer: RCCL or peer copies)
 //   batch_api.cpp      the unit-level batch entry points (hair BSDF, intersection, BVH build, curves, self-tests)
 //   gbuffer.cpp        yh_trace_gbuffer / _device: the first-hit feature pass over the state's image (unit/gbuffer.hip)
+//   denoise.cpp        yh_denoise and friends: the a-trous filter over the resolved render, guided by that pass (unit/denoise.hip, unit/atrous_math.h)
 //   scene_edit.cpp     edits of an uploaded scene that keep its geometry: yh_update_camera / _materials / _environments / _objects, and the
 //                      scene level again (the tree over the objects' world boxes, which the shape edits move too)
 //   shape_edit.cpp     one shape's vertices: yh_update_shape / _device (its tree again), yh_refit_shape / _device (that tree's boxes only,
@@ -112,6 +113,15 @@ int yhk_volume_lanes(const yhd_scene* sc, int n, const void* mats, const float* 
 int yhk_quad_forms(int n, const float* normal, const float* rn, const float* a, const float* b, float* out, hipStream_t);  // unit/volume_quad.hip
 int yhk_selftest(int, float, float, uint64_t, uint64_t, int, const float*, double*, unsigned int*, hipStream_t);
 int yhk_display(const yhd_state*, int samples, float exposure, int filmic, int srgb, void* rgba8, hipStream_t);  // unit/display.hip
+int yhk_display_image(const void* rgba, int width, int height, float exposure, int filmic, int srgb, void* rgba8, hipStream_t);  // ... of a float4 image in device memory
+// unit/denoise.hip (yh_denoise ...), all pointers DEVICE pointers, float4 images 16-byte aligned: the pack step (rgba_in NULL: accum / samples;
+// plain: the colour alone into u), one level of the filter in form 0 (taps from memory) or 1 (levels below yhk_dn_tiled_levels from LDS)
+int yhk_dn_tile(void);
+int yhk_dn_tiled_levels(void);
+int yhk_dn_pack(const void* rgba_in, const void* accum, int samples, int width, int height, const int* object, const float* normal, const float* position,
+    const float* albedo, void* u, void* g0, void* g1, int plain, hipStream_t);
+int yhk_dn_level(int form, int width, int height, int level, const yh_denoise_params* P, const void* u, const void* g0, const void* g1, const float* albedo,
+    int last, void* out, hipStream_t);
 // unit/objects.hip (yh_update_objects): a lane per row of `rows` (yh_object, device memory); root6 = per shape its root box, 6 floats; writes
 // frame, inv_frame, material and the padded world box into objects[0 .. count) unless NULL, and the world box proper, 6 floats per row, to boxes6
 int yhk_object_rows(int count, const void* rows, const float* root6, void* objects, float* boxes6, hipStream_t);
@@ -304,6 +314,8 @@ struct yh_context {
   int              num_tiles_total = 0;
   float            last_ms = 0;
   int              last_launches = 0;
+  float            dn_ms[1 + YH_DENOISE_MAX_ITERATIONS] = {};  // yh_atrous_level_ms: the last yh_atrous_filter_gpu kernel by kernel
+  int              dn_ms_count = 0;
   int              last_nsamples = 0;   // samples of the launch the item costs come from
   unsigned         launches_of_image = 0;  // synchronous launches since this IMAGE (scene, resolution, sampler, bounces) was first initialised: the re-planning schedule. A
                                            // re-initialised render of a known image is planned already (item_cost survives it) and goes on where the schedule was
@@ -402,6 +414,7 @@ int trace_impl(yh_context* ctx, int nsamples, bool counted, bool sync);
 int wait_for_launch(yh_context* ctx);  // hipStreamSynchronize(ctx->stream) with a deadline (host/deadline.h)
 int side_by_side_impl(yh_context* ctx, int nsamples, bool sync);
 void destroy_communicators(yh_context* ctx);
+int gbuffer_pass(yh_context* ctx, const char* who, int mode, void* const planes[11]);  // gbuffer.cpp: the feature pass into device planes, for denoise.cpp
 inline int tiles_of(int n) { return (n + YH_TILE - 1) / YH_TILE; }
 void make_material(const yh_material& m, yhd_material& d);  // scene_upload.cpp
 // scene_upload.cpp, shared with the edits: the device rows of `count` materials (`maps` / `dmaps`: theirs, or NULL in a scene without effective

@@ -53,6 +53,13 @@ int gbuffer_checks(yh_context* ctx, const char* who, int mode, const yh_gbuffer*
 }
 }  // namespace
 
+// for host/denoise.cpp, which traces its own guides: the pass into device planes (the caller has checked scene, state and pending launches)
+int gbuffer_pass(yh_context* ctx, const char* who, int mode, void* const planes[PLANES]) {
+  if (!lane_kernels_can_address(ctx))
+    return fail(ctx, YH_E_INVALID, "%s: the one-lane form reads the scene's trees through 32-bit byte offsets and this scene's exceed 4 GB", who);
+  return gbuffer_impl(ctx, who, mode, planes);
+}
+
 int yh_trace_gbuffer_device(yh_context* ctx, int mode, const yh_gbuffer* out) {
   if (!ctx) return YH_E_INVALID;
   void* planes[PLANES];

@@ -684,5 +684,25 @@ inline gbuffer trace_gbuffer(state* st, const scene*, const camera*, const trace
   detail::check(yh_trace_gbuffer(ctx, (int)mode, &out), ctx);
   return g;
 }
+
+// EXTENSION (no reference counterpart; off unless called): the image of `st` denoised (include/yhair.h: DENOISE) — the edge-avoiding
+// a-trous filter guided by the centre-mode feature pass. The image is downloaded first (with several devices: gathered), context 0 alone
+// filters it and traces the guides; the state's samples and `render` keep what a download gives them. default_denoise_params: the
+// library's defaults for the uploaded scene (call after init_state).
+using denoise_params = yh_denoise_params;
+inline denoise_params default_denoise_params() {
+  denoise_params p;
+  detail::check(yh_denoise_default_params(detail::require_context(), &p));
+  return p;
+}
+inline image<vec4f> denoise_image(state* st, const scene*, const camera*, const trace_params&, const denoise_params& dparams) {
+  bind_state(st);
+  download(st);
+  image<vec4f> out;
+  out.width = st->width, out.height = st->height, out.pixels.resize((size_t)st->width * st->height);
+  auto ctx = detail::require_context();
+  detail::check(yh_denoise(ctx, &dparams, (const float*)st->render.data(), (float*)out.pixels.data()), ctx);
+  return out;
+}
 }  // namespace yhair::pathtrace
 #endif

@@ -162,4 +162,12 @@ inline void save_features(ptr::state* state, const ptr::scene* scene, const ptr:
   for (size_t i = 0; i < n; i++) img[i] = {(float)g.object.pixels[i], (float)g.element.pixels[i], (float)g.material.pixels[i], 1};
   save("ids");
 }
+// "--denoise FILE" (an extension of both command lines): the state's image denoised with the library's default parameters
+// (ptr::denoise_image: from the gathered image on context 0, whatever --gpus says), written next to the untouched output
+inline void save_denoised(ptr::state* state, const ptr::scene* scene, const ptr::camera* camera, const ptr::trace_params& params, const std::string& name) {
+  const auto img = ptr::denoise_image(state, scene, camera, params, ptr::default_denoise_params());
+  char       error[512];
+  if (yh_save_image(name.c_str(), img.width, img.height, (const float*)img.pixels.data(), error, sizeof(error)) != YH_OK) print_fatal(error);
+  printf("save denoised: %s\n", name.c_str());
+}
 #endif

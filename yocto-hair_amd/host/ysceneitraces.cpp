@@ -10,7 +10,7 @@
 // Same flags as the app (ysceneitraces.cpp:313-327): --camera, --resolution,-r, --samples,-s, --shader,-t,
 // --bounces,-b, --clamp, --output,-o, positional scene. Extensions: --pratio (trace_params::pratio, default
 // 8), --preview-image FILE, --stop-after-ms N, --seed, --device, --gpus / --devices, --features PREFIX [--features-mode centre|next] (the first-hit
-// feature pass after the preview: yscene_cli.h, save_features), --sway STEPS [--sway-refit] (the vertex edit's gesture: the first
+// feature pass after the preview: yscene_cli.h, save_features), --denoise FILE (the preview pass denoised: save_denoised), --sway STEPS [--sway-refit] (the vertex edit's gesture: the first
 // line shape displaced step by step, passed on through yh_update_shape or, with --sway-refit, yh_refit_shape) and --turntable STEPS: the app's one gesture, the
 // camera orbit (ysceneitraces.cpp:392-410: update_turntable on app->camera->frame, then reset_display), headless — after the first
 // reset_display, STEPS - 1 times a rotation by 2 pi / STEPS followed by reset_display again; step k is saved as <stem>-<kkk><ext>.
@@ -53,7 +53,7 @@ static void update_turntable(frame3f& frame, float& focus, const vec2f& rotate) 
 
 int main(int argc, const char* argv[]) {
   auto        params = ptr::trace_params{};
-  std::string camera_name, imagename = "out.hdr", preview_name, filename, shader = "path", features, features_mode_name = "centre";
+  std::string camera_name, imagename = "out.hdr", preview_name, filename, shader = "path", features, features_mode_name = "centre", denoise;
   int         stop_after_ms = -1, gpus = 1, first_device = 0, turntable = 0;
   bool        turn_objects = false, sway_refit = false;
   int         sway = 0;
@@ -68,7 +68,7 @@ int main(int argc, const char* argv[]) {
       printf("usage: ysceneitraces [--camera NAME] [--resolution,-r N] [--samples,-s N] [--shader,-t naive|path|eyelight|normal]\n"
              "                     [--bounces,-b N] [--clamp F] [--output,-o FILE] [--pratio N] [--preview-image FILE]\n"
              "                     [--stop-after-ms N] [--seed N] [--device N] [--gpus N] [--devices A,B,..] [--turntable STEPS [--turntable-objects]]\n"
-             "                     [--sway STEPS [--sway-refit]] [--features PREFIX] [--features-mode centre|next] scene\n"
+             "                     [--sway STEPS [--sway-refit]] [--features PREFIX] [--features-mode centre|next] [--denoise FILE] scene\n"
              "Progressive path tracing of hair scenes on MI355X (headless: preview pass, then samples until done or stopped)\n");
       return 0;
     } else if (a == "--camera") camera_name = next();
@@ -91,6 +91,7 @@ int main(int argc, const char* argv[]) {
     else if (a == "--sway-refit") sway_refit = true;
     else if (a == "--features") features = next();
     else if (a == "--features-mode") features_mode_name = next();
+    else if (a == "--denoise") denoise = next();
     else if (!a.empty() && a[0] == '-') print_fatal("unknown option " + a);
     else filename = a;
   }
@@ -147,6 +148,7 @@ int main(int argc, const char* argv[]) {
           scene->uploads > uploads0 ? "the scene was uploaded again" : turn_objects ? "the objects alone were passed on" : "the camera alone was passed on");
     if (!preview_name.empty() && yh_save_image(preview_name.c_str(), W, H, (const float*)render.data(), error, sizeof(error)) != YH_OK)
       print_fatal(error);
+    if (!denoise.empty()) save_denoised(pstate.get(), scene.get(), camera, pprms, denoise);  // (yscene_cli.h: the 1-spp preview denoised, at the preview's resolution)
     if (!features.empty()) save_features(render_state.get(), scene.get(), camera, params, features, feature_mode);  // (yscene_cli.h; binds the render state again)
     // start render
     std::atomic<bool> render_stop{false};

@@ -7,7 +7,7 @@
 // --seed, --exact-bsdf, --device, --spp-per-launch, --timing (one "timing: {json}" line with the wall-clock of every phase: what
 // bench.py's config.end_to_end reads), --gpus N / --devices A,B,.. (tile-sharded over
 // the GPUs of one node, one RCCL gather of the float4 framebuffer at the end), --features PREFIX [--features-mode centre|next] (the first-hit
-// feature pass after the render: yscene_cli.h, save_features). Same flow: load scene -> convert through
+// feature pass after the render: yscene_cli.h, save_features), --denoise FILE (the image denoised, next to the untouched output: save_denoised). Same flow: load scene -> convert through
 // the add_* / set_* API -> init_bvh -> init_lights -> init_state -> sample loop
 // -> save_image. Errors print and exit(1) like print_fatal
 // (yocto_commonio.h:258-261).
@@ -26,13 +26,13 @@ int main(int argc, const char* argv[]) {
   auto save_batch = false, timing = false;
   std::string camera_name, imfilename = "out.hdr", filename, shader = "path";
   int  spp_per_launch = 256, gpus = 1, first_device = 0;  // (every launch waits for its unluckiest pixel: C1 0.2375 ms per sample at 64 per launch, 0.228 at 256, 0.2226 in one launch of 1536)
-  std::string device_list, features, features_mode_name = "centre";
+  std::string device_list, features, features_mode_name = "centre", denoise;
 
   auto usage = [&]() {
     printf("usage: yscenetrace [--camera NAME] [--resolution,-r N] [--samples,-s N] [--shader,-t naive|path|eyelight|normal]\n"
            "                   [--bounces,-b N] [--clamp F] [--save-batch] [--output-image,-o FILE]\n"
            "                   [--seed N] [--exact-bsdf] [--device N] [--gpus N] [--devices A,B,..] [--spp-per-launch N] [--timing]\n"
-           "                   [--features PREFIX] [--features-mode centre|next] scene\n"
+           "                   [--features PREFIX] [--features-mode centre|next] [--denoise FILE] scene\n"
            "Offline path tracing of hair scenes on MI355X. --gpus N: the image's 8x8 tiles are dealt round-robin to N\n"
            "GPUs of this node (devices --device .. --device + N - 1, or --devices), one RCCL gather at the end.\n"
            "--features PREFIX: after the render, the first hit of every pixel as PREFIX.normal.hdr, .albedo.hdr, .depth.hdr and .ids.hdr\n"
@@ -61,6 +61,7 @@ int main(int argc, const char* argv[]) {
     else if (a == "--devices") device_list = next();
     else if (a == "--features") features = next();
     else if (a == "--features-mode") features_mode_name = next();
+    else if (a == "--denoise") denoise = next();
     else if (a == "--spp-per-launch") spp_per_launch = std::max(1, atoi(next().c_str()));
     else if (!a.empty() && a[0] == '-') print_fatal("unknown option " + a);
     else filename = a;
@@ -153,6 +154,7 @@ int main(int argc, const char* argv[]) {
           ph_load, ph_convert, ph_bvh, ph_lights, ph_state, ph_render, kernel_ms / 1e3, launches, requests, ph_download, ph_save, secs(), state->width, state->height,
           params.samples, (int)yhair::detail::devices().size());
     if (!features.empty()) save_features(state.get(), scene.get(), camera, params, features, feature_mode);
+    if (!denoise.empty()) save_denoised(state.get(), scene.get(), camera, params, denoise);  // (yscene_cli.h: the image above stays as it is)
   } catch (const std::exception& e) {
     print_fatal(e.what());
   }

@@ -107,6 +107,21 @@ class GBuffer(C.Structure):
     _fields_ = [(n, c_int_p if t is np.int32 else c_float_p) for n, t, _ in GBUFFER_PLANES]
 
 
+DENOISE_MAX_ITERATIONS = 6
+
+
+class DenoiseParams(C.Structure):
+    """yh_denoise_params (include/yhair.h: DENOISE)."""
+    _fields_ = [("iterations", C.c_int), ("sigma_color", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float),
+                ("demodulate", C.c_int), ("match_object", C.c_int)]
+
+    def copy(self, **changes):
+        q = DenoiseParams.from_buffer_copy(self)
+        for k, v in changes.items():
+            setattr(q, k, v)
+        return q
+
+
 class WorkCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "nodes", "seg_tests", "tri_tests",
                                           "hair_shades", "surf_shades", "env_lookups",
@@ -204,6 +219,14 @@ _SIGS = {
     "yh_download_rng": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64)]),
     "yh_trace_gbuffer": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(GBuffer)]),
     "yh_trace_gbuffer_device": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(GBuffer)]),
+    "yh_denoise_default_params": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams)]),
+    "yh_denoise_image_device": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_void_p, C.POINTER(GBuffer), C.c_void_p]),
+    "yh_denoise": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), c_float_p, c_float_p]),
+    "yh_denoise_display": (C.c_int, [C.c_void_p, C.POINTER(DenoiseParams), C.c_float, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
+    "yh_atrous_filter": (C.c_int, [C.c_int, C.c_int, C.POINTER(DenoiseParams), c_float_p, c_int_p, c_float_p, c_float_p, c_float_p, c_float_p]),
+    "yh_atrous_filter_gpu": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(DenoiseParams), c_float_p, c_int_p, c_float_p, c_float_p,
+                                       c_float_p, c_float_p]),
+    "yh_atrous_level_ms": (C.c_int, [C.c_void_p, c_float_p, C.c_int]),
     "yh_trace_samples_counted": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(WorkCounts)]),
     "yh_last_trace_ms": (C.c_int, [C.c_void_p, c_float_p, c_int_p]),
     "yh_launch_shape": (C.c_int, [C.c_void_p]),
@@ -308,6 +331,35 @@ def triangle_cdf(positions, triangles):
     rc = load().yh_triangle_cdf(len(positions), fptr(positions), len(triangles), iptr(triangles), fptr(out))
     if rc != YH_OK:
         raise YhError(f"yhair error {rc}: yh_triangle_cdf")
+    return out
+
+
+def denoise_default_params(ctx=None):
+    """yh_denoise_default_params: the defaults, sigma_position from the scene `ctx` (a Context) has uploaded, 0 without one."""
+    p = DenoiseParams()
+    rc = load().yh_denoise_default_params(ctx.h if ctx is not None else None, C.byref(p))
+    if rc != YH_OK:
+        raise YhError(f"yhair error {rc}: yh_denoise_default_params")
+    return p
+
+
+def _filter_args(rgba, object, normal, position, albedo):
+    rgba = np.ascontiguousarray(rgba, np.float32)
+    h, w = rgba.shape[:2]
+    object = np.ascontiguousarray(object, np.int32) if object is not None else None
+    planes = [np.ascontiguousarray(a, np.float32) if a is not None else None for a in (normal, position, albedo)]
+    assert rgba.shape == (h, w, 4) and (object is None or object.shape == (h, w)) and all(a is None or a.shape == (h, w, 3) for a in planes)
+    held = [rgba, object] + planes
+    ptrs = [fptr(rgba), iptr(object) if object is not None else None] + [fptr(a) if a is not None else None for a in planes]
+    return w, h, held, ptrs, np.zeros((h, w, 4), np.float32)
+
+
+def atrous_filter(params, rgba, object, normal=None, position=None, albedo=None):
+    """yh_atrous_filter (host, no GPU): the a-trous filter of yh_denoise on (H, W, 4) rgba, (H, W) object ids and (H, W, 3) planes."""
+    w, h, held, ptrs, out = _filter_args(rgba, object, normal, position, albedo)
+    rc = load().yh_atrous_filter(w, h, C.byref(params), *ptrs, fptr(out))
+    if rc != YH_OK:
+        raise YhError(f"yhair error {rc}: yh_atrous_filter")
     return out
 
 
@@ -620,6 +672,62 @@ class Context:
         if device is not None:
             torch.cuda.current_stream(device).synchronize()
         self._chk(self.lib.yh_trace_gbuffer_device(self.h, mode, C.byref(g)))
+
+    # the denoiser (include/yhair.h: DENOISE)
+    def denoise_default_params(self):
+        return denoise_default_params(self)
+
+    def denoise(self, params=None, rgba=None):
+        """yh_denoise: the denoised (H, W, 4) image of `rgba` (None: the context's own render); params None: the defaults."""
+        params = params if params is not None else self.denoise_default_params()
+        rgba = np.ascontiguousarray(rgba, np.float32) if rgba is not None else None
+        out = np.zeros((getattr(self, "height", 0), getattr(self, "width", 0), 4), np.float32)
+        assert rgba is None or rgba.shape == out.shape
+        self._chk(self.lib.yh_denoise(self.h, C.byref(params), fptr(rgba) if rgba is not None else None, fptr(out)))
+        return out
+
+    def denoise_display(self, params=None, exposure=0.0, filmic=False, srgb=True):
+        """yh_denoise_display: the own render, denoised and tone-mapped on the device, as (H, W, 4) bytes."""
+        params = params if params is not None else self.denoise_default_params()
+        img = np.zeros((getattr(self, "height", 0), getattr(self, "width", 0), 4), np.uint8)
+        self._chk(self.lib.yh_denoise_display(self.h, C.byref(params), exposure, int(filmic), int(srgb), img.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return img
+
+    def denoise_image_device(self, params, rgba_out, rgba_in=None, **guides):
+        """yh_denoise_image_device: contiguous float32 torch tensors of (H, W, 4) on the context's device (rgba_in None: the own
+        render); guides: object / normal / position / albedo tensors as trace_gbuffer_device fills them, none: traced by the call.
+        The current torch stream is synchronised before the call, which runs on the context's own stream."""
+        import torch
+        kinds = {n: (t, c) for n, t, c in GBUFFER_PLANES}
+        npix = self.height * self.width
+
+        def ptr(t, dtype, comps, what):
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.numel() < npix * comps:
+                raise YhError(f"denoise_image_device: {what} must be a contiguous {dtype} tensor on the GPU of at least {self.height} x {self.width} x {comps} elements")
+            return t.data_ptr()
+        out_p = ptr(rgba_out, torch.float32, 4, "rgba_out")
+        in_p = ptr(rgba_in, torch.float32, 4, "rgba_in") if rgba_in is not None else None
+        g = GBuffer()
+        for n, t in guides.items():
+            if n not in kinds:
+                raise YhError(f"denoise_image_device: unknown plane {n}")
+            if t is not None:
+                dtype = torch.int32 if kinds[n][0] is np.int32 else torch.float32
+                setattr(g, n, C.cast(ptr(t, dtype, kinds[n][1], n), c_int_p if dtype == torch.int32 else c_float_p))
+        torch.cuda.current_stream(rgba_out.device).synchronize()
+        self._chk(self.lib.yh_denoise_image_device(self.h, C.byref(params), in_p, C.byref(g) if guides else None, out_p))
+
+    def atrous_filter_gpu(self, form, params, rgba, object, normal=None, position=None, albedo=None):
+        """yh_atrous_filter_gpu: atrous_filter's arrays through the device kernels (form 0: taps from memory, 1: from an LDS tile)."""
+        w, h, held, ptrs, out = _filter_args(rgba, object, normal, position, albedo)
+        self._chk(self.lib.yh_atrous_filter_gpu(self.h, form, w, h, C.byref(params), *ptrs, fptr(out)))
+        return out
+
+    def atrous_level_ms(self):
+        """yh_atrous_level_ms: the event times of the last atrous_filter_gpu: [pack, level 0, level 1, ...]."""
+        ms = (C.c_float * (1 + DENOISE_MAX_ITERATIONS))()
+        n = self.lib.yh_atrous_level_ms(self.h, ms, len(ms))
+        return [float(ms[k]) for k in range(max(n, 0))]
 
     def shard_pixels(self, rank, world):
         return int(self.lib.yh_shard_pixels(self.h, rank, world))
