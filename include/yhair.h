@@ -202,7 +202,8 @@ typedef struct yh_context yh_context;
 
 /* Creates a context on HIP device `device`. Returns NULL when no usable GPU
  * or the HIP code object is missing: there is NO CPU fallback.
- * Every call that waits for the device waits at most YHAIR_LAUNCH_TIMEOUT_S seconds (environment, default 1800): a launch that
+ * Every call that waits for the device waits at most YHAIR_LAUNCH_TIMEOUT_S seconds (environment, default 1800; this and every other
+ * YHAIR_* variable the library reads: the table at the head of yocto-hair_amd/host/switches.h): a launch that
  * does not complete in time returns YH_E_DEVICE, and from then on the context refuses every call that would touch the device
  * (a hung kernel cannot be recalled); yh_destroy of such a context returns at once and frees nothing. A caller that wants to
  * retry starts a fresh process. (The reference's trace_samples cannot hang: CPU threads over rows, yocto_pathtrace.cpp:1954-1989.) */

@@ -290,6 +290,31 @@ def test_launch_deadline_logic(tmp_path):
     assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout + out.stderr
 
 
+def test_developer_switches(tmp_path):
+    """Every YHAIR_* environment variable is read by one accessor of yocto-hair_amd/host/switches.h, at every call: tests/cpp/test_switches.cpp
+    sets and unsets each and checks the parse rules and clamps (YHAIR_TIMING=0 is off; YHAIR_SHAPE, YHAIR_ST_SLOTS and YHAIR_INTERSECT clamp;
+    YHAIR_DEVICE_SHARE as a number and as the trial record's key) and that a value changed between two calls is seen by the second."""
+    exe = str(tmp_path / "test_switches")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-I" + os.path.join(ROOT, "yocto-hair_amd", "host"),
+                           os.path.join(ROOT, "tests", "cpp", "test_switches.cpp"), "-o", exe])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0 and "all checks passed" in out.stdout, out.stdout + out.stderr
+
+
+def test_stream_report_text(tmp_path):
+    """What YHAIR_ST_WAVELOG and YHAIR_ST_PROF print about a k_stream launch is read by tools/ (branch_budget.py, shard_ab.py,
+    stream_step_parts.sh, gpu_check.sh): tests/cpp/test_stream_report.cpp compiles the REAL host/stream_report.cpp with the device's copy
+    mocked and prints two wave logs and one counter table from fixed inputs; tests/golden/stream_report.txt is what the same inputs
+    printed before the reports moved out of stream_impl."""
+    exe = str(tmp_path / "test_stream_report")
+    subprocess.check_call(["g++", "-O1", "-std=c++17", "-pthread", "-D__HIP_PLATFORM_AMD__", "-Wno-unused-function", "-I/opt/rocm/include",
+                           "-I" + os.path.join(ROOT, "include"), "-I" + os.path.join(ROOT, "yocto-hair_amd", "host"),
+                           os.path.join(ROOT, "tests", "cpp", "test_stream_report.cpp"), "-o", exe, "-ldl"])
+    out = subprocess.run([exe], capture_output=True, text=True, timeout=60)
+    assert out.returncode == 0, out.stdout + out.stderr
+    assert out.stderr == open(os.path.join(ROOT, "tests", "golden", "stream_report.txt")).read()
+
+
 def test_eight_cold_ranks_share_one_trial_record(tmp_path):
     """Eight cold ranks on one node, rehearsed on CPU: tests/cpp/test_trial_ranks.cpp compiles the REAL
     host/launch_plan.cpp with the device mocked and drives its trial bookkeeping for eight ranks (threads) against ONE trials_v2.txt.

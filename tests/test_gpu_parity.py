@@ -912,6 +912,46 @@ def test_launch_shapes_and_kernels_render_identical_pixels(ctx, yh, name, kw, mo
     sf.close()
 
 
+def test_stream_reports_print_without_changing_the_render(ctx, yh, monkeypatch, capfd):
+    """The developer reports of a k_stream launch (host/stream_report.cpp: YHAIR_ST_WAVELOG's wave log, YHAIR_ST_PROF's tables of the
+    instrumented build) on the device: two launches with both switched on print their lines — one wave log per launch, the correlation
+    with the previous launch from the second on, the ten branch lines of each table — and render the bits and leave the RNG states of
+    the same two launches without them."""
+    sf = yh.SceneFile(scene_path("sphere-hairblock", scale=0.02))
+    ctx.upload_scene(sf.desc)
+    p = yh.TraceParams.default(resolution=40)
+    monkeypatch.setenv("YHAIR_SHAPE", "3")
+
+    def render(reports):
+        ctx.init_state(p)
+        if reports:  # (after yh_init_state: its probe launch of a new image would report too)
+            capfd.readouterr()
+            monkeypatch.setenv("YHAIR_ST_WAVELOG", "1")
+            monkeypatch.setenv("YHAIR_ST_PROF", "1")
+        shapes = []
+        for n in (2, 3):
+            ctx.trace_samples(n)
+            shapes.append(ctx.launch_shape())
+        return ctx.download(), ctx.download_rng(), shapes
+
+    plain = render(False)
+    reported = render(True)
+    err = capfd.readouterr().err
+    monkeypatch.delenv("YHAIR_ST_WAVELOG"), monkeypatch.delenv("YHAIR_ST_PROF"), monkeypatch.delenv("YHAIR_SHAPE")
+    assert plain[2] == [3, 3] and reported[2] == [3, 3]
+    assert plain[0][..., 3].max() > 0
+    assert np.array_equal(reported[0], plain[0]), "the reports change the pixels"
+    assert np.array_equal(reported[1], plain[1]), "the reports change the RNG states"
+    lines = err.splitlines()
+    logs = [i for i, l in enumerate(lines) if l.startswith("[yhair] k_stream wave log: ")]
+    assert len(logs) == 2, err
+    # (a launch prints its correlation line above its wave-log line)
+    assert any("correlation of the waves' ends with the previous launch's:" in l for l in lines[logs[0] + 1:logs[1]]), err
+    branches = [l.split()[2] for l in lines if l.startswith("[yhair]   branch ")]
+    assert branches == 2 * ["step", "pop", "scene", "enter", "fetch", "node", "line-leaf", "tri-leaf", "push", "2nd-seg"], err
+    sf.close()
+
+
 @pytest.mark.parametrize("name,kw", [("sphere-hairblock", dict(scale=0.05, zoom=True)), ("straight-hair", dict(scale=0.05))],
                          ids=["sphere-hairblock", "straight-hair"])
 def test_kernel_trials_are_cut_off_a_long_request(ctx, yh, name, kw, monkeypatch):

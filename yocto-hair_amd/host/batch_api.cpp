@@ -25,6 +25,24 @@ int finish(yh_context* ctx, int launch_err, void* dst, const void* src, size_t b
   HIPCHK(ctx, hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
   return YH_OK;
 }
+// the closest hits of n rays, after the wait for their kernel: object, element, uv and distance
+int download_hits(yh_context* ctx, int n, const int* dob, const int* del, const float* duv, const float* dd, int* object, int* element, float* uv, float* distance) {
+  HIPCHK(ctx, hipMemcpy(object, dob, 4 * (size_t)n, hipMemcpyDeviceToHost));
+  HIPCHK(ctx, hipMemcpy(element, del, 4 * (size_t)n, hipMemcpyDeviceToHost));
+  HIPCHK(ctx, hipMemcpy(uv, duv, 8 * (size_t)n, hipMemcpyDeviceToHost));
+  HIPCHK(ctx, hipMemcpy(distance, dd, 4 * (size_t)n, hipMemcpyDeviceToHost));
+  return YH_OK;
+}
+// a tree's nodes as the batch interface passes them, 8 floats each: min.xyz, max.xyz, start, num | internal << 16 | axis << 24
+void pack_nodes(const yhh::Tree& tree, float* nodes) {
+  for (size_t i = 0; i < tree.nodes.size(); i++) {
+    auto&  nd = tree.nodes[i];
+    float* o  = nodes + 8 * i;
+    memcpy(o, nd.bbox.min, 12), memcpy(o + 3, nd.bbox.max, 12);
+    int a = nd.start, c = (int)nd.num | ((int)nd.internal << 16) | ((int)nd.axis << 24);
+    memcpy(o + 6, &a, 4), memcpy(o + 7, &c, 4);
+  }
+}
 }  // namespace
 
 int yh_hair_brdf_batch(yh_context* ctx, int n, const yh_material* materials, const float* v, const float* normal,
@@ -130,14 +148,7 @@ int yh_bvh_build_gpu(yh_context* ctx, int n, const float* boxes, float* nodes, i
   yhh::Tree tree;
   int       rc = build_bvh_device(ctx, b, tree);
   if (rc) return rc;
-  if (nodes)
-    for (size_t i = 0; i < tree.nodes.size(); i++) {
-      auto&  nd = tree.nodes[i];
-      float* o  = nodes + 8 * i;
-      memcpy(o, nd.bbox.min, 12), memcpy(o + 3, nd.bbox.max, 12);
-      int a = nd.start, c = (int)nd.num | ((int)nd.internal << 16) | ((int)nd.axis << 24);
-      memcpy(o + 6, &a, 4), memcpy(o + 7, &c, 4);
-    }
+  if (nodes) pack_nodes(tree, nodes);
   if (primitives && n) memcpy(primitives, tree.primitives.data(), sizeof(int) * (size_t)n);
   return (int)tree.nodes.size();
 }
@@ -233,14 +244,7 @@ int yh_bvh_build(int n, const float* boxes, float* nodes, int* primitives) {
     for (int k = 0; k < 3; k++) b[(size_t)i].min[k] = boxes[6 * (size_t)i + k], b[(size_t)i].max[k] = boxes[6 * (size_t)i + 3 + k];
   yhh::Tree tree;
   yhh::build_bvh(tree, b);
-  if (nodes)
-    for (size_t i = 0; i < tree.nodes.size(); i++) {
-      auto&  nd = tree.nodes[i];
-      float* o  = nodes + 8 * i;
-      memcpy(o, nd.bbox.min, 12), memcpy(o + 3, nd.bbox.max, 12);
-      int a = nd.start, c = (int)nd.num | ((int)nd.internal << 16) | ((int)nd.axis << 24);
-      memcpy(o + 6, &a, 4), memcpy(o + 7, &c, 4);
-    }
+  if (nodes) pack_nodes(tree, nodes);
   if (primitives && n) memcpy(primitives, tree.primitives.data(), sizeof(int) * (size_t)n);
   return (int)tree.nodes.size();
 }
@@ -295,15 +299,15 @@ int yh_intersect_batch(yh_context* ctx, int n, const float* rays, int* object, i
   // Large batches of rays that start at the reference's ray_eps (every ray the path tracer itself makes) go one lane
   // per ray through the trace-only kernel (csrc/stream.hip: k_intersect_lanes), five waves per SIMD; small
   // ones, and rays with another tmin, a quad per ray (k_intersect). Same closest hits either way.
-  // YHAIR_INTERSECT=quad | lane4 | lane5 | lane6 | lane8: developer switch (waves per SIMD of the lane kernel).
-  const char* mode  = getenv("YHAIR_INTERSECT");
-  int         waves = 5;  // 91 registers without a spill: five waves per SIMD (6 and 8 spill 39 / 61 registers, measured slower)
-  bool        lanes = n >= 65536 && lane_kernels_can_address(ctx);
-  if (mode && !strcmp(mode, "quad")) lanes = false;
-  else if (mode && !strncmp(mode, "lane", 4)) {
+  // YHAIR_INTERSECT (developer switch): one of the two whatever the batch, and the lane kernel's waves per SIMD.
+  const yhh::IntersectSwitch forced = yhh::intersect_switch();
+  const int                  waves  = forced.waves;
+  bool                       lanes  = n >= 65536 && lane_kernels_can_address(ctx);
+  if (forced.mode == yhh::IntersectSwitch::QUAD) lanes = false;
+  else if (forced.mode == yhh::IntersectSwitch::LANES) {
     if (!lane_kernels_can_address(ctx))  // (beyond 4 GB the buffer resource clamps and the loads return zeros: wrong hits, no error)
-      return fail(ctx, YH_E_INVALID, "YHAIR_INTERSECT=%s: the one-lane kernel reads the scene's trees through 32-bit byte offsets and this scene's exceed 4 GB", mode);
-    lanes = true, waves = std::max(4, std::min(8, atoi(mode + 4)));
+      return fail(ctx, YH_E_INVALID, "YHAIR_INTERSECT=%s: the one-lane kernel reads the scene's trees through 32-bit byte offsets and this scene's exceed 4 GB", forced.text);
+    lanes = true;
   }
   for (int i = 0; lanes && i < n; i++) lanes = rays[8 * (size_t)i + 6] == 1e-4f;
   HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
@@ -311,15 +315,13 @@ int yh_intersect_batch(yh_context* ctx, int n, const float* rays, int* object, i
     const int occupancy = std::min(waves, yhk_intersect_lanes_occupancy(&ctx->scene, waves));  // (256-thread blocks: one wave per SIMD each)
     if (occupancy < 1) return fail(ctx, YH_E_DEVICE, "k_intersect_lanes cannot run with its LDS layout on this device");
     const int    grid        = (int)std::max<int64_t>(1, std::min<int64_t>(((int64_t)n + 255) / 256, (int64_t)ctx->num_cus * occupancy));
-    const int    ovf_entries = 2 * std::max(8, ctx->stack_need);
+    const int    ovf_entries = lane_overflow_entries(ctx);
     auto         dcur        = (int*)s.out(16);
     auto         dovf        = (unsigned int*)s.out((size_t)grid * 4 * ovf_entries * 64 * 4);
     if (s.rc) return s.rc;
-    if (!ctx->d_scene_copy.p) {
-      int rc = upload(ctx, ctx->d_scene_copy, &ctx->scene, sizeof(yhd_scene));
-      if (rc) return rc;
-    }
-    int e = yhk_intersect_lanes(&ctx->scene, (const yhd_scene*)ctx->d_scene_copy.p, n, dr, dcur, dovf, ovf_entries, dob, del, duv, dd, waves, grid, ctx->stream);
+    const yhd_scene* sc_dev = nullptr;
+    if (int rc = scene_copy(ctx, &sc_dev)) return rc;
+    int e = yhk_intersect_lanes(&ctx->scene, sc_dev, n, dr, dcur, dovf, ovf_entries, dob, del, duv, dd, waves, grid, ctx->stream);
     if (e) return fail(ctx, YH_E_DEVICE, "k_intersect_lanes launch: %s", hipGetErrorString((hipError_t)e));
   } else {
     int e = yhk_intersect(&ctx->scene, n, dr, dob, del, duv, dd, ctx->stream);
@@ -329,11 +331,7 @@ int yh_intersect_batch(yh_context* ctx, int n, const float* rays, int* object, i
   YH_WAIT(ctx);
   HIPCHK(ctx, hipEventElapsedTime(&ctx->last_ms, ctx->ev0, ctx->ev1));  // (yh_last_trace_ms: the kernel alone, without the copies)
   ctx->last_launches = 1;
-  HIPCHK(ctx, hipMemcpy(object, dob, 4 * (size_t)n, hipMemcpyDeviceToHost));
-  HIPCHK(ctx, hipMemcpy(element, del, 4 * (size_t)n, hipMemcpyDeviceToHost));
-  HIPCHK(ctx, hipMemcpy(uv, duv, 8 * (size_t)n, hipMemcpyDeviceToHost));
-  HIPCHK(ctx, hipMemcpy(distance, dd, 4 * (size_t)n, hipMemcpyDeviceToHost));
-  return YH_OK;
+  return download_hits(ctx, n, dob, del, duv, dd, object, element, uv, distance);
 }
 
 // intersect_scene_bvh through the traversal of the PLAIN 512-thread sample-loop kernels (unit/intersect_quad.hip)
@@ -354,11 +352,7 @@ int yh_intersect_plain_batch(yh_context* ctx, int form, int n, const float* rays
   int e = yhk_intersect_plain(&ctx->scene, form, n, dr, dob, del, duv, dd, ctx->stream);
   if (e) return fail(ctx, YH_E_DEVICE, "k_intersect_plain launch: %s", hipGetErrorString((hipError_t)e));
   YH_WAIT(ctx);
-  HIPCHK(ctx, hipMemcpy(object, dob, 4 * (size_t)n, hipMemcpyDeviceToHost));
-  HIPCHK(ctx, hipMemcpy(element, del, 4 * (size_t)n, hipMemcpyDeviceToHost));
-  HIPCHK(ctx, hipMemcpy(uv, duv, 8 * (size_t)n, hipMemcpyDeviceToHost));
-  HIPCHK(ctx, hipMemcpy(distance, dd, 4 * (size_t)n, hipMemcpyDeviceToHost));
-  return YH_OK;
+  return download_hits(ctx, n, dob, del, duv, dd, object, element, uv, distance);
 }
 
 int yh_scene_once(const yh_context* ctx) { return !ctx ? YH_E_INVALID : !ctx->have_scene ? YH_E_STATE : ctx->scene.scene_once; }
@@ -378,14 +372,12 @@ int yh_lights_batch(yh_context* ctx, int form, int n, const float* position, con
   if (form == 0) return finish(ctx, yhk_lights(&ctx->scene, n, dp, dd, dr, o, ctx->stream), out, o, 32 * (size_t)n);
   if (!lane_kernels_can_address(ctx))
     return fail(ctx, YH_E_INVALID, "yh_lights_batch: the one-lane form reads the scene's trees through 32-bit byte offsets and this scene's exceed 4 GB");
-  const int ovf_entries = 2 * std::max(8, ctx->stack_need);  // (as yh_intersect_batch sizes it)
+  const int ovf_entries = lane_overflow_entries(ctx);
   auto      dovf        = (unsigned int*)s.out((size_t)((n + 255) / 256) * 4 * ovf_entries * 64 * 4);
   if (s.rc) return s.rc;
-  if (!ctx->d_scene_copy.p) {
-    int rc = upload(ctx, ctx->d_scene_copy, &ctx->scene, sizeof(yhd_scene));
-    if (rc) return rc;
-  }
-  return finish(ctx, yhk_lights_lanes(&ctx->scene, (const yhd_scene*)ctx->d_scene_copy.p, n, dp, dd, dr, dovf, ovf_entries, o, ctx->stream), out, o, 32 * (size_t)n);
+  const yhd_scene* sc_dev = nullptr;
+  if (int rc = scene_copy(ctx, &sc_dev)) return rc;
+  return finish(ctx, yhk_lights_lanes(&ctx->scene, sc_dev, n, dp, dd, dr, dovf, ovf_entries, o, ctx->stream), out, o, 32 * (size_t)n);
 }
 
 // The homogeneous-medium code of a path (dev_path.h: medium_crossing, the free flight and the scatter of path_step) on the material rows

@@ -64,6 +64,14 @@ int alloc_zero(yh_context* ctx, DevBuf& buf, size_t bytes) {
   return YH_OK;
 }
 
+int lane_overflow_entries(const yh_context* ctx) { return 2 * std::max(8, ctx->stack_need); }
+int scene_copy(yh_context* ctx, const yhd_scene** sc_dev) {
+  if (!ctx->d_scene_copy.p)
+    if (int rc = upload(ctx, ctx->d_scene_copy, &ctx->scene, sizeof(yhd_scene))) return rc;
+  *sc_dev = (const yhd_scene*)ctx->d_scene_copy.p;
+  return YH_OK;
+}
+
 yhd_float4 node_lo(const yhh::Node& n) {
   yhd_float4 r{n.bbox.min[0], n.bbox.min[1], n.bbox.min[2], 0};
   memcpy(&r.w, &n.start, 4);

@@ -6,6 +6,8 @@
 //                      records, inverse frames, per-material hair constants, light CDFs; the wide-node and lane-blob arrays
 //   launch_plan.cpp    which kernel runs (timing trials, their record in memory and on disk) and the hand-out order of the work items
 //   trace_launch.cpp   yh_init_state (pt.cpp:1931-1946) and the launches: yh_trace_samples and friends
+//   stream_report.cpp  what the developer switches print about a launch (YHAIR_ST_WAVELOG, YHAIR_ST_PROF) and the laps of YHAIR_TIMING
+//   (switches.h: every YHAIR_* environment variable, one accessor each)
 //   gather.cpp         tile packing and the one collective (yh_gather_framebuffer: RCCL or peer copies)
 //   batch_api.cpp      the unit-level batch entry points (hair BSDF, intersection, BVH build, curves, self-tests)
 //   gbuffer.cpp        yh_trace_gbuffer / _device: the first-hit feature pass over the state's image (unit/gbuffer.hip)
@@ -49,6 +51,7 @@
 #include "../unit/light_list.h"   // yhk_light_job
 #include "bvh_build.h"
 #include "deadline.h"
+#include "switches.h"
 #include "yhair.h"
 
 // launchers in csrc/kernels.hip
@@ -386,10 +389,17 @@ int fail(yh_context* ctx, int code, const char* fmt, ...);
 int upload(yh_context* ctx, DevBuf& buf, const void* src, size_t bytes);
 int upload_keep(yh_context* ctx, DevBuf& buf, const void* src, size_t bytes);  // ... into a buffer that is kept while it is large enough
 int alloc_zero(yh_context* ctx, DevBuf& buf, size_t bytes);
+// what every sample-loop launch clears before it starts (begin_launch) and yh_init_state allocates: the cursors of the work list — one, or
+// k_stream's one per item group 64 bytes apart — and a cost per work item, four items per tile
+constexpr size_t YH_TILE_CURSOR_BYTES = 8 * 16 * 4;
+inline size_t tile_cost_bytes(const yh_context* ctx) { return (size_t)ctx->num_tiles_total * 16; }
+// entries per lane of the overflow of the lane kernels' LDS stack windows (dev_lane.h): a main ray plus a light-pdf ray above it
+int lane_overflow_entries(const yh_context* ctx);
+// the scene table in device memory, for the lane kernels' out-of-line callees: uploaded at the first use
+int scene_copy(yh_context* ctx, const yhd_scene** sc_dev);
 int dev_alloc(yh_context* ctx, DevBuf& buf, size_t bytes);  // a plain allocation: no wait, no copy, content undefined
 yhd_float4 node_lo(const yhh::Node& n);
 yhd_float4 node_hi(const yhh::Node& n);
-int forced_shape();  // YHAIR_SHAPE, -1 when unset
 void trials_load(yh_context* ctx);
 bool trials_off();
 void record_launch(yh_context* ctx, int nsamples, bool fresh_costs);
@@ -410,6 +420,18 @@ void note_stream_wave_log(yh_context* ctx, const unsigned long long* log, size_t
 void deal_items_for_stream(yh_context* ctx, std::vector<int>& items);
 int build_bvh_device(yh_context* ctx, const std::vector<yhh::Box>& boxes, yhh::Tree& tree);
 int stream_impl(yh_context* ctx, int nsamples, bool sync);
+// stream_report.cpp: the developer reports of a k_stream launch on stderr — YHAIR_ST_WAVELOG's, from the waves' {begin, end} stamps, and
+// YHAIR_ST_PROF's, which reads the launch's counters (d_st_prof) back — and YHAIR_TIMING's stage times of one call: lap(what) prints
+// "[yhair] <prefix>: <what> <ms since the last lap>", nothing when timing is off
+void report_stream_waves(const yh_context* ctx, const unsigned long long* stamps, size_t waves, int waves_per_block);
+int report_stream_prof(yh_context* ctx, int grid, int waves_per_block, int slots_per_wave);
+struct Lap {
+  const char*                           prefix;
+  const bool                            on = yhh::timing();
+  std::chrono::steady_clock::time_point t_last = std::chrono::steady_clock::now();
+  explicit Lap(const char* prefix_) : prefix(prefix_) {}
+  void operator()(const char* what);
+};
 int trace_impl(yh_context* ctx, int nsamples, bool counted, bool sync);
 int wait_for_launch(yh_context* ctx);  // hipStreamSynchronize(ctx->stream) with a deadline (host/deadline.h)
 int side_by_side_impl(yh_context* ctx, int nsamples, bool sync);

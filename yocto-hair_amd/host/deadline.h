@@ -24,6 +24,8 @@
 #include <mutex>
 #include <thread>
 
+#include "switches.h"  // yhh::launch_timeout_s: the deadline itself, YHAIR_LAUNCH_TIMEOUT_S
+
 namespace yhh {
 
 enum { WAIT_DONE = 0, WAIT_EXPIRED = 1, WAIT_ERROR = 2 };
@@ -120,19 +122,6 @@ class BoundedCall {
     return WAIT_DONE;
   }
 };
-
-// YHAIR_LAUNCH_TIMEOUT_S (seconds, fractions allowed; <= 0 or unparsable: the default). Read at every wait: a test sets it per call.
-inline double launch_timeout_s() {
-  const char* e = getenv("YHAIR_LAUNCH_TIMEOUT_S");
-  if (e && *e) {
-    char*        end = nullptr;
-    const double v   = strtod(e, &end);
-    // (clamped: duration<double> -> the condition variable's integer nanoseconds overflows above ~9.2e9 s, and a deadline in the past would
-    // poison a healthy context at its first long wait; 1e8 s = three years is "never")
-    if (end != e && v > 0) return v < 1e8 ? v : 1e8;
-  }
-  return 1800.0;
-}
 
 }  // namespace yhh
 #endif

@@ -99,11 +99,9 @@ int yh_gather_framebuffer(yh_context** ctxs, int n, float* rgba) {
   bool distinct = true;
   for (int i = 0; i < n; i++)
     for (int j = 0; j < i; j++) distinct = distinct && ctxs[i]->device != ctxs[j]->device;
-  // YHAIR_GATHER=peer: device-to-device copies even between distinct devices; YHAIR_GATHER=rccl: the collective even
-  // for ONE context (a communicator of one rank: how a one-GPU box executes the RCCL calls, tests/test_gpu_parity.py)
-  const char* mode_env = getenv("YHAIR_GATHER");
-  const bool  force_rccl = mode_env && !strcmp(mode_env, "rccl");
-  const bool  use_rccl = distinct && (n > 1 || force_rccl) && !(mode_env && !strcmp(mode_env, "peer"));
+  // (YHAIR_GATHER: peer copies even between distinct devices, or the collective even for ONE context)
+  const yhh::GatherSwitch forced = yhh::gather_switch();
+  const bool use_rccl = distinct && (n > 1 || forced == yhh::GATHER_RCCL) && forced != yhh::GATHER_PEER;
   // every context packs its own tiles on its own stream
   for (int i = 0; i < n; i++) {
     yh_context* c = ctxs[i];

@@ -21,11 +21,10 @@ static bool dense_by_costs(const yh_context* ctx, bool* known, bool* chain_bound
     }
   *known = mx != 0;
   if (mx == 0) return false;
-  // YHAIR_DEVICE_SHARE=k: k processes render on this device at once (bench.py with more ranks than devices): a k-th of the waves is ours
-  static const double share = std::max(1, getenv("YHAIR_DEVICE_SHARE") ? atoi(getenv("YHAIR_DEVICE_SHARE")) : 1);
+  const double share = yhh::device_share();  // (that many processes render on this device at once: a share-th of the waves is ours)
   int    lds      = yhk_trace_lds_bytes(&ctx->scene, YH_SHAPE_QUAD);
   double resident = (double)ctx->num_cus * std::max(1, yhk_trace_occupancy(lds, ctx->scene.general_materials, YH_SHAPE_QUAD)) * (yhk_block_threads(YH_SHAPE_QUAD) / 64) / share;
-  if (getenv("YHAIR_TIMING")) fprintf(stderr, "[yhair] launch shape: worth %.0f items, resident waves %.0f\n", (double)sum / (double)mx, resident);
+  if (yhh::timing()) fprintf(stderr, "[yhair] launch shape: worth %.0f items, resident waves %.0f\n", (double)sum / (double)mx, resident);
   if (chain_bound) {  // the octet kernel needs two waves per expensive item: all of them resident at once, with room to spare
     const int    lds4 = yhk_trace_lds_bytes(&ctx->scene, YH_SHAPE_OCT);
     const double res4 = (double)ctx->num_cus * std::max(1, yhk_trace_occupancy(lds4, ctx->scene.general_materials, YH_SHAPE_OCT)) * (yhk_block_threads(YH_SHAPE_OCT) / 64) / share;
@@ -35,9 +34,6 @@ static bool dense_by_costs(const yh_context* ctx, bool* known, bool* chain_bound
     if (chain16) *chain16 = 4.0 * (double)sum / (double)mx <= 2.5 * res4;
   }
   return (double)sum / (double)mx >= resident;
-}
-int forced_shape() {  // YHAIR_SHAPE=s (developer switch): every launch runs shape s, or its fallback (settle_launch_shape); -1 when unset
-  return getenv("YHAIR_SHAPE") ? std::max(0, std::min(YH_SHAPES - 1, atoi(getenv("YHAIR_SHAPE")))) : -1;
 }
 static int quad_by_costs(const yh_context* ctx) { return ctx->dense > 0 ? YH_SHAPE_QUAD_DENSE : YH_SHAPE_QUAD; }
 // Kernel selection by MEASUREMENT (every kernel renders the same bits, so trying one costs time only). k_trace at
@@ -99,9 +95,9 @@ int yh_set_trial_cache_dir(const char* dir) {
   return YH_OK;
 }
 static std::string disk_cache_path() {
-  if (getenv("YHAIR_NO_DISK_CACHE") || getenv("YHAIR_NO_TRIAL_CACHE")) return "";
+  if (yhh::no_disk_cache() || yhh::no_trial_cache()) return "";
   std::string dir;
-  if (const char* e = getenv("YHAIR_CACHE_DIR")) dir = e;
+  if (const char* e = yhh::cache_dir()) dir = e;
   else {
     std::lock_guard<std::mutex> lock(g_cache_dir_mutex);
     dir = g_cache_dir;
@@ -132,9 +128,8 @@ static const std::string& library_fingerprint() {
   return fp;
 }
 static std::string disk_key(const yh_context* ctx) {
-  const char* share = getenv("YHAIR_DEVICE_SHARE");
   char buf[320];
-  snprintf(buf, sizeof(buf), "%s|%s|%s|%016llx|%d|%d|%d|%d|%d", ctx->device_name.c_str(), library_fingerprint().c_str(), share ? share : "1",
+  snprintf(buf, sizeof(buf), "%s|%s|%s|%016llx|%d|%d|%d|%d|%d", ctx->device_name.c_str(), library_fingerprint().c_str(), yhh::device_share_key(),
       (unsigned long long)ctx->scene_key, ctx->state.width, ctx->state.height, ctx->rank, ctx->world, ctx->state.bounces);
   return buf;
 }
@@ -202,7 +197,7 @@ static void trials_store(const yh_context* ctx) {
 }
 void trials_load(yh_context* ctx) {
   ctx->trials_from_disk = false, ctx->trials_on_disk = false;
-  if (getenv("YHAIR_NO_TRIAL_CACHE")) return;  // developer switch
+  if (yhh::no_trial_cache()) return;
   TrialRecord r{};
   bool        have = false;
   {
@@ -213,16 +208,13 @@ void trials_load(yh_context* ctx) {
   if (!have && !trials_off() && disk_load(ctx, r)) {
     have = true;
     ctx->trials_from_disk = true, ctx->trials_on_disk = true;
-    if (getenv("YHAIR_TIMING")) fprintf(stderr, "[yhair] kernel trials of this image: read from %s\n", disk_cache_path().c_str());
+    if (yhh::timing()) fprintf(stderr, "[yhair] kernel trials of this image: read from %s\n", disk_cache_path().c_str());
   }
   if (!have) return;
   for (int k = 0; k < YH_SHAPES; k++) ctx->shape_ms[k] = r.ms[k], ctx->shape_trials[k] = r.trials[k];
   ctx->dense = r.dense, ctx->chain = r.chain, ctx->chain16 = r.chain16;
 }
-bool trials_off() {
-  static const bool off = getenv("YHAIR_NO_TRIALS") != nullptr;  // developer switch: the cost heuristic only
-  return off || forced_shape() >= 0;
-}
+bool trials_off() { return yhh::no_trials() || yhh::forced_shape() >= 0; }
 // k_trace 512 x 4 always; the dense quad shape unless the image is chain-bound; k_stream on dense images; the side-by-side
 // launch on sparse ones; on chain-bound
 // ones (a shard of a sparse image on one of several GPUs, a small image) the octet kernel and, when even four waves per
@@ -245,7 +237,7 @@ static int candidates(const yh_context* ctx, int cand[6]) {
 void record_launch(yh_context* ctx, int nsamples, bool fresh_costs) {
   const int last = ctx->last_shape;
   bool trial = false;
-  static const bool prof_build = getenv("YHAIR_ST_PROF") && atoi(getenv("YHAIR_ST_PROF")) != 0;  // the instrumented k_stream: its times rank nothing
+  const bool prof_build = yhh::st_prof() != 0;  // the instrumented k_stream: its times rank nothing
   if (!prof_build && nsamples >= YH_TRIAL_SPP && nsamples < 2 * YH_TRIAL_SPP && ctx->planned_settled && !ctx->last_counted && !ctx->params.hair_exact && last >= 0 && last < YH_SHAPES && ctx->last_ms > 0) {
     const double ms = (double)ctx->last_ms / nsamples;
     ctx->shape_ms[last] = ctx->shape_trials[last] > 0 ? std::min(ctx->shape_ms[last], ms) : ms;
@@ -293,7 +285,7 @@ bool trial_pending(const yh_context* ctx) {
 // The kernel for a launch of `nsamples`.
 int pick_launch_shape(const yh_context* ctx, int nsamples) {
   if (ctx->params.hair_exact) return YH_SHAPE_QUAD;  // the exact arithmetic exists as the 512 x 4 quad kernel only (csrc/exact.hip)
-  if (const int forced = forced_shape(); forced >= 0) return forced;
+  if (const int forced = yhh::forced_shape(); forced >= 0) return forced;
   if (!ctx->have_costs) return ctx->launch_shape;  // the first launch of an image: unplanned, not a measurement
   const int by_costs = quad_by_costs(ctx);
   if (trials_off()) return by_costs;
@@ -450,14 +442,14 @@ int upload_work_items(yh_context* ctx) {
 bool settle_launch_shape(yh_context* ctx, bool counted, int nsamples, bool sync) {
   if (ctx->state.shader != YH_SHADER_PATH) return false;  // (the preview shaders have one launch shape)
   int shape = counted ? ctx->state.launch_shape : pick_launch_shape(ctx, sync ? nsamples : 0);  // (an asynchronous launch is not timed: never a trial)
-  if (!counted && shape != ctx->state.launch_shape && getenv("YHAIR_TIMING")) {
+  if (!counted && shape != ctx->state.launch_shape && yhh::timing()) {
     for (int k = 0; k < YH_SHAPES; k++) fprintf(stderr, "%s %s: %.4f", k ? "," : "[yhair] kernel times (ms per spp):", yhd_shapes[k].name, ctx->shape_ms[k]);
     fprintf(stderr, " -> %d (%d spp)\n", shape, nsamples);
   }
   auto fallback = [ctx](int s) { return yhd_shapes[s].fallback < 0 ? quad_by_costs(ctx) : yhd_shapes[s].fallback; };
   const int general = ctx->scene.general_materials;
   if (counted && !(general ? yhd_shapes[shape].counted_general : yhd_shapes[shape].counted_plain)) shape = fallback(shape);
-  if (forced_shape() < 0) {  // (a forced shape that cannot run fails at its launch)
+  if (yhh::forced_shape() < 0) {  // (a forced shape that cannot run fails at its launch)
     const int kind = yhd_shapes[shape].kind;
     int       P = 0, grid = 0;
     if ((kind == YH_SHAPE_KIND_STREAM && !stream_geometry(ctx, (int)ctx->owned.size() * 4, &P, &grid, nullptr)) ||  // (as many items as deal_items_for_stream deals)
@@ -504,12 +496,13 @@ int stream_geometry(const yh_context* ctx, int num_items, int* slots_per_wave, i
   const int     wpb    = yhk_stream_block_threads() / 64;
   const int64_t pixels = (int64_t)num_items * 16;  // work items are 4x4 pixel quadrants
   int           P      = (int)std::max<int64_t>(128, std::min<int64_t>(192, (pixels / ((int64_t)ctx->num_cus * 16) + 63) / 64 * 64));
-  const bool    forced = getenv("YHAIR_ST_SLOTS") != nullptr;
-  if (forced) P = std::max(64, std::min(4096, atoi(getenv("YHAIR_ST_SLOTS")) / 64 * 64));
+  const int     slots  = yhh::st_slots();
+  const bool    forced = slots != 0;
+  if (forced) P = slots;
   int lds_bytes = yhk_stream_lds_bytes(YHD_LDS_TABLES_F4(&ctx->scene), P);
   int occupancy = yhk_stream_occupancy(lds_bytes, ctx->scene.general_materials);
   if (occupancy < 1) return 0;
-  if (const char* env = getenv("YHAIR_ST_WAVES")) occupancy = std::max(1, std::min(occupancy, (atoi(env) + wpb - 1) / wpb));  // waves per CU
+  occupancy = yhh::st_occupancy(occupancy, wpb);
   int64_t want = (pixels + (int64_t)P * wpb - 1) / ((int64_t)P * wpb);
   int     grid = (int)std::max<int64_t>(1, std::min<int64_t>(want, (int64_t)ctx->num_cus * occupancy));
   // ONE GENERATION (round 5): when the resident waves hold the whole image at once (C2 at 720^2: 127 pixels per wave) no wave ever takes a
@@ -599,7 +592,7 @@ static bool deal_shares_by_speed(yh_context* ctx, std::vector<int>& items, int P
         }
         ctx->st_wave_speed[w] = std::min(1.5f, std::max(0.67f, ctx->st_wave_speed[w] * (float)std::pow(ratio, -0.33)));
       }
-      if (getenv("YHAIR_TIMING")) {
+      if (yhh::timing()) {
         fprintf(stderr, "[yhair] k_stream shares: wave-slot speeds (dispatch rounds)");
         for (double v : ctx->stream_speed) fprintf(stderr, " %.3f", v);
         fprintf(stderr, "\n");

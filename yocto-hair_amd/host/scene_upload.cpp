@@ -207,9 +207,8 @@ StackNeeds stack_needs(bool scene_wide, int scene_wide_depth, int scene_tree_dep
 // (the configs' sphere and lights: 10 ms together) are built on the host and their trees and records uploaded into the same arrays;
 // the collapses are the device's for both. YHAIR_BVH=host: every shape the small way; YHAIR_BVH=device: every shape on the device.
 bool shape_builds_on_device(int num_prims) {
-  const char* bvh_env   = getenv("YHAIR_BVH");  // developer switch, read per call
-  const bool  host_only = bvh_env && !strcmp(bvh_env, "host"), device_all = bvh_env && !strcmp(bvh_env, "device");
-  return (num_prims >= 32768 || device_all) && !host_only;
+  const yhh::BvhSwitch forced = yhh::bvh_switch();
+  return (num_prims >= 32768 || forced == yhh::BVH_DEVICE) && forced != yhh::BVH_HOST;
 }
 
 // `s`: the shape, its indices checked; its arrays on the host, or (arrays_on_device, which needs on_device) in device memory. The records
@@ -373,15 +372,7 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
         if (id < 0 || id > sd->num_textures) return fail(ctx, YH_E_INVALID, "material %d: a map references a missing texture (%d of %d)", i, id, sd->num_textures);
       any_maps = any_maps || has_effective_map(m);
     }
-  // YHAIR_TIMING=1: stage times of the upload on stderr
-  const bool timing = getenv("YHAIR_TIMING") && atoi(getenv("YHAIR_TIMING")) != 0;
-  auto       t_last = std::chrono::steady_clock::now();
-  auto       lap    = [&](const char* what) {
-    if (!timing) return;
-    auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[yhair] upload: %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-    t_last = now;
-  };
+  Lap lap("upload");  // YHAIR_TIMING=1: stage times of the upload on stderr
   // ---- per-shape BVHs and leaf-ordered records ---------------------------------------------------------------------------
   // (build_shape_tree above: big shapes on the device, small ones on the host, the collapses the device's for both)
   struct ShapeInfo : ShapeTree {

@@ -51,14 +51,7 @@ int yh_init_state(yh_context* ctx, const yh_trace_params* params) {
   if (params->hair_exact && params->shader != YH_SHADER_PATH) return fail(ctx, YH_E_INVALID, "hair_exact exists for the path shader only");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   YH_WAIT(ctx);  // (an asynchronous launch may still be running on the buffers this call replaces: wait for it, within the deadline)
-  const bool timing = getenv("YHAIR_TIMING") && atoi(getenv("YHAIR_TIMING")) != 0;
-  auto       t_last = std::chrono::steady_clock::now();
-  auto       lap    = [&](const char* what) {
-    if (!timing) return;
-    auto now = std::chrono::steady_clock::now();
-    fprintf(stderr, "[yhair] init_state: %-28s %8.1f ms\n", what, std::chrono::duration<double, std::milli>(now - t_last).count());
-    t_last = now;
-  };
+  Lap        lap("init_state");
   const bool same_work = ctx->have_state && ctx->params.shader == params->shader && ctx->params.bounces == params->bounces;  // (what the items' relative costs depend on besides the image)
   ctx->params = *params;
   // image size (pt.cpp:1933-1939)
@@ -98,7 +91,7 @@ int yh_init_state(yh_context* ctx, const yh_trace_params* params) {
   }
   std::vector<int> tiles;
   build_work_items(ctx, tiles);
-  const int first_shape = forced_shape() >= 0 ? forced_shape() : ctx->launch_shape;
+  const int first_shape = yhh::forced_shape() >= 0 ? yhh::forced_shape() : ctx->launch_shape;
   prepare_work_list(ctx, tiles, params->shader == YH_SHADER_PATH ? first_shape : YH_SHAPE_QUAD);
   tiles.reserve(4 * (size_t)ctx->num_tiles_total * 4 + 4);  // (the list's buffer holds the octet / sixteen-lane kernels' longer lists too)
   int rc;
@@ -113,8 +106,8 @@ int yh_init_state(yh_context* ctx, const yh_trace_params* params) {
     tiles.resize(n);
   }
   if ((rc = alloc_zero(ctx, ctx->d_counters, sizeof(yhd_counters)))) return rc;
-  if ((rc = alloc_zero(ctx, ctx->d_tile_cursor, 8 * 16 * 4))) return rc;  // one cursor, or k_stream's one per item group 64 bytes apart
-  if ((rc = alloc_zero(ctx, ctx->d_tile_cost, (size_t)ctx->num_tiles_total * 16))) return rc;
+  if ((rc = alloc_zero(ctx, ctx->d_tile_cursor, YH_TILE_CURSOR_BYTES))) return rc;
+  if ((rc = alloc_zero(ctx, ctx->d_tile_cost, tile_cost_bytes(ctx)))) return rc;
   auto& s = ctx->state;
   s.tile_cursor = (int*)ctx->d_tile_cursor.p, s.tile_cost = (unsigned int*)ctx->d_tile_cost.p;
   s.rng_state = (uint64_t*)ctx->d_rng_state.p, s.rng_inc = (uint64_t*)ctx->d_rng_inc.p;
@@ -134,7 +127,7 @@ int yh_init_state(yh_context* ctx, const yh_trace_params* params) {
   bool measured = false;
   for (int t : owned)
     for (int q = 0; q < 4 && !measured; q++) measured = ctx->item_cost[(size_t)t * 4 + q] != 0;
-  if (!measured && !owned.empty() && params->shader == YH_SHADER_PATH && !getenv("YHAIR_NO_PROBE")) {
+  if (!measured && !owned.empty() && params->shader == YH_SHADER_PATH && !yhh::no_probe()) {
     ctx->state.launch_shape = YH_SHAPE_QUAD;
     int prc = trace_impl(ctx, 1, false, true);  // blocking; re-plans the hand-out order from the measured costs
     if (prc) return prc;
@@ -148,6 +141,13 @@ int yh_init_state(yh_context* ctx, const yh_trace_params* params) {
   return YH_OK;
 }
 
+// The start of every sample-loop launch: the work list's cursors and the items' costs cleared, and the start event.
+static int begin_launch(yh_context* ctx) {
+  HIPCHK(ctx, hipMemsetAsync(ctx->d_tile_cursor.p, 0, YH_TILE_CURSOR_BYTES, ctx->stream));
+  HIPCHK(ctx, hipMemsetAsync(ctx->d_tile_cost.p, 0, tile_cost_bytes(ctx), ctx->stream));
+  HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  return YH_OK;
+}
 // The end of every sample-loop launch: its stop event and samples and, for a blocking one, the bounded wait, its time, what the
 // kernel leaves to read back (`read_back`: k_stream's wave stamps) and the re-plan.
 template <typename F>
@@ -187,8 +187,7 @@ int stream_impl(yh_context* ctx, int nsamples, bool sync) {
       return fail(ctx, YH_E_STATE, "k_stream: the work list was shared out for %zu waves of %d slots and the launch has %zu of %d", ctx->st_share_waves, ctx->st_share_slots, waves, P);
   }
   const size_t  slots  = waves * P;
-  // overflow of the per-lane LDS stack windows (dev_lane.h): a main ray plus a light-pdf ray above it
-  const int    ovf_entries = 2 * std::max(8, ctx->stack_need);
+  const int    ovf_entries = lane_overflow_entries(ctx);
   const size_t ovf_words   = waves * (size_t)ovf_entries * 64;
   int rc;
   if (slots > ctx->st_slots) {
@@ -207,17 +206,17 @@ int stream_impl(yh_context* ctx, int nsamples, bool sync) {
   }
   ctx->stream_pool.slots_per_wave = P, ctx->stream_pool.ovf_entries = ovf_entries, ctx->stream_pool.total_slots = (long long)ctx->st_slots;
   ctx->stream_pool.suspend_lanes  = one_generation ? 8 : 16;  // (csrc/stream.hip: YH_SUSPEND_LANES)
-  const bool prof = getenv("YHAIR_ST_PROF") && atoi(getenv("YHAIR_ST_PROF")) != 0;  // developer switch: per-stage counters on stderr
+  const int prof = yhh::st_prof();  // developer switch: per-stage counters on stderr
   if (prof) {
     if ((rc = alloc_zero(ctx, ctx->d_st_prof, 64 * 8))) return rc;
     ctx->stream_pool.prof = (unsigned long long*)ctx->d_st_prof.p;
-    ctx->stream_pool.prof_parts_only = atoi(getenv("YHAIR_ST_PROF")) == 2;
+    ctx->stream_pool.prof_parts_only = prof == 2;
   } else {
     ctx->stream_pool.prof = nullptr;
   }
   // every launch keeps the waves' begin / end stamps and work (32 bytes per wave): the speeds of the hardware wave slots the next
   // hand-out is sized by (launch_plan.cpp: note_stream_wave_log); YHAIR_ST_WAVELOG prints their distribution
-  const bool wave_log = getenv("YHAIR_ST_WAVELOG") != nullptr;
+  const bool wave_log = yhh::st_wavelog();
   if (ctx->d_st_wave_log.bytes < waves * 16)
     if ((rc = alloc_zero(ctx, ctx->d_st_wave_log, waves * 16))) return rc;
   ctx->stream_pool.wave_log = (unsigned long long*)ctx->d_st_wave_log.p;
@@ -227,79 +226,17 @@ int stream_impl(yh_context* ctx, int nsamples, bool sync) {
       if ((rc = alloc_zero(ctx, ctx->d_st_wave_fill, waves * 4))) return rc;
     ctx->stream_pool.wave_fill = (int*)ctx->d_st_wave_fill.p;
   }
-  if (!ctx->d_scene_copy.p) {  // the scene table in device memory, for the kernel's out-of-line callees
-    if ((rc = upload(ctx, ctx->d_scene_copy, &ctx->scene, sizeof(yhd_scene)))) return rc;
-  }
-  HIPCHK(ctx, hipMemsetAsync(ctx->d_tile_cursor.p, 0, 8 * 16 * 4, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(ctx->d_tile_cost.p, 0, (size_t)ctx->num_tiles_total * 16, ctx->stream));
-  HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int e = yhk_stream(&ctx->scene, (const yhd_scene*)ctx->d_scene_copy.p, &ctx->state, nsamples, &ctx->stream_pool, grid, ctx->stream);
+  const yhd_scene* sc_dev = nullptr;
+  if ((rc = scene_copy(ctx, &sc_dev))) return rc;
+  if ((rc = begin_launch(ctx))) return rc;
+  int e = yhk_stream(&ctx->scene, sc_dev, &ctx->state, nsamples, &ctx->stream_pool, grid, ctx->stream);
   if (e) return fail(ctx, YH_E_DEVICE, "k_stream launch: %s", hipGetErrorString((hipError_t)e));
   return end_launch(ctx, nsamples, sync, [&]() -> int {
     std::vector<unsigned long long> w(waves * 2);
     HIPCHK(ctx, hipMemcpy(w.data(), ctx->d_st_wave_log.p, w.size() * 8, hipMemcpyDeviceToHost));
     note_stream_wave_log(ctx, w.data(), waves);
-    if (wave_log) {
-      unsigned long long t0 = ~0ull, t1 = 0;
-      for (size_t i = 0; i < waves; i++) t0 = std::min(t0, w[2 * i]), t1 = std::max(t1, w[2 * i + 1]);
-      const double span = (double)(t1 - t0);
-      // by hardware wave slot (= dispatch round of the wave's workgroup: num_cus workgroups per round) and by XCC (workgroup % 8)
-      double sum_slot[16] = {}, n_slot[16] = {}, sum_x[8] = {}, n_x[8] = {}, start_slot[16] = {};
-      std::vector<double> ends;
-      double resident = 0;
-      for (size_t i = 0; i < waves; i++) {
-        const size_t blk = i / wpb;
-        const int    sl = (int)std::min<size_t>(15, blk / ctx->num_cus), x = (int)(blk % 8);
-        const double e = (double)(w[2 * i + 1] - t0) / span, b = (double)(w[2 * i] - t0) / span;
-        sum_slot[sl] += e, n_slot[sl] += 1, sum_x[x] += e, n_x[x] += 1, start_slot[sl] += b;
-        ends.push_back(e), resident += e - b;
-      }
-      {  // do the same waves end late launch after launch? correlation of the end stamps with the previous launch's (same wave count)
-        static std::vector<double> prev;
-        if (prev.size() == ends.size()) {
-          double ma = 0, mb = 0, saa = 0, sbb = 0, sab = 0;
-          for (size_t i = 0; i < ends.size(); i++) ma += ends[i], mb += prev[i];
-          ma /= ends.size(), mb /= ends.size();
-          for (size_t i = 0; i < ends.size(); i++) saa += (ends[i] - ma) * (ends[i] - ma), sbb += (prev[i] - mb) * (prev[i] - mb), sab += (ends[i] - ma) * (prev[i] - mb);
-          fprintf(stderr, "[yhair]   correlation of the waves' ends with the previous launch's: %.3f\n", sab / std::sqrt(std::max(1e-30, saa * sbb)));
-        }
-        prev = ends;
-      }
-      std::sort(ends.begin(), ends.end());
-      fprintf(stderr, "[yhair] k_stream wave log: %zu waves, span %.2f ms; a wave is resident %.3f of the span on average; ends at p10 %.3f p50 %.3f p90 %.3f p99 %.3f\n", waves,
-          span / 1e5, resident / waves, ends[waves / 10], ends[waves / 2], ends[waves * 9 / 10], ends[waves * 99 / 100]);
-      for (int k = 0; k < 16; k++)
-        if (n_slot[k] > 0) fprintf(stderr, "[yhair]   dispatch round %d: %4.0f waves, begin %.3f, mean end %.3f\n", k, n_slot[k], start_slot[k] / n_slot[k], sum_slot[k] / n_slot[k]);
-      fprintf(stderr, "[yhair]   mean end by XCC:");
-      for (int k = 0; k < 8; k++) fprintf(stderr, " %.3f", n_x[k] > 0 ? sum_x[k] / n_x[k] : 0.0);
-      fprintf(stderr, "\n");
-    }
-    if (prof) {
-      unsigned long long c[64];
-      HIPCHK(ctx, hipMemcpy(c, ctx->d_st_prof.p, sizeof(c), hipMemcpyDeviceToHost));
-      const char* names[6] = {"items", "sort", "finish", "hair", "surf", "trace"};
-      double total = 0;
-      for (int k = 0; k < 6; k++) total += (double)c[k];
-      fprintf(stderr, "[yhair] k_stream %.2f ms, grid %d x %d waves, %d slots per wave\n", ctx->last_ms, grid, wpb, P);
-      for (int k = 0; k < 6; k++)
-        fprintf(stderr, "[yhair]   %-7s %5.1f %% of wave time, %9llu trips, mean batch %.1f lanes\n", names[k], 100.0 * (double)c[k] / total,
-            c[8 + k], c[8 + k] ? (double)c[16 + k] / (double)c[8 + k] : 0.0);
-      fprintf(stderr, "[yhair]   trace: %llu wave steps, %.1f lanes busy on average, %.0f cycles per step\n", c[24],
-          c[24] ? (double)c[25] / (double)c[24] : 0.0, c[24] ? (double)c[5] / (double)c[24] : 0.0);
-      {  // the five parts of a step (csrc/dev_lane.h: stamp), shader-clock cycles per wave step
-        const char* part[5] = {"head (pop, scene level, ENTER)", "own loads, exchange, segment loads issued", "ray pulls, the wait for memory, node code", "the wave's line tests",
-            "results back, accept"};
-        double      sum = 0;
-        for (int k = 0; k < 5; k++) sum += (double)c[52 + k];
-        for (int k = 0; k < 5 && c[24]; k++)
-          fprintf(stderr, "[yhair]   step part %d %-46s %7.0f cycles per step (%4.1f %% of the stamped step)\n", k, part[k], (double)c[52 + k] / (double)c[24], sum > 0 ? 100.0 * (double)c[52 + k] / sum : 0.0);
-      }
-      // per branch of lane_step (csrc/dev_lane.h: LP_*): the share of the wave steps that ran it, and the lanes in it when it ran
-      const char* br[10] = {"step", "pop", "scene", "enter", "fetch", "node", "line-leaf", "tri-leaf", "push", "2nd-seg"};
-      for (int b = 0; b < 10; b++)
-        fprintf(stderr, "[yhair]   branch %-9s ran in %5.1f %% of the wave steps (%llu times), %.1f lanes on average\n", br[b],
-            c[32] ? 100.0 * (double)c[32 + 2 * b] / (double)c[32] : 0.0, c[32 + 2 * b], c[32 + 2 * b] ? (double)c[33 + 2 * b] / (double)c[32 + 2 * b] : 0.0);
-    }
+    if (wave_log) report_stream_waves(ctx, w.data(), waves, wpb);
+    if (prof) return report_stream_prof(ctx, grid, wpb, P);
     return YH_OK;
   });
 }
@@ -337,9 +274,7 @@ int trace_impl(yh_context* ctx, int nsamples, bool counted, bool sync) {
   int resident        = ctx->num_cus * occupancy;
   int want            = (ctx->state.num_tiles + waves_per_block - 1) / waves_per_block;
   int grid            = std::max(1, std::min(want, resident));
-  HIPCHK(ctx, hipMemsetAsync(ctx->d_tile_cursor.p, 0, 8 * 16 * 4, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(ctx->d_tile_cost.p, 0, (size_t)ctx->num_tiles_total * 16, ctx->stream));
-  HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if (int rc = begin_launch(ctx)) return rc;
   int e = exact ? yhk_trace_exact(&ctx->scene, &ctx->state, nsamples, lds_bytes, grid, ctx->stream)
                 : yhk_trace(&ctx->scene, &ctx->state, nsamples, counted ? (yhd_counters*)ctx->d_counters.p : nullptr, shape, grid, ctx->stream);
   if (e) return fail(ctx, YH_E_DEVICE, "k_trace launch: %s", hipGetErrorString((hipError_t)e));
@@ -350,9 +285,7 @@ int trace_impl(yh_context* ctx, int nsamples, bool counted, bool sync) {
 int side_by_side_impl(yh_context* ctx, int nsamples, bool sync) {
   int G_o = 0, G_q = 0;
   if (!side_by_side_grids(ctx, &G_o, &G_q)) return fail(ctx, YH_E_DEVICE, "k_trace_sbs cannot run with %d bytes of LDS per block", yhk_trace_sbs_lds_bytes(&ctx->scene));
-  HIPCHK(ctx, hipMemsetAsync(ctx->d_tile_cursor.p, 0, 8 * 16 * 4, ctx->stream));
-  HIPCHK(ctx, hipMemsetAsync(ctx->d_tile_cost.p, 0, (size_t)ctx->num_tiles_total * 16, ctx->stream));
-  HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if (int rc = begin_launch(ctx)) return rc;
   int e = yhk_trace_sbs(&ctx->scene, &ctx->state, nsamples, G_o, ctx->hy_quad_items, ctx->hy_oct_entries, std::max(1, G_o + G_q), ctx->stream);
   if (e) return fail(ctx, YH_E_DEVICE, "k_trace_sbs launch: %s", hipGetErrorString((hipError_t)e));
   return end_launch(ctx, nsamples, sync, [] { return YH_OK; });

@@ -19,6 +19,7 @@
 
 #include <thread>
 
+#include "switches.h"
 #include "yscene_cli.h"
 
 int main(int argc, const char* argv[]) {
@@ -132,7 +133,7 @@ int main(int argc, const char* argv[]) {
       float ms = 0;
       int   l  = 0;
       if (yh_last_trace_ms(yhair::detail::context(), &ms, &l) == YH_OK) kernel_ms += ms, launches += l;  // (context 0; the others run beside it)
-      if (timing && getenv("YHAIR_TIMING")) fprintf(stderr, "[yhair] request %d: %d spp, %.2f ms wall, %.2f ms of kernels in %d launch(es)\n", requests, n, (secs() - r0) * 1e3, ms, l);
+      if (timing && yhh::timing()) fprintf(stderr, "[yhair] request %d: %d spp, %.2f ms wall, %.2f ms of kernels in %d launch(es)\n", requests, n, (secs() - r0) * 1e3, ms, l);
       if (save_batch) {  // cli.cpp:259-267: "<stem>-s<sample><ext>"
         auto dot_pos = imfilename.rfind('.');
         auto stem = imfilename.substr(0, dot_pos), ext = dot_pos == std::string::npos ? "" : imfilename.substr(dot_pos);
