@@ -315,19 +315,9 @@ def test_empty_and_invalid_batches(ctx, yh):
     c2.close()
 
 
-def test_a_failed_upload_leaves_a_context_without_a_scene(yh):
-    """yh_upload_scene replaces the device arrays of the previous scene as it goes (round 6: the records and the trees are made on the device): a call that
-    fails half-way — here a vertex index out of range in the LAST shape, found after the first shapes were built — must leave a context that refuses to
-    render ("before yh_upload_scene"), never one whose scene table points at freed arrays; and a good upload afterwards renders as a fresh context does."""
+def _bad_index(yh, d, keep):
+    """a vertex index out of range in the LAST shape, found after the first shapes were built"""
     import ctypes as C
-    c = yh.Context(0)
-    sf = yh.SceneFile(scene_path("hair-curls", scale=0.05))
-    c.upload_scene(sf.desc)
-    p = yh.TraceParams.default(resolution=48)
-    c.init_state(p)
-    c.trace_samples(2)
-    want = c.download()
-    d = sf.desc.contents
     shapes = (yh.Shape * d.num_shapes)(*[d.shapes[i] for i in range(d.num_shapes)])
     last = shapes[d.num_shapes - 1]
     tri = last.num_triangles > 0
@@ -340,7 +330,115 @@ def test_a_failed_upload_leaves_a_context_without_a_scene(yh):
         last.lines = idx.ctypes.data_as(C.POINTER(C.c_int))
     bad = yh.SceneDesc.from_buffer_copy(d)
     bad.shapes = shapes
-    assert c.lib.yh_upload_scene(c.h, C.byref(bad)) == yh.YH_E_INVALID and b"out of range" in c.lib.yh_last_error(c.h)
+    keep += [shapes, idx]
+    return bad
+
+
+def _bad_objects(yh, d, keep, edit, count=None):
+    """the object list copied (`count` rows: the list repeated from its start), `edit(objects)` applied"""
+    n = d.num_objects if count is None else count
+    objects = (yh.Object * n)(*[d.objects[i % d.num_objects] for i in range(n)])
+    edit(objects)
+    bad = yh.SceneDesc.from_buffer_copy(d)
+    bad.num_objects, bad.objects = n, objects
+    keep.append(objects)
+    return bad
+
+
+def _bad_materials(yh, d, keep, edit):
+    materials = (yh.Material * d.num_materials)(*[d.materials[i] for i in range(d.num_materials)])
+    edit(materials)
+    bad = yh.SceneDesc.from_buffer_copy(d)
+    bad.materials = materials
+    keep.append(materials)
+    return bad
+
+
+def _bad_shape_named(yh, d, keep):
+    def edit(objects):
+        objects[d.num_objects - 1].shape = d.num_shapes
+    return _bad_objects(yh, d, keep, edit)
+
+
+def _bad_material_named(yh, d, keep):
+    def edit(objects):
+        objects[d.num_objects - 1].material = d.num_materials
+    return _bad_objects(yh, d, keep, edit)
+
+
+def _bad_color_tex(yh, d, keep):
+    def edit(materials):
+        materials[0].color_tex = d.num_textures + 1
+    return _bad_materials(yh, d, keep, edit)
+
+
+def _bad_empty_texture(yh, d, keep):
+    """one more texture behind the scene's, of zero width (no material needs to name it: every texture is looked at)"""
+    pixels = np.zeros(3, np.uint8)
+    textures = (yh.Texture * (d.num_textures + 1))(*[d.textures[i] for i in range(d.num_textures)])
+    textures[d.num_textures] = yh.Texture(0, 1, 1, pixels.ctypes.data)
+    bad = yh.SceneDesc.from_buffer_copy(d)
+    bad.num_textures, bad.textures = d.num_textures + 1, textures
+    keep += [textures, pixels]
+    return bad
+
+
+def _bad_no_lights(yh, d, keep):
+    def edit(materials):
+        for m in materials:
+            m.emission[:] = [0, 0, 0]
+    bad = _bad_materials(yh, d, keep, edit)
+    envs = (yh.Environment * d.num_environments)(*[d.environments[i] for i in range(d.num_environments)])
+    for e in envs:
+        e.emission[:] = [0, 0, 0]
+    bad.environments = envs
+    keep.append(envs)
+    return bad
+
+
+def _bad_too_many_lights(yh, d, keep):
+    """YH_MAX_LIGHTS + 1 emissive instances of the two-triangle light behind the scene's other objects"""
+    emitters = [i for i in range(d.num_objects) if any(d.materials[d.objects[i].material].emission)
+                and d.shapes[d.objects[i].shape].num_triangles == 2]
+    others = [i for i in range(d.num_objects) if not any(d.materials[d.objects[i].material].emission)]
+    assert emitters
+    rows = [d.objects[i] for i in others] + [d.objects[emitters[0]]] * 17
+
+    def edit(objects):
+        for k, row in enumerate(rows):
+            objects[k] = row
+    return _bad_objects(yh, d, keep, edit, count=len(rows))
+
+
+FAILED_UPLOADS = {
+    "vertex index out of range": (_bad_index, b"out of range"),
+    "object names shape num_shapes": (_bad_shape_named, b"references a missing shape or material"),
+    "object names material num_materials": (_bad_material_named, b"references a missing shape or material"),
+    "color_tex is num_textures + 1": (_bad_color_tex, b"references a missing texture"),
+    "texture of zero width": (_bad_empty_texture, b"is empty"),
+    "no lights": (_bad_no_lights, b"scene has no lights (the path sampler needs at least one)"),
+    "more than YH_MAX_LIGHTS lights": (_bad_too_many_lights, b"more than 16 lights: object"),
+}
+
+
+@pytest.mark.parametrize("case", list(FAILED_UPLOADS))
+def test_a_failed_upload_leaves_a_context_without_a_scene(yh, case):
+    """yh_upload_scene replaces the device arrays of the previous scene as it goes (round 6: the records and the trees are made on the device): a call that
+    fails half-way — one bad description per case, each refused at another exit behind the point where the previous scene is dropped — must leave a context
+    that refuses to render ("before yh_upload_scene"), never one whose scene table points at freed arrays; and a good upload afterwards renders as a fresh
+    context does."""
+    import ctypes as C
+    make_bad, text = FAILED_UPLOADS[case]
+    c = yh.Context(0)
+    sf = yh.SceneFile(scene_path("hair-curls", scale=0.05))
+    c.upload_scene(sf.desc)
+    p = yh.TraceParams.default(resolution=48)
+    c.init_state(p)
+    c.trace_samples(2)
+    want = c.download()
+    keep = []  # (the arrays the bad description points at)
+    bad = make_bad(yh, sf.desc.contents, keep)
+    assert c.lib.yh_upload_scene(c.h, C.byref(bad)) == yh.YH_E_INVALID and text in c.lib.yh_last_error(c.h), c.lib.yh_last_error(c.h)
     assert c.lib.yh_trace_samples(c.h, 1) == yh.YH_E_STATE and b"before" in c.lib.yh_last_error(c.h)
     assert c.lib.yh_init_state(c.h, p) == yh.YH_E_STATE
     c.upload_scene(sf.desc)

@@ -3,7 +3,8 @@
 // interface is include/yhair.h.
 //   context.cpp        create / destroy, errors, shard, downloads (yh_download_display: unit/display.hip)
 //   scene_upload.cpp   yh_upload_scene = init_bvh + init_lights (pt.cpp:755-818,1695-1740): reference-identical BVHs, leaf-ordered
-//                      records, inverse frames, per-material hair constants, light CDFs; the wide-node and lane-blob arrays
+//                      records, inverse frames, per-material hair constants, light CDFs; the wide-node and lane-blob arrays — a list of
+//                      stages (UploadStage); the ones without a HIP call are upload_stages.h, the traversal array's layout blob_layout.h
 //   launch_plan.cpp    which kernel runs (timing trials, their record in memory and on disk) and the hand-out order of the work items
 //   trace_launch.cpp   yh_init_state (pt.cpp:1931-1946) and the launches: yh_trace_samples and friends
 //   stream_report.cpp  what the developer switches print about a launch (YHAIR_ST_WAVELOG, YHAIR_ST_PROF) and the laps of YHAIR_TIMING
@@ -18,7 +19,7 @@
 //                      unit/refit.hip); yh_shape_nodes, yh_shape_refit_growth
 //   light_edit.cpp     yh_set_light_edits: the light list again where an edit changes it (unit/light_list.hip; the rule itself:
 //                      light_layout.h, shared with the upload); yh_light_list, yh_triangle_cdf / _gpu
-//   (edit_internal.h: what crosses those three)
+//   (edit_internal.h: what crosses those three and the upload; light_layout.h, blob_layout.h: the two layouts both sides follow)
 #ifndef YH_CONTEXT_INTERNAL_H_
 #define YH_CONTEXT_INTERNAL_H_
 #include <hip/hip_runtime_api.h>
@@ -51,6 +52,7 @@
 #include "../unit/light_list.h"   // yhk_light_job
 #include "bvh_build.h"
 #include "deadline.h"
+#include "parallel_for.h"
 #include "switches.h"
 #include "yhair.h"
 
@@ -228,23 +230,6 @@ float powt(float v) {  // ext.cpp:95-109
 }
 
 }  // namespace
-
-// Splits [0, n) over a few host threads (upload-time array fills; not a hot path).
-template <typename F>
-void parallel_for(int n, F&& fn) {
-  int nt = (int)std::min<unsigned>(16u, std::max(1u, std::thread::hardware_concurrency()));
-  if (n < 65536 || nt == 1) {
-    for (int i = 0; i < n; i++) fn(i);
-    return;
-  }
-  std::vector<std::thread> pool;
-  for (int t = 0; t < nt; t++)
-    pool.emplace_back([=, &fn] {
-      int lo = (int)((int64_t)n * t / nt), hi = (int)((int64_t)n * (t + 1) / nt);
-      for (int i = lo; i < hi; i++) fn(i);
-    });
-  for (auto& th : pool) th.join();
-}
 
 struct yh_context {
   int         device = 0;
@@ -444,15 +429,11 @@ void make_material(const yh_material& m, yhd_material& d);  // scene_upload.cpp
 // fingerprint of the description the context keeps; and what a new scene does to the image state and the launch planning
 bool make_material_rows(const yh_material* materials, const yh_material_maps* maps, int count, yhd_material* rows, yhd_maps* dmaps);
 void settle_scene_variant(const yh_context* ctx, yhd_scene& sc, bool general_rows);
-// scene_upload.cpp, shared with the light edits: the texel cdf of a textured environment (pt.cpp:1720-1734, the host's sine), `stride` floats
-// per texel, appended to `cdf` as one float chain
-void append_env_cdf(const float* texels, int stride, int width, int height, std::vector<float>& cdf);
 uint64_t scene_fingerprint(const yh_context* ctx);
 void forget_image_of_scene(yh_context* ctx);
-// scene_upload.cpp, shared with yh_update_objects: the levels of a host-built tree as the device builder reports them (false: more than 128);
-// whether a scene level of that size is walked as 4-wide nodes out of the lane blob (and the float4 count of its LDS table otherwise); what
-// the scene level adds to every traversal stack; and the three stack needs with the check every scene has to pass
-// ... and with yh_update_shape: one shape's binary tree on the device until its collapses are made, with the index of its wide nodes;
+// scene_upload.cpp: the levels of a host-built tree as the device builder reports them (false: more than 128); the three stack needs of
+// a scene (the scene level itself, shared with the edits: edit_internal.h)
+// ... and shared with yh_update_shape: one shape's binary tree on the device until its collapses are made, with the index of its wide nodes;
 // the upload's rule for where a shape is built; the build itself (bounds, the reference's tree, leaf-ordered records to d_recs), the
 // index of its wide nodes and their collapse with the shape's test records into a traversal array
 struct ShapeTree {
@@ -479,8 +460,19 @@ bool tree_levels(const yhh::Tree& tree, int& levels, int* level_first);
 // blob — its levels, the three arrays, the nodes' copy and yhk_wide_index (which synchronises: the count comes back); `who` begins the
 // message about the levels ("" for the upload)
 int index_scene_tree(yh_context* ctx, const char* who, const yhh::Tree& tree, DevBuf& d_stree, DevBuf& d_sflag, DevBuf& d_sidx, int* wide_count, int* wide_depth);
-bool scene_level_is_wide(int num_objects, int num_scene_nodes, int* lds_scene_f4);
 struct StackNeeds { int need, need8, need16; };
-StackNeeds stack_needs(bool scene_wide, int scene_wide_depth, int scene_tree_depth, int depth4, int depth8, int depth16);
+// the deepest shape tree per width, over built shapes (ShapeTree) or kept ones (ShapeState); `edited`: the shape whose tree is `built` instead
+struct ShapeDepths { int depth4 = 0, depth8 = 0, depth16 = 0; };
+template <class Shapes>
+ShapeDepths deepest_shape_trees(const Shapes& shapes, int edited = -1, const ShapeTree* built = nullptr) {
+  ShapeDepths d;
+  for (size_t s = 0; s < shapes.size(); s++) {
+    const bool e = (int)s == edited;
+    d.depth4  = std::max(d.depth4, e ? built->depth : shapes[s].depth);
+    d.depth8  = std::max(d.depth8, e ? built->depth8 : shapes[s].depth8);
+    d.depth16 = std::max(d.depth16, e ? built->depth16 : shapes[s].depth16);
+  }
+  return d;
+}
 #pragma GCC visibility pop
 #endif

@@ -7,7 +7,7 @@
 
 // stage_lights refuses what the upload refuses (more than YH_MAX_LIGHTS lights, none at all), allocates the new light_cdf and light table
 // and sees to it that every textured environment of the new list has its texel cdf on the device (ctx->d_env_cdf: saved from the
-// light_cdf in force, or made with the upload's loop from the texels read back from d_env_texels — the host's sine, scene_upload.cpp:
+// light_cdf in force, or made with the upload's loop from the texels read back from d_env_texels — the host's sine, upload_stages.h:
 // append_env_cdf). Nothing the kernels read is written.
 int stage_lights(yh_context* ctx, const char* entry, const yh_material* materials, const yh_object* rows, const float* emission, LightStage& S) {
   const yhd_scene& sc = ctx->scene;
@@ -86,15 +86,18 @@ int commit_lights(yh_context* ctx, const char* entry, LightStage& S) {
     if (e) return fail(ctx, YH_E_DEVICE, "%s: coarse index of the environment cdf: %s", entry, hipGetErrorString((hipError_t)e));
   }
   ctx->d_light_cdf.swap(S.d_cdf), ctx->d_light_table.swap(S.d_table), ctx->d_env_tab.swap(S.d_tab);
-  yhd_scene& sc = ctx->scene;
+  set_light_fields(ctx, ctx->scene, L);  // (settle_scene_variant reads them: the caller runs that next)
+  return YH_OK;
+}
+
+void set_light_fields(yh_context* ctx, yhd_scene& sc, const LightLayout& L) {
   sc.num_lights = L.num_lights;
   memcpy(sc.lights, L.lights, sizeof(sc.lights));
   sc.light_cdf = (const float*)ctx->d_light_cdf.p;
   sc.light_table = (const yhd_float4*)ctx->d_light_table.p, sc.light_table_f4 = L.table_f4;
   sc.env_tab = (const float*)ctx->d_env_tab.p;
   sc.env_tab_light = L.env_tab_light, sc.env_tab_k = L.env_tab_k, sc.env_tab_stride = L.env_tab_stride;
-  ctx->big_lights = L.big_lights;  // (settle_scene_variant reads it: the caller runs that next)
-  return YH_OK;
+  ctx->big_lights = L.big_lights;  // (a light sampled and intersected through memory: the general kernel variant)
 }
 
 // A VERTEX edit of an emitter's shape changes no light's place: the list, every offset, the kernel variant and every other light's

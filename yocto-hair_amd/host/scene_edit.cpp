@@ -137,26 +137,15 @@ int yh_update_environments(yh_context* ctx, int count, const yh_environment* env
 
 // ---- the scene level again: what yh_update_objects and the shape edits share (edit_internal.h) --------------------------------------------
 int stage_scene_level(yh_context* ctx, const char* entry, const std::vector<yhh::Box>& boxes, int depth4, int depth8, int depth16, SceneLevelStage& S) {
-  const int total = ctx->scene.num_objects;
-  // ---- the scene-level tree, as the upload builds it, and what the upload derives from it ----
-  yhh::Tree& tree = S.tree;
-  yhh::build_bvh(tree, boxes);
-  const int nn = S.nn = (int)tree.nodes.size();
-  const bool scene_wide = S.scene_wide = scene_level_is_wide(total, nn, &S.lds_scene_f4), was_wide = ctx->scene.scene_wide_root >= 0;
-  if (scene_wide != was_wide)
+  const int         total = ctx->scene.num_objects;
+  const std::string who   = std::string(entry) + ": ";
+  if (int rc = derive_scene_level(ctx, who.c_str(), boxes, total, depth4, depth8, depth16, S)) return rc;
+  if (S.scene_wide != (ctx->scene.scene_wide_root >= 0))
     return fail(ctx, YH_E_INVALID, "%s: the scene tree of the moved objects has %d nodes and its scene level %s: room for wide scene nodes exists only where the upload put it, upload the scene",
-        entry, nn, scene_wide ? "no longer fits the kernels' table (it would be walked as 4-wide nodes)" : "fits the kernels' table again (it was uploaded as 4-wide nodes)");
-  if (scene_wide) {
-    if (int rc = index_scene_tree(ctx, (std::string(entry) + ": ").c_str(), tree, S.d_stree, S.d_sflag, S.d_sidx, &S.wide_count, &S.wide_depth)) return rc;
-    if (S.wide_count > ctx->scene_wide_room)
-      return fail(ctx, YH_E_INVALID, "%s: %d wide scene nodes, the upload left room for %d: upload the scene", entry, S.wide_count, ctx->scene_wide_room);
-  }
-  S.needs = stack_needs(scene_wide, S.wide_depth, tree.max_depth, depth4, depth8, depth16);
-  if (S.needs.need > yhk_stack_entries())
-    return fail(ctx, YH_E_INVALID, "%s: BVH too deep for the traversal stack (%d > %d)", entry, S.needs.need, yhk_stack_entries());
-  for (auto& n : tree.nodes) S.scene_nodes.push_back(node_lo(n)), S.scene_nodes.push_back(node_hi(n));
-  S.scene_prims = tree.primitives;
-  S.scene_prims.resize((S.scene_prims.size() + 3) / 4 * 4, 0);  // staged to LDS as float4
+        entry, S.nn, S.scene_wide ? "no longer fits the kernels' table (it would be walked as 4-wide nodes)" : "fits the kernels' table again (it was uploaded as 4-wide nodes)");
+  if (S.wide_count > ctx->scene_wide_room)
+    return fail(ctx, YH_E_INVALID, "%s: %d wide scene nodes, the upload left room for %d: upload the scene", entry, S.wide_count, ctx->scene_wide_room);
+  if (int rc = check_stack_needs(ctx, who.c_str(), S.needs)) return rc;
   // (a tree over the same objects has up to 2 n - 1 nodes: more than the uploaded one may have had)
   if (ctx->d_scene_nodes.bytes < S.scene_nodes.size() * 16)
     if (int rc = dev_alloc(ctx, S.d_nodes_grown, (size_t)(2 * total) * 32)) return rc;
@@ -171,25 +160,14 @@ int commit_scene_level(yh_context* ctx, SceneLevelStage& S) {
   if (S.d_prims_grown.p) ctx->d_scene_prims.swap(S.d_prims_grown);
   HIPCHK(ctx, hipMemcpyAsync(ctx->d_scene_nodes.p, S.scene_nodes.data(), S.scene_nodes.size() * 16, hipMemcpyHostToDevice, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync(ctx->d_scene_prims.p, S.scene_prims.data(), S.scene_prims.size() * 4, hipMemcpyHostToDevice, ctx->stream));
-  if (S.scene_wide) {  // the reserved front of the blob: zero as the upload leaves what it does not use, then the new nodes
+  if (S.scene_wide)  // the reserved front of the blob: zero as the upload leaves what it does not use, then the new nodes
     HIPCHK(ctx, hipMemsetAsync(ctx->d_lane_blob.p, 0, (size_t)ctx->scene_wide_room * 128, ctx->stream));
-    int e = yhk_wide_collapse(2, S.nn, (const float*)S.d_stree.p, (const unsigned int*)S.d_sflag.p, (const unsigned int*)S.d_sidx.p, 1, 0, 0, ctx->d_lane_blob.p, ctx->stream);
-    if (e) return fail(ctx, YH_E_DEVICE, "wide collapse of the scene tree: %s", hipGetErrorString((hipError_t)e));
-  }
-  return YH_OK;
+  return collapse_scene_tree(ctx, S, ctx->d_lane_blob.p);
 }
 
 void settle_scene_level(yh_context* ctx, const SceneLevelStage& S) {
-  ctx->stack_need = S.needs.need, ctx->stack_need8 = S.needs.need8, ctx->stack_need16 = S.needs.need16;
-  yhd_scene& sc = ctx->scene;
-  sc.scene_nodes = (const yhd_float4*)ctx->d_scene_nodes.p, sc.scene_prims = (const int*)ctx->d_scene_prims.p;
-  sc.num_scene_nodes = S.nn;
-  sc.lds_scene_f4    = S.scene_wide ? 0 : S.lds_scene_f4;
-  sc.scene_wide_root = S.scene_wide ? 0 : -1;
-  sc.stack_entries   = std::max(8, (S.needs.need + 7) / 8 * 8);
-  sc.stack_entries8  = std::max(8, (S.needs.need8 + 7) / 8 * 8);
-  sc.stack_entries16 = std::max(8, (S.needs.need16 + 7) / 8 * 8);
-  settle_scene_variant(ctx, sc, S.general_rows);
+  set_scene_level_fields(ctx, ctx->scene, S);
+  settle_scene_variant(ctx, ctx->scene, S.general_rows);
 }
 
 // ---- yh_update_objects: set_frame / set_material on an object (yocto_pathtrace.h:110-111) ------------------------------------------------

@@ -1,7 +1,6 @@
 // scene_upload.cpp — yh_upload_scene = init_bvh + init_lights (pt.cpp:755-818,1695-1740): everything a launch reads is made here, big shapes
 // entirely on the device (csrc/bvh_gpu.hip); nothing is deferred to a first launch (rounds 3-5 built the 8- / 16-wide nodes there).
-#include "context_internal.h"
-#include "light_layout.h"
+#include "edit_internal.h"  // SceneLevelStage, and the rules the upload shares with the edits
 
 #include <atomic>
 
@@ -187,7 +186,7 @@ int index_scene_tree(yh_context* ctx, const char* who, const yhh::Tree& tree, De
 // scene-level LDS table: objects (YH_OBJECT_F4 = 11 float4 each), scene BVH nodes (2 float4 each), primitive ids; up to 10 KB = 46
 // objects. A scene with more runs the GENERAL kernel variants, which read the table from memory, and walks its scene level as 4-wide
 // nodes out of the blob (an instanced scene has thousands of objects)
-bool scene_level_is_wide(int num_objects, int num_scene_nodes, int* lds_scene_f4) {
+static bool scene_level_is_wide(int num_objects, int num_scene_nodes, int* lds_scene_f4) {
   static_assert(sizeof(yhd_object) == 16 * YH_OBJECT_F4, "yhd_object is staged to LDS as float4");
   *lds_scene_f4 = YH_OBJECT_F4 * num_objects + 2 * num_scene_nodes + (num_objects + 3) / 4;
   return *lds_scene_f4 * 16 > 10240;
@@ -196,9 +195,46 @@ bool scene_level_is_wide(int num_objects, int num_scene_nodes, int* lds_scene_f4
 // a wide node pushes at most three entries and keeps the fourth in a register; the scene level: a binary node pushes one, a leaf up to three
 // objects — or, walked as 4-wide nodes, three per node and the leaf's three (the same quad form under every launch shape). An 8-wide node
 // pushes at most seven, a 16-wide one fifteen
-StackNeeds stack_needs(bool scene_wide, int scene_wide_depth, int scene_tree_depth, int depth4, int depth8, int depth16) {
+static StackNeeds stack_needs(bool scene_wide, int scene_wide_depth, int scene_tree_depth, int depth4, int depth8, int depth16) {
   const int scene_need = scene_wide ? 3 * scene_wide_depth + 4 : scene_tree_depth + 4;
   return {scene_need + 3 * depth4 + 2, scene_need + 7 * depth8 + 2, scene_need + 15 * depth16 + 2};
+}
+
+// Everything the scene level is, from every object's world box and the deepest shape tree per width (edit_internal.h): the reference's
+// tree, whether it is walked as 4-wide nodes and their index if so, the stack needs, and the two arrays the kernels stage to LDS.
+int derive_scene_level(yh_context* ctx, const char* who, const std::vector<yhh::Box>& boxes, int num_objects, int depth4, int depth8, int depth16, SceneLevelStage& S) {
+  yhh::build_bvh(S.tree, boxes);
+  S.nn         = (int)S.tree.nodes.size();
+  S.scene_wide = scene_level_is_wide(num_objects, S.nn, &S.lds_scene_f4);
+  if (S.scene_wide)
+    if (int rc = index_scene_tree(ctx, who, S.tree, S.d_stree, S.d_sflag, S.d_sidx, &S.wide_count, &S.wide_depth)) return rc;
+  S.needs = stack_needs(S.scene_wide, S.wide_depth, S.tree.max_depth, depth4, depth8, depth16);
+  for (auto& n : S.tree.nodes) S.scene_nodes.push_back(node_lo(n)), S.scene_nodes.push_back(node_hi(n));  // (binary, also of a scene walked through its wide nodes: the counted builds' yardstick)
+  S.scene_prims = S.tree.primitives;
+  S.scene_prims.resize((S.scene_prims.size() + 3) / 4 * 4, 0);  // staged to LDS as float4
+  return YH_OK;
+}
+int check_stack_needs(yh_context* ctx, const char* who, const StackNeeds& needs) {
+  if (needs.need > yhk_stack_entries()) return fail(ctx, YH_E_INVALID, "%sBVH too deep for the traversal stack (%d > %d)", who, needs.need, yhk_stack_entries());
+  return YH_OK;
+}
+// ... its 4-wide nodes into the front of the traversal array `blob`: leaf references as of a line shape whose test records start at 0,
+// count << 27 | first scene primitive
+int collapse_scene_tree(yh_context* ctx, const SceneLevelStage& S, void* blob) {
+  if (!S.scene_wide) return YH_OK;
+  int e = yhk_wide_collapse(2, S.nn, (const float*)S.d_stree.p, (const unsigned int*)S.d_sflag.p, (const unsigned int*)S.d_sidx.p, 1, 0, 0, blob, ctx->stream);
+  if (e) return fail(ctx, YH_E_DEVICE, "wide collapse of the scene tree: %s", hipGetErrorString((hipError_t)e));
+  return YH_OK;
+}
+// ... and its fields of a scene table whose two arrays are in the context's buffers, with the three stack sizes
+void set_scene_level_fields(yh_context* ctx, yhd_scene& sc, const SceneLevelStage& S) {
+  ctx->stack_need = S.needs.need, ctx->stack_need8 = S.needs.need8, ctx->stack_need16 = S.needs.need16;
+  sc.scene_nodes = (const yhd_float4*)ctx->d_scene_nodes.p, sc.scene_prims = (const int*)ctx->d_scene_prims.p;
+  sc.num_scene_nodes = S.nn;
+  sc.lds_scene_f4    = S.scene_wide ? 0 : S.lds_scene_f4;
+  sc.scene_wide_root = S.scene_wide ? 0 : -1;
+  auto entries = [](int need) { return std::max(8, (need + 7) / 8 * 8); };
+  sc.stack_entries = entries(S.needs.need), sc.stack_entries8 = entries(S.needs.need8), sc.stack_entries16 = entries(S.needs.need16);
 }
 
 // ---- one shape's tree and leaf-ordered records: what the upload runs per shape and yh_update_shape for the one it edits ----------------
@@ -341,29 +377,56 @@ int collapse_shape_tree(yh_context* ctx, const char* who, const ShapeTree& T, co
   return YH_OK;
 }
 
-void append_env_cdf(const float* texels, int stride, int width, int height, std::vector<float>& cdf) {
-  const size_t n = (size_t)width * height, at = cdf.size();
-  for (size_t i = 0; i < n; i++) {
-    int   iy    = (int)(i / width);
-    float th    = (iy + 0.5f) * pif / height;
-    float mx    = fmax_(fmax_(texels[stride * i], texels[stride * i + 1]), texels[stride * i + 2]);
-    float value = mx * std::sin(th);
-    if (i) value += cdf[at + i - 1];
-    cdf.push_back(value);
+// What a built shape leaves for its edits (context_internal.h: ShapeState): depths, counts, the room of its regions of the traversal array
+// (the upload: exactly its nodes; yh_update_shape: what it chose, blob_layout.h), the levels of its wide trees, and the slot areas as built.
+void shape_state_of_build(yh_context::ShapeState& E, const ShapeTree& T, const int room[3], const double area[3]) {
+  E.depth = T.depth, E.depth8 = T.depth8, E.depth16 = T.depth16;
+  for (int w = 0; w < 3; w++) {
+    E.count[w] = T.wide_count[w], E.room[w] = room[w];
+    E.wide_levels[w] = T.wide_levels[w];
+    memcpy(E.wide_first[w], T.wide_first[w], sizeof(E.wide_first[w]));
+    E.area_build[w] = E.area_now[w] = area[w];
   }
 }
 
-int yh_upload_scene(yh_context* ctx, const yh_scene_desc* sd) { return yh_upload_scene_maps(ctx, sd, nullptr); }
+// ---- yh_upload_scene_maps, a stage at a time. The stages hand each other one UploadStage; what can refuse after drop_previous_scene leaves a
+// context WITHOUT a scene (every launch then says "before yh_upload_scene"), never one whose scene table points at freed arrays. ----------------
+namespace {
+struct UploadShape : ShapeTree {
+  int prim_base, vert_base, elem_base, has_normals;
+};
+struct UploadStage {
+  const yh_scene_desc*      sd   = nullptr;
+  const yh_material_maps*   maps = nullptr;  // the caller's, where some material has an effective map; else NULL
+  std::vector<UploadShape>  shapes;
+  size_t                    total_prim_f4 = 0;
+  std::vector<yhd_float4>   vpos;   // the per-vertex rows of the shapes that have some (upload_shapes)
+  std::vector<float>        vtex;   // 2 per vertex, zeros for shapes without texture coordinates
+  std::vector<yhd_int4>     elems;
+  std::vector<yhh::Box>     obj_boxes, shape_roots;
+  SceneLevelStage           level;
+  BlobLayout                blob;
+  std::vector<double>       slot_areas;  // 3 per shape
+  std::vector<yhd_object>   objects;
+  std::vector<yhd_material> materials;
+  std::vector<yhd_maps>     mat_maps;
+  bool                      general_rows = false;
+  yhd_scene                 sc{};  // the scene table: the environments' rows and the lights from upload_lights on, the rest at fill_scene_table
+  LightLayout               lights;
+  std::vector<yhd_float4>   env_texels, light_table, tex_texels;
+  std::vector<float>        light_cdf, env_tab;
+  std::vector<yhd_texture>  textures;
+};
+}  // namespace
 
-int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_material_maps* maps) {
-  if (!ctx) return YH_E_INVALID;
+// The checks that run before anything of the context is freed: a refusal here leaves the previous scene in place.
+static int check_upload(yh_context* ctx, const yh_scene_desc* sd, const yh_material_maps* maps, UploadStage& U) {
   if (!sd) return fail(ctx, YH_E_INVALID, "scene is NULL");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   if (ctx->poisoned) return refuse_poisoned(ctx);
   YH_WAIT(ctx);  // (an asynchronous launch may still be reading the scene this call replaces: wait for it, within the deadline)
   if (sd->num_objects <= 0) return fail(ctx, YH_E_INVALID, "scene has no objects");
   if (sd->num_environments > YH_MAX_ENVS) return fail(ctx, YH_E_INVALID, "more than %d environments", YH_MAX_ENVS);
-  // the maps are checked before anything of the context is freed: a bad index leaves the previous scene in place
   bool any_maps = false;
   if (maps)
     for (int i = 0; i < sd->num_materials; i++) {
@@ -372,42 +435,41 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
         if (id < 0 || id > sd->num_textures) return fail(ctx, YH_E_INVALID, "material %d: a map references a missing texture (%d of %d)", i, id, sd->num_textures);
       any_maps = any_maps || has_effective_map(m);
     }
-  Lap lap("upload");  // YHAIR_TIMING=1: stage times of the upload on stderr
-  // ---- per-shape BVHs and leaf-ordered records ---------------------------------------------------------------------------
-  // (build_shape_tree above: big shapes on the device, small ones on the host, the collapses the device's for both)
-  struct ShapeInfo : ShapeTree {
-    int prim_base, vert_base, elem_base, has_normals;
-  };
-  std::vector<ShapeInfo>  info(sd->num_shapes);
-  std::vector<yhd_float4> vpos;
-  std::vector<float>      vtex;  // 2 per vertex, zeros for shapes without texture coordinates
-  std::vector<yhd_int4>   elems;
-  size_t total_prim_f4 = 0;
+  U.sd = sd, U.maps = any_maps ? maps : nullptr;
+  U.shapes.resize((size_t)sd->num_shapes);
   for (int si = 0; si < sd->num_shapes; si++) {
     auto& s = sd->shapes[si];
+    auto& I = U.shapes[(size_t)si];
     if (s.num_vertices <= 0 || !s.positions) return fail(ctx, YH_E_INVALID, "shape %d has no vertices", si);
     const bool lines = s.num_lines > 0;
     if (!lines && s.num_triangles <= 0) return fail(ctx, YH_E_INVALID, "shape %d has no lines or triangles", si);
     const int nel = lines ? s.num_lines : s.num_triangles;
     // a leaf reference packs its first record into 27 bits (host/bvh_build.cpp: count << 27 | start)
     if (nel >= (1 << 27)) return fail(ctx, YH_E_INVALID, "shape %d has %d elements (limit %d)", si, nel, (1 << 27) - 1);
-    info[si].kind = lines ? YH_KIND_LINES : YH_KIND_TRIANGLES, info[si].num_prims = nel, info[si].has_normals = s.normals != nullptr;
-    info[si].prim_base = (int)total_prim_f4;
-    total_prim_f4 += (size_t)nel * (lines ? 4 : 6);
+    I.kind = lines ? YH_KIND_LINES : YH_KIND_TRIANGLES, I.num_prims = nel, I.has_normals = s.normals != nullptr;
+    I.prim_base = (int)U.total_prim_f4;
+    U.total_prim_f4 += (size_t)nel * (lines ? 4 : 6);
   }
-  if (total_prim_f4 > (size_t)std::numeric_limits<int>::max()) return fail(ctx, YH_E_INVALID, "scene too large for 32-bit record offsets (%zu primitive float4)", total_prim_f4);
-  int rc;
-  // From here on the previous scene's device arrays are being replaced: a call that fails half-way must leave a context WITHOUT a scene (every launch
-  // then says "before yh_upload_scene"), never one whose scene table points at freed arrays.
+  if (U.total_prim_f4 > (size_t)std::numeric_limits<int>::max())
+    return fail(ctx, YH_E_INVALID, "scene too large for 32-bit record offsets (%zu primitive float4)", U.total_prim_f4);
+  return YH_OK;
+}
+
+// The one place that drops the previous scene: from here on its device arrays are being replaced.
+static void drop_previous_scene(yh_context* ctx) {
   ctx->have_scene = false, ctx->have_state = false;
   ctx->scene.lane_blob = nullptr, ctx->scene.prims = nullptr;
   ctx->d_prims.reset(), ctx->d_lane_blob.reset();  // (nothing of this context is running: waited for above)
   for (DevBuf& kept : ctx->d_env_cdf) kept.reset();  // (the texel cdfs a light edit kept: another scene's)
-  if ((rc = dev_alloc(ctx, ctx->d_prims, total_prim_f4 * 16))) return rc;
-  lap("validation, record array");
+}
+
+// Per shape: the index check, the tree with its leaf-ordered records (build_shape_tree above: big shapes on the device, small ones on the
+// host), and its rows of the per-vertex arrays.
+static int upload_shapes(yh_context* ctx, UploadStage& U, Lap& lap) {
+  const yh_scene_desc* sd = U.sd;
   for (int si = 0; si < sd->num_shapes; si++) {
     auto&      s     = sd->shapes[si];
-    auto&      I     = info[si];
+    auto&      I     = U.shapes[(size_t)si];
     const bool lines = I.kind == YH_KIND_LINES;
     const int  nel   = I.num_prims;
     const int* idx   = lines ? s.lines : s.triangles;
@@ -418,363 +480,245 @@ int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_mate
       });
       if (bad) return fail(ctx, YH_E_INVALID, "shape %d: vertex index out of range", si);
     }
-    I.vert_base = (int)vpos.size(), I.elem_base = (int)elems.size();
-    if ((rc = build_shape_tree(ctx, "", si, s, false, shape_builds_on_device(nel), (yhd_float4*)ctx->d_prims.p + I.prim_base, I))) return rc;
+    if (int rc = build_shape_tree(ctx, "", si, s, false, shape_builds_on_device(nel), (yhd_float4*)ctx->d_prims.p + I.prim_base, I)) return rc;
     lap(I.host_prims.empty() ? "device: bounds, tree, leaf records" : "host: small shape");
-    {
-      // Per-vertex positions and per-element indices are read on the device only to sample a point
-      // on an area light (triangles, pt.cpp:1287-1292) and to interpolate texture coordinates; the
-      // traversal and the shading of a hit use the leaf records. Hair without texture coordinates —
-      // nearly all of a scene's bytes — therefore has no entry in these arrays.
-      const bool per_vertex = !lines || s.texcoords != nullptr;
-      if (!per_vertex) {
-        I.vert_base = 0, I.elem_base = 0;
-      } else {
-        auto pos = [&](int v) { return ld3(s.positions + 3 * (size_t)v); };
-        const size_t at = vpos.size();
-        vpos.resize(at + (size_t)s.num_vertices);
-        vtex.resize(2 * (at + (size_t)s.num_vertices), 0.0f);
-        if (s.texcoords) memcpy(&vtex[2 * at], s.texcoords, sizeof(float) * 2 * (size_t)s.num_vertices);
-        parallel_for(s.num_vertices, [&](int v) {
-          F3 p = pos(v);
-          vpos[at + (size_t)v] = {p.x, p.y, p.z, lines ? (s.radius ? s.radius[v] : 0.001f) : 0.0f};
-        });
-        const size_t ea = elems.size();
-        elems.resize(ea + (size_t)nel);
-        parallel_for(nel, [&](int e) {
-          elems[ea + (size_t)e] = lines ? yhd_int4{idx[2 * e], idx[2 * e + 1], 0, 0}
-                                        : yhd_int4{idx[3 * e], idx[3 * e + 1], idx[3 * e + 2], 0};
-        });
-      }
-    }
+    // Per-vertex positions and per-element indices are read on the device only to sample a point
+    // on an area light (triangles, pt.cpp:1287-1292) and to interpolate texture coordinates; the
+    // traversal and the shading of a hit use the leaf records. Hair without texture coordinates —
+    // nearly all of a scene's bytes — therefore has no entry in these arrays.
+    I.vert_base = 0, I.elem_base = 0;
+    if (lines && !s.texcoords) continue;
+    const size_t at = U.vpos.size(), ea = U.elems.size();
+    I.vert_base = (int)at, I.elem_base = (int)ea;
+    U.vpos.resize(at + (size_t)s.num_vertices);
+    U.vtex.resize(2 * (at + (size_t)s.num_vertices), 0.0f);
+    if (s.texcoords) memcpy(&U.vtex[2 * at], s.texcoords, sizeof(float) * 2 * (size_t)s.num_vertices);
+    parallel_for(s.num_vertices, [&](int v) {
+      F3 p = ld3(s.positions + 3 * (size_t)v);
+      U.vpos[at + (size_t)v] = {p.x, p.y, p.z, lines ? (s.radius ? s.radius[v] : 0.001f) : 0.0f};
+    });
+    U.elems.resize(ea + (size_t)nel);
+    parallel_for(nel, [&](int e) {
+      U.elems[ea + (size_t)e] = lines ? yhd_int4{idx[2 * e], idx[2 * e + 1], 0, 0} : yhd_int4{idx[3 * e], idx[3 * e + 1], idx[3 * e + 2], 0};
+    });
   }
-  // ---- the scene-level BVH (pt.cpp:792-814): the reference's tree over the objects' world boxes, made here because a scene too big for the
-  // kernels' LDS table has its scene level collapsed into the blob like a shape (below) ----
-  std::vector<yhh::Box> obj_boxes(sd->num_objects);
+  return YH_OK;
+}
+
+// The scene level (pt.cpp:792-814): the objects' world boxes and what follows from the reference's tree over them (derive_scene_level).
+static int upload_scene_level(yh_context* ctx, UploadStage& U) {
+  const yh_scene_desc* sd = U.sd;
+  U.obj_boxes.resize((size_t)sd->num_objects);
   for (int oi = 0; oi < sd->num_objects; oi++) {
     auto& o = sd->objects[oi];
     if (o.shape < 0 || o.shape >= sd->num_shapes || o.material < 0 || o.material >= sd->num_materials)
       return fail(ctx, YH_E_INVALID, "object %d references a missing shape or material", oi);
-    const yhh::Box& b = info[o.shape].root;
-    transform_bbox(o.frame, b.min, b.max, obj_boxes[oi].min, obj_boxes[oi].max);  // (unit/object_math.h)
+    const yhh::Box& b = U.shapes[(size_t)o.shape].root;
+    transform_bbox(o.frame, b.min, b.max, U.obj_boxes[(size_t)oi].min, U.obj_boxes[(size_t)oi].max);  // (unit/object_math.h)
   }
-  yhh::Tree scene_tree;
-  yhh::build_bvh(scene_tree, obj_boxes);
-  int        lds_scene_f4 = 0;
-  const bool scene_wide   = scene_level_is_wide(sd->num_objects, (int)scene_tree.nodes.size(), &lds_scene_f4);
-  DevBuf d_stree, d_sflag, d_sidx;
-  int    scene_wide_count = 0, scene_wide_depth = 0;
-  if (scene_wide && (rc = index_scene_tree(ctx, "", scene_tree, d_stree, d_sflag, d_sidx, &scene_wide_count, &scene_wide_depth))) return rc;
-  // ---- the wide collapses: the index of every wide node (one flag pass + one scan per width), then the layout of the ONE array the traversal
-  // kernels read (yh_device.h: lane_blob, 32-byte units): [4-wide nodes of the scene tree, if any][test records of every shape][4-wide nodes][8-wide nodes][16-wide nodes] ----
-  for (int si = 0; si < sd->num_shapes; si++)
-    if ((rc = index_shape_tree(ctx, "", info[si]))) return rc;
-  ctx->lane_shapes.assign((size_t)sd->num_shapes, yh_context::LaneShape{});
-  long long U8 = 0, U16 = 0, blob_units = 0;
+  const ShapeDepths deepest = deepest_shape_trees(U.shapes);
+  return derive_scene_level(ctx, "", U.obj_boxes, sd->num_objects, deepest.depth4, deepest.depth8, deepest.depth16, U.level);
+}
+
+// The ONE array the traversal kernels read: the index of every wide node (one flag pass + one scan per width), where everything sits
+// (blob_layout.h), the allocation, the collapses, and the half-area sums of every shape's slot boxes as built (what yh_shape_refit_growth
+// compares a refitted tree with). The binary trees go when it is made.
+static int upload_traversal_array(yh_context* ctx, UploadStage& U) {
+  const int num_shapes = (int)U.shapes.size();
+  for (auto& I : U.shapes)
+    if (int rc = index_shape_tree(ctx, "", I)) return rc;
+  std::vector<BlobShape> in;
+  for (auto& I : U.shapes) in.push_back({I.kind == YH_KIND_LINES, I.num_prims, {I.wide_count[0], I.wide_count[1], I.wide_count[2]}});
+  long long at = 0;
+  switch (blob_layout(U.level.scene_wide, U.sd->num_objects, in.data(), num_shapes, U.blob, &at)) {
+    case YH_BLOB_LEAF_OFFSETS: return fail(ctx, YH_E_INVALID, "scene too large for 27-bit leaf offsets (%lld test-record units)", at);
+    case YH_BLOB_NODE_OFFSETS: return fail(ctx, YH_E_INVALID, "scene too large for 30-bit node offsets (%lld units)", at);
+  }
+  ctx->lane_shapes.assign((size_t)num_shapes, yh_context::LaneShape{});
+  for (int si = 0; si < num_shapes; si++) {
+    const auto& I = U.shapes[(size_t)si];
+    const auto& R = U.blob.shapes[(size_t)si];
+    ctx->lane_shapes[(size_t)si] = {I.kind, I.wide_count[0], I.prim_base, I.num_prims, R.node_off[0], R.test_off, R.node_off[1], R.node_off[2]};
+  }
+  ctx->lane_units = U.blob.lane_units;
+  if (int rc = alloc_zero(ctx, ctx->d_lane_blob, (size_t)U.blob.units * 32)) return rc;
+  for (int si = 0; si < num_shapes; si++)
+    if (int rc = collapse_shape_tree(ctx, "", U.shapes[(size_t)si], ctx->lane_shapes[(size_t)si], ctx->d_lane_blob.p)) return rc;
+  if (int rc = collapse_scene_tree(ctx, U.level, ctx->d_lane_blob.p)) return rc;
+  U.slot_areas.resize(3 * (size_t)num_shapes);
   {
-    // (in front of the test records: a scene node's offset stays below 2^27, what tells it from a scene leaf on a stack. Room for as many
-    // nodes as the scene has objects: a wide node stands for an internal binary node, of which a tree over n objects has at most n - 1,
-    // so yh_update_objects can write the nodes of any tree over them; the slots behind scene_wide_count stay zero)
-    long long at = scene_wide ? 4ll * sd->num_objects : 0;
-    for (int si = 0; si < sd->num_shapes; si++) {
-      auto& L = ctx->lane_shapes[(size_t)si];
-      L.kind = info[si].kind, L.num_nodes = info[si].wide_count[0], L.prim_base = info[si].prim_base, L.num_prims = info[si].num_prims;
-      L.test_off = at, at += (long long)L.num_prims * (L.kind == YH_KIND_LINES ? 1 : 2);
-    }
-    at = (at + 3) / 4 * 4 + 4;  // (nodes on 128-byte lines; four units of slack behind the last test record: a leaf step reads 64 bytes)
-    if (at >= (1ll << 27)) return fail(ctx, YH_E_INVALID, "scene too large for 27-bit leaf offsets (%lld test-record units)", at);
-    for (int si = 0; si < sd->num_shapes; si++) ctx->lane_shapes[(size_t)si].node_off = at, at += 4ll * info[si].wide_count[0];
-    ctx->lane_units = at + 4;  // what the one-lane kernels address (32-bit byte offsets: launch_plan.cpp: lane_kernels_can_address)
-    U8 = (ctx->lane_units + 3) / 4 * 4, at = U8;
-    for (int si = 0; si < sd->num_shapes; si++) ctx->lane_shapes[(size_t)si].node_off8 = at, at += 8ll * info[si].wide_count[1];
-    U16 = at;
-    for (int si = 0; si < sd->num_shapes; si++) ctx->lane_shapes[(size_t)si].node_off16 = at, at += 16ll * info[si].wide_count[2];
-    blob_units = at + 4;
-    if (blob_units >= (1ll << 30)) return fail(ctx, YH_E_INVALID, "scene too large for 30-bit node offsets (%lld units)", blob_units);
-    (void)U16;
-  }
-  if ((rc = alloc_zero(ctx, ctx->d_lane_blob, (size_t)blob_units * 32))) return rc;
-  for (int si = 0; si < sd->num_shapes; si++)
-    if ((rc = collapse_shape_tree(ctx, "", info[si], ctx->lane_shapes[(size_t)si], ctx->d_lane_blob.p))) return rc;
-  if (scene_wide) {  // leaf references as of a line shape whose test records start at 0: count << 27 | first scene primitive
-    int e = yhk_wide_collapse(2, (int)scene_tree.nodes.size(), (const float*)d_stree.p, (const unsigned int*)d_sflag.p, (const unsigned int*)d_sidx.p, 1, 0, 0, ctx->d_lane_blob.p, ctx->stream);
-    if (e) return fail(ctx, YH_E_DEVICE, "wide collapse of the scene tree: %s", hipGetErrorString((hipError_t)e));
-  }
-  // the half-area sums of every shape's slot boxes as built: what yh_shape_refit_growth compares a refitted tree with
-  std::vector<double> slot_areas(3 * (size_t)sd->num_shapes);
-  {
-    std::vector<int> counts(3 * (size_t)sd->num_shapes);
-    for (int si = 0; si < sd->num_shapes; si++) memcpy(&counts[3 * (size_t)si], info[si].wide_count, sizeof(info[si].wide_count));
-    if ((rc = shape_slot_areas(ctx, "", sd->num_shapes, ctx->lane_shapes.data(), (const int(*)[3])counts.data(), ctx->d_lane_blob.p, slot_areas.data()))) return rc;
+    std::vector<int> counts(3 * (size_t)num_shapes);
+    for (int si = 0; si < num_shapes; si++) memcpy(&counts[3 * (size_t)si], U.shapes[(size_t)si].wide_count, sizeof(U.shapes[(size_t)si].wide_count));
+    if (int rc = shape_slot_areas(ctx, "", num_shapes, ctx->lane_shapes.data(), (const int(*)[3])counts.data(), ctx->d_lane_blob.p, U.slot_areas.data())) return rc;
   }
   YH_WAIT(ctx);
-  for (auto& I : info) {
+  for (auto& I : U.shapes) {
     I.d_tree.reset();
     for (int w = 0; w < 3; w++) I.d_wflag[w].reset(), I.d_widx[w].reset();
   }
-  d_stree.reset(), d_sflag.reset(), d_sidx.reset();
-  lap("device: wide collapses, blob");
-  // ---- objects ------------------------------------------------------------
-  std::vector<yhd_object> objects(sd->num_objects);
+  U.level.d_stree.reset(), U.level.d_sflag.reset(), U.level.d_sidx.reset();
+  return YH_OK;
+}
+
+// The object rows (upload_stages.h: object_row), and the two limits the device's offsets and stacks set.
+static int upload_object_rows(yh_context* ctx, UploadStage& U) {
+  const yh_scene_desc* sd = U.sd;
+  U.objects.resize((size_t)sd->num_objects);
   for (int oi = 0; oi < sd->num_objects; oi++) {
-    auto& o = sd->objects[oi];
-    auto& I = info[o.shape];
-    auto& d = objects[oi];
-    memcpy(d.frame, o.frame, 48);
-    inverse_frame(o.frame, true, d.inv_frame);
-    d.kind = I.kind, d.node_base = 0, d.prim_base = I.prim_base, d.vert_base = I.vert_base;
-    d.elem_base = I.elem_base, d.has_normals = I.has_normals, d.material = o.material, d.has_texcoords = sd->shapes[o.shape].texcoords != nullptr;
-    const auto& LS = ctx->lane_shapes[(size_t)o.shape];
-    d.lane_root = (int)LS.node_off, d.lane_test = (int)LS.test_off, d.lane_root8 = (int)LS.node_off8, d.lane_root16 = (int)LS.node_off16;
-    padded_world_box(obj_boxes[oi].min, obj_boxes[oi].max, d.wbox_min, d.wbox_max);
+    const yh_object& o = sd->objects[oi];
+    const auto&      I = U.shapes[(size_t)o.shape];
+    const auto&      R = U.blob.shapes[(size_t)o.shape];
+    object_row(o, {I.kind, I.prim_base, I.vert_base, I.elem_base, I.has_normals, sd->shapes[o.shape].texcoords != nullptr, R.test_off, {R.node_off[0], R.node_off[1], R.node_off[2]}},
+        U.obj_boxes[(size_t)oi], U.objects[(size_t)oi]);
   }
   // array offsets on the device are 32-bit float4 indices
-  if (vpos.size() > (size_t)std::numeric_limits<int>::max()) return fail(ctx, YH_E_INVALID, "scene too large for 32-bit vertex offsets (%zu)", vpos.size());
-  std::vector<yhd_float4> scene_nodes;  // (binary, also of a scene walked through its wide nodes: the counted builds' yardstick)
-  for (auto& n : scene_tree.nodes) scene_nodes.push_back(node_lo(n)), scene_nodes.push_back(node_hi(n));
-  int max_shape_depth = 0;
-  for (auto& I : info) max_shape_depth = std::max(max_shape_depth, I.depth);
-  int max_shape_depth8 = 0, max_shape_depth16 = 0;
-  for (auto& I : info) max_shape_depth8 = std::max(max_shape_depth8, I.depth8), max_shape_depth16 = std::max(max_shape_depth16, I.depth16);
-  const StackNeeds needs = stack_needs(scene_wide, scene_wide_depth, scene_tree.max_depth, max_shape_depth, max_shape_depth8, max_shape_depth16);
-  ctx->stack_need = needs.need, ctx->stack_need8 = needs.need8, ctx->stack_need16 = needs.need16;
-  if (ctx->stack_need > yhk_stack_entries())
-    return fail(ctx, YH_E_INVALID, "BVH too deep for the traversal stack (%d > %d)", ctx->stack_need, yhk_stack_entries());
-  // ---- materials ---------------------------------------------------------
-  std::vector<yhd_material> materials(sd->num_materials);
-  std::vector<yhd_maps> mat_maps(any_maps ? (size_t)sd->num_materials : 0);
-  const bool general_rows = make_material_rows(sd->materials, any_maps ? maps : nullptr, sd->num_materials, materials.data(), mat_maps.data());
-  // ---- environments, and the lights (pt.cpp:1695-1740): which they are and where their entries sit is light_layout.h's rule; the cdf
-  // values, the small lights' records and the index entries are computed here, from the arrays the caller lent ----
-  yhd_scene sc{};
-  std::vector<yhd_float4> env_texels;
-  sc.num_environments = sd->num_environments;
+  if (U.vpos.size() > (size_t)std::numeric_limits<int>::max()) return fail(ctx, YH_E_INVALID, "scene too large for 32-bit vertex offsets (%zu)", U.vpos.size());
+  return check_stack_needs(ctx, "", U.level.needs);
+}
+
+// Materials, environments and the lights (pt.cpp:1695-1740): which they are and where their entries sit is light_layout.h's rule; the cdf
+// values, the small lights' records and the index entries are upload_stages.h's, from the arrays the caller lent.
+static int upload_lights(yh_context* ctx, UploadStage& U) {
+  const yh_scene_desc* sd = U.sd;
+  U.materials.resize((size_t)sd->num_materials);
+  U.mat_maps.resize(U.maps ? (size_t)sd->num_materials : 0);
+  U.general_rows = make_material_rows(sd->materials, U.maps, sd->num_materials, U.materials.data(), U.mat_maps.data());
+  U.sc.num_environments = sd->num_environments;
   float env_emission[3 * YH_MAX_ENVS] = {};
-  int   env_texel_count[YH_MAX_ENVS] = {};
-  for (int ei = 0; ei < sd->num_environments; ei++) {
-    auto& e = sd->environments[ei];
-    auto& d = sc.environments[ei];
-    memcpy(d.frame, e.frame, 48);
-    inverse_frame(e.frame, false, d.inv_frame);
-    memcpy(d.emission, e.emission, 12);
-    d.tex_w = e.texels ? e.tex_width : 0, d.tex_h = e.texels ? e.tex_height : 0;
-    d.texel_base = (int)env_texels.size();
-    if (e.texels)
-      for (size_t t = 0; t < (size_t)e.tex_width * e.tex_height; t++)
-        env_texels.push_back({e.texels[3 * t], e.texels[3 * t + 1], e.texels[3 * t + 2], 0});
-    memcpy(env_emission + 3 * ei, e.emission, 12);
-    env_texel_count[ei] = e.texels ? (int)((size_t)e.tex_width * e.tex_height) : 0;
+  int   env_texel_count[YH_MAX_ENVS]  = {};
+  environment_rows(*sd, U.sc.environments, U.env_texels, env_emission, env_texel_count);
+  std::vector<LightShape> light_shapes;
+  for (auto& I : U.shapes) light_shapes.push_back({I.kind == YH_KIND_LINES, I.num_prims});
+  int at = 0;
+  switch (light_layout({sd->num_objects, sd->objects, sd->materials, light_shapes.data(), sd->num_environments, env_emission, env_texel_count}, U.lights, &at)) {
+    // (every object with an emissive material is a light of its own, so every frame of an instanced emitter is one: init_lights walks objects)
+    case YH_LIGHTS_OBJECT_TOO_MANY:
+      return fail(ctx, YH_E_INVALID, "more than %d lights: object %d of %d is emissive too (each instance of an emitter counts)", YH_MAX_LIGHTS, at, sd->num_objects);
+    case YH_LIGHTS_ENVIRONMENT_TOO_MANY: return fail(ctx, YH_E_INVALID, "more than %d lights", YH_MAX_LIGHTS);
+    case YH_LIGHTS_NONE: return fail(ctx, YH_E_INVALID, "scene has no lights (the path sampler needs at least one)");
   }
-  LightLayout lights;
-  {
-    std::vector<LightShape> light_shapes;
-    for (auto& I : info) light_shapes.push_back({I.kind == YH_KIND_LINES, I.num_prims});
-    int at = 0;
-    switch (light_layout({sd->num_objects, sd->objects, sd->materials, light_shapes.data(), sd->num_environments, env_emission, env_texel_count}, lights, &at)) {
-      // (every object with an emissive material is a light of its own, so every frame of an instanced emitter is one: init_lights walks objects)
-      case YH_LIGHTS_OBJECT_TOO_MANY:
-        return fail(ctx, YH_E_INVALID, "more than %d lights: object %d of %d is emissive too (each instance of an emitter counts)", YH_MAX_LIGHTS, at, sd->num_objects);
-      case YH_LIGHTS_ENVIRONMENT_TOO_MANY: return fail(ctx, YH_E_INVALID, "more than %d lights", YH_MAX_LIGHTS);
-      case YH_LIGHTS_NONE: return fail(ctx, YH_E_INVALID, "scene has no lights (the path sampler needs at least one)");
-    }
-  }
-  sc.num_lights = lights.num_lights;
-  memcpy(sc.lights, lights.lights, sizeof(sc.lights));
-  std::vector<float> light_cdf;  // every light's segment, in list order: an area cdf by element, or a texel cdf
-  for (int li = 0; li < sc.num_lights; li++) {
-    const yhd_light& L = sc.lights[li];
-    if (L.object >= 0) {
-      auto& s = sd->shapes[sd->objects[L.object].shape];
-      for (int t = 0; t < s.num_triangles; t++) {
-        float area = triangle_area(ld3(s.positions + 3 * (size_t)s.triangles[3 * t]), ld3(s.positions + 3 * (size_t)s.triangles[3 * t + 1]),
-            ld3(s.positions + 3 * (size_t)s.triangles[3 * t + 2]));  // (unit/light_math.h: triangle_area, math.h:3306)
-        if (t) area += light_cdf.back();
-        light_cdf.push_back(area);
-      }
-    } else if (L.cdf_count > 0) {
-      auto& e = sd->environments[L.environment];
-      append_env_cdf(e.texels, 3, e.tex_width, e.tex_height, light_cdf);
-    }
-  }
-  // ---- tables the kernels keep in LDS (yh_device.h) -----------------------------------------------------
-  // small area lights: root box, leaf-ordered triangles, area cdf — everything sample_lights / sample_lights_pdf read
-  std::vector<yhd_float4> light_table;
-  for (int li = 0; li < sc.num_lights; li++) {
-    const yhd_light& L = sc.lights[li];
+  light_cdfs(*sd, U.lights, U.light_cdf);
+  for (int li = 0; li < U.lights.num_lights; li++) {
+    const yhd_light& L = U.lights.lights[li];
     if (L.small_base < 0) continue;  // (light_table.size() is L.small_base here: the records follow each other in list order)
-    auto& I  = info[sd->objects[L.object].shape];
+    auto& I = U.shapes[(size_t)sd->objects[L.object].shape];
     if (I.host_prims.empty()) {  // (a shape made on the device — YHAIR_BVH=device: a light of <= 4 triangles is otherwise a small shape): its few records back
       I.host_prims.resize((size_t)6 * L.cdf_count);
       HIPCHK(ctx, hipMemcpy(I.host_prims.data(), (const yhd_float4*)ctx->d_prims.p + I.prim_base, I.host_prims.size() * 16, hipMemcpyDeviceToHost));
     }
-    const yhd_float4* rec = I.host_prims.data();
-    yhd_float4 b0{I.root.min[0], I.root.min[1], I.root.min[2], 0}, b1{I.root.max[0], I.root.max[1], I.root.max[2], light_cdf[(size_t)L.cdf_base + L.cdf_count - 1]};
-    memcpy(&b0.w, &L.cdf_count, 4);
-    light_table.push_back(b0), light_table.push_back(b1);
-    for (int t = 0; t < YH_SMALL_LIGHT_TRIS; t++)
-      for (int k = 0; k < 3; k++) light_table.push_back(t < L.cdf_count ? rec[6 * t + k] : yhd_float4{0, 0, 0, 0});
-    yhd_float4 cdf{0, 0, 0, 0};
-    for (int t = 0; t < L.cdf_count; t++) (&cdf.x)[t] = light_cdf[(size_t)L.cdf_base + t];
-    light_table.push_back(cdf);
+    small_light_record(L, I.root, I.host_prims.data(), U.light_cdf.data(), U.light_table);
   }
-  // coarse index of the first textured environment light's cdf: 2048 entries (8 KB) halve the dependent fetches of
-  // its 21-step binary search
-  std::vector<float> env_tab;
-  sc.env_tab_light = lights.env_tab_light, sc.env_tab_k = lights.env_tab_k, sc.env_tab_stride = lights.env_tab_stride;
-  if (sc.env_tab_light >= 0) {
-    const yhd_light& L = sc.lights[sc.env_tab_light];
-    const int n = L.cdf_count, S = sc.env_tab_stride, K = sc.env_tab_k;
-    env_tab.resize((size_t)K);
-    for (int k = 0; k < K; k++) env_tab[(size_t)k] = light_cdf[(size_t)L.cdf_base + (size_t)std::min<int64_t>(n, (int64_t)(k + 1) * S) - 1];
+  coarse_index(U.lights, U.light_cdf.data(), U.env_tab);
+  return YH_OK;
+}
+
+static int upload_textures(yh_context* ctx, UploadStage& U) {
+  int at = 0;
+  switch (convert_textures(*U.sd, U.maps, U.textures, U.tex_texels, &at)) {
+    case YH_TEXTURES_MISSING: return fail(ctx, YH_E_INVALID, "material %d references a missing texture", at);
+    case YH_TEXTURES_EMPTY: return fail(ctx, YH_E_INVALID, "texture %d is empty", at);
   }
-  // ---- material colour textures (lookup_texture's per-texel conversion done once, pt.cpp:147-164) --------
-  std::vector<yhd_texture> textures((size_t)std::max(0, sd->num_textures));
-  std::vector<yhd_float4>  tex_texels;
-  {
-    std::vector<char> need_linear(textures.size(), 0);
-    for (int i = 0; i < sd->num_materials; i++) {
-      auto& m = sd->materials[i];
-      for (int id : {m.emission_tex, m.color_tex, m.scattering_tex})
-        if (id < 0 || id > sd->num_textures) return fail(ctx, YH_E_INVALID, "material %d references a missing texture", i);
-      if (m.emission_tex > 0) need_linear[(size_t)m.emission_tex - 1] = 1;  // transmission *= emission_tex.x, linear (pt.cpp:421)
-      if (any_maps)  // every map is looked up linear (pt.cpp:413-424, 337)
-        for (int id : {maps[i].specular_tex, maps[i].metallic_tex, maps[i].roughness_tex, maps[i].opacity_tex, maps[i].normal_tex})
-          if (id > 0) need_linear[(size_t)id - 1] = 1;
-    }
-    auto srgb_to_rgb = [](float srgb) {  // math.h:3742-3745
-      return (srgb <= 0.04045) ? srgb / 12.92f : std::pow((srgb + 0.055f) / (1.0f + 0.055f), 2.4f);
-    };
-    std::vector<char> used(textures.size(), !any_maps);  // (with maps: a texture only a transmission map names is not uploaded)
-    if (any_maps)
-      for (int i = 0; i < sd->num_materials; i++) {
-        auto& m = sd->materials[i];
-        for (int id : {m.emission_tex, m.color_tex, m.scattering_tex})
-          if (id > 0) used[(size_t)id - 1] = 1;
-      }
-    for (size_t t = 0; t < textures.size(); t++) used[t] = used[t] || need_linear[t];
-    for (size_t t = 0; t < textures.size(); t++) {
-      auto& src = sd->textures[t];
-      if (src.width <= 0 || src.height <= 0 || !src.pixels) return fail(ctx, YH_E_INVALID, "texture %d is empty", (int)t);
-      size_t n = (size_t)src.width * src.height;
-      auto&  d = textures[t];
-      d.width = src.width, d.height = src.height, d.srgb_base = (int)tex_texels.size(), d.linear_base = -1;
-      if (!used[t]) {
-        d.srgb_base = -1;
-        continue;
-      }
-      tex_texels.resize(tex_texels.size() + n);
-      yhd_float4* out = tex_texels.data() + d.srgb_base;
-      if (src.is_byte) {
-        auto b = (const unsigned char*)src.pixels;
-        parallel_for((int)n, [&](int i) {
-          out[i] = {srgb_to_rgb(b[3 * (size_t)i] / 255.0f), srgb_to_rgb(b[3 * (size_t)i + 1] / 255.0f),
-              srgb_to_rgb(b[3 * (size_t)i + 2] / 255.0f), 0};
-        });
-        if (need_linear[t]) {
-          d.linear_base = (int)tex_texels.size();
-          tex_texels.resize(tex_texels.size() + n);
-          yhd_float4* lin = tex_texels.data() + d.linear_base;
-          parallel_for((int)n, [&](int i) { lin[i] = {b[3 * (size_t)i] / 255.0f, b[3 * (size_t)i + 1] / 255.0f, b[3 * (size_t)i + 2] / 255.0f, 0}; });
-        }
-      } else {
-        auto f = (const float*)src.pixels;
-        parallel_for((int)n, [&](int i) { out[i] = {f[3 * (size_t)i], f[3 * (size_t)i + 1], f[3 * (size_t)i + 2], 0}; });
-        d.linear_base = d.srgb_base;
-      }
-    }
-  }
-  lap("objects, materials, lights");
-  // ---- upload ------------------------------------------------------------
-  if ((rc = upload(ctx, ctx->d_vpos, vpos.data(), vpos.size() * 16))) return rc;
-  if ((rc = upload(ctx, ctx->d_elems, elems.data(), elems.size() * 16))) return rc;
-  if ((rc = upload(ctx, ctx->d_objects, objects.data(), objects.size() * sizeof(yhd_object)))) return rc;
-  if ((rc = upload(ctx, ctx->d_materials, materials.data(), materials.size() * sizeof(yhd_material)))) return rc;
-  if ((rc = upload(ctx, ctx->d_scene_nodes, scene_nodes.data(), scene_nodes.size() * 16))) return rc;
-  std::vector<int> scene_prims_padded = scene_tree.primitives;
-  scene_prims_padded.resize((scene_prims_padded.size() + 3) / 4 * 4, 0);  // staged to LDS as float4
-  if ((rc = upload(ctx, ctx->d_scene_prims, scene_prims_padded.data(), scene_prims_padded.size() * 4))) return rc;
-  if ((rc = upload(ctx, ctx->d_light_cdf, light_cdf.data(), light_cdf.size() * 4))) return rc;
-  if ((rc = upload(ctx, ctx->d_light_table, light_table.data(), light_table.size() * 16))) return rc;
-  if ((rc = upload(ctx, ctx->d_env_tab, env_tab.data(), env_tab.size() * 4))) return rc;
-  if ((rc = upload(ctx, ctx->d_env_texels, env_texels.data(), env_texels.size() * 16))) return rc;
-  if ((rc = upload(ctx, ctx->d_textures, textures.data(), textures.size() * sizeof(yhd_texture)))) return rc;
-  if ((rc = upload(ctx, ctx->d_tex_texels, tex_texels.data(), tex_texels.size() * 16))) return rc;
-  if ((rc = upload(ctx, ctx->d_vtex, vtex.data(), vtex.size() * 4))) return rc;
-  std::vector<yhh::Box> shape_roots;  // (what yh_update_objects starts from: context_internal.h)
-  for (auto& I : info) shape_roots.push_back(I.root);
-  if ((rc = upload(ctx, ctx->d_shape_roots, shape_roots.data(), shape_roots.size() * sizeof(yhh::Box)))) return rc;
-  if (any_maps) {
-    if ((rc = upload(ctx, ctx->d_maps, mat_maps.data(), mat_maps.size() * sizeof(yhd_maps)))) return rc;
-  } else {
-    ctx->d_maps.reset();
-  }
-  lap("hipMalloc + H2D copies");
+  return YH_OK;
+}
+
+// The copies to the device ...
+static int upload_arrays(yh_context* ctx, UploadStage& U) {
+  int rc;
+  if ((rc = upload(ctx, ctx->d_vpos, U.vpos.data(), U.vpos.size() * 16))) return rc;
+  if ((rc = upload(ctx, ctx->d_elems, U.elems.data(), U.elems.size() * 16))) return rc;
+  if ((rc = upload(ctx, ctx->d_objects, U.objects.data(), U.objects.size() * sizeof(yhd_object)))) return rc;
+  if ((rc = upload(ctx, ctx->d_materials, U.materials.data(), U.materials.size() * sizeof(yhd_material)))) return rc;
+  if ((rc = upload(ctx, ctx->d_scene_nodes, U.level.scene_nodes.data(), U.level.scene_nodes.size() * 16))) return rc;
+  if ((rc = upload(ctx, ctx->d_scene_prims, U.level.scene_prims.data(), U.level.scene_prims.size() * 4))) return rc;
+  if ((rc = upload(ctx, ctx->d_light_cdf, U.light_cdf.data(), U.light_cdf.size() * 4))) return rc;
+  if ((rc = upload(ctx, ctx->d_light_table, U.light_table.data(), U.light_table.size() * 16))) return rc;
+  if ((rc = upload(ctx, ctx->d_env_tab, U.env_tab.data(), U.env_tab.size() * 4))) return rc;
+  if ((rc = upload(ctx, ctx->d_env_texels, U.env_texels.data(), U.env_texels.size() * 16))) return rc;
+  if ((rc = upload(ctx, ctx->d_textures, U.textures.data(), U.textures.size() * sizeof(yhd_texture)))) return rc;
+  if ((rc = upload(ctx, ctx->d_tex_texels, U.tex_texels.data(), U.tex_texels.size() * 16))) return rc;
+  if ((rc = upload(ctx, ctx->d_vtex, U.vtex.data(), U.vtex.size() * 4))) return rc;
+  for (auto& I : U.shapes) U.shape_roots.push_back(I.root);  // (what yh_update_objects starts from: context_internal.h)
+  if ((rc = upload(ctx, ctx->d_shape_roots, U.shape_roots.data(), U.shape_roots.size() * sizeof(yhh::Box)))) return rc;
+  if (U.maps) return upload(ctx, ctx->d_maps, U.mat_maps.data(), U.mat_maps.size() * sizeof(yhd_maps));
+  ctx->d_maps.reset();
+  return YH_OK;
+}
+
+// ... and the scene table over them
+static void fill_scene_table(yh_context* ctx, UploadStage& U) {
+  const yh_scene_desc* sd = U.sd;
+  yhd_scene&           sc = U.sc;
   sc.prims = (const yhd_float4*)ctx->d_prims.p;
   sc.vpos = (const yhd_float4*)ctx->d_vpos.p;
   sc.elems = (const yhd_int4*)ctx->d_elems.p;
   sc.objects = (const yhd_object*)ctx->d_objects.p, sc.materials = (const yhd_material*)ctx->d_materials.p;
-  sc.scene_nodes = (const yhd_float4*)ctx->d_scene_nodes.p, sc.scene_prims = (const int*)ctx->d_scene_prims.p;
-  sc.num_scene_nodes = (int)scene_tree.nodes.size(), sc.num_objects = sd->num_objects;
-  sc.light_cdf = (const float*)ctx->d_light_cdf.p, sc.env_texels = (const yhd_float4*)ctx->d_env_texels.p;
-  sc.light_table = (const yhd_float4*)ctx->d_light_table.p, sc.light_table_f4 = (int)light_table.size();
-  sc.env_tab = (const float*)ctx->d_env_tab.p;
-  sc.stack_entries = std::max(8, (ctx->stack_need + 7) / 8 * 8);
-  sc.stack_entries8 = std::max(8, (ctx->stack_need8 + 7) / 8 * 8);
-  sc.stack_entries16 = std::max(8, (ctx->stack_need16 + 7) / 8 * 8);
-  sc.lane_blob = (const yhd_float4*)ctx->d_lane_blob.p, sc.lane_blob_units = blob_units;
+  sc.num_objects = sd->num_objects;
+  sc.env_texels = (const yhd_float4*)ctx->d_env_texels.p;
+  sc.lane_blob = (const yhd_float4*)ctx->d_lane_blob.p, sc.lane_blob_units = U.blob.units;
   sc.textures = (const yhd_texture*)ctx->d_textures.p, sc.tex_texels = (const yhd_float4*)ctx->d_tex_texels.p;
   sc.vtex = (const float*)ctx->d_vtex.p;
-  sc.maps = any_maps ? (const yhd_maps*)ctx->d_maps.p : nullptr;
+  sc.maps = U.maps ? (const yhd_maps*)ctx->d_maps.p : nullptr;
   memcpy(sc.camera.frame, sd->camera.frame, 48);
   sc.camera.lens = sd->camera.lens, sc.camera.film_x = sd->camera.film[0], sc.camera.film_y = sd->camera.film[1];
   sc.camera.focus = sd->camera.focus, sc.camera.aperture = sd->camera.aperture;
-  sc.num_nodes_total = 0, sc.num_prim_f4 = (int)total_prim_f4;
-  for (auto& I : info) sc.num_nodes_total += I.wide_count[0];
-  sc.lds_scene_f4    = scene_wide ? 0 : lds_scene_f4;  // (made with the scene tree, above)
-  sc.scene_wide_root = scene_wide ? 0 : -1;
+  sc.num_nodes_total = 0, sc.num_prim_f4 = (int)U.total_prim_f4;
+  for (auto& I : U.shapes) sc.num_nodes_total += I.wide_count[0];
   static_assert(sizeof(yhd_material) == 16 * YH_MATERIAL_F4, "yhd_material is staged to LDS as float4");
   sc.lds_materials = sd->num_materials <= 24 ? sd->num_materials : 0;  // the material table in LDS
-  ctx->big_lights  = lights.big_lights;  // (a light sampled and intersected through memory: the general kernel variant, settle_scene_variant)
-  settle_scene_variant(ctx, sc, general_rows);
-  ctx->scene      = sc;
-  {  // what the edits of this scene start from (host/edit_internal.h), and the bytes its fingerprint mixes, in the fingerprint's order
-    auto bytes = [](std::vector<unsigned char>& to, const void* p, size_t n) { to.insert(to.end(), (const unsigned char*)p, (const unsigned char*)p + n); };
-    ctx->key_camera = sd->camera;
-    ctx->h_materials.assign(sd->materials, sd->materials + sd->num_materials);
-    ctx->key_geometry.clear(), ctx->key_envs.clear();
-    ctx->shape_states.assign((size_t)sd->num_shapes, yh_context::ShapeState{});
-    bytes(ctx->key_geometry, sd->objects, sizeof(yh_object) * (size_t)sd->num_objects);
-    for (int i = 0; i < sd->num_shapes; i++) {
-      const yh_shape& sh = sd->shapes[i];
-      int counts[3] = {sh.num_vertices, sh.num_lines, sh.num_triangles};
-      bytes(ctx->key_geometry, counts, sizeof(counts));
-      {  // what yh_update_shape needs of this shape (context_internal.h); at an upload every width has room for exactly its nodes
-        auto& E = ctx->shape_states[(size_t)i];
-        auto& I = info[(size_t)i];
-        E.num_vertices = sh.num_vertices, E.has_normals = sh.normals != nullptr, E.has_texcoords = sh.texcoords != nullptr;
-        E.per_vertex = sh.num_lines <= 0 || sh.texcoords != nullptr, E.vert_base = I.vert_base, E.elem_base = I.elem_base;
-        E.depth = I.depth, E.depth8 = I.depth8, E.depth16 = I.depth16;
-        for (int w = 0; w < 3; w++) {
-          E.count[w] = E.room[w] = I.wide_count[w];
-          E.wide_levels[w] = I.wide_levels[w];
-          memcpy(E.wide_first[w], I.wide_first[w], sizeof(E.wide_first[w]));
-          E.area_build[w] = E.area_now[w] = slot_areas[3 * (size_t)i + w];
-        }
-        E.key_positions = ctx->key_geometry.size();
-      }
-      if (sh.positions && sh.num_vertices > 0) {
-        const size_t n = (size_t)sh.num_vertices, take = std::min<size_t>(n, 256);
-        bytes(ctx->key_geometry, sh.positions, take * 12), bytes(ctx->key_geometry, sh.positions + 3 * (n - take), take * 12);
-      }
-    }
-    for (int i = 0; i < sd->num_environments; i++) bytes(ctx->key_envs, &sd->environments[i], offsetof(yh_environment, texels));
-    if (any_maps) ctx->h_maps.assign(maps, maps + sd->num_materials), ctx->h_dmaps = mat_maps;
-    else ctx->h_maps.clear(), ctx->h_dmaps.clear();
-    ctx->h_shape_roots.swap(shape_roots), ctx->h_obj_boxes.swap(obj_boxes);
-    ctx->max_shape_depth = max_shape_depth, ctx->max_shape_depth8 = max_shape_depth8, ctx->max_shape_depth16 = max_shape_depth16;
-    ctx->scene_wide_room = scene_wide ? sd->num_objects : 0;
-    ctx->scene_key = scene_fingerprint(ctx);
+  set_scene_level_fields(ctx, sc, U.level);
+  set_light_fields(ctx, sc, U.lights);
+  settle_scene_variant(ctx, sc, U.general_rows);
+  ctx->scene = sc;
+}
+
+// What the edits of this scene start from (host/edit_internal.h), and its fingerprint over the bytes the context keeps of the description.
+static void keep_for_edits(yh_context* ctx, UploadStage& U) {
+  const yh_scene_desc* sd = U.sd;
+  ctx->key_camera = sd->camera;
+  ctx->h_materials.assign(sd->materials, sd->materials + sd->num_materials);
+  std::vector<size_t> key_positions;
+  description_key_bytes(*sd, ctx->key_geometry, ctx->key_envs, key_positions);
+  ctx->shape_states.assign((size_t)sd->num_shapes, yh_context::ShapeState{});
+  for (int i = 0; i < sd->num_shapes; i++) {  // (at an upload every width has room for exactly its nodes)
+    const yh_shape& sh = sd->shapes[i];
+    auto&           E  = ctx->shape_states[(size_t)i];
+    const auto&     I  = U.shapes[(size_t)i];
+    E.num_vertices = sh.num_vertices, E.has_normals = sh.normals != nullptr, E.has_texcoords = sh.texcoords != nullptr;
+    E.per_vertex = sh.num_lines <= 0 || sh.texcoords != nullptr, E.vert_base = I.vert_base, E.elem_base = I.elem_base;
+    E.key_positions = key_positions[(size_t)i];
+    shape_state_of_build(E, I, I.wide_count, &U.slot_areas[3 * (size_t)i]);
   }
+  if (U.maps) ctx->h_maps.assign(U.maps, U.maps + sd->num_materials), ctx->h_dmaps = U.mat_maps;
+  else ctx->h_maps.clear(), ctx->h_dmaps.clear();
+  ctx->h_shape_roots.swap(U.shape_roots), ctx->h_obj_boxes.swap(U.obj_boxes);
+  const ShapeDepths deepest = deepest_shape_trees(U.shapes);
+  ctx->max_shape_depth = deepest.depth4, ctx->max_shape_depth8 = deepest.depth8, ctx->max_shape_depth16 = deepest.depth16;
+  ctx->scene_wide_room = U.level.scene_wide ? sd->num_objects : 0;
+  ctx->scene_key = scene_fingerprint(ctx);
+}
+
+int yh_upload_scene(yh_context* ctx, const yh_scene_desc* sd) { return yh_upload_scene_maps(ctx, sd, nullptr); }
+
+int yh_upload_scene_maps(yh_context* ctx, const yh_scene_desc* sd, const yh_material_maps* maps) {
+  if (!ctx) return YH_E_INVALID;
+  Lap         lap("upload");  // YHAIR_TIMING=1: stage times of the upload on stderr
+  UploadStage U;
+  if (int rc = check_upload(ctx, sd, maps, U)) return rc;
+  drop_previous_scene(ctx);
+  if (int rc = dev_alloc(ctx, ctx->d_prims, U.total_prim_f4 * 16)) return rc;
+  lap("validation, record array");
+  if (int rc = upload_shapes(ctx, U, lap)) return rc;
+  if (int rc = upload_scene_level(ctx, U)) return rc;
+  if (int rc = upload_traversal_array(ctx, U)) return rc;
+  lap("device: wide collapses, blob");
+  if (int rc = upload_object_rows(ctx, U)) return rc;
+  if (int rc = upload_lights(ctx, U)) return rc;
+  if (int rc = upload_textures(ctx, U)) return rc;
+  lap("objects, materials, lights");
+  if (int rc = upload_arrays(ctx, U)) return rc;
+  lap("hipMalloc + H2D copies");
+  fill_scene_table(ctx, U);
+  keep_for_edits(ctx, U);
   ctx->have_scene = true;
   forget_image_of_scene(ctx);  // a new scene: no measured costs yet
   lap("scene table, fingerprint");

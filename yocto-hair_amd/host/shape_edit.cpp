@@ -178,7 +178,7 @@ static int queue_vertex_rows(yh_context* ctx, const char* who, const yh_context:
 // (scene_upload.cpp: build_shape_tree, index_shape_tree, collapse_shape_tree) and unit/shapes.hip. The node counts depend on the
 // positions: a width whose new count exceeds the room of the shape's region gets a new region behind the end of the traversal array
 // (count + count / 8 nodes, on a multiple of 4 units), the array is reallocated and the old bytes copied device to device, the vacated
-// region is zeroed and stays unused until an upload. No other shape moves: the collapse writes absolute references.
+// region is zeroed and stays unused until an upload (the rule: blob_layout.h). No other shape moves: the collapse writes absolute references.
 static int update_shape(yh_context* ctx, const char* entry, int shape, const yh_shape* now, bool device) {
   if (!ctx) return YH_E_INVALID;
   std::vector<yh_object> rows;
@@ -201,29 +201,18 @@ static int update_shape(yh_context* ctx, const char* entry, int shape, const yh_
   if (int rc = dev_alloc(ctx, d_recs, nel * per * 16)) return rc;
   if (int rc = build_shape_tree(ctx, who, shape, on_device ? dev : *now, on_device, on_device, (yhd_float4*)d_recs.p, T)) return rc;
   if (int rc = index_shape_tree(ctx, who, T)) return rc;
-  // ---- where the wide nodes go ----
-  yh_context::LaneShape  Lnew = L;
-  yh_context::ShapeState Enew = E;
-  const long long old_units = ctx->scene.lane_blob_units, width[3] = {4, 8, 16}, old_off[3] = {L.node_off, L.node_off8, L.node_off16};
-  long long       end = old_units, off[3] = {old_off[0], old_off[1], old_off[2]};
-  for (int w = 0; w < 3; w++) {
-    Enew.count[w] = T.wide_count[w];
-    if (T.wide_count[w] <= E.room[w]) continue;
-    off[w]       = (end + 3) / 4 * 4;
-    Enew.room[w] = T.wide_count[w] + T.wide_count[w] / 8;
-    end          = off[w] + width[w] * Enew.room[w] + 4;  // (four units of slack behind the last node, as the upload leaves)
-  }
-  if (end >= (1ll << 30)) return fail(ctx, YH_E_INVALID, "%sscene too large for 30-bit node offsets (%lld units): upload the scene", who, end);
-  Lnew.num_nodes = T.wide_count[0], Lnew.node_off = off[0], Lnew.node_off8 = off[1], Lnew.node_off16 = off[2];
-  Enew.depth = T.depth, Enew.depth8 = T.depth8, Enew.depth16 = T.depth16;
+  // ---- where the wide nodes go (blob_layout.h: blob_growth) ----
+  const long long old_units = ctx->scene.lane_blob_units, old_off[3] = {L.node_off, L.node_off8, L.node_off16};
+  BlobGrowth      G;
+  if (blob_growth(old_units, old_off, E.room, T.wide_count, G) != YH_BLOB_OK)
+    return fail(ctx, YH_E_INVALID, "%sscene too large for 30-bit node offsets (%lld units): upload the scene", who, G.units);
+  const long long       end  = G.units;
+  yh_context::LaneShape Lnew = L;
+  Lnew.num_nodes = T.wide_count[0], Lnew.node_off = G.off[0], Lnew.node_off8 = G.off[1], Lnew.node_off16 = G.off[2];
   DevBuf d_blob_grown;
   if (end > old_units)
     if (int rc = dev_alloc(ctx, d_blob_grown, (size_t)end * 32)) return rc;
-  int depth4 = 0, depth8 = 0, depth16 = 0;
-  for (int s = 0; s < num_shapes; s++) {
-    const yh_context::ShapeState& D = s == shape ? Enew : ctx->shape_states[(size_t)s];
-    depth4 = std::max(depth4, D.depth), depth8 = std::max(depth8, D.depth8), depth16 = std::max(depth16, D.depth16);
-  }
+  const ShapeDepths deepest = deepest_shape_trees(ctx->shape_states, shape, &T);
   // ---- the world boxes of the objects that name the shape, from its new root box; the scene level over all boxes ----
   std::vector<yhh::Box> boxes = ctx->h_obj_boxes;
   NamedBoxes            N;
@@ -233,7 +222,7 @@ static int update_shape(yh_context* ctx, const char* entry, int shape, const yh_
   YH_WAIT(ctx);
   for (size_t k = 0; k < N.named.size(); k++) boxes[(size_t)N.named[k]] = N.boxes[k];
   SceneLevelStage S;
-  if (int rc = stage_scene_level(ctx, entry, boxes, depth4, depth8, depth16, S)) return rc;
+  if (int rc = stage_scene_level(ctx, entry, boxes, deepest.depth4, deepest.depth8, deepest.depth16, S)) return rc;
   LightStage LS;  // an emitter's shape: the cdf and the record of the lights that name it, made once the new arrays sit in the context's rows
   if (emits)
     if (int rc = stage_lights_of_shape(ctx, shape, rows.data(), LS)) return rc;
@@ -246,7 +235,7 @@ static int update_shape(yh_context* ctx, const char* entry, int shape, const yh_
     ctx->scene.lane_blob = nullptr;
   }
   for (int w = 0; w < 3; w++)  // the shape's regions as they were: vacated, or written again with the unused rest zero
-    if (E.room[w] > 0) HIPCHK(ctx, hipMemsetAsync((char*)ctx->d_lane_blob.p + (size_t)old_off[w] * 32, 0, (size_t)(width[w] * E.room[w]) * 32, ctx->stream));
+    if (E.room[w] > 0) HIPCHK(ctx, hipMemsetAsync((char*)ctx->d_lane_blob.p + (size_t)old_off[w] * 32, 0, (size_t)YH_BLOB_WIDTH[w] * E.room[w] * 32, ctx->stream));
   HIPCHK(ctx, hipMemcpyAsync((yhd_float4*)ctx->d_prims.p + L.prim_base, d_recs.p, nel * per * 16, hipMemcpyDeviceToDevice, ctx->stream));
   if (int rc = collapse_shape_tree(ctx, who, T, Lnew, ctx->d_lane_blob.p)) return rc;
   if (int rc = queue_vertex_rows(ctx, who, E, dev, lines, nel)) return rc;
@@ -262,21 +251,17 @@ static int update_shape(yh_context* ctx, const char* entry, int shape, const yh_
   YH_WAIT(ctx);
   memcpy(ctx->key_geometry.data() + E.key_positions, key_bytes.data(), key_bytes.size());
   ctx->scene.num_nodes_total += T.wide_count[0] - E.count[0];
-  for (int w = 0; w < 3; w++) {
-    Enew.wide_levels[w] = T.wide_levels[w];
-    memcpy(Enew.wide_first[w], T.wide_first[w], sizeof(Enew.wide_first[w]));
-  }
-  if (int rc = shape_slot_areas(ctx, who, 1, &Lnew, &Enew.count, ctx->d_lane_blob.p, Enew.area_build)) return rc;
-  memcpy(Enew.area_now, Enew.area_build, sizeof(Enew.area_now));
-  ctx->lane_shapes[(size_t)shape]  = Lnew;
-  ctx->shape_states[(size_t)shape] = Enew;  // (E and L are these: not read below)
+  double area[3];
+  if (int rc = shape_slot_areas(ctx, who, 1, &Lnew, &T.wide_count, ctx->d_lane_blob.p, area)) return rc;
+  ctx->lane_shapes[(size_t)shape] = Lnew;
+  shape_state_of_build(ctx->shape_states[(size_t)shape], T, G.room, area);  // (E and L are these: not read below)
   ctx->lane_units = 0;
   for (int s = 0; s < num_shapes; s++)  // the end of the furthest 4-wide region: what the one-lane kernels address
-    ctx->lane_units = std::max(ctx->lane_units, ctx->lane_shapes[(size_t)s].node_off + 4ll * ctx->shape_states[(size_t)s].room[0] + 4);
+    ctx->lane_units = std::max(ctx->lane_units, blob_lane_end(ctx->lane_shapes[(size_t)s].node_off, ctx->shape_states[(size_t)s].room[0]));
   ctx->scene.lane_blob = (const yhd_float4*)ctx->d_lane_blob.p, ctx->scene.lane_blob_units = end;
   ctx->h_shape_roots[(size_t)shape] = T.root;
   ctx->h_obj_boxes.swap(boxes);
-  ctx->max_shape_depth = depth4, ctx->max_shape_depth8 = depth8, ctx->max_shape_depth16 = depth16;
+  ctx->max_shape_depth = deepest.depth4, ctx->max_shape_depth8 = deepest.depth8, ctx->max_shape_depth16 = deepest.depth16;
   settle_scene_level(ctx, S);
   ctx->have_scene = true;
   edit_end(ctx);
