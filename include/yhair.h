@@ -743,10 +743,27 @@ int yh_intersect_batch(yh_context* ctx, int n, const float* rays, int* object,
  * (the scene level resolved once per ray where it is one leaf node). form 0:
  * a quad per ray over 4-wide nodes (launch shape 0, the quad half of shape
  * 5); form 1: an octet per ray over 8-wide nodes (the octet half of shape 5).
- * Arguments and results as yh_intersect_batch. YH_E_INVALID for a scene that
+ * Forms 2-6 run the traversal of the 256-thread launch shapes, with their
+ * workgroup size and LDS stack stride, in the form without the once-per-ray
+ * scene level (none of those shapes has one):
+ *   2  a quad per ray, the dense form              (launch shape 1)
+ *   3  an octet per ray over 8-wide nodes          (launch shape 4)
+ *   4  an octet per ray with leaf pairs            (launch shape 7)
+ *   5  sixteen lanes per ray over 16-wide nodes    (launch shape 6)
+ *   6  sixteen lanes per ray with leaf groups      (launch shape 8)
+ * form | YH_INTERSECT_TABLE_IN_MEMORY (forms 3-6 only): the scene level read
+ * from memory, as the GENERAL variants of those shapes read a table that does
+ * not fit LDS — a 4-wide scene node then runs in every quad of the octet or
+ * the sixteen. Arguments and results as yh_intersect_batch. YH_E_INVALID for
+ * an unknown form, and — the memory-table forms apart — for a scene that
  * renders with the GENERAL kernel variants.                                  */
+#define YH_INTERSECT_FORMS 7
+#define YH_INTERSECT_TABLE_IN_MEMORY 16
 int yh_intersect_plain_batch(yh_context* ctx, int form, int n, const float* rays,
     int* object, int* element, float* uv, float* distance);
+/* The lanes that own a ray in `form` of yh_intersect_plain_batch (4, 8 or 16);
+ * YH_E_INVALID for a form it does not have: the answer the batch gives too.    */
+int yh_intersect_plain_form(int form);
 /* Whether the plain 512-thread kernels resolve the uploaded scene's scene
  * level once per ray, ahead of the traversal loop (a scene level of ONE leaf
  * node: at most four objects): the number of objects, else 0; YH_E_STATE

@@ -17,6 +17,10 @@ tmin are a batch of their own (quad_only) for the quad forms.
     g  crowding: 128 hit rows of b, each 64 times in a row, the last 16 of each 64 moved an ulp
     h  through: rays that hit one object and would hit another just behind it, both ways
 
+Variant `ties` has one batch of its own (ties: N rows on primitives that are there many times over, whose copies fill several leaves),
+variant `deep` another (deep_rays); wide_walk and wide_walk_any walk yh_bvh_build_wide's nodes as the device does, for the CPU proofs of
+tests/test_hit_cases.py.
+
 An edge row is built ON the edge, exactly (the scene's numbers are multiples of 2^-10), with the same ray one float of the deciding
 input to either side next to it: rows 3 k, 3 k + 1, 3 k + 2 of a block are (below, on, above), Stratum.triple holds k or -1.
 Strata b - e are aimed at the two objects under the identity frame (a-strands, c-tris), whose object space is world space: their
@@ -489,6 +493,125 @@ def deep_rays():
     return rays
 
 
+TIES_NAMES = ("t",)
+TIES_OBJECTS = {"stack": 4, "sheaf": 5, "plates": 6, "rungs": 7}  # variant `ties`: its shapes' objects, behind those of `four`
+_SIGNS = np.array([[(-1.0) ** (k >> 2 & 1), (-1.0) ** (k >> 1 & 1), (-1.0) ** (k & 1)] for k in range(8)])
+_MAGS = np.array([(1, 0.5, 0.25), (0.25, 1, 0.5), (0.5, 0.25, 1), (1, 1, 1), (1, 0.125, 0.75), (0.375, 1, 0.0625)])
+_AXES6 = np.concatenate([np.eye(3), -np.eye(3)])
+
+
+def _ties_segment(R, obj, p0, p1, r0, r1, prim, rng, n_general):
+    """Strata b's families on one segment along an axis that is there many times: distance r exactly at dyadic s, the ends, and rays of
+    every sign triple and along every axis through points of it."""
+    p0, p1 = np.asarray(p0, np.float64), np.asarray(p1, np.float64)
+    ax = int(np.abs(p1 - p0).argmax())
+    for s in (0.0, 0.25, 0.5, 0.75, 1.0):
+        c, rr = p0 * (1 - s) + p1 * s, r0 * (1 - s) + r1 * s
+        for e_ax in range(3):
+            if e_ax == ax:
+                continue
+            w_ax = 3 - ax - e_ax
+            for sign in (1.0, -1.0):
+                e, w = np.zeros(3), np.zeros(3)
+                e[e_ax], w[w_ax] = sign, 1.0
+                R.add_triples(obj, c + rr * e - 2 * w, w, prim, e_ax)
+                R.add_triples(obj, c + rr * e + 1.5 * w, -w, prim, e_ax)
+    d = (_SIGNS[:, None] * _MAGS[None]).reshape(-1, 3)
+    for v in (p0, p1):  # through an end, moved along the segment: s crosses 0 or 1
+        R.add_triples(obj, v - 2 * d, d, prim, ax)
+    s = _dy(rng, 0, 1, (n_general, 1), 16)
+    c = p0 * (1 - s) + p1 * s
+    off = np.zeros((n_general, 3))
+    off[:, (ax + 1) % 3] = _dy(rng, -8 / 1024, 8 / 1024, n_general, 1024)
+    d = np.concatenate([d, _AXES6[np.abs(_AXES6[:, ax]) == 0]])[rng.integers(0, len(d) + 4, n_general)]
+    R.add(obj, c + off - 2 * d, d, prim)
+
+
+def _ties_rows(geo):
+    rng = np.random.default_rng(701)
+    R = _Rows(geo)
+    ob = TIES_OBJECTS
+    # the stack: one segment, 64 times
+    _ties_segment(R, ob["stack"], (-0.5, 0, 0), (0.5, 0, 0), 24 / 1024, 16 / 1024, 1, rng, 700)
+    # the sheaf: the joints and ends of a strand along z that is there six times
+    z = [-1 + 0.5 * k for k in range(5)]
+    rad = [20 / 1024, 16 / 1024, 12 / 1024, 8 / 1024, 4 / 1024]
+    for k in range(4):
+        _ties_segment(R, ob["sheaf"], (0, 0, z[k]), (0, 0, z[k + 1]), rad[k], rad[k + 1], k, rng, 120)
+    # the plates: stratum c's families on one triangle that is there 32 times — vertices, points of its edges at dyadic parameters, inside
+    v = np.array([(-0.5, -0.5, 0.0), (0.5, -0.5, 0.0), (0.0, 0.5, 0.0)])
+    k = _dy(rng, 0, 1, (240, 1), 16)
+    e = rng.integers(0, 3, 240)
+    pts = np.concatenate([v, v[e] * (1 - k) + v[(e + 1) % 3] * k])
+    u, w = _dy(rng, 0, 1, (400, 1), 64), _dy(rng, 0, 1, (400, 1), 64)
+    flip = (u + w) > 1
+    u, w = np.where(flip, 1 - u, u), np.where(flip, 1 - w, w)
+    inside = v[0] * (1 - u - w) + v[1] * u + v[2] * w
+    d = np.concatenate([(_SIGNS[:, None] * _MAGS[None]).reshape(-1, 3), [(0, 0, 1.0), (0, 0, -1.0)]])
+    dd = d[rng.integers(0, len(d), len(pts))]
+    R.add_triples(ob["plates"], pts - 2 * dd, dd, 0, rng.integers(0, 2, len(pts)))
+    dd = d[rng.integers(0, len(d), len(inside))]
+    R.add(ob["plates"], inside - 2 * dd, dd, 0)
+    for vert in v[:2]:  # along z through a lower vertex: on a face of the shape's box in x, of the triangle's own box in x and y (0 * inf twice)
+        for sz in (1.0, -1.0):
+            for ax in (0, 1):
+                R.add_triples(ob["plates"], np.tile(vert - (0, 0, 2 * sz), (4, 1)), (0, 0, sz), 0, ax)
+                R.add_triples(ob["plates"], np.tile(vert - (0, 0, 2 * sz), (4, 1)), (0, 0, 2 * sz), 0, ax)
+    small = np.array([(-0.25, -1.5, 0.0), (0.25, -1.5, 0.0), (0.0, -1.0, 0.0)])
+    dd = d[rng.integers(0, len(d), 24)]
+    R.add_triples(ob["plates"], small[rng.integers(0, 3, 24)] - 2 * dd, dd, 32, rng.integers(0, 2, 24))
+    for dirn, o in (((1.0, 0, 0), (-2.0, 0, 0)), ((-1.0, 0, 0), (2.0, 0, 0)), ((0, 1.0, 0), (0, -2.0, 0)), ((0.5, -1.0, 0), (0, 2.0, 0))):  # in its plane: det == 0
+        m = 20
+        o = np.tile(np.array(o, np.float64), (m, 1))
+        o[:, 1 if dirn[1] == 0 else 0] = _dy(rng, -0.5, 0.5, m, 32)
+        R.add_triples(ob["plates"], o, dirn, 0, 2)
+    # the rungs: across one site (+-z: its leaves alone) and along +-y through all four (every leaf of the shape on one line)
+    for y, first in ((-3.0, 0), (-1.0, 4), (1.0, 12), (3.0, 21)):
+        x = _dy(rng, -0.25, 0.25, (20, 1), 64)
+        for sz in (1.0, -1.0):
+            for sy in (1.0, -1.0):
+                o = np.concatenate([x, np.full((20, 1), y + sy * 16 / 1024), np.full((20, 1), -2.0 * sz)], 1)
+                R.add_triples(ob["rungs"], o, (0, 0, sz), first, 1)
+        dd = (_SIGNS[:, None] * np.array([(0.5, 0.0625, 1), (1, 0.03125, 0.5), (0.25, 0.0625, 1)])[None]).reshape(-1, 3)
+        R.add(ob["rungs"], np.array([0.0, y, 0.0]) - 2 * dd, dd, first)
+    x = _dy(rng, -0.25, 0.25, (30, 1), 64)
+    for sy in (1.0, -1.0):
+        for zz in (0.0, 16 / 1024, -16 / 1024, 8 / 1024):
+            R.add_triples(ob["rungs"], np.concatenate([x, np.full((30, 1), -5.0 * sy), np.full((30, 1), zz)], 1), (0, sy, 0), 0 if sy > 0 else 21, 2)
+        for tilt in (0.03125, -0.03125):
+            R.add(ob["rungs"], np.concatenate([x, np.full((30, 1), -5.0 * sy), np.zeros((30, 1))], 1), (tilt, sy, 0), 0 if sy > 0 else 21)
+    # a finite tmax on the tie's t and its float neighbours: t = 2 and t = 1 by construction (the closest approach to the axis; the plane)
+    x = _dy(rng, -0.5, 0.5, (40, 1), 64)
+    rr = 24 / 1024 * (1 - (x + 0.5)) + 16 / 1024 * (x + 0.5)
+    for sgn in (1.0, -1.0):
+        o = np.concatenate([x, sgn * rr, np.full((40, 1), -2.0 * sgn)], 1)
+        R.add_tmax_triples(ob["stack"], o, (0, 0, sgn), 1, 2.0)
+        R.add_tmax_triples(ob["stack"], o, (0, 0, 2 * sgn), 1, 1.0)
+        R.add_tmax_triples(ob["plates"], inside[:40] + (0, 0, 2.0 * sgn), (0, 0, -sgn), 0, 2.0)
+        R.add_tmax_triples(ob["plates"], inside[40:80] + (0, 0, 2.0 * sgn), (0, 0, -2 * sgn), 0, 1.0)
+        R.add_tmax_triples(ob["rungs"], np.concatenate([x[:, :1] / 2, np.full((40, 1), -5.0 * sgn), np.zeros((40, 1))], 1), (0, sgn, 0), 0 if sgn > 0 else 21, 2.0)
+        R.add_tmax_triples(ob["rungs"], np.concatenate([x[:, :1] / 2, np.full((40, 1), -5.0 * sgn), np.zeros((40, 1))], 1), (0, sgn, 0), 4 if sgn > 0 else 12, 4.0)
+    return R
+
+
+@functools.lru_cache(maxsize=None)
+def ties():
+    """The Stratum of variant `ties` (four and the shapes of make_scenes._hits_ties): N rows that follow strata b and c onto primitives that
+    are there many times over — at the ends, at distance r exactly, on edges and vertices, with both signs of every direction component
+    and along every axis, and a slice with a finite tmax on the tie's t and its float neighbours. Every hit on such a primitive is a hit
+    on each of its copies at the same t as bits, and the copies fill several leaves: who wins is the visiting order's to say."""
+    R = _ties_rows(make_scenes.hits_unit_geometry("ties"))
+    built = sum(len(r) for r in R.rays)
+    assert N // 2 <= built <= N, built  # (every block as built; the rest repeats rows from the start)
+    s = R.stratum()
+    assert s.rays.shape == (N, 8) and np.isfinite(s.rays).all() and (s.rays[:, 6] == TMIN).all() and np.abs(s.rays[:, 3:6]).max(1).min() > 0
+    return s
+
+
+def ties_rays():
+    return ties().rays
+
+
 def wide_walk(slots, o, d):
     """The heights of the traversal stack while rays (o, d: (n, 3), the shape's own space) walk a 4-wide tree, yh_bvh_build_wide's
     `slots` (nodes, 4, 8), in the order of csrc/dev_lane.h: lane_step — of a node's hit slots the first in near-first order is
@@ -543,6 +666,75 @@ def wide_walk(slots, o, d):
     return top, first
 
 
+_AXES_AT = (0, 2, 6, 14)  # host/bvh_build.cpp: bit offset of the axes of the binary nodes at each level below a wide node's root
+
+
+def wide_walk_any(slots, o, d):
+    """wide_walk for yh_bvh_build_wide's `slots` (nodes, width, 8) at width 4, 8 or 16, with the rank rules of csrc/dev_trace.h: slot o is
+    the path of sides s1 s2 .. from the wide node's root, and its place in the visiting order is those bits, each flipped when the ray
+    runs against the axis of the binary node it was taken at (two, three or four near / far decisions from the axes word). Returns per
+    ray (the largest height, the height at the first leaf, the leaf entries on top of the stack at the first leaf, whether a node entry
+    ends that run: else the bottom of the stack does)."""
+    width = slots.shape[1]
+    levels = {4: 2, 8: 3, 16: 4}[width]
+    w = np.ascontiguousarray(slots).view(np.uint32)
+    n = len(o)
+    o, d = o.astype(np.float32), d.astype(np.float32)
+    with np.errstate(all="ignore"):
+        dinv = (np.float32(1) / d).astype(np.float32)
+    sign = (dinv < 0).astype(np.int64)
+    none, leaf = -1, -2
+    cur, sp = np.zeros(n, np.int64), np.zeros(n, np.int64)
+    stack = np.full((n, width * len(slots) + width), none, np.int64)
+    top, first = np.zeros(n, np.int64), np.full(n, -1, np.int64)
+    run, under = np.zeros(n, np.int64), np.zeros(n, bool)
+    slot = np.arange(width)
+    while ((cur != none) | (sp > 0)).any():
+        pop = np.flatnonzero((cur == none) & (sp > 0))
+        sp[pop] -= 1
+        cur[pop] = stack[pop, sp[pop]]
+        at_leaf = cur == leaf
+        for i in np.flatnonzero(at_leaf & (first < 0)):  # the stack as a leaf group finds it
+            k = 0
+            while k < sp[i] and stack[i, sp[i] - 1 - k] == leaf:
+                k += 1
+            run[i], under[i] = k, k < sp[i]
+        first = np.where(at_leaf & (first < 0), sp, first)
+        cur[at_leaf] = none
+        idx = np.flatnonzero(cur >= 0)
+        if idx.size == 0:
+            continue
+        node = slots[cur[idx]].astype(np.float32)                      # (m, width, 8)
+        ref, axes = w[cur[idx], :, 6].astype(np.int64), w[cur[idx], 0, 7].astype(np.int64)
+        with np.errstate(all="ignore"):
+            ta = (node[:, :, 0:3] - o[idx, None]) * dinv[idx, None]
+            tb = (np.stack([node[:, :, 3], node[:, :, 4], node[:, :, 5]], -1) - o[idx, None]) * dinv[idx, None]
+            t0 = np.fmax(np.fmin(ta, tb).max(-1), TMIN)
+            t1 = np.fmax(ta, tb).min(-1) * np.float32(1.00000024)
+        hm = (t0 <= t1) & (ref != 0xFFFFFFFF)
+        rank = np.zeros((len(idx), width), np.int64)
+        for j in range(levels):  # level j: the node reached by the first j sides of the slot's path
+            path = slot >> (levels - j) if j else np.zeros(width, np.int64)
+            ax = (axes[:, None] >> (_AXES_AT[j] + 2 * path[None])) & 3
+            near = np.take_along_axis(sign[idx], ax, 1)
+            rank |= (((slot >> (levels - 1 - j)) & 1)[None] ^ near) << (levels - 1 - j)
+        order = np.argsort(rank, 1)                                     # order[:, k]: the slot visited k-th
+        vh, vref = np.take_along_axis(hm, order, 1), np.take_along_axis(ref, order, 1)
+        vref = np.where(vref & 0x80000000, leaf, vref)
+        before = np.cumsum(vh, 1) - vh
+        nxt = np.full(len(idx), none, np.int64)
+        for k in range(width - 1, -1, -1):
+            nxt = np.where(vh[:, k] & (before[:, k] == 0), vref[:, k], nxt)
+        for k in range(width - 1, 0, -1):                               # the last visited lies deepest
+            m = vh[:, k] & (before[:, k] >= 1)
+            put = idx[m]
+            stack[put, sp[put]] = vref[m, k]
+            sp[put] += 1
+        cur[idx] = nxt
+        top = np.maximum(top, sp)
+    return top, first, run, under
+
+
 def primitive_form(variant, name):
     """Strata b - e at primitive level: the rows aimed at a primitive of an identity-frame object as (rays, p0, p1, r0, r1) for the
     segments, (rays, p0, p1, p2) for the triangles, and (rays, boxes) for both: the primitive's box and the shape's."""
@@ -573,6 +765,8 @@ def oracle_hits(variant, yh, oracle, scene_path):
         osc = oracle.scene(sf.desc)
         if variant == "deep":  # (one batch: deep_rays)
             _ORACLE[variant] = (osc.intersect(deep_rays()),)
+        elif variant == "ties":  # (one batch: ties_rays)
+            _ORACLE[variant] = (osc.intersect(ties_rays()),)
         else:
             _ORACLE[variant] = (osc.intersect(main_batch(variant)), osc.intersect(quad_only(variant).rays))
         osc.close(), sf.close()

@@ -42,6 +42,21 @@ def test_library_exports_every_declared_symbol(yh):
     assert b"gfx950" in lib.yh_version()
 
 
+def test_intersect_plain_batch_refuses_an_unknown_form(yh):
+    """yh_intersect_plain_batch has forms 0 .. 6 and, on forms 3 .. 6, the flag YH_INTERSECT_TABLE_IN_MEMORY: everything else is YH_E_INVALID
+    (yh_intersect_plain_form is the batch's own check; the batch on a context: tests/test_hits_unit.py). The binding's numbers are the header's."""
+    lib = yh.load()
+    header = open(os.path.join(ROOT, "include", "yhair.h")).read()
+    assert re.search(rf"#define YH_INTERSECT_FORMS +{yh.INTERSECT_FORMS}\b", header) and yh.INTERSECT_FORMS == 7
+    assert re.search(rf"#define YH_INTERSECT_TABLE_IN_MEMORY +{yh.INTERSECT_TABLE_IN_MEMORY}\b", header) and yh.INTERSECT_TABLE_IN_MEMORY == 16
+    lanes = {0: 4, 1: 8, 2: 4, 3: 8, 4: 8, 5: 16, 6: 16, 16 | 3: 8, 16 | 4: 8, 16 | 5: 16, 16 | 6: 16}
+    for form in list(range(-40, 80)) + [1 << 20, (1 << 20) | 3, -(1 << 31), (1 << 31) - 1]:
+        assert lib.yh_intersect_plain_form(form) == lanes.get(form, yh.YH_E_INVALID), form
+    # ... and the batch itself says so before it looks at anything else it was given
+    for form in (-1, 7, 16, 16 | 2, 16 | 7, 32 | 3):
+        assert lib.yh_intersect_plain_batch(None, form, 0, None, None, None, None, None) == yh.YH_E_INVALID
+
+
 def test_code_object_is_gfx950_only(built):
     so = os.path.join(ROOT, "yocto-hair_amd", "libyhair.so")
     blob = open(so, "rb").read()

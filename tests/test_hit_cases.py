@@ -15,7 +15,7 @@ VARIANTS = ("four", "six", "far")
 
 @pytest.fixture(scope="module")
 def hits(yh, oracle):
-    return {v: hc.oracle_hits(v, yh, oracle, scene_path) for v in VARIANTS + ("deep",)}
+    return {v: hc.oracle_hits(v, yh, oracle, scene_path) for v in VARIANTS + ("deep", "ties")}
 
 
 def _prim_boxes(g):
@@ -138,7 +138,108 @@ def test_the_deep_chain_fills_the_stacks_past_their_windows(hits, yh):
     assert (np.isin(obj, behind) & (first > 16)).sum() >= 500, (behind, np.unique(obj[first > 16], return_counts=True))
 
 
-@pytest.mark.parametrize("variant", VARIANTS + ("deep",))
+def _wide(yh, boxes, width):
+    """yh_bvh_build_wide's nodes over (n, 6) float32 boxes: (nodes, width, 8) float32."""
+    lib, boxes = yh.load(), np.ascontiguousarray(boxes, np.float32)
+    slots = np.zeros((lib.yh_bvh_build_wide(len(boxes), yh.fptr(boxes), width, None), width, 8), np.float32)
+    assert lib.yh_bvh_build_wide(len(boxes), yh.fptr(boxes), width, yh.fptr(slots)) == len(slots)
+    return slots
+
+
+def _wide_depth(slots):
+    """The levels of wide nodes, from the nodes themselves (breadth-first numbering: a node's children lie behind it)."""
+    ref, level = slots.view(np.uint32)[..., 6], np.zeros(len(slots), np.int64)
+    for i in range(len(slots)):
+        for q in ref[i][(ref[i] != 0xFFFFFFFF) & (ref[i] & 0x80000000 == 0)]:
+            level[q] = level[i] + 1
+    return int(level.max()) + 1
+
+
+def _wide_node_of_leaf(slots):
+    """first place of a leaf in the leaf order -> the wide node that holds it in a slot."""
+    ref = slots.view(np.uint32)[..., 6]
+    node, _ = np.nonzero((ref & 0x80000000 != 0) & (ref != 0xFFFFFFFF))
+    return {int(r & 0x07FFFFFF): int(k) for k, r in zip(node, ref[(ref & 0x80000000 != 0) & (ref != 0xFFFFFFFF)])}
+
+
+def _object_space(g, rays):
+    f = g["frame"].astype(np.float64).reshape(4, 3)
+    return (rays[:, 0:3].astype(np.float64) - f[3]) @ np.linalg.inv(f[:3]), rays[:, 3:6].astype(np.float64) @ np.linalg.inv(f[:3])
+
+
+def test_ties_are_shared_across_leaves_and_the_visiting_order_decides(hits, yh):
+    """Variant `ties` before any GPU run. A primitive's twins (make_scenes._hits_ties: the very same record) are tested with the very same
+    arithmetic: a hit on one is a hit on each at the same t as bits, whatever tmax has shrunk to among them (t == tmax is accepted). So a
+    row's closest hit is shared across leaves wherever the winner's twins lie in two or more binary leaves (yh_bvh_build), and across slots
+    of ONE wide node wherever two of those leaves are slots of one 8- or 16-wide node (yh_bvh_build_wide). Who wins is the visiting
+    order's to say: on the rows aimed at the stack at least three copies win, and another one when the ray runs against x."""
+    obj, elem, uv, dist = hits["ties"][0]
+    s, geo = hc.ties(), hc.make_scenes.hits_unit_geometry("ties")
+    cross, same = np.zeros(hc.N, bool), {8: np.zeros(hc.N, bool), 16: np.zeros(hc.N, bool)}
+    for name, k in hc.TIES_OBJECTS.items():
+        g = geo[k]
+        leaf, place = _leaves(yh, _prim_boxes(g))
+        start = {l: int(place[leaf == l].min()) for l in np.unique(leaf)}
+        node_of = {w: _wide_node_of_leaf(_wide(yh, _prim_boxes(g), w)) for w in (8, 16)}
+        print(f"ties {name}: {len(leaf)} primitives in {len(start)} leaves, {len(set(node_of[8].values()))} 8-wide and {len(set(node_of[16].values()))} 16-wide nodes with leaves")
+        for e in np.unique(elem[obj == k]):
+            leaves = np.unique(leaf[g["twin"] == g["twin"][e]])
+            rows = (obj == k) & (elem == e)
+            cross |= rows & (len(leaves) >= 2)
+            for w in (8, 16):
+                nodes = [node_of[w][start[l]] for l in leaves]
+                same[w] |= rows & (len(nodes) > len(set(nodes)))
+    print("ties: rows whose closest hit is shared across leaves", int(cross.sum()), "across slots of one 8-wide node", int(same[8].sum()), "of one 16-wide node", int(same[16].sum()))
+    assert cross.sum() >= 1000 and same[8].sum() >= 256 and same[16].sum() >= 256
+    for name in ("stack", "plates"):
+        k = hc.TIES_OBJECTS[name]
+        rows = (s.object == k) & (obj == k)
+        dx = s.rays[:, 3]
+        won = {sign: np.unique(elem[rows & (dx * sign > 0)], return_counts=True) for sign in (1, -1)}
+        print(f"ties {name}: winners with the ray along +x", dict(zip(*won[1])), "against x", dict(zip(*won[-1])))
+        assert len(np.unique(elem[rows])) >= 3
+        assert won[1][0][won[1][1].argmax()] != won[-1][0][won[-1][1].argmax()]  # the copy that wins most often changes with the sign
+        assert min(won[1][1].max(), won[-1][1].max()) >= 64
+
+
+def test_the_walk_at_widths_8_and_16(hits, yh):
+    """hit_cases.wide_walk_any — the walk at widths 4, 8 and 16 with the rank rules of csrc/dev_trace.h — is the 4-wide walk on `deep`, finds
+    the leaf runs a leaf group looks for on top of the stack (`ties`, stratum g of `four`), and on stratum x of `deep` never stands
+    higher than the shape's part of stack_needs: 7 * depth8 + 2 and 15 * depth16 + 2, the depths from the wide nodes themselves. A
+    column that overruns its entries writes into its neighbour's."""
+    geo = hc.make_scenes.hits_unit_geometry("deep")
+    chain = geo[hc._CHAIN]
+    o, d = _object_space(chain, hc.deep_rays()[:hc.N])
+    top4, first4 = hc.wide_walk(_wide(yh, _prim_boxes(chain), 4), o, d)
+    heights = {}
+    for width, per_level in ((4, 3), (8, 7), (16, 15)):
+        slots = _wide(yh, _prim_boxes(chain), width)
+        top, first, run, under = hc.wide_walk_any(slots, o, d)
+        if width == 4:
+            assert np.array_equal(top, top4) and np.array_equal(first, first4)
+        depth = _wide_depth(slots)
+        heights[width] = (int(top.max()), depth, per_level * depth + 2)
+        assert top.max() <= per_level * depth + 2, heights
+    print("deep: the highest stack, the depth in wide nodes and the bound per width", heights)
+    assert heights[8][0] > 16 and heights[16][0] > 16  # (the wide stacks stand high too)
+    # leaf runs on top of the stack at a ray's first leaf
+    tg, fg = hc.make_scenes.hits_unit_geometry("ties"), hc.make_scenes.hits_unit_geometry("four")
+    batches = [(tg[k], hc.ties().rays[hc.ties().object == k]) for k in hc.TIES_OBJECTS.values()]
+    g = hc.strata("four")["g"]
+    batches.append((fg[0], g.rays[g.object == 0]))
+    for width in (8, 16):
+        runs, unders = [], []
+        for gk, rays in batches:
+            top, first, run, under = hc.wide_walk_any(_wide(yh, _prim_boxes(gk), width), *_object_space(gk, rays))
+            runs.append(run[first >= 0]), unders.append(under[first >= 0])
+        run, under = np.concatenate(runs), np.concatenate(unders)
+        count = {"0": int((run == 0).sum()), "1": int((run == 1).sum()), "2": int((run == 2).sum()), "3+": int((run >= 3).sum()),
+                 "ended by a node": int(((run >= 1) & under).sum()), "ended by the bottom": int(((run >= 1) & ~under).sum())}
+        print(f"width {width}: rays by leaf entries on top of the stack at their first leaf", count)
+        assert min(count.values()) >= 64, (width, count)
+
+
+@pytest.mark.parametrize("variant", VARIANTS + ("deep", "ties"))
 def test_float64_holds_the_oracle(hits, variant):
     """No tree, box or cull of the oracle loses a hit that float64 finds with a margin (hit_f64.compare), and the constants are the
     measured ones: M is the smallest power of two that holds, T twice the largest error on stratum a. The cap that keeps the bar honest:

@@ -6,7 +6,9 @@ lane_pop spill the rest into the overflow array), the quads' LDS stack (YH_QSTAC
 reserves, and that hundreds of them end on an object whose ENTER entry lay beneath all that.
 
 The rays (hit_cases.deep_rays): 8 192 along and near +-x through the chain and 8 192 of stratum a, repeated to the 65 536 of the
-one-lane kernel, as they are through the quad and the plain forms. The bars are tests/test_hits_unit.py's 1 and 3: every row the
+one-lane kernel, as they are through the quad form and the eleven forms of yh_intersect_plain_batch (test_hits_unit.FORMS: the wide
+stacks stand as high here — 30 entries over 8- and 16-wide nodes too, within the 7 * depth8 + 2 and 15 * depth16 + 2 the upload reserves,
+tests/test_hit_cases.py — and a leaf group can sit on top of ENTER entries that went through a long walk). The bars are tests/test_hits_unit.py's 1 and 3: every row the
 oracle's as bits, in order and shuffled, and float64's hit on every row above its margin (tests/hit_f64.py)."""
 import numpy as np
 import pytest

@@ -19,16 +19,25 @@ holds the oracle to the live reference on every one of them.
     h        through one object into another just behind, both ways     the pop-time cull of the once-per-ray scene level
 
 The bars, per variant (four: a scene level of one leaf, the once-per-ray form; six: a scene tree; far: six at 2^12 ... 2^16) and per
-form (yh_intersect_batch's one-lane kernel and, with YHAIR_INTERSECT=quad, its quad kernel; yh_intersect_plain_batch forms 0 and 1):
+form — yh_intersect_batch's one-lane kernel and, with YHAIR_INTERSECT=quad, its quad kernel; yh_intersect_plain_batch forms 0 and 1 (512
+threads), forms 2-6 (the traversal of launch shapes 1, 4, 7, 6 and 8 at their 256 threads: the dense quad, the octet, the octet with
+leaf pairs, the sixteen, the sixteen with leaf groups) and forms 3-6 with the scene level read from memory, as the GENERAL variants of
+those shapes read it: thirteen in all (FORMS):
     1  object, element, uv and distance are the oracle's on every row, as bits — in stratum order and shuffled
     2  the same against the reference's committed rows (tests/golden/hits_unit.npz)
     3  the float64 restatement (tests/hit_f64.py) names the same hit on every row above its margin
-    4  every launch shape renders `four` and `six` to the same bits (the sixteen-lane kernels, leaf pairs and leaf groups)
-What an error of one token in the device's tests does to bar 1: profiles/hits_unit/mutations.txt.
+    4  every launch shape renders `four` and `six` to the same bits
+Variant `ties` (four and shapes whose primitives are there 4 to 64 times over, hit_cases.ties): bit-equal hits in different leaves, in
+different slots of one 8-wide and one 16-wide node, leaf runs of 0, 1, 2 and more entries on top of the stack — what the visiting order
+across slots, the rank arithmetic and the key merge across a group's leaves decide; bars 1-3 through the thirteen forms.
+What an error of one token in the device's tests does to bar 1: profiles/hits_unit/mutations.txt (the sixteen-lane step of the exact
+pass, the leaf-group key and the 16-wide rank among them: each moves rows in the forms that run it and in no other).
 
-What these rows found in the exact second pass, and what was changed for it: DESIGN.md and profiles/hits_unit/exact_pass_ab.txt. The
-sixteen-lane and octet forms of that change are reached by bar 4 alone, whose camera rays never lie on a box face: they are held by
-reading, not by a row here. The stacks past their windows: tests/test_hits_deep.py. Run time on an MI355X: profiles/hits_unit/gpu_time.txt."""
+What these rows found in the exact second pass, and what was changed for it: DESIGN.md and profiles/hits_unit/exact_pass_ab.txt. Its
+sixteen-lane and octet forms, the leaf pairs and the leaf groups are now held row by row (forms 3-6). Still held by bar 4 and by reading
+alone: the once-per-ray scene level under a wide MODE (no launch shape runs it) and the side-by-side kernel's own hand-out. The stacks
+past their windows: tests/test_hits_deep.py. The 4-wide scene level from memory under eight and sixteen lanes: tests/test_instances.py.
+Run time on an MI355X: profiles/hits_unit/gpu_time.txt."""
 import numpy as np
 import pytest
 
@@ -38,7 +47,11 @@ from conftest import golden, scene_path
 
 pytestmark = pytest.mark.gpu
 VARIANTS = ("four", "six", "far")
-FORMS = ("lanes", "quad", "plain-quad", "plain-octet")
+# yh_intersect_plain_batch's form per name: 0 and 1 at 512 threads; 2-6 the traversal of launch shapes 1, 4, 7, 6 and 8 at their 256 threads;
+# mem-*: forms 3-6 with the scene level read from memory (YH_INTERSECT_TABLE_IN_MEMORY = 16), as the GENERAL variants of those shapes read it
+PLAIN = {"plain-quad": 0, "plain-octet": 1, "dense-quad": 2, "octet": 3, "octet-pairs": 4, "sixteen": 5, "sixteen-groups": 6,
+         "mem-octet": 16 | 3, "mem-octet-pairs": 16 | 4, "mem-sixteen": 16 | 5, "mem-sixteen-groups": 16 | 6}
+FORMS = ("lanes", "quad") + tuple(PLAIN)
 FIELDS = ("object", "element", "uv", "distance")
 
 
@@ -56,7 +69,7 @@ def _run(ctx, form, rays, monkeypatch):
         got = ctx.intersect(rays)
         monkeypatch.delenv("YHAIR_INTERSECT")
         return got
-    return ctx.intersect_plain(FORMS.index(form) - 2, rays)
+    return ctx.intersect_plain(PLAIN[form], rays)
 
 
 @pytest.fixture(scope="module")
@@ -144,6 +157,54 @@ def test_rows_with_another_tmin(ctx, uploaded, form, monkeypatch):
     variant, c = uploaded
     _upload(ctx, {variant: c}, variant)
     _same(c["ref_quad"], _run(ctx, form, c["quad"], monkeypatch), lambda r: f"quad-only row {r}", f"{variant}, {form}")
+
+
+@pytest.fixture(scope="module")
+def ties(yh, oracle):
+    """Variant `ties`: the scene, its one batch (hit_cases.ties_rays) and the oracle's hits of it."""
+    sf = yh.SceneFile(scene_path("hits-unit", variant="ties"))
+    rays, ref = hc.ties_rays(), hc.oracle_hits("ties", yh, oracle, scene_path)[0]
+    yield dict(sf=sf, rays=rays, ref=ref, perm=np.random.default_rng(12).permutation(len(rays)))
+    sf.close()
+
+
+@pytest.mark.parametrize("form", FORMS)
+def test_ties_across_leaves_go_to_the_copy_the_oracle_names(ctx, ties, form, monkeypatch):
+    """Variant `ties` — primitives that are there many times over, their copies in different leaves, slots and wide nodes
+    (tests/test_hit_cases.py proves it on the CPU), so that the visiting order across slots and the merge across a group's leaves decide
+    who wins — through every form: bar 1 in order and shuffled, bar 2 on the reference's committed rows, bar 3 (float64 knows the copies
+    of a primitive as one, tests/hit_f64.py). The 8 192 rows are sent eight times over where the one-lane kernel wants 65 536."""
+    if _UPLOADED.get("variant") != "ties":
+        ctx.upload_scene(ties["sf"].desc)
+        _UPLOADED["variant"] = "ties"
+    assert ctx.scene_once() == 0
+    n = len(ties["rays"])
+    rep = 8 if form == "lanes" else 1
+    where = lambda r: hc.where(r % n, hc.TIES_NAMES)  # noqa: E731
+    got = _run(ctx, form, np.tile(ties["rays"], (rep, 1)), monkeypatch)
+    _same([np.concatenate([a] * rep) for a in ties["ref"]], got, where, f"ties, {form}")
+    g = golden("hits_unit.npz")
+    m = len(g["ties_t_rays"])
+    assert np.array_equal(_bits(g["ties_t_rays"]), _bits(ties["rays"][:m]))
+    _same([g[f"ties_t_{f}"] for f in FIELDS], [a[:m] for a in got], lambda r: f"row {r}", f"ties, {form}, committed rows")
+    hit_f64.compare("ties", [a[:n] for a in got], f"the device ({form})")
+    perm = ties["perm"] if rep == 1 else np.random.default_rng(13).permutation(rep * n)
+    shuffled = _run(ctx, form, np.tile(ties["rays"], (rep, 1))[perm], monkeypatch)
+    _same([np.concatenate([a] * rep)[perm] for a in ties["ref"]], shuffled, lambda r: where(perm[r]) + " (shuffled)", f"ties, {form}")
+
+
+def test_an_unknown_form_is_refused(ctx, yh, uploaded):
+    """Every form outside PLAIN is YH_E_INVALID on an uploaded scene, the memory-table flag on forms 0-2 among them; every form of PLAIN answers."""
+    variant, c = uploaded
+    _upload(ctx, {variant: c}, variant)
+    known = set(PLAIN.values())
+    assert yh.INTERSECT_TABLE_IN_MEMORY == 16 and known == set(range(yh.INTERSECT_FORMS)) | {16 | k for k in (3, 4, 5, 6)}
+    for form in list(range(-2, 40)) + [16 | 7, 32 | 3, 48 | 3, 1 << 30]:
+        if form in known:
+            assert len(ctx.intersect_plain(form, c["main"][:4])[0]) == 4
+        else:
+            with pytest.raises(yh.YhError):
+                ctx.intersect_plain(form, c["main"][:4])
 
 
 @pytest.mark.parametrize("variant", ("four", "six"))

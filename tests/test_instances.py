@@ -267,6 +267,49 @@ def test_instanced_closest_hits_bit_exact(ctx, oracle, yh, kw):
     osc.close(), sf.close()
 
 
+def _world_box_face_rays(boxes, rng, m):
+    """m axis-parallel rays that lie ON a face of an object's world box (`boxes`: (n, 6) float32), both ways along either axis of the face: a
+    slab of the box, and of every scene node whose box ends there, is 0 * inf."""
+    k, ax, hi = rng.integers(0, len(boxes), m), rng.integers(0, 3, m), rng.integers(0, 2, m)
+    run = (ax + 1 + rng.integers(0, 2, m)) % 3
+    sign = np.where(rng.integers(0, 2, m) == 1, 1.0, -1.0).astype(np.float32)
+    rows = np.arange(m)
+    lo, up = boxes[k, :3], boxes[k, 3:]
+    o = (lo + (up - lo) * rng.random((m, 3)).astype(np.float32)).astype(np.float32)
+    o[rows, ax] = boxes[k, ax + 3 * hi]                     # on the face, as the float32 the box holds
+    o[rows, run] = np.where(sign > 0, lo[rows, run] - 1, up[rows, run] + 1)  # from outside, towards the box
+    d = np.zeros((m, 3), np.float32)
+    d[rows, run] = sign
+    return np.concatenate([o, d, np.full((m, 1), 1e-4, np.float32), np.full((m, 1), 3.4028235e38, np.float32)], 1).astype(np.float32)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("kw", GPU_KW[1:], ids=GPU_IDS[1:])
+def test_wide_forms_walk_the_scene_level_from_memory(ctx, oracle, yh, kw):
+    """The scene level as 4-wide nodes read from memory under eight and sixteen lanes per ray — every quad of the octet or the sixteen runs
+    the scene node — through the four memory-table forms of yh_intersect_plain_batch (the traversal of the GENERAL variants of launch shapes
+    4, 7, 6 and 8): _field_rays and 512 axis-parallel rays on faces of the objects' world boxes, the oracle's hits bit for bit. The plain
+    forms refuse this scene, whose table does not fit LDS."""
+    sf = yh.SceneFile(scene_path("fur-field", **kw))
+    ctx.upload_scene(sf.desc)
+    rng = np.random.default_rng(17)
+    rays = np.concatenate([_field_rays(kw), _world_box_face_rays(_object_boxes(sf.desc.contents), rng, 512)])
+    osc = oracle.scene(sf.desc)
+    ho = osc.intersect(rays)
+    faces = ho[0][-512:] >= 0
+    print(f"count {kw['count']}: {np.mean(ho[0] >= 0):.3f} of the rays hit, {int(faces.sum())} of the 512 on box faces")
+    assert 0.2 < np.mean(ho[0][:-512] >= 0) < 1.0 and len(np.unique(ho[0])) > kw["count"] // 8 and 16 <= faces.sum() <= 496  # (the rays: hits on many objects, misses, both on the faces)
+    for form in (3, 4, 5, 6):
+        with pytest.raises(yh.YhError):
+            ctx.intersect_plain(form, rays[:4])
+        hg = ctx.intersect_plain(form | yh.INTERSECT_TABLE_IN_MEMORY, rays)
+        for name, a, b in zip(("object", "element", "uv", "distance"), ho, hg):
+            same = (a.view(np.uint32) == b.view(np.uint32)) if a.dtype == np.float32 else (a == b)
+            bad = np.flatnonzero(~same.reshape(len(a), -1).all(1))
+            assert bad.size == 0, f"form {form} from memory: {name} differs on {bad.size} rows, first {bad[0]}: oracle {a[bad[0]]} device {b[bad[0]]}"
+    osc.close(), sf.close()
+
+
 @pytest.mark.gpu
 @pytest.mark.parametrize("exact", [False, True], ids=["fast-bsdf", "exact-bsdf"])
 @pytest.mark.parametrize("kw", GPU_KW, ids=GPU_IDS)

@@ -106,6 +106,19 @@ def test_hits_unit_bit_exact(oracle, yh, variant):
             assert np.array_equal(np.ascontiguousarray(a).view(np.uint32), want.view(np.uint32)), (variant, name, what)
 
 
+def test_hits_unit_ties_bit_exact(oracle, yh):
+    """The same on variant `ties`: the first rows of hit_cases.ties_rays, where who wins among a primitive's copies is the visiting order's."""
+    import hit_cases as hc
+    g = golden("hits_unit.npz")
+    got = hc.oracle_hits("ties", yh, oracle, scene_path)[0]
+    rays = g["ties_t_rays"]
+    n = len(rays)
+    assert n == 512 and np.array_equal(rays.view(np.uint32), hc.ties_rays()[:n].view(np.uint32))
+    assert len(np.unique(g["ties_t_element"][g["ties_t_object"] == hc.TIES_OBJECTS["stack"]])) >= 3  # (more than one copy wins on the committed rows)
+    for what, a in zip(("object", "element", "uv", "distance"), got):
+        assert np.array_equal(np.ascontiguousarray(a[:n]).view(np.uint32), g[f"ties_t_{what}"].view(np.uint32)), what
+
+
 def test_surface_lobes_bit_exact(oracle, yh):
     """Fresnel terms and the nine surface lobes (yocto_math.h:4215-4755)
     — value * |cos|, pdf and sampled direction — against vectors made by the reference."""

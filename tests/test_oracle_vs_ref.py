@@ -107,7 +107,7 @@ def test_material_maps_bit_identical_to_reference(oracle, ref, yh, prefix, kw, r
             assert np.array_equal(got[k], live[k], equal_nan=True), f"{k} differs from the live reference"
 
 
-HITS_VARIANTS = ("four", "six", "far", "deep")
+HITS_VARIANTS = ("four", "six", "far", "deep", "ties")
 
 
 def _same_bits(a, b):
@@ -138,12 +138,12 @@ def test_primitive_tests_on_the_edge_strata(oracle, ref, name):
 @pytest.mark.parametrize("variant", HITS_VARIANTS)
 def test_closest_hits_on_every_stratum(oracle, ref, yh, variant):
     """yo_scene_intersect against the live reference's intersect_scene_bvh on every row of every stratum of tests/hit_cases.py and
-    on the quad-only batch, bit for bit (a NaN uv — an r = 0 tip met exactly — included); on `deep`, on hit_cases.deep_rays."""
+    on the quad-only batch, bit for bit (a NaN uv — an r = 0 tip met exactly — included); on `deep`, on hit_cases.deep_rays; on `ties`, on hit_cases.ties_rays."""
     import hit_cases as hc
     if ref is None:
         pytest.skip("oracle/_ref has not been built")
     rsc = ref.scene(scene_path("hits-unit", variant=variant))
-    batches = (hc.deep_rays(),) if variant == "deep" else (hc.main_batch(variant), hc.quad_only(variant).rays)
+    batches = (hc.deep_rays(),) if variant == "deep" else (hc.ties_rays(),) if variant == "ties" else (hc.main_batch(variant), hc.quad_only(variant).rays)
     for rays, got in zip(batches, hc.oracle_hits(variant, yh, oracle, scene_path)):
         want = rsc.intersect(rays)
         for what, a, b in zip(("object", "element", "uv", "distance"), got, want):

@@ -888,7 +888,7 @@ def make_scene_once(outdir, scale=1.0, name="scene-once", variant="disjoint"):
     return os.path.join(d, name + ".json"), nseg
 
 
-HITS_UNIT_VARIANTS = ("four", "six", "far", "deep")
+HITS_UNIT_VARIANTS = ("four", "six", "far", "deep", "ties")
 HITS_CHAIN_SEGMENTS = 44
 _Q = 1.0 / 1024  # the grid of hits-unit: every coordinate, radius and frame entry is a multiple of 2^-10 below 2^6
 
@@ -949,6 +949,50 @@ def _hits_chain(n=HITS_CHAIN_SEGMENTS):
     return pos, np.repeat(c / 8, 2), [[2 * k, 2 * k + 1] for k in range(n)]
 
 
+def _hits_ties():
+    """The shapes of variant `ties` of hits-unit, on the 2^-10 grid: primitives that are there many times over, so that one ray meets
+    bit-equal hits in different leaves of a shape's tree (identical centroids: the builder halves them by index, split_middle's fall-back,
+    every node's axis x). name -> dict(positions, radius, polylines | triangles, twin, canon): twin[k] = the first primitive with k's very
+    record (same vertices in the same order: the same arithmetic, the same t as bits), canon[k] = the first with k's geometry in any
+    vertex order (the same box, another record).
+      stack    ONE tapering segment along x 64 times, copies 0, 31 and 63 with their ends swapped: 16 leaves of four, one full 16-wide node
+      sheaf    a four-segment strand along z six times, the fourth of them listed from its tip: 24 segments
+      plates   ONE triangle in the plane z = 0 32 times, copies 5, 18 and 31 with their vertices rotated: 8 leaves of four, one full 8-wide node;
+               then a small one below it 8 times, so that the shape's box is larger than the 32's: a ray along z through a lower vertex of the
+               large one lies on a face of the shape's box in x alone, and on faces of the boxes of all 32 in x and y
+      rungs    four sites along y, a segment along x at each, there 4, 8, 9 and 16 times: 1, 2, 3 and 4 leaves"""
+    out = {}
+
+    def lines_shape(name, strands):  # strands: (points, radii, reversed)
+        pos, rad, poly, key = [], [], [], []
+        for pts, rr, rev in strands:
+            idx = list(range(len(pos), len(pos) + len(pts)))
+            pos.extend(pts), rad.extend(rr)
+            poly.append(idx[::-1] if rev else idx)
+            seg = [(tuple(pts[k]), rr[k], tuple(pts[k + 1]), rr[k + 1]) for k in range(len(pts) - 1)]
+            key += [(b, rb, a, ra) for a, ra, b, rb in seg[::-1]] if rev else seg
+        twin = [key.index(k) for k in key]
+        canon = [min(key.index(k) if k in key else len(key), key.index(k[2:] + k[:2]) if k[2:] + k[:2] in key else len(key)) for k in key]
+        out[name] = dict(positions=np.array(pos, np.float64), radius=np.array(rad, np.float64), polylines=poly, twin=np.array(twin), canon=np.array(canon))
+    seg = ([(-0.5, 0.0, 0.0), (0.5, 0.0, 0.0)], [24 * _Q, 16 * _Q])
+    lines_shape("stack", [(*seg, k in (0, 31, 63)) for k in range(64)])
+    strand = ([(0.0, 0.0, -1 + 0.5 * k) for k in range(5)], [20 * _Q, 16 * _Q, 12 * _Q, 8 * _Q, 4 * _Q])
+    lines_shape("sheaf", [(*strand, k == 3) for k in range(6)])
+    lines_shape("rungs", [([(-0.25, y, 0.0), (0.25, y, 0.0)], [16 * _Q, 16 * _Q], False) for y, n in ((-3.0, 4), (-1.0, 8), (1.0, 9), (3.0, 16)) for _ in range(n)])
+    verts, tris, turns = [], [], []
+    for k in range(32):
+        verts += [(-0.5, -0.5, 0.0), (0.5, -0.5, 0.0), (0.0, 0.5, 0.0)]
+        turn = {5: 1, 18: 2, 31: 1}.get(k, 0)
+        tris.append(tuple(3 * k + (j + turn) % 3 for j in range(3))), turns.append(turn)
+    for k in range(32, 40):
+        verts += [(-0.25, -1.5, 0.0), (0.25, -1.5, 0.0), (0.0, -1.0, 0.0)]
+        tris.append((3 * k, 3 * k + 1, 3 * k + 2)), turns.append(3)
+    out["plates"] = dict(positions=np.array(verts, np.float64), radius=np.zeros(len(verts)), triangles=np.array(tris, np.int32),
+                         twin=np.array([turns.index(t) for t in turns]),
+                         canon=np.array([0] * 32 + [32] * 8))
+    return out
+
+
 def hits_unit_geometry(variant="four"):
     """The scene hits-unit as arrays, for the tests that aim rays at it: a list of objects in the scene's object order, each a dict
     of name, shape, frame (12 float32: x, y, z axes and origin), positions (V, 3) and radius (V,) as float32, lines (S, 2) or
@@ -960,6 +1004,10 @@ def hits_unit_geometry(variant="four"):
     shapes = {"strands": dict(positions=sp, radius=sr, lines=np.array([(l[k], l[k + 1]) for l in sl for k in range(len(l) - 1)], np.int32)),
               "tris": dict(positions=tp, radius=np.zeros(len(tp)), triangles=tt),
               "chain": dict(positions=cp, radius=cr, lines=np.array(cl, np.int32))}
+    if variant == "ties":
+        for name, t in _hits_ties().items():
+            prims = dict(triangles=t["triangles"]) if "triangles" in t else dict(lines=np.array([(l[k], l[k + 1]) for l in t["polylines"] for k in range(len(l) - 1)], np.int32))
+            shapes[name] = dict(positions=t["positions"], radius=t["radius"], twin=t["twin"], canon=t["canon"], **prims)
     rot = rotation_frame((1, 2, 3), 40)
     objects = [("a-strands", "strands", IDENT[:9] + [0, 0, 0]),
                ("b-sheared", "strands", [1.5, 0.25, 0, 0, 0.75, 0.5, 0, 0, 1.25, 3, 0, 0]),
@@ -968,6 +1016,9 @@ def hits_unit_geometry(variant="four"):
     if variant in ("six", "far"):
         objects += [("e-mirrored", "strands", [-1, 0, 0, 0, 1, 0, 0, 0, 1, 0, 3, 0]),
                     ("f-tris2", "tris", [2, 0, 0, 0, 2, 0, 0, 0, 0.5, 3, 3.5, 0.5])]
+    if variant == "ties":  # (translations on the grid: object space is world space moved, exactly)
+        objects += [("g-stack", "stack", IDENT[:9] + [0, -4, 0]), ("h-sheaf", "sheaf", IDENT[:9] + [3, -4, 0]),
+                    ("i-plates", "plates", IDENT[:9] + [0, -4, 3]), ("j-rungs", "rungs", IDENT[:9] + [-4, 0, 0])]
     if variant == "deep":  # (first by name: where it shares a leaf of the scene tree, the others are entered after it)
         objects = [("a-chain", "chain", [2.0 ** -19, 0, 0, 0, 2.0 ** -19, 0, 0, 0, 2.0 ** -19, -8, 0, -0.75])] + objects
     out = []
@@ -977,7 +1028,7 @@ def hits_unit_geometry(variant="four"):
             frame[9:] += (65536, -2048, 8192) if name == "f-tris2" else (4096, -2048, 8192)
         sh = shapes[shape]
         out.append(dict(name=name, shape=shape, frame=frame.astype(np.float32), positions=sh["positions"].astype(np.float32),
-                        radius=sh["radius"].astype(np.float32), **{k2: sh[k2] for k2 in ("lines", "triangles") if k2 in sh}))
+                        radius=sh["radius"].astype(np.float32), **{k2: sh[k2] for k2 in ("lines", "triangles", "twin", "canon") if k2 in sh}))
     return out
 
 
@@ -1013,6 +1064,8 @@ def make_hits_unit(outdir, scale=1.0, name="hits-unit", variant="four"):
       deep   a `chain` (_hits_chain, off the grid: powers of two from 2^-21 to 2^24, in a frame that scales them by 2^-19, its small
              end at (-8, 0, -0.75)) and four: a shape tree deep enough that a ray along it fills the traversal stacks past their LDS
              windows, on its way to the objects of `four` behind
+      ties   four and four shapes whose primitives are there many times over (_hits_ties): bit-equal hits in different leaves, slots
+             and wide nodes, so that visiting order and the merge across a group's leaves decide who wins
     Hair and diffuse materials only: the plain kernel variants take the scenes."""
     d = _prep(outdir, name)
     sp, sr, sl = _hits_strands()
@@ -1022,6 +1075,9 @@ def make_hits_unit(outdir, scale=1.0, name="hits-unit", variant="four"):
     if variant == "deep":
         cp, cr, cl = _hits_chain()
         _write_f32_ply(os.path.join(d, "shapes", "chain.ply"), cp, cr, polylines=cl)
+    if variant == "ties":
+        for shape, t in _hits_ties().items():
+            _write_f32_ply(os.path.join(d, "shapes", shape + ".ply"), t["positions"], t["radius"], polylines=t.get("polylines"), triangles=t.get("triangles"))
     geo = hits_unit_geometry(variant)
     objects = {o["name"]: {"frame": [float(v) for v in o["frame"]], "shape": o["shape"],
                            "material": "hair" if o["shape"] != "tris" else "diffuse"} for o in geo}

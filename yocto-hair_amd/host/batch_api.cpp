@@ -334,11 +334,22 @@ int yh_intersect_batch(yh_context* ctx, int n, const float* rays, int* object, i
   return download_hits(ctx, n, dob, del, duv, dd, object, element, uv, distance);
 }
 
-// intersect_scene_bvh through the traversal of the PLAIN 512-thread sample-loop kernels (unit/intersect_quad.hip)
+// The lanes that own a ray in a form of yh_intersect_plain_batch; YH_E_INVALID for a form it does not have
+int yh_intersect_plain_form(int form) {
+  const bool in_memory = form >= 0 && (form & YH_INTERSECT_TABLE_IN_MEMORY) != 0;
+  const int  base      = in_memory ? form & ~YH_INTERSECT_TABLE_IN_MEMORY : form;
+  if (base < 0 || base >= YH_INTERSECT_FORMS || (in_memory && base < 3)) return YH_E_INVALID;
+  return base >= 5 ? 16 : base == 1 || base >= 3 ? 8 : 4;
+}
+
+// intersect_scene_bvh through the traversal of the sample-loop kernels: forms 0 and 1 the PLAIN 512-thread ones (unit/intersect_quad.hip), forms
+// 2-6 the 256-thread launch shapes and, with YH_INTERSECT_TABLE_IN_MEMORY on forms 3-6, their scene level read from memory (unit/intersect_wide.hip)
 int yh_intersect_plain_batch(yh_context* ctx, int form, int n, const float* rays, int* object, int* element, float* uv, float* distance) {
-  if (!ctx || n < 0 || (form != 0 && form != 1) || (n && (!rays || !object || !element || !uv || !distance))) return YH_E_INVALID;
+  const bool in_memory = form >= 0 && (form & YH_INTERSECT_TABLE_IN_MEMORY) != 0;
+  const int  base      = in_memory ? form & ~YH_INTERSECT_TABLE_IN_MEMORY : form;
+  if (!ctx || n < 0 || yh_intersect_plain_form(form) < 0 || (n && (!rays || !object || !element || !uv || !distance))) return YH_E_INVALID;
   if (!ctx->have_scene) return fail(ctx, YH_E_STATE, "yh_intersect_plain_batch before yh_upload_scene");
-  if (ctx->scene.general_materials || ctx->scene.lds_scene_f4 == 0)
+  if (!in_memory && (ctx->scene.general_materials || ctx->scene.lds_scene_f4 == 0))
     return fail(ctx, YH_E_INVALID, "yh_intersect_plain_batch: this scene renders with the GENERAL kernel variants (materials beyond diffuse / hair, a light read through memory, or tables too large for LDS)");
   if (n == 0) return YH_OK;
   HIPCHK(ctx, hipSetDevice(ctx->device));
@@ -349,8 +360,9 @@ int yh_intersect_plain_batch(yh_context* ctx, int form, int n, const float* rays
   auto   duv = (float*)s.out(8 * (size_t)n);
   auto   dd  = (float*)s.out(4 * (size_t)n);
   if (s.rc) return s.rc;
-  int e = yhk_intersect_plain(&ctx->scene, form, n, dr, dob, del, duv, dd, ctx->stream);
-  if (e) return fail(ctx, YH_E_DEVICE, "k_intersect_plain launch: %s", hipGetErrorString((hipError_t)e));
+  int e = base < 2 ? yhk_intersect_plain(&ctx->scene, base, n, dr, dob, del, duv, dd, ctx->stream)
+                   : yhk_intersect_wide(&ctx->scene, base, in_memory ? 1 : 0, n, dr, dob, del, duv, dd, ctx->stream);
+  if (e) return fail(ctx, YH_E_DEVICE, "%s launch: %s", base < 2 ? "k_intersect_plain" : "k_intersect_wide", hipGetErrorString((hipError_t)e));
   YH_WAIT(ctx);
   return download_hits(ctx, n, dob, del, duv, dd, object, element, uv, distance);
 }

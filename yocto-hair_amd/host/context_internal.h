@@ -96,6 +96,7 @@ int yhk_surface_lobe(int, int, const float*, const float*, const float*, const f
 int yhk_surface_bsdf(int, const void*, const float*, const float*, const float*, const float*, float*, hipStream_t);
 int yhk_lights(const yhd_scene*, int, const float*, const float*, const float*, float*, hipStream_t);
 int yhk_intersect_plain(const yhd_scene*, int form, int, const float*, int*, int*, float*, float*, hipStream_t);  // unit/intersect_quad.hip
+int yhk_intersect_wide(const yhd_scene*, int form, int in_memory, int, const float*, int*, int*, float*, float*, hipStream_t);  // unit/intersect_wide.hip
 int yhk_lights_lanes(const yhd_scene* sc, const yhd_scene* sc_dev, int n, const float* position, const float* direction, const float* rn,
     unsigned int* stack_ovf, int ovf_entries, float* out, hipStream_t stream);
 // unit/hair_shade.hip, unit/hair_shade_exact.hip (yh_hair_shade_batch): mats = n rows of yhd_material; form 0 a quad per row, 1 a lane per row (fast only)

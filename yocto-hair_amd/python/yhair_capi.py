@@ -19,6 +19,8 @@ HAIR_SHADE_FLOATS = 15
 SURFACE_BSDF_FLOATS = 29
 VOLUME_FLOATS = 24
 QUAD_FORMS_FLOATS = 12
+INTERSECT_FORMS = 7  # yh_intersect_plain_batch: forms 0 .. 6
+INTERSECT_TABLE_IN_MEMORY = 16  # ... and, on forms 3 .. 6, the scene level read from memory
 # yh_point_batch: the columns of a row (include/yhair.h: YH_POINT_*)
 POINT_FLOATS = 53
 POINT_COLUMNS = {"position": slice(0, 3), "normal": slice(3, 6), "shading_normal": slice(6, 9), "texcoord": slice(9, 11),
@@ -258,6 +260,7 @@ _SIGS = {
                                       c_float_p, c_float_p, c_float_p, c_float_p]),
     "yh_intersect_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_int_p, c_int_p, c_float_p, c_float_p]),
     "yh_intersect_plain_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, c_int_p, c_int_p, c_float_p, c_float_p]),
+    "yh_intersect_plain_form": (C.c_int, [C.c_int]),
     "yh_scene_once": (C.c_int, [C.c_void_p]),
     "yh_lights_const_env": (C.c_int, [C.c_void_p]),
     "yh_shade_regions": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
@@ -863,7 +866,9 @@ class Context:
 
     def intersect_plain(self, form, rays):
         """yh_intersect_plain_batch: closest hits through the traversal of the plain 512-thread sample-loop kernels (form 0: a
-        quad per ray, 1: an octet per ray), the scene level staged in LDS and walked as a launch on this scene walks it."""
+        quad per ray, 1: an octet per ray), the scene level staged in LDS and walked as a launch on this scene walks it; forms 2-6:
+        the traversal of the 256-thread launch shapes (2 the dense quad, 3 octet, 4 octet with leaf pairs, 5 sixteen lanes, 6 sixteen
+        with leaf groups), and form | INTERSECT_TABLE_IN_MEMORY (3-6): their scene level read from memory."""
         rays = np.ascontiguousarray(rays, np.float32).reshape(-1, 8)
         n = len(rays)
         obj, elem = np.zeros(n, np.int32), np.zeros(n, np.int32)
