@@ -557,6 +557,82 @@ int yh_atrous_filter_gpu(yh_context* ctx, int form, int w, int h, const yh_denoi
  * level. Writes min(capacity, 1 + iterations) numbers, returns 1 + iterations of that call (0: none yet).                         */
 int yh_atrous_level_ms(const yh_context* ctx, float* ms, int capacity);
 
+/* TEMPORAL (an extension: the reference has no counterpart; the temporal stage of SVGF, Schied et al. 2017, in front of the filter
+ * above). The render of the previous step is reprojected into the new view through the CENTRE-mode position plane, validated against
+ * ids and positions, and blended with the new render by sample count.
+ * Per pixel p = (i, j) of a W x H image: colour c (float4) with n >= 1 samples in it, id (-1: a miss), world position x. The history:
+ * per pixel an accumulated rgb with an integer length (samples in it, 0: none), id and position; the camera it was made under; per
+ * object the frame at that time and a flag `usable`. dot(a, b) = (a.x b.x + a.y b.y) + a.z b.z throughout.
+ *   1 pass-through     a miss, or a pixel with a channel of c.rgb not finite: out has c's bits, length_out = 0
+ *   2 previous point   y = x when the object's previous frame has the bits of its current frame (12 floats) or no motion is given;
+ *                      else y = transform_point(prev_frame[id], transform_point(inverse(frame[id], non_rigid), x)) as the object
+ *                      rows are made (unit/object_math.h). usable[id] == 0: no history. (An id outside the object list: static.)
+ *   3 projection       into the PREVIOUS camera (frame axes ax, ay, az, origin o), the inverse of the centre-mode ray: d = y - o,
+ *                      lx = dot(d, ax), ly = dot(d, ay), lz = dot(d, az); no history unless lz < 0;
+ *                      u = 0.5 - (lens lx) / (film_x lz), v = 0.5 + (lens ly) / (film_y lz), fx = u W - 0.5, fy = v H - 0.5;
+ *                      no history unless both are finite, -1 < fx < W and -1 < fy < H
+ *   4 taps             when the previous camera's 17 floats have the current camera's bits and step 2 gave y = x by its bit-equal
+ *                      rule: the one tap (i, j) with weight 1 (a still view accumulates without blur). Otherwise i0 = floor(fx),
+ *                      tx = fx - i0, j0 = floor(fy), ty = fy - j0, four taps (i0, j0), (i0 + 1, j0), (i0, j0 + 1), (i0 + 1, j0 + 1)
+ *                      with weights (1 - tx)(1 - ty), tx (1 - ty), (1 - tx) ty, tx ty
+ *   5 tap validity     inside the image; length > 0; its id equals the pixel's where `match_object` is set; its rgb finite;
+ *                      |y - x_q|^2 <= sigma_position^2 (no test when sigma_position <= 0). A tap of weight 0 is not added.
+ *   6 history          one float accumulator per channel and one for the weights, summed in tap order: S = sum w; no history
+ *                      unless S > 0; h = sum w c_q / S; N = min(the smallest length among the added taps, max_history)
+ *   7 blend            a = (float)n / (float)(N + n); out.rgb = h + (c.rgb - h) a; out.a = c.a (alpha is never blended);
+ *                      length_out = N + n. Without a history: out has c's bits and length_out = n.
+ *   8 new history      out.rgb with length_out, the current id and position, the current camera and frames
+ * + - x / and comparisons only (unit/reproject_math.h, one text for host and device), so device, host and a float32 restatement
+ * give the same bits.
+ * The context keeps the history (two float4 planes per pixel, twice over; the camera; the objects' frames; `usable`). It SURVIVES
+ * yh_update_camera, yh_update_objects (an object whose material changed is unusable until the next accumulate), yh_update_shape /
+ * yh_refit_shape and their device forms (the shape's objects are unusable until the next accumulate) and a yh_init_state of the same
+ * image size; it is DROPPED by yh_upload_scene, a yh_init_state of another size, yh_update_materials, yh_update_environments, any
+ * change of the light list, and yh_temporal_reset: the next accumulate then starts afresh.
+ * The entry points change no accumulator, stream, sample count, item cost, trial record or launch shape. Blocking on the context's
+ * stream; yh_last_trace_ms reports the kernels' event time and launch count (the feature pass included where the call runs it).
+ * YH_E_STATE before yh_upload_scene / yh_init_state, with an asynchronous launch pending, for rgba_in NULL with no sample traced, and
+ * for rgba_in NULL on a sharded context (gather first and pass the image). YH_E_INVALID: NULL params, max_history < 1, samples_in < 1
+ * with an image given, guides without the object or the position plane, a device image that is not 16-byte aligned. Every refusal
+ * comes before the first write.                                                                                                    */
+typedef struct yh_temporal_params {
+  int   max_history;    /* in samples: the cap of a history's length before the blend */
+  float sigma_position; /* world units */
+  int   match_object;
+} yh_temporal_params;
+/* The defaults: max_history 4, sigma_position = 0.2 x the diagonal of the uploaded scene's bounds as they are now (0 = off with ctx
+ * NULL or before an upload), match_object 1; settled with yh_reproject on an eight-step orbit (profiles/temporal/quality.txt).       */
+int yh_temporal_default_params(const yh_context* ctx, yh_temporal_params* p);
+/* Everything a DEVICE pointer: rgba_in a float4 image of the state's size with samples_in samples in it (NULL: the context's own
+ * render and its sample count; samples_in is not read); guides NULL: the call traces the centre-mode object and position planes
+ * itself, else those two planes of the struct; rgba_out the accumulated image (may be rgba_in; NULL: the history is only updated). */
+int yh_temporal_accumulate_device(yh_context* ctx, const yh_temporal_params* p, const void* rgba_in, int samples_in, const yh_gbuffer* guides,
+    void* rgba_out);
+/* The same with HOST pointers, staged.                                                                                             */
+int yh_temporal_accumulate(yh_context* ctx, const yh_temporal_params* p, const float* rgba_in, int samples_in, const yh_gbuffer* guides,
+    float* rgba_out);
+/* The context's own render accumulated, then yh_denoise's filter on the accumulated image (dp NULL: no filter) — one feature pass
+ * serves both stages — then the tone map of yh_download_display, as bytes.                                                         */
+int yh_temporal_display(yh_context* ctx, const yh_temporal_params* tp, const yh_denoise_params* dp, float exposure, int filmic, int srgb,
+    uint8_t* rgba8);
+int yh_temporal_reset(yh_context* ctx);
+/* The history's lengths, one int per pixel (lengths may be NULL). Returns the pixel count, 0 without a history, < 0 on an error.   */
+int yh_temporal_lengths(yh_context* ctx, int* lengths);
+/* One step at unit level on the caller's arrays (HOST pointers; w x h pixels): rgba (4 floats per pixel) with `samples` samples,
+ * object, position (3) of the current frame; the history hist_rgba (4 floats per pixel, alpha not read: a previous out_rgba),
+ * hist_length, hist_object, hist_position (hist_length NULL: no history at all, the four are not read); both cameras; frames /
+ * prev_frames: 12 floats per object, num_objects of them, and usable (NULL: all are) — frames NULL: no motion is given.
+ * Writes out_rgba (may be rgba) and out_length; with object and position they are the next step's history.
+ * yh_reproject: the host's form (no GPU, no context). yh_reproject_gpu: the same arrays through the device kernel. Same bits.      */
+int yh_reproject(int w, int h, const yh_temporal_params* p, const float* rgba, int samples, const int* object, const float* position,
+    const float* hist_rgba, const int* hist_length, const int* hist_object, const float* hist_position, const yh_camera* camera,
+    const yh_camera* prev_camera, int num_objects, const float* frames, const float* prev_frames, const int* usable, float* out_rgba,
+    int* out_length);
+int yh_reproject_gpu(yh_context* ctx, int w, int h, const yh_temporal_params* p, const float* rgba, int samples, const int* object,
+    const float* position, const float* hist_rgba, const int* hist_length, const int* hist_object, const float* hist_position,
+    const yh_camera* camera, const yh_camera* prev_camera, int num_objects, const float* frames, const float* prev_frames,
+    const int* usable, float* out_rgba, int* out_length);
+
 /* Work counters of the launches since the last reset (instrumented build of
  * the same kernel; 0 = ok).                                                  */
 int yh_trace_samples_counted(yh_context* ctx, int nsamples, yh_workcounts* out);

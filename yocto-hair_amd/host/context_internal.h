@@ -13,6 +13,8 @@
 //   batch_api.cpp      the unit-level batch entry points (hair BSDF, intersection, BVH build, curves, self-tests)
 //   gbuffer.cpp        yh_trace_gbuffer / _device: the first-hit feature pass over the state's image (unit/gbuffer.hip)
 //   denoise.cpp        yh_denoise and friends: the a-trous filter over the resolved render, guided by that pass (unit/denoise.hip, unit/atrous_math.h)
+//   temporal.cpp       yh_temporal_accumulate and friends: the previous step's render reprojected into the new view and blended by sample
+//                      count, in front of that filter (unit/reproject.hip, unit/reproject_math.h); the history it keeps between steps
 //   scene_edit.cpp     edits of an uploaded scene that keep its geometry: yh_update_camera / _materials / _environments / _objects, and the
 //                      scene level again (the tree over the objects' world boxes, which the shape edits move too)
 //   shape_edit.cpp     one shape's vertices: yh_update_shape / _device (its tree again), yh_refit_shape / _device (that tree's boxes only,
@@ -128,6 +130,14 @@ int yhk_dn_pack(const void* rgba_in, const void* accum, int samples, int width, 
     const float* albedo, void* u, void* g0, void* g1, int plain, hipStream_t);
 int yhk_dn_level(int form, int width, int height, int level, const yh_denoise_params* P, const void* u, const void* g0, const void* g1, const float* albedo,
     int last, void* out, hipStream_t);
+// unit/reproject.hip (yh_temporal_accumulate ...), all pointers DEVICE pointers unless said otherwise, float4 images 16-byte aligned: one step of
+// the temporal stage (rgba_in NULL: accum / samples; have_history 0: the history planes are not read; cam / pcam: 17 floats on the HOST;
+// motion: a yht::Motion of device pointers on the HOST, NULL: none; hc_out / hg_out are not hc_in / hg_in; rgba_out may be NULL), and
+// the lengths of a history plane as ints
+int yhk_reproject(const void* rgba_in, const void* accum, int samples, const int* object, const float* position, int width, int height, const void* hc_in,
+    const void* hg_in, int have_history, const float* cam, const float* pcam, const void* motion, const yh_temporal_params* P, void* hc_out, void* hg_out,
+    void* rgba_out, hipStream_t);
+int yhk_tp_lengths(const void* hc, int width, int height, int* lengths, hipStream_t);
 // unit/objects.hip (yh_update_objects): a lane per row of `rows` (yh_object, device memory); root6 = per shape its root box, 6 floats; writes
 // frame, inv_frame, material and the padded world box into objects[0 .. count) unless NULL, and the world box proper, 6 floats per row, to boxes6
 int yhk_object_rows(int count, const void* rows, const float* root6, void* objects, float* boxes6, hipStream_t);
@@ -305,6 +315,16 @@ struct yh_context {
   int              last_launches = 0;
   float            dn_ms[1 + YH_DENOISE_MAX_ITERATIONS] = {};  // yh_atrous_level_ms: the last yh_atrous_filter_gpu kernel by kernel
   int              dn_ms_count = 0;
+  // the history of the temporal stage (temporal.cpp; include/yhair.h: TEMPORAL): per pixel hc = {rgb, length bits} and hg = {position, id
+  // bits}, twice over — a step reads side `side` and writes the other —, the camera and the objects' frames (12 floats each, copied from
+  // the object rows on the device) it was made under, and per object whether its pixels may be reused (the edits clear it, a step sets it)
+  struct Temporal {
+    bool             have = false;
+    int              width = 0, height = 0, side = 0, num_objects = 0;
+    DevBuf           hc[2], hg[2], d_frames, d_usable;
+    yh_camera        camera{};
+    std::vector<int> usable;
+  } tp;
   int              last_nsamples = 0;   // samples of the launch the item costs come from
   unsigned         launches_of_image = 0;  // synchronous launches since this IMAGE (scene, resolution, sampler, bounces) was first initialised: the re-planning schedule. A
                                            // re-initialised render of a known image is planned already (item_cost survives it) and goes on where the schedule was
@@ -423,6 +443,14 @@ int wait_for_launch(yh_context* ctx);  // hipStreamSynchronize(ctx->stream) with
 int side_by_side_impl(yh_context* ctx, int nsamples, bool sync);
 void destroy_communicators(yh_context* ctx);
 int gbuffer_pass(yh_context* ctx, const char* who, int mode, void* const planes[11]);  // gbuffer.cpp: the feature pass into device planes, for denoise.cpp
+// denoise.cpp, for temporal.cpp: the diagonal of the uploaded scene's bounds (0 without one), and the shipped filter over a device image
+// with the given device planes (those the parameters do not read may be NULL)
+float scene_diagonal(const yh_context* ctx);
+int denoise_with_planes(yh_context* ctx, const char* who, const yh_denoise_params& P, const void* d_in, const int* object, const float* normal,
+    const float* position, const float* albedo, void* d_out);
+// temporal.cpp, for the edits: the history is dropped; one object's pixels are not to be reused by the next step
+void temporal_drop(yh_context* ctx);
+void temporal_mark_object(yh_context* ctx, int object);
 inline int tiles_of(int n) { return (n + YH_TILE - 1) / YH_TILE; }
 void make_material(const yh_material& m, yhd_material& d);  // scene_upload.cpp
 // scene_upload.cpp, shared with the edits: the device rows of `count` materials (`maps` / `dmaps`: theirs, or NULL in a scene without effective

@@ -122,17 +122,26 @@ int denoise_on_device(yh_context* ctx, const char* who, const yh_denoise_params&
 bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 }  // namespace
 
+float scene_diagonal(const yh_context* ctx) {  // of the union of the objects' world boxes
+  if (!ctx || !ctx->have_scene || ctx->h_obj_boxes.empty()) return 0.0f;
+  float lo[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, hi[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
+  for (const yhh::Box& b : ctx->h_obj_boxes)
+    for (int k = 0; k < 3; k++) lo[k] = std::min(lo[k], b.min[k]), hi[k] = std::max(hi[k], b.max[k]);
+  double d2 = 0;
+  for (int k = 0; k < 3; k++) d2 += ((double)hi[k] - lo[k]) * ((double)hi[k] - lo[k]);
+  return (float)std::sqrt(d2);
+}
+
+int denoise_with_planes(yh_context* ctx, const char* who, const yh_denoise_params& P, const void* d_in, const int* object, const float* normal,
+    const float* position, const float* albedo, void* d_out) {
+  const Guides g = P.iterations > 0 ? needed_of(P, Guides{object, normal, position, albedo}) : Guides{};
+  return run_filter(ctx, who, SHIPPED_FORM, ctx->state.width, ctx->state.height, P, d_in, g, d_out, false);
+}
+
 int yh_denoise_default_params(const yh_context* ctx, yh_denoise_params* p) {
   if (!p) return YH_E_INVALID;
   *p = yh_denoise_params{5, 4.0f, 0.5f, 0.0f, 1, 1};
-  if (ctx && ctx->have_scene && !ctx->h_obj_boxes.empty()) {  // the diagonal of the union of the objects' world boxes
-    float lo[3] = {3.402823466e+38f, 3.402823466e+38f, 3.402823466e+38f}, hi[3] = {-3.402823466e+38f, -3.402823466e+38f, -3.402823466e+38f};
-    for (const yhh::Box& b : ctx->h_obj_boxes)
-      for (int k = 0; k < 3; k++) lo[k] = std::min(lo[k], b.min[k]), hi[k] = std::max(hi[k], b.max[k]);
-    double d2 = 0;
-    for (int k = 0; k < 3; k++) d2 += ((double)hi[k] - lo[k]) * ((double)hi[k] - lo[k]);
-    p->sigma_position = 0.05f * (float)std::sqrt(d2);
-  }
+  if (ctx && ctx->have_scene && !ctx->h_obj_boxes.empty()) p->sigma_position = 0.05f * scene_diagonal(ctx);
   return YH_OK;
 }
 

@@ -86,6 +86,7 @@ int commit_lights(yh_context* ctx, const char* entry, LightStage& S) {
     if (e) return fail(ctx, YH_E_DEVICE, "%s: coarse index of the environment cdf: %s", entry, hipGetErrorString((hipError_t)e));
   }
   ctx->d_light_cdf.swap(S.d_cdf), ctx->d_light_table.swap(S.d_table), ctx->d_env_tab.swap(S.d_tab);
+  temporal_drop(ctx);  // (another light list: the temporal history shows another lighting)
   set_light_fields(ctx, ctx->scene, L);  // (settle_scene_variant reads them: the caller runs that next)
   return YH_OK;
 }

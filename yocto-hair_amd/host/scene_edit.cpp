@@ -95,6 +95,7 @@ int yh_update_materials(yh_context* ctx, int first, int count, const yh_material
   if (mapped) ctx->h_dmaps.swap(dmaps);
   settle_scene_variant(ctx, ctx->scene, general_rows);
   ctx->have_scene = true;
+  temporal_drop(ctx);  // (other materials: the temporal history shows another lighting)
   edit_end(ctx);
   return YH_OK;
 }
@@ -131,6 +132,7 @@ int yh_update_environments(yh_context* ctx, int count, const yh_environment* env
     memcpy(d.emission, environments[i].emission, 12);
     memcpy(ctx->key_envs.data() + head * (size_t)i, &environments[i], edited);
   }
+  temporal_drop(ctx);
   edit_end(ctx);
   return YH_OK;
 }
@@ -228,6 +230,8 @@ int yh_update_objects(yh_context* ctx, int first, int count, const yh_object* ob
   if (lights_change)
     if (int rc = commit_lights(ctx, "yh_update_objects", LS)) return rc;
   YH_WAIT(ctx);
+  for (int i = 0; i < count; i++)  // (an object with another material: its pixels of the temporal history are not reused)
+    if (objects[i].material != rows[(size_t)first + i].material || lights_change) temporal_mark_object(ctx, first + i);
   if (count > 0) memcpy(ctx->key_geometry.data() + sizeof(yh_object) * (size_t)first, objects, sizeof(yh_object) * (size_t)count);
   ctx->h_obj_boxes.swap(boxes);
   settle_scene_level(ctx, S);

@@ -458,6 +458,7 @@ static int check_upload(yh_context* ctx, const yh_scene_desc* sd, const yh_mater
 // The one place that drops the previous scene: from here on its device arrays are being replaced.
 static void drop_previous_scene(yh_context* ctx) {
   ctx->have_scene = false, ctx->have_state = false;
+  temporal_drop(ctx);  // (another scene's history)
   ctx->scene.lane_blob = nullptr, ctx->scene.prims = nullptr;
   ctx->d_prims.reset(), ctx->d_lane_blob.reset();  // (nothing of this context is running: waited for above)
   for (DevBuf& kept : ctx->d_env_cdf) kept.reset();  // (the texel cdfs a light edit kept: another scene's)

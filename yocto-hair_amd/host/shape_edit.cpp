@@ -264,6 +264,8 @@ static int update_shape(yh_context* ctx, const char* entry, int shape, const yh_
   ctx->max_shape_depth = deepest.depth4, ctx->max_shape_depth8 = deepest.depth8, ctx->max_shape_depth16 = deepest.depth16;
   settle_scene_level(ctx, S);
   ctx->have_scene = true;
+  for (size_t o = 0; o < rows.size(); o++)  // (the shape's objects: their pixels of the temporal history are not reused)
+    if (rows[o].shape == shape) temporal_mark_object(ctx, (int)o);
   edit_end(ctx);
   return YH_OK;
 }
@@ -342,6 +344,8 @@ static int refit_shape(yh_context* ctx, const char* entry, int shape, const yh_s
   ctx->h_obj_boxes.swap(boxes);
   settle_scene_level(ctx, S);
   ctx->have_scene = true;
+  for (size_t o = 0; o < rows.size(); o++)  // (the shape's objects: their pixels of the temporal history are not reused)
+    if (rows[o].shape == shape) temporal_mark_object(ctx, (int)o);
   edit_end(ctx);
   return YH_OK;
 }

@@ -65,6 +65,7 @@ int yh_init_state(yh_context* ctx, const yh_trace_params* params) {
     h = params->resolution;
   }
   if (w <= 0 || h <= 0) return fail(ctx, YH_E_INVALID, "empty image");
+  if (ctx->tp.have && (ctx->tp.width != w || ctx->tp.height != h)) temporal_drop(ctx);  // (the temporal history is another image's)
   size_t npix = (size_t)w * h;
   // per-pixel streams (pt.cpp:1942-1945), pixel order j * W + i
   std::vector<uint64_t> st(npix), inc(npix);

@@ -704,5 +704,30 @@ inline image<vec4f> denoise_image(state* st, const scene*, const camera*, const 
   detail::check(yh_denoise(ctx, &dparams, (const float*)st->render.data(), (float*)out.pixels.data()), ctx);
   return out;
 }
+
+// EXTENSION (no reference counterpart; off unless called): the image of `st` accumulated over the steps of an interactive loop
+// (include/yhair.h: TEMPORAL) — the previous call's result reprojected into this view through the centre-mode position plane and blended
+// with the state's image by sample count; with `dparams` the accumulated image is then denoised as denoise_image denoises. Context 0
+// keeps the history: it survives the camera, object and shape edits init_state passes on and a state of the same size, and starts
+// afresh after an upload, a state of another size or a change of the lighting. The state needs at least one sample; its samples and
+// `render` keep what a download gives them. default_temporal_params: the library's defaults for the uploaded scene (call after init_state).
+using temporal_params = yh_temporal_params;
+inline temporal_params default_temporal_params() {
+  temporal_params p;
+  detail::check(yh_temporal_default_params(detail::require_context(), &p));
+  return p;
+}
+inline image<vec4f> accumulate_image(state* st, const scene*, const camera*, const trace_params&, const temporal_params& tparams,
+    const denoise_params* dparams = nullptr) {
+  bind_state(st);
+  download(st);
+  image<vec4f> out;
+  out.width = st->width, out.height = st->height, out.pixels.resize((size_t)st->width * st->height);
+  auto ctx = detail::require_context();
+  detail::check(yh_temporal_accumulate(ctx, &tparams, (const float*)st->render.data(), st->samples, nullptr, (float*)out.pixels.data()), ctx);
+  if (dparams) detail::check(yh_denoise(ctx, dparams, (const float*)out.pixels.data(), (float*)out.pixels.data()), ctx);
+  return out;
+}
+inline void reset_accumulation() { detail::check(yh_temporal_reset(detail::require_context())); }
 }  // namespace yhair::pathtrace
 #endif

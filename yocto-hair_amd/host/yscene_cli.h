@@ -170,4 +170,20 @@ inline void save_denoised(ptr::state* state, const ptr::scene* scene, const ptr:
   if (yh_save_image(name.c_str(), img.width, img.height, (const float*)img.pixels.data(), error, sizeof(error)) != YH_OK) print_fatal(error);
   printf("save denoised: %s\n", name.c_str());
 }
+// "--temporal FILE" (an extension of ysceneitraces --turntable): every step's finished render is accumulated over the steps
+// (ptr::accumulate_image with the library's default parameters, on context 0 whatever --gpus says); at the last step the accumulated
+// image is written to `name` and, with --denoise FILE given too, denoised (the library's defaults) to `denoised_name`
+inline void accumulate_step(ptr::state* state, const ptr::scene* scene, const ptr::camera* camera, const ptr::trace_params& params, const std::string& name,
+    const std::string& denoised_name, bool last) {
+  auto img = ptr::accumulate_image(state, scene, camera, params, ptr::default_temporal_params());
+  if (!last) return;
+  char error[512];
+  if (yh_save_image(name.c_str(), img.width, img.height, (const float*)img.pixels.data(), error, sizeof(error)) != YH_OK) print_fatal(error);
+  printf("save accumulated: %s\n", name.c_str());
+  if (denoised_name.empty()) return;
+  const auto dp = ptr::default_denoise_params();
+  if (yh_denoise(yhair::detail::context(), &dp, (const float*)img.pixels.data(), (float*)img.pixels.data()) != YH_OK) print_fatal("yh_denoise of the accumulated image failed");
+  if (yh_save_image(denoised_name.c_str(), img.width, img.height, (const float*)img.pixels.data(), error, sizeof(error)) != YH_OK) print_fatal(error);
+  printf("save accumulated and denoised: %s\n", denoised_name.c_str());
+}
 #endif

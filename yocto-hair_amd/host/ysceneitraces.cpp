@@ -53,7 +53,7 @@ static void update_turntable(frame3f& frame, float& focus, const vec2f& rotate) 
 
 int main(int argc, const char* argv[]) {
   auto        params = ptr::trace_params{};
-  std::string camera_name, imagename = "out.hdr", preview_name, filename, shader = "path", features, features_mode_name = "centre", denoise;
+  std::string camera_name, imagename = "out.hdr", preview_name, filename, shader = "path", features, features_mode_name = "centre", denoise, temporal;
   int         stop_after_ms = -1, gpus = 1, first_device = 0, turntable = 0;
   bool        turn_objects = false, sway_refit = false;
   int         sway = 0;
@@ -68,7 +68,8 @@ int main(int argc, const char* argv[]) {
       printf("usage: ysceneitraces [--camera NAME] [--resolution,-r N] [--samples,-s N] [--shader,-t naive|path|eyelight|normal]\n"
              "                     [--bounces,-b N] [--clamp F] [--output,-o FILE] [--pratio N] [--preview-image FILE]\n"
              "                     [--stop-after-ms N] [--seed N] [--device N] [--gpus N] [--devices A,B,..] [--turntable STEPS [--turntable-objects]]\n"
-             "                     [--sway STEPS [--sway-refit]] [--features PREFIX] [--features-mode centre|next] [--denoise FILE] scene\n"
+             "                     [--sway STEPS [--sway-refit]] [--features PREFIX] [--features-mode centre|next] [--denoise FILE]\n"
+             "                     [--temporal FILE] scene\n"
              "Progressive path tracing of hair scenes on MI355X (headless: preview pass, then samples until done or stopped)\n");
       return 0;
     } else if (a == "--camera") camera_name = next();
@@ -92,6 +93,7 @@ int main(int argc, const char* argv[]) {
     else if (a == "--features") features = next();
     else if (a == "--features-mode") features_mode_name = next();
     else if (a == "--denoise") denoise = next();
+    else if (a == "--temporal") temporal = next();
     else if (!a.empty() && a[0] == '-') print_fatal("unknown option " + a);
     else filename = a;
   }
@@ -99,6 +101,8 @@ int main(int argc, const char* argv[]) {
   if (turn_objects && turntable <= 0) print_fatal("--turntable-objects needs --turntable STEPS");
   if (sway_refit && sway <= 0) print_fatal("--sway-refit needs --sway STEPS");
   if (sway > 0 && turntable > 0) print_fatal("--sway and --turntable are gestures of their own");
+  if (!temporal.empty() && turntable <= 0) print_fatal("--temporal needs --turntable STEPS");
+  if (!temporal.empty()) params.pratio = 1;  // (the history lives at one image size: the preview pass has the render's)
   yh_set_trial_cache_dir(yh_default_trial_cache_dir());  // the command line keeps its kernel-trial record on disk (include/yhair.h); a library caller has to ask
   set_devices(first_device, gpus, device_list);
   bool known = false;
@@ -119,7 +123,7 @@ int main(int argc, const char* argv[]) {
 
     // ---- reset_display (ysceneitraces.cpp:255-300) -------------------------------------------------------
     std::chrono::steady_clock::time_point t_edit;  // --turntable: when the camera was moved
-    auto reset_display = [&](const std::string& imagename, bool orbit) {
+    auto reset_display = [&](const std::string& imagename, bool orbit, bool last = true) {
     const int uploads0 = scene->uploads;
     auto render_state = std::make_unique<ptr::state>();
     ptr::init_state(render_state.get(), scene.get(), camera, params);
@@ -148,7 +152,7 @@ int main(int argc, const char* argv[]) {
           scene->uploads > uploads0 ? "the scene was uploaded again" : turn_objects ? "the objects alone were passed on" : "the camera alone was passed on");
     if (!preview_name.empty() && yh_save_image(preview_name.c_str(), W, H, (const float*)render.data(), error, sizeof(error)) != YH_OK)
       print_fatal(error);
-    if (!denoise.empty()) save_denoised(pstate.get(), scene.get(), camera, pprms, denoise);  // (yscene_cli.h: the 1-spp preview denoised, at the preview's resolution)
+    if (!denoise.empty() && temporal.empty()) save_denoised(pstate.get(), scene.get(), camera, pprms, denoise);  // (yscene_cli.h: the 1-spp preview denoised, at the preview's resolution)
     if (!features.empty()) save_features(render_state.get(), scene.get(), camera, params, features, feature_mode);  // (yscene_cli.h; binds the render state again)
     // start render
     std::atomic<bool> render_stop{false};
@@ -171,6 +175,9 @@ int main(int argc, const char* argv[]) {
     printf("render: %d of %d samples in %.3fs%s\n", (int)render_counter, params.samples, dt, render_stop ? " (stopped)" : "");
     if (yh_save_image(imagename.c_str(), W, H, (const float*)render.data(), error, sizeof(error)) != YH_OK) print_fatal(error);
     printf("save image: %s\n", imagename.c_str());
+    // --temporal FILE: this step's finished render joins the steps before it (yscene_cli.h: accumulate_step); the last step's accumulated
+    // image is written, and with --denoise FILE that file holds it denoised
+    if (!temporal.empty() && render_state->samples > 0) accumulate_step(render_state.get(), scene.get(), camera, params, temporal, denoise, last);
     };
     if (sway > 0) {  // the vertex edit's gesture: step k displaces the first line shape by x += a_k y^2, a_k = 0.1 k / STEPS, tangents recomputed
       const size_t slash = imagename.find_last_of('/'), dot = imagename.find_last_of('.');
@@ -230,7 +237,7 @@ int main(int argc, const char* argv[]) {
         }
         char number[16];
         snprintf(number, sizeof(number), "-%03d", k);
-        reset_display(stem + number + suffix, k > 0);
+        reset_display(stem + number + suffix, k > 0, k == turntable - 1);
       }
     }
   } catch (const std::exception& e) {

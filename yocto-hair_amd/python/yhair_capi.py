@@ -124,6 +124,17 @@ class DenoiseParams(C.Structure):
         return q
 
 
+class TemporalParams(C.Structure):
+    """yh_temporal_params (include/yhair.h: TEMPORAL)."""
+    _fields_ = [("max_history", C.c_int), ("sigma_position", C.c_float), ("match_object", C.c_int)]
+
+    def copy(self, **changes):
+        q = TemporalParams.from_buffer_copy(self)
+        for k, v in changes.items():
+            setattr(q, k, v)
+        return q
+
+
 class WorkCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "nodes", "seg_tests", "tri_tests",
                                           "hair_shades", "surf_shades", "env_lookups",
@@ -229,6 +240,16 @@ _SIGS = {
     "yh_atrous_filter_gpu": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(DenoiseParams), c_float_p, c_int_p, c_float_p, c_float_p,
                                        c_float_p, c_float_p]),
     "yh_atrous_level_ms": (C.c_int, [C.c_void_p, c_float_p, C.c_int]),
+    "yh_temporal_default_params": (C.c_int, [C.c_void_p, C.POINTER(TemporalParams)]),
+    "yh_temporal_accumulate_device": (C.c_int, [C.c_void_p, C.POINTER(TemporalParams), C.c_void_p, C.c_int, C.POINTER(GBuffer), C.c_void_p]),
+    "yh_temporal_accumulate": (C.c_int, [C.c_void_p, C.POINTER(TemporalParams), c_float_p, C.c_int, C.POINTER(GBuffer), c_float_p]),
+    "yh_temporal_display": (C.c_int, [C.c_void_p, C.POINTER(TemporalParams), C.POINTER(DenoiseParams), C.c_float, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
+    "yh_temporal_reset": (C.c_int, [C.c_void_p]),
+    "yh_temporal_lengths": (C.c_int, [C.c_void_p, c_int_p]),
+    "yh_reproject": (C.c_int, [C.c_int, C.c_int, C.POINTER(TemporalParams), c_float_p, C.c_int, c_int_p, c_float_p, c_float_p, c_int_p, c_int_p, c_float_p,
+                               C.POINTER(Camera), C.POINTER(Camera), C.c_int, c_float_p, c_float_p, c_int_p, c_float_p, c_int_p]),
+    "yh_reproject_gpu": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(TemporalParams), c_float_p, C.c_int, c_int_p, c_float_p, c_float_p, c_int_p, c_int_p,
+                                   c_float_p, C.POINTER(Camera), C.POINTER(Camera), C.c_int, c_float_p, c_float_p, c_int_p, c_float_p, c_int_p]),
     "yh_trace_samples_counted": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(WorkCounts)]),
     "yh_last_trace_ms": (C.c_int, [C.c_void_p, c_float_p, c_int_p]),
     "yh_launch_shape": (C.c_int, [C.c_void_p]),
@@ -364,6 +385,62 @@ def atrous_filter(params, rgba, object, normal=None, position=None, albedo=None)
     if rc != YH_OK:
         raise YhError(f"yhair error {rc}: yh_atrous_filter")
     return out
+
+
+def temporal_default_params(ctx=None):
+    """yh_temporal_default_params: the defaults, sigma_position from the scene `ctx` (a Context) has uploaded, 0 without one."""
+    p = TemporalParams()
+    rc = load().yh_temporal_default_params(ctx.h if ctx is not None else None, C.byref(p))
+    if rc != YH_OK:
+        raise YhError(f"yhair error {rc}: yh_temporal_default_params")
+    return p
+
+
+def camera_of(floats17):
+    """A Camera from the 17 floats frame (12), lens, film (2), focus, aperture."""
+    a = np.ascontiguousarray(floats17, np.float32).reshape(17)
+    return Camera.from_buffer_copy(a.tobytes())
+
+
+def _reproject_args(rgba, samples, object, position, history, camera, prev_camera, frames, prev_frames, usable):
+    """The arguments of yh_reproject after (w, h, params): history = None or (rgba, length, object, position) of the previous step;
+    cameras = Camera or 17 floats; frames / prev_frames (n, 12) or None; usable (n,) or None."""
+    rgba = np.ascontiguousarray(rgba, np.float32)
+    h, w = rgba.shape[:2]
+    object, position = np.ascontiguousarray(object, np.int32), np.ascontiguousarray(position, np.float32)
+    assert rgba.shape == (h, w, 4) and object.shape == (h, w) and position.shape == (h, w, 3)
+    held = [rgba, object, position]
+    hist = [None] * 4
+    if history is not None:
+        hr, hl, ho, hp = history
+        hist = [np.ascontiguousarray(hr, np.float32), np.ascontiguousarray(hl, np.int32), np.ascontiguousarray(ho, np.int32), np.ascontiguousarray(hp, np.float32)]
+        assert hist[0].shape == (h, w, 4) and hist[1].shape == (h, w) and hist[2].shape == (h, w) and hist[3].shape == (h, w, 3)
+    cams = [c if isinstance(c, Camera) or c is None else camera_of(c) for c in (camera, prev_camera)]
+    n = 0
+    fr = [None, None]
+    if frames is not None:
+        prev_frames = prev_frames if prev_frames is not None else frames  # (without a history they are not read)
+        fr = [np.ascontiguousarray(frames, np.float32).reshape(-1, 12), np.ascontiguousarray(prev_frames, np.float32).reshape(-1, 12)]
+        n = len(fr[0])
+        assert fr[1].shape == fr[0].shape
+    use = np.ascontiguousarray(usable, np.int32) if usable is not None else None
+    assert use is None or use.shape == (n,)
+    held += hist + cams + fr + [use]
+    out, length = np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.int32)
+    opt = lambda a, f: f(a) if a is not None else None  # noqa: E731
+    args = [fptr(rgba), int(samples), iptr(object), fptr(position), opt(hist[0], fptr), opt(hist[1], iptr), opt(hist[2], iptr), opt(hist[3], fptr),
+            opt(cams[0], C.byref), opt(cams[1], C.byref), n, opt(fr[0], fptr), opt(fr[1], fptr), opt(use, iptr), fptr(out), iptr(length)]
+    return w, h, held, args, out, length
+
+
+def reproject(params, rgba, samples, object, position, history, camera, prev_camera=None, frames=None, prev_frames=None, usable=None):
+    """yh_reproject (host, no GPU): one step of the temporal stage; returns (out_rgba, out_length), which with `object` and `position`
+    are the next step's `history`."""
+    w, h, held, args, out, length = _reproject_args(rgba, samples, object, position, history, camera, prev_camera, frames, prev_frames, usable)
+    rc = load().yh_reproject(w, h, C.byref(params) if params is not None else None, *args)
+    if rc != YH_OK:
+        raise YhError(f"yhair error {rc}: yh_reproject")
+    return out, length
 
 
 def set_trial_cache_dir(path=None, default=False):
@@ -731,6 +808,87 @@ class Context:
         ms = (C.c_float * (1 + DENOISE_MAX_ITERATIONS))()
         n = self.lib.yh_atrous_level_ms(self.h, ms, len(ms))
         return [float(ms[k]) for k in range(max(n, 0))]
+
+    # the temporal stage (include/yhair.h: TEMPORAL)
+    def temporal_default_params(self):
+        return temporal_default_params(self)
+
+    def _host_guides(self, object, position):
+        if object is None and position is None:
+            return None, []
+        g, held = GBuffer(), []
+        if object is not None:
+            held.append(np.ascontiguousarray(object, np.int32))
+            g.object = iptr(held[-1])
+        if position is not None:
+            held.append(np.ascontiguousarray(position, np.float32))
+            g.position = fptr(held[-1])
+        return g, held
+
+    def temporal_accumulate(self, params=None, rgba=None, samples=0, object=None, position=None, want_image=True):
+        """yh_temporal_accumulate: the (H, W, 4) image `rgba` with `samples` samples in it (None: the context's own render) blended
+        with the reprojected history; object / position: centre-mode planes (neither: traced by the call). Returns the accumulated
+        image, or None with want_image False (the history is only updated). params None: the defaults."""
+        params = params if params is not None else self.temporal_default_params()
+        rgba = np.ascontiguousarray(rgba, np.float32) if rgba is not None else None
+        out = np.zeros((getattr(self, "height", 0), getattr(self, "width", 0), 4), np.float32) if want_image else None
+        assert rgba is None or out is None or rgba.shape == out.shape
+        g, held = self._host_guides(object, position)
+        self._chk(self.lib.yh_temporal_accumulate(self.h, C.byref(params), fptr(rgba) if rgba is not None else None, int(samples),
+                                                  C.byref(g) if g is not None else None, fptr(out) if out is not None else None))
+        return out
+
+    def temporal_accumulate_device(self, params, rgba_out=None, rgba_in=None, samples=0, object=None, position=None):
+        """yh_temporal_accumulate_device: contiguous torch tensors on the context's device, float32 (H, W, 4) images (rgba_in None: the
+        own render; rgba_out None: the history is only updated), int32 (H, W) object and float32 (H, W, 3) position as
+        trace_gbuffer_device fills them (neither: traced by the call). The current torch stream is synchronised before the call."""
+        import torch
+        npix = self.height * self.width
+
+        def ptr(t, dtype, comps, what):
+            if t is None:
+                return None
+            if not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.numel() < npix * comps:
+                raise YhError(f"temporal_accumulate_device: {what} must be a contiguous {dtype} tensor on the GPU of at least {self.height} x {self.width} x {comps} elements")
+            return t.data_ptr()
+        out_p, in_p = ptr(rgba_out, torch.float32, 4, "rgba_out"), ptr(rgba_in, torch.float32, 4, "rgba_in")
+        g = None
+        if object is not None or position is not None:
+            g = GBuffer()
+            if object is not None:
+                g.object = C.cast(ptr(object, torch.int32, 1, "object"), c_int_p)
+            if position is not None:
+                g.position = C.cast(ptr(position, torch.float32, 3, "position"), c_float_p)
+        torch.cuda.synchronize()
+        self._chk(self.lib.yh_temporal_accumulate_device(self.h, C.byref(params), in_p, int(samples), C.byref(g) if g is not None else None, out_p))
+
+    def temporal_display(self, params=None, denoise_params=None, exposure=0.0, filmic=False, srgb=True):
+        """yh_temporal_display: the own render accumulated, filtered with `denoise_params` (None: no filter) and tone-mapped on the
+        device, as (H, W, 4) bytes."""
+        params = params if params is not None else self.temporal_default_params()
+        img = np.zeros((getattr(self, "height", 0), getattr(self, "width", 0), 4), np.uint8)
+        self._chk(self.lib.yh_temporal_display(self.h, C.byref(params), C.byref(denoise_params) if denoise_params is not None else None, exposure,
+                                               int(filmic), int(srgb), img.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return img
+
+    def temporal_reset(self):
+        self._chk(self.lib.yh_temporal_reset(self.h))
+
+    def temporal_lengths(self):
+        """yh_temporal_lengths: the history's lengths as an (H, W) int32 array, or None without a history."""
+        n = self.lib.yh_temporal_lengths(self.h, None)
+        self._chk(min(n, 0))
+        if n == 0:
+            return None
+        out = np.zeros(n, np.int32)
+        self._chk(min(self.lib.yh_temporal_lengths(self.h, iptr(out)), 0))
+        return out.reshape(self.height, self.width) if n == getattr(self, "height", 0) * getattr(self, "width", 0) else out
+
+    def reproject_gpu(self, params, rgba, samples, object, position, history, camera, prev_camera=None, frames=None, prev_frames=None, usable=None):
+        """yh_reproject_gpu: reproject's arrays through the device kernel."""
+        w, h, held, args, out, length = _reproject_args(rgba, samples, object, position, history, camera, prev_camera, frames, prev_frames, usable)
+        self._chk(self.lib.yh_reproject_gpu(self.h, w, h, C.byref(params) if params is not None else None, *args))
+        return out, length
 
     def shard_pixels(self, rank, world):
         return int(self.lib.yh_shard_pixels(self.h, rank, world))
