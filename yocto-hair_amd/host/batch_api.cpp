@@ -1,24 +1,9 @@
 // batch_api.cpp — the unit-level batch entry points of include/yhair.h (hair BSDF, intersection, BVH build, curves, self-tests).
 #include "edit_internal.h"
+#include "image_pass.h"  // Staged; the refusal of a scene beyond the one-lane kernels' offsets
 
 // ---- unit-level batches ----------------------------------------------------
 namespace {
-struct Staged {
-  std::vector<DevBuf> bufs;
-  yh_context*         ctx;
-  int                 rc = YH_OK;
-  explicit Staged(yh_context* c) : ctx(c) { bufs.reserve(8); }
-  void* in(const void* src, size_t bytes) {
-    bufs.emplace_back();
-    if (rc == YH_OK) rc = upload(ctx, bufs.back(), src, bytes);
-    return bufs.back().p;
-  }
-  void* out(size_t bytes) {
-    bufs.emplace_back();
-    if (rc == YH_OK) rc = alloc_zero(ctx, bufs.back(), bytes);
-    return bufs.back().p;
-  }
-};
 int finish(yh_context* ctx, int launch_err, void* dst, const void* src, size_t bytes) {
   if (launch_err) return fail(ctx, YH_E_DEVICE, "kernel launch: %s", hipGetErrorString((hipError_t)launch_err));
   YH_WAIT(ctx);
@@ -306,11 +291,11 @@ int yh_intersect_batch(yh_context* ctx, int n, const float* rays, int* object, i
   if (forced.mode == yhh::IntersectSwitch::QUAD) lanes = false;
   else if (forced.mode == yhh::IntersectSwitch::LANES) {
     if (!lane_kernels_can_address(ctx))  // (beyond 4 GB the buffer resource clamps and the loads return zeros: wrong hits, no error)
-      return fail(ctx, YH_E_INVALID, "YHAIR_INTERSECT=%s: the one-lane kernel reads the scene's trees through 32-bit byte offsets and this scene's exceed 4 GB", forced.text);
+      return refuse_lane_offsets(ctx, (std::string("YHAIR_INTERSECT=") + forced.text).c_str(), "kernel");
     lanes = true;
   }
   for (int i = 0; lanes && i < n; i++) lanes = rays[8 * (size_t)i + 6] == 1e-4f;
-  HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if (int rc = timed_begin(ctx)) return rc;
   if (lanes) {
     const int occupancy = std::min(waves, yhk_intersect_lanes_occupancy(&ctx->scene, waves));  // (256-thread blocks: one wave per SIMD each)
     if (occupancy < 1) return fail(ctx, YH_E_DEVICE, "k_intersect_lanes cannot run with its LDS layout on this device");
@@ -327,10 +312,7 @@ int yh_intersect_batch(yh_context* ctx, int n, const float* rays, int* object, i
     int e = yhk_intersect(&ctx->scene, n, dr, dob, del, duv, dd, ctx->stream);
     if (e) return fail(ctx, YH_E_DEVICE, "k_intersect launch: %s", hipGetErrorString((hipError_t)e));
   }
-  HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  YH_WAIT(ctx);
-  HIPCHK(ctx, hipEventElapsedTime(&ctx->last_ms, ctx->ev0, ctx->ev1));  // (yh_last_trace_ms: the kernel alone, without the copies)
-  ctx->last_launches = 1;
+  if (int rc = timed_end(ctx, 1)) return rc;  // (yh_last_trace_ms: the kernel alone, without the copies)
   return download_hits(ctx, n, dob, del, duv, dd, object, element, uv, distance);
 }
 
@@ -382,8 +364,7 @@ int yh_lights_batch(yh_context* ctx, int form, int n, const float* position, con
   auto   o  = (float*)s.out(32 * (size_t)n);
   if (s.rc) return s.rc;
   if (form == 0) return finish(ctx, yhk_lights(&ctx->scene, n, dp, dd, dr, o, ctx->stream), out, o, 32 * (size_t)n);
-  if (!lane_kernels_can_address(ctx))
-    return fail(ctx, YH_E_INVALID, "yh_lights_batch: the one-lane form reads the scene's trees through 32-bit byte offsets and this scene's exceed 4 GB");
+  if (!lane_kernels_can_address(ctx)) return refuse_lane_offsets(ctx, "yh_lights_batch");
   const int ovf_entries = lane_overflow_entries(ctx);
   auto      dovf        = (unsigned int*)s.out((size_t)((n + 255) / 256) * 4 * ovf_entries * 64 * 4);
   if (s.rc) return s.rc;

@@ -1,7 +1,7 @@
 // context.cpp — the C ABI of include/yhair.h, part 1: the context (create / destroy / errors), shards and downloads (the image, its
 // tone-mapped bytes, the rng, the costs); the shared helpers (fail, dev_alloc, upload, alloc_zero). There is no CPU fallback: without a GPU yh_create returns NULL. See context_internal.h
 // for the other translation units.
-#include "context_internal.h"
+#include "image_pass.h"
 
 std::string g_create_error = "no error";
 
@@ -167,10 +167,7 @@ int yh_download_display(yh_context* ctx, float exposure, int filmic, int srgb, u
   if (!ctx->have_state) return fail(ctx, YH_E_STATE, "yh_download_display before yh_init_state");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   const size_t bytes = (size_t)ctx->state.width * ctx->state.height * 4;
-  if (!ctx->d_display.p || ctx->d_display.bytes < bytes) {
-    YH_WAIT(ctx);
-    if (int rc = dev_alloc(ctx, ctx->d_display, bytes)) return rc;
-  }
+  if (int rc = ensure_display(ctx, true)) return rc;
   int e = yhk_display(&ctx->state, ctx->state.samples_done, exposure, filmic ? 1 : 0, srgb ? 1 : 0, ctx->d_display.p, ctx->stream);
   if (e) return fail(ctx, YH_E_DEVICE, "k_display launch: %s", hipGetErrorString((hipError_t)e));
   HIPCHK(ctx, hipMemcpyAsync(rgba8, ctx->d_display.p, bytes, hipMemcpyDeviceToHost, ctx->stream));

@@ -15,6 +15,8 @@
 //   denoise.cpp        yh_denoise and friends: the a-trous filter over the resolved render, guided by that pass (unit/denoise.hip, unit/atrous_math.h)
 //   temporal.cpp       yh_temporal_accumulate and friends: the previous step's render reprojected into the new view and blended by sample
 //                      count, in front of that filter (unit/reproject.hip, unit/reproject_math.h); the history it keeps between steps
+//   image_pass.cpp     what those three share (image_pass.h): the state refusals, staging (Staged, also batch_api.cpp's), guide planes traced
+//                      or staged by name (image_planes.h: the planes of yh_gbuffer and which of them a stage reads), timing, the display tail
 //   scene_edit.cpp     edits of an uploaded scene that keep its geometry: yh_update_camera / _materials / _environments / _objects, and the
 //                      scene level again (the tree over the objects' world boxes, which the shape edits move too)
 //   shape_edit.cpp     one shape's vertices: yh_update_shape / _device (its tree again), yh_refit_shape / _device (that tree's boxes only,
@@ -442,12 +444,11 @@ int trace_impl(yh_context* ctx, int nsamples, bool counted, bool sync);
 int wait_for_launch(yh_context* ctx);  // hipStreamSynchronize(ctx->stream) with a deadline (host/deadline.h)
 int side_by_side_impl(yh_context* ctx, int nsamples, bool sync);
 void destroy_communicators(yh_context* ctx);
-int gbuffer_pass(yh_context* ctx, const char* who, int mode, void* const planes[11]);  // gbuffer.cpp: the feature pass into device planes, for denoise.cpp
+int gbuffer_pass(yh_context* ctx, const char* who, int mode, const yh_gbuffer& planes);  // gbuffer.cpp: the feature pass into device planes (NULL: skipped), for image_pass.cpp
 // denoise.cpp, for temporal.cpp: the diagonal of the uploaded scene's bounds (0 without one), and the shipped filter over a device image
 // with the given device planes (those the parameters do not read may be NULL)
 float scene_diagonal(const yh_context* ctx);
-int denoise_with_planes(yh_context* ctx, const char* who, const yh_denoise_params& P, const void* d_in, const int* object, const float* normal,
-    const float* position, const float* albedo, void* d_out);
+int denoise_with_planes(yh_context* ctx, const char* who, const yh_denoise_params& P, const void* d_in, const yh_gbuffer& guides, void* d_out);
 // temporal.cpp, for the edits: the history is dropped; one object's pixels are not to be reused by the next step
 void temporal_drop(yh_context* ctx);
 void temporal_mark_object(yh_context* ctx, int object);

@@ -1,37 +1,17 @@
 // denoise.cpp — yh_denoise and friends (include/yhair.h: DENOISE): the edge-avoiding a-trous filter over the resolved render, guided by
 // the centre-mode planes of the first-hit feature pass (gbuffer.cpp). The arithmetic is unit/atrous_math.h, compiled here for
 // yh_atrous_filter (the host's form) and by unit/denoise.hip for the device; this file checks, stages and launches.
-#include "context_internal.h"
+#include "image_pass.h"
 #include "../unit/atrous_math.h"
 
 namespace {
 using yha::V4;
-
-struct Guides {  // the four planes the filter reads; device or host pointers as the caller says
-  const int*   object;
-  const float *normal, *position, *albedo;
-};
-// the planes a parameter set reads, the others dropped (so that a plane that is given but not needed changes nothing)
-Guides needed_of(const yh_denoise_params& P, Guides g) {
-  if (!(P.sigma_normal > 0)) g.normal = nullptr;
-  if (!(P.sigma_position > 0)) g.position = nullptr;
-  if (!P.demodulate) g.albedo = nullptr;
-  return g;
-}
-const char* missing_plane(const yh_denoise_params& P, const Guides& g) {
-  if (!g.object) return "object";
-  if (P.sigma_normal > 0 && !g.normal) return "normal";
-  if (P.sigma_position > 0 && !g.position) return "position";
-  if (P.demodulate && !g.albedo) return "albedo";
-  return nullptr;
-}
-constexpr int64_t MAX_PIXELS = 1ll << 28;
 // the form of unit/denoise.hip the context entries run: the faster one by the A/B of tools/denoise_latency.py (profiles/denoise/latency.txt)
 constexpr int SHIPPED_FORM = 1;
 
 // The filter's kernels on the context's stream, blocking: d_in (NULL: accum / samples) -> d_out, both float4 device images of w x h
-// pixels (they may be the same); g: device planes, already reduced by needed_of. Sets yh_last_trace_ms; `per_kernel`: ctx->dn_ms too.
-int run_filter(yh_context* ctx, const char* who, int form, int w, int h, const yh_denoise_params& P, const void* d_in, const Guides& g, void* d_out, bool per_kernel) {
+// pixels (they may be the same); g: device planes, only those the parameters read (planes_in). Sets yh_last_trace_ms; `per_kernel`: ctx->dn_ms too.
+int run_filter(yh_context* ctx, const char* who, int form, int w, int h, const yh_denoise_params& P, const void* d_in, const yh_gbuffer& g, void* d_out, bool per_kernel) {
   const size_t npix = (size_t)w * h;
   const int    N    = P.iterations;
   DevBuf       u[2], g0, g1;
@@ -53,7 +33,7 @@ int run_filter(yh_context* ctx, const char* who, int form, int w, int h, const y
     }
   const void* accum   = ctx->have_state ? (const void*)ctx->state.accum : nullptr;
   const int   samples = ctx->have_state ? ctx->state.samples_done : 0;
-  HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
+  if (int rc = timed_begin(ctx)) return rc;
   int e = yhk_dn_pack(d_in, accum, samples, w, h, g.object, g.normal, g.position, g.albedo, N ? u[0].p : d_out, g0.p, g1.p, N == 0, ctx->stream);
   if (e) return fail(ctx, YH_E_DEVICE, "%s: k_dn_pack launch: %s", who, hipGetErrorString((hipError_t)e));
   for (int l = 0; l < N; l++) {
@@ -62,10 +42,7 @@ int run_filter(yh_context* ctx, const char* who, int form, int w, int h, const y
     e = yhk_dn_level(form, w, h, l, &P, u[l & 1].p, g0.p, g1.p, last ? g.albedo : nullptr, last, last ? d_out : u[(l + 1) & 1].p, ctx->stream);
     if (e) return fail(ctx, YH_E_DEVICE, "%s: k_dn_level launch: %s", who, hipGetErrorString((hipError_t)e));
   }
-  HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  YH_WAIT(ctx);
-  HIPCHK(ctx, hipEventElapsedTime(&ctx->last_ms, ctx->ev0, ctx->ev1));
-  ctx->last_launches = 1 + N;
+  if (int rc = timed_end(ctx, 1 + N)) return rc;
   if (per_kernel) {
     for (int k = 0; k <= N; k++)
       HIPCHK(ctx, hipEventElapsedTime(&ctx->dn_ms[k], k == 0 ? ctx->ev0 : ev[(size_t)k - 1], k == N ? ctx->ev1 : ev[(size_t)k]));
@@ -78,48 +55,26 @@ int run_filter(yh_context* ctx, const char* who, int form, int w, int h, const y
 int context_checks(yh_context* ctx, const char* who, const yh_denoise_params* p, bool own_render, bool own_guides) {
   if (!p) return fail(ctx, YH_E_INVALID, "%s: params is NULL", who);
   if (!yha::params_ok(*p)) return fail(ctx, YH_E_INVALID, "%s: %d iterations (0 .. %d)", who, p->iterations, YH_DENOISE_MAX_ITERATIONS);
-  if (ctx->poisoned) return refuse_poisoned(ctx);
-  if (own_guides && !ctx->have_scene) return fail(ctx, YH_E_STATE, "%s before yh_upload_scene", who);
-  if (!ctx->have_state) return fail(ctx, YH_E_STATE, "%s before yh_init_state", who);
-  if (ctx->async_pending) return fail(ctx, YH_E_STATE, "%s with an asynchronous launch pending: call yh_synchronize first", who);
-  if (own_render && ctx->world > 1)
-    return fail(ctx, YH_E_STATE, "%s: rgba_in is NULL on shard %d of %d, which holds part of the image: gather first (yh_gather_framebuffer) and pass the image", who,
-        ctx->rank, ctx->world);
-  return YH_OK;
+  return state_checks(ctx, who, CHECK_POISONED | NEED_STATE | (own_guides ? NEED_SCENE : 0) | (own_render ? OWN_RENDER : 0));
 }
 
 // d_in (NULL: the own render) -> d_out on the device; guides NULL: traced here into temporary planes
-int denoise_on_device(yh_context* ctx, const char* who, const yh_denoise_params& P, const void* d_in, const Guides* guides, void* d_out) {
-  const int    w = ctx->state.width, h = ctx->state.height;
-  const size_t npix = (size_t)w * h;
-  if ((int64_t)npix > MAX_PIXELS) return fail(ctx, YH_E_INVALID, "%s: the image has too many pixels", who);
-  if (P.iterations == 0) return run_filter(ctx, who, SHIPPED_FORM, w, h, P, d_in, Guides{}, d_out, false);
-  Guides g{};
-  DevBuf own[4];
-  float  pass_ms = 0;
-  if (guides) {
-    g = needed_of(P, *guides);
-  } else {
-    void* planes[11] = {};
-    if (int rc = dev_alloc(ctx, own[0], npix * 4)) return rc;
-    planes[0] = own[0].p;
-    const int   slot[3] = {6, 5, 9};  // yh_gbuffer: normal, position, albedo
-    const bool  want[3] = {P.sigma_normal > 0, P.sigma_position > 0, P.demodulate != 0};
-    for (int k = 0; k < 3; k++) {
-      if (!want[k]) continue;
-      if (int rc = dev_alloc(ctx, own[k + 1], npix * 12)) return rc;
-      planes[slot[k]] = own[k + 1].p;
-    }
-    if (int rc = gbuffer_pass(ctx, who, YH_GBUFFER_CENTRE, planes)) return rc;
-    pass_ms = ctx->last_ms;
-    g = Guides{(const int*)planes[0], (const float*)planes[6], (const float*)planes[5], (const float*)planes[9]};
+int denoise_on_device(yh_context* ctx, const char* who, const yh_denoise_params& P, const void* d_in, const yh_gbuffer* guides, void* d_out) {
+  const int w = ctx->state.width, h = ctx->state.height;
+  if ((int64_t)w * h > MAX_PIXELS) return refuse_too_many_pixels(ctx, who);
+  const unsigned mask = filter_planes(&P);
+  Staged         own(ctx);
+  yh_gbuffer     g{};
+  PassTime       t;
+  if (guides) g = planes_in(mask, *guides);
+  else if (mask) {
+    if (int rc = trace_guides(own, who, mask, g)) return rc;
+    t.add(ctx);
   }
   if (int rc = run_filter(ctx, who, SHIPPED_FORM, w, h, P, d_in, g, d_out, false)) return rc;
-  if (!guides) ctx->last_ms += pass_ms, ctx->last_launches += 1;
+  t.add(ctx);
   return YH_OK;
 }
-
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 }  // namespace
 
 float scene_diagonal(const yh_context* ctx) {  // of the union of the objects' world boxes
@@ -132,10 +87,8 @@ float scene_diagonal(const yh_context* ctx) {  // of the union of the objects' w
   return (float)std::sqrt(d2);
 }
 
-int denoise_with_planes(yh_context* ctx, const char* who, const yh_denoise_params& P, const void* d_in, const int* object, const float* normal,
-    const float* position, const float* albedo, void* d_out) {
-  const Guides g = P.iterations > 0 ? needed_of(P, Guides{object, normal, position, albedo}) : Guides{};
-  return run_filter(ctx, who, SHIPPED_FORM, ctx->state.width, ctx->state.height, P, d_in, g, d_out, false);
+int denoise_with_planes(yh_context* ctx, const char* who, const yh_denoise_params& P, const void* d_in, const yh_gbuffer& guides, void* d_out) {
+  return run_filter(ctx, who, SHIPPED_FORM, ctx->state.width, ctx->state.height, P, d_in, planes_in(filter_planes(&P), guides), d_out, false);
 }
 
 int yh_denoise_default_params(const yh_context* ctx, yh_denoise_params* p) {
@@ -150,16 +103,11 @@ int yh_denoise_image_device(yh_context* ctx, const yh_denoise_params* p, const v
   const char* who = "yh_denoise_image_device";
   if (int rc = context_checks(ctx, who, p, !rgba_in, !guides)) return rc;
   if (!rgba_out) return fail(ctx, YH_E_INVALID, "%s: rgba_out is NULL", who);
-  if (!aligned16(rgba_in) || !aligned16(rgba_out)) return fail(ctx, YH_E_INVALID, "%s: the float4 images must be 16-byte aligned", who);
-  Guides g{};
-  if (guides) {
-    g = Guides{guides->object, guides->normal, guides->position, guides->albedo};
-    if (p->iterations > 0)
-      if (const char* m = missing_plane(*p, g)) return fail(ctx, YH_E_INVALID, "%s: the parameters need the guide plane `%s`, which is NULL", who, m);
-  }
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  YH_WAIT(ctx);
-  return denoise_on_device(ctx, who, *p, rgba_in, guides ? &g : nullptr, rgba_out);
+  if (!aligned16(rgba_in) || !aligned16(rgba_out)) return refuse_unaligned(ctx, who);
+  if (guides)
+    if (const char* m = missing_plane(filter_planes(p), *guides)) return fail(ctx, YH_E_INVALID, "%s: the parameters need the guide plane `%s`, which is NULL", who, m);
+  if (int rc = enter_device(ctx)) return rc;
+  return denoise_on_device(ctx, who, *p, rgba_in, guides, rgba_out);
 }
 
 int yh_denoise(yh_context* ctx, const yh_denoise_params* p, const float* rgba_in, float* rgba_out) {
@@ -167,8 +115,7 @@ int yh_denoise(yh_context* ctx, const yh_denoise_params* p, const float* rgba_in
   const char* who = "yh_denoise";
   if (int rc = context_checks(ctx, who, p, !rgba_in, true)) return rc;
   if (!rgba_out) return fail(ctx, YH_E_INVALID, "%s: rgba_out is NULL", who);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  YH_WAIT(ctx);
+  if (int rc = enter_device(ctx)) return rc;
   const size_t bytes = (size_t)ctx->state.width * ctx->state.height * 16;
   DevBuf       img;
   if (int rc = dev_alloc(ctx, img, bytes)) return rc;
@@ -183,34 +130,21 @@ int yh_denoise_display(yh_context* ctx, const yh_denoise_params* p, float exposu
   const char* who = "yh_denoise_display";
   if (int rc = context_checks(ctx, who, p, true, true)) return rc;
   if (!rgba8) return fail(ctx, YH_E_INVALID, "%s: rgba8 is NULL", who);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  YH_WAIT(ctx);
-  const int    w = ctx->state.width, h = ctx->state.height;
-  const size_t npix = (size_t)w * h;
-  DevBuf       img;
-  if (int rc = dev_alloc(ctx, img, npix * 16)) return rc;
-  if (!ctx->d_display.p || ctx->d_display.bytes < npix * 4)
-    if (int rc = dev_alloc(ctx, ctx->d_display, npix * 4)) return rc;
+  if (int rc = enter_device(ctx)) return rc;
+  DevBuf img;
+  if (int rc = dev_alloc(ctx, img, (size_t)ctx->state.width * ctx->state.height * 16)) return rc;
+  if (int rc = ensure_display(ctx, false)) return rc;
   if (int rc = denoise_on_device(ctx, who, *p, nullptr, nullptr, img.p)) return rc;
-  const float ms       = ctx->last_ms;
-  const int   launches = ctx->last_launches;
-  HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int e = yhk_display_image(img.p, w, h, exposure, filmic ? 1 : 0, srgb ? 1 : 0, ctx->d_display.p, ctx->stream);
-  if (e) return fail(ctx, YH_E_DEVICE, "%s: k_display_image launch: %s", who, hipGetErrorString((hipError_t)e));
-  HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(rgba8, ctx->d_display.p, npix * 4, hipMemcpyDeviceToHost, ctx->stream));
-  YH_WAIT(ctx);
-  float tm = 0;
-  HIPCHK(ctx, hipEventElapsedTime(&tm, ctx->ev0, ctx->ev1));
-  ctx->last_ms = ms + tm, ctx->last_launches = launches + 1;
-  return YH_OK;
+  PassTime t;
+  t.add(ctx);
+  return display_tail(ctx, who, img.p, exposure, filmic, srgb, rgba8, t);
 }
 
 // ---- the unit-level pair ----------------------------------------------------------------------------------------------------------------
 namespace {
-bool filter_args(int w, int h, const yh_denoise_params* p, const float* rgba, const Guides& g, const float* out) {
+bool filter_args(int w, int h, const yh_denoise_params* p, const float* rgba, const yh_gbuffer& g, const float* out) {
   if (w < 1 || h < 1 || (int64_t)w * h > MAX_PIXELS || !p || !yha::params_ok(*p) || !rgba || !out) return false;
-  return p->iterations == 0 || !missing_plane(*p, g);
+  return !missing_plane(filter_planes(p), g);
 }
 struct HostFetch {
   const V4 *u, *g0, *g1;
@@ -224,13 +158,14 @@ struct HostFetch {
 
 int yh_atrous_filter(int w, int h, const yh_denoise_params* p, const float* rgba, const int* object, const float* normal, const float* position,
     const float* albedo, float* out) {
-  if (!filter_args(w, h, p, rgba, Guides{object, normal, position, albedo}, out)) return YH_E_INVALID;
+  const yh_gbuffer given = guides_of(object, normal, position, albedo);
+  if (!filter_args(w, h, p, rgba, given, out)) return YH_E_INVALID;
   const size_t npix = (size_t)w * h;
   if (p->iterations == 0) {
     if (out != rgba) memmove(out, rgba, npix * 16);
     return YH_OK;
   }
-  const Guides    g = needed_of(*p, Guides{object, normal, position, albedo});
+  const yh_gbuffer g = planes_in(filter_planes(p), given);
   std::vector<V4> u[2], g0(npix), g1(npix);
   u[0].resize(npix), u[1].resize(npix);
   for (size_t i = 0; i < npix; i++) {
@@ -257,34 +192,21 @@ int yh_atrous_filter_gpu(yh_context* ctx, int form, int w, int h, const yh_denoi
   if (!ctx) return YH_E_INVALID;
   const char* who = "yh_atrous_filter_gpu";
   if (form != 0 && form != 1) return fail(ctx, YH_E_INVALID, "%s: unknown form %d", who, form);
-  if (!filter_args(w, h, p, rgba, Guides{object, normal, position, albedo}, out))
+  const yh_gbuffer given = guides_of(object, normal, position, albedo);
+  if (!filter_args(w, h, p, rgba, given, out))
     return fail(ctx, YH_E_INVALID, "%s: an empty image, a NULL params, image or output, iterations outside 0 .. %d, or a guide plane the parameters need is NULL", who,
         YH_DENOISE_MAX_ITERATIONS);
-  if (ctx->poisoned) return refuse_poisoned(ctx);
-  if (ctx->async_pending) return fail(ctx, YH_E_STATE, "%s with an asynchronous launch pending: call yh_synchronize first", who);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  YH_WAIT(ctx);
+  if (int rc = state_checks(ctx, who, CHECK_POISONED)) return rc;
+  if (int rc = enter_device(ctx)) return rc;
   const size_t npix = (size_t)w * h;
-  const Guides hg   = p->iterations ? needed_of(*p, Guides{object, normal, position, albedo}) : Guides{};
-  DevBuf       img, d_obj, d_f[3];
-  if (int rc = dev_alloc(ctx, img, npix * 16)) return rc;
-  HIPCHK(ctx, hipMemcpy(img.p, rgba, npix * 16, hipMemcpyHostToDevice));
-  Guides dg{};
-  if (hg.object) {
-    if (int rc = dev_alloc(ctx, d_obj, npix * 4)) return rc;
-    HIPCHK(ctx, hipMemcpy(d_obj.p, hg.object, npix * 4, hipMemcpyHostToDevice));
-    dg.object = (const int*)d_obj.p;
-  }
-  const float*  src[3] = {hg.normal, hg.position, hg.albedo};
-  const float** dst[3] = {&dg.normal, &dg.position, &dg.albedo};
-  for (int k = 0; k < 3; k++) {
-    if (!src[k]) continue;
-    if (int rc = dev_alloc(ctx, d_f[k], npix * 12)) return rc;
-    HIPCHK(ctx, hipMemcpy(d_f[k].p, src[k], npix * 12, hipMemcpyHostToDevice));
-    *dst[k] = (const float*)d_f[k].p;
-  }
-  if (int rc = run_filter(ctx, who, form, w, h, *p, img.p, dg, img.p, true)) return rc;
-  HIPCHK(ctx, hipMemcpy(out, img.p, npix * 16, hipMemcpyDeviceToHost));
+  Staged       s(ctx);
+  void*        img = s.in(rgba, npix * 16);
+  yh_gbuffer   dg{};
+  for (Plane k : guide_order)
+    if (filter_planes(p) & plane_bit(k)) set_plane(dg, k, s.in(plane_of(given, k), plane_bytes[k] * npix));
+  if (s.rc) return s.rc;
+  if (int rc = run_filter(ctx, who, form, w, h, *p, img, dg, img, true)) return rc;
+  HIPCHK(ctx, hipMemcpy(out, img, npix * 16, hipMemcpyDeviceToHost));
   return YH_OK;
 }
 

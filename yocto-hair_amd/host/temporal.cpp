@@ -2,16 +2,14 @@
 // through the centre-mode position plane of the first-hit feature pass (gbuffer.cpp), validated and blended by sample count, in front of
 // the a-trous filter (denoise.cpp). The arithmetic is unit/reproject_math.h, compiled here for yh_reproject (the host's form) and by
 // unit/reproject.hip for the device; this file checks, stages, launches and keeps the history (yh_context::Temporal) between steps.
-#include "context_internal.h"
+#include "image_pass.h"
 #include "../unit/reproject_math.h"
 
 namespace {
 using yht::V4;
 static_assert(sizeof(yh_camera) == 17 * 4, "a camera is the 17 floats unit/reproject_math.h reads");
 static_assert(sizeof(yhd_object) % 4 == 0 && offsetof(yhd_object, frame) == 0 && offsetof(yhd_object, inv_frame) == 48, "the object rows' frames are read in place");
-constexpr int64_t MAX_PIXELS = 1ll << 28;
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
 const float* floats_of(const yh_camera& c) { return c.frame; }  // (frame, lens, film, focus, aperture: contiguous)
 
 // what every context entry refuses, before anything is written
@@ -19,23 +17,18 @@ int context_checks(yh_context* ctx, const char* who, const yh_temporal_params* p
   if (!p) return fail(ctx, YH_E_INVALID, "%s: params is NULL", who);
   if (!yht::params_ok(*p)) return fail(ctx, YH_E_INVALID, "%s: max_history %d (1 .. 2^30)", who, p->max_history);
   if (!own_render && !yht::samples_ok(samples_in)) return fail(ctx, YH_E_INVALID, "%s: an image with %d samples (1 .. 2^30)", who, samples_in);
-  if (guides && (!guides->object || !guides->position)) return fail(ctx, YH_E_INVALID, "%s: the guide plane `%s` is NULL", who, guides->object ? "position" : "object");
-  if (ctx->poisoned) return refuse_poisoned(ctx);
-  if (!ctx->have_scene) return fail(ctx, YH_E_STATE, "%s before yh_upload_scene", who);
-  if (!ctx->have_state) return fail(ctx, YH_E_STATE, "%s before yh_init_state", who);
-  if (ctx->async_pending) return fail(ctx, YH_E_STATE, "%s with an asynchronous launch pending: call yh_synchronize first", who);
-  if (own_render && ctx->world > 1)
-    return fail(ctx, YH_E_STATE, "%s: rgba_in is NULL on shard %d of %d, which holds part of the image: gather first (yh_gather_framebuffer) and pass the image", who,
-        ctx->rank, ctx->world);
+  if (guides)
+    if (const char* m = missing_plane(temporal_planes(), *guides)) return fail(ctx, YH_E_INVALID, "%s: the guide plane `%s` is NULL", who, m);
+  if (int rc = state_checks(ctx, who, CHECK_POISONED | NEED_SCENE | NEED_STATE | (own_render ? OWN_RENDER : 0))) return rc;
   if (own_render && ctx->state.samples_done < 1) return fail(ctx, YH_E_STATE, "%s: rgba_in is NULL and no sample has been traced", who);
   if (own_render && !yht::samples_ok(ctx->state.samples_done)) return fail(ctx, YH_E_INVALID, "%s: too many samples", who);
-  if ((int64_t)ctx->state.width * ctx->state.height > MAX_PIXELS) return fail(ctx, YH_E_INVALID, "%s: the image has too many pixels", who);
+  if ((int64_t)ctx->state.width * ctx->state.height > MAX_PIXELS) return refuse_too_many_pixels(ctx, who);
   return YH_OK;
 }
 
-// One step on the device, blocking: d_in (NULL: the own render) with `samples` samples and the device planes object / position -> d_out
-// (may be NULL, or d_in) and the other side of the history, which becomes the history. Sets yh_last_trace_ms.
-int step_on_device(yh_context* ctx, const char* who, const yh_temporal_params& P, const void* d_in, int samples, const int* d_object, const float* d_position, void* d_out) {
+// One step on the device, blocking: d_in (NULL: the own render) with `samples` samples and the device planes object / position of `g` ->
+// d_out (may be NULL, or d_in) and the other side of the history, which becomes the history. Sets yh_last_trace_ms.
+int step_on_device(yh_context* ctx, const char* who, const yh_temporal_params& P, const void* d_in, int samples, const yh_gbuffer& g, void* d_out) {
   yh_context::Temporal& T = ctx->tp;
   const int    w = ctx->state.width, h = ctx->state.height, nobj = ctx->scene.num_objects;
   const size_t npix = (size_t)w * h;
@@ -55,17 +48,15 @@ int step_on_device(yh_context* ctx, const char* who, const yh_temporal_params& P
     m = yht::Motion{rows, rows + 12, (const float*)T.d_frames.p, (const int*)T.d_usable.p, (int)(sizeof(yhd_object) / 4), nobj};
   }
   const yh_camera now = ctx->key_camera;
-  HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int e = yhk_reproject(d_in, ctx->state.accum, d_in ? samples : ctx->state.samples_done, d_object, d_position, w, h, T.hc[from].p, T.hg[from].p, have ? 1 : 0,
+  if (int rc = timed_begin(ctx)) return rc;
+  int e = yhk_reproject(d_in, ctx->state.accum, d_in ? samples : ctx->state.samples_done, g.object, g.position, w, h, T.hc[from].p, T.hg[from].p, have ? 1 : 0,
       floats_of(now), floats_of(have ? T.camera : now), have && nobj > 0 ? &m : nullptr, &P, T.hc[to].p, T.hg[to].p, d_out, ctx->stream);
   if (e) return fail(ctx, YH_E_DEVICE, "%s: k_reproject launch: %s", who, hipGetErrorString((hipError_t)e));
-  HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
+  if (int rc = timed_stop(ctx)) return rc;
   if (nobj > 0)  // the frames this step's history was made under: the rows' own, after the kernel that read the previous ones
     HIPCHK(ctx, hipMemcpy2DAsync(T.d_frames.p, 48, ctx->d_objects.p, sizeof(yhd_object), 48, (size_t)nobj, hipMemcpyDeviceToDevice, ctx->stream));
   T.have = false;  // (an error below leaves no history)
-  YH_WAIT(ctx);
-  HIPCHK(ctx, hipEventElapsedTime(&ctx->last_ms, ctx->ev0, ctx->ev1));
-  ctx->last_launches = 1;
+  if (int rc = timed_read(ctx, 1)) return rc;
   T.have = true, T.width = w, T.height = h, T.side = to, T.num_objects = nobj, T.camera = now;
   T.usable.assign((size_t)nobj, 1);
   return YH_OK;
@@ -73,17 +64,14 @@ int step_on_device(yh_context* ctx, const char* who, const yh_temporal_params& P
 
 // ... with the guides traced here where none are given (guides: DEVICE planes)
 int accumulate_on_device(yh_context* ctx, const char* who, const yh_temporal_params& P, const void* d_in, int samples, const yh_gbuffer* guides, void* d_out) {
-  if (guides) return step_on_device(ctx, who, P, d_in, samples, guides->object, guides->position, d_out);
-  const size_t npix = (size_t)ctx->state.width * ctx->state.height;
-  DevBuf       d_obj, d_pos;
-  if (int rc = dev_alloc(ctx, d_obj, npix * 4)) return rc;
-  if (int rc = dev_alloc(ctx, d_pos, npix * 12)) return rc;
-  void* planes[11] = {};
-  planes[0] = d_obj.p, planes[5] = d_pos.p;
-  if (int rc = gbuffer_pass(ctx, who, YH_GBUFFER_CENTRE, planes)) return rc;
-  const float pass_ms = ctx->last_ms;
-  if (int rc = step_on_device(ctx, who, P, d_in, samples, (const int*)d_obj.p, (const float*)d_pos.p, d_out)) return rc;
-  ctx->last_ms += pass_ms, ctx->last_launches += 1;
+  if (guides) return step_on_device(ctx, who, P, d_in, samples, *guides, d_out);
+  Staged     own(ctx);
+  yh_gbuffer g{};
+  PassTime   t;
+  if (int rc = trace_guides(own, who, temporal_planes(), g)) return rc;
+  t.add(ctx);
+  if (int rc = step_on_device(ctx, who, P, d_in, samples, g, d_out)) return rc;
+  t.add(ctx);
   return YH_OK;
 }
 }  // namespace
@@ -107,8 +95,7 @@ int yh_temporal_reset(yh_context* ctx) {
 
 int yh_temporal_lengths(yh_context* ctx, int* lengths) {
   if (!ctx) return YH_E_INVALID;
-  if (ctx->poisoned) return refuse_poisoned(ctx);
-  if (ctx->async_pending) return fail(ctx, YH_E_STATE, "yh_temporal_lengths with an asynchronous launch pending: call yh_synchronize first");
+  if (int rc = state_checks(ctx, "yh_temporal_lengths", CHECK_POISONED)) return rc;
   const yh_context::Temporal& T = ctx->tp;
   if (!T.have) return 0;
   const size_t npix = (size_t)T.width * T.height;
@@ -127,9 +114,8 @@ int yh_temporal_accumulate_device(yh_context* ctx, const yh_temporal_params* p, 
   if (!ctx) return YH_E_INVALID;
   const char* who = "yh_temporal_accumulate_device";
   if (int rc = context_checks(ctx, who, p, !rgba_in, samples_in, guides)) return rc;
-  if (!aligned16(rgba_in) || !aligned16(rgba_out)) return fail(ctx, YH_E_INVALID, "%s: the float4 images must be 16-byte aligned", who);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  YH_WAIT(ctx);
+  if (!aligned16(rgba_in) || !aligned16(rgba_out)) return refuse_unaligned(ctx, who);
+  if (int rc = enter_device(ctx)) return rc;
   return accumulate_on_device(ctx, who, *p, rgba_in, samples_in, guides, rgba_out);
 }
 
@@ -137,23 +123,17 @@ int yh_temporal_accumulate(yh_context* ctx, const yh_temporal_params* p, const f
   if (!ctx) return YH_E_INVALID;
   const char* who = "yh_temporal_accumulate";
   if (int rc = context_checks(ctx, who, p, !rgba_in, samples_in, guides)) return rc;
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  YH_WAIT(ctx);
+  if (int rc = enter_device(ctx)) return rc;
   const size_t npix = (size_t)ctx->state.width * ctx->state.height;
-  DevBuf       img, d_obj, d_pos;
-  if (rgba_in || rgba_out)
-    if (int rc = dev_alloc(ctx, img, npix * 16)) return rc;
-  if (rgba_in) HIPCHK(ctx, hipMemcpy(img.p, rgba_in, npix * 16, hipMemcpyHostToDevice));
+  Staged       s(ctx);
+  void*        img = rgba_in || rgba_out ? s.scratch(npix * 16) : nullptr;
+  if (s.rc) return s.rc;
+  if (rgba_in) HIPCHK(ctx, hipMemcpy(img, rgba_in, npix * 16, hipMemcpyHostToDevice));
   yh_gbuffer dg{};
-  if (guides) {
-    if (int rc = dev_alloc(ctx, d_obj, npix * 4)) return rc;
-    if (int rc = dev_alloc(ctx, d_pos, npix * 12)) return rc;
-    HIPCHK(ctx, hipMemcpy(d_obj.p, guides->object, npix * 4, hipMemcpyHostToDevice));
-    HIPCHK(ctx, hipMemcpy(d_pos.p, guides->position, npix * 12, hipMemcpyHostToDevice));
-    dg.object = (int*)d_obj.p, dg.position = (float*)d_pos.p;
-  }
-  if (int rc = accumulate_on_device(ctx, who, *p, rgba_in ? img.p : nullptr, samples_in, guides ? &dg : nullptr, rgba_out ? img.p : nullptr)) return rc;
-  if (rgba_out) HIPCHK(ctx, hipMemcpy(rgba_out, img.p, npix * 16, hipMemcpyDeviceToHost));
+  if (guides)
+    if (int rc = stage_guides(s, temporal_planes(), *guides, npix, dg)) return rc;
+  if (int rc = accumulate_on_device(ctx, who, *p, rgba_in ? img : nullptr, samples_in, guides ? &dg : nullptr, rgba_out ? img : nullptr)) return rc;
+  if (rgba_out) HIPCHK(ctx, hipMemcpy(rgba_out, img, npix * 16, hipMemcpyDeviceToHost));
   return YH_OK;
 }
 
@@ -164,43 +144,22 @@ int yh_temporal_display(yh_context* ctx, const yh_temporal_params* tp, const yh_
   if (dp && (dp->iterations < 0 || dp->iterations > YH_DENOISE_MAX_ITERATIONS))
     return fail(ctx, YH_E_INVALID, "%s: %d iterations (0 .. %d)", who, dp->iterations, YH_DENOISE_MAX_ITERATIONS);
   if (!rgba8) return fail(ctx, YH_E_INVALID, "%s: rgba8 is NULL", who);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  YH_WAIT(ctx);
-  const int    w = ctx->state.width, h = ctx->state.height;
-  const size_t npix = (size_t)w * h;
-  const bool   filter = dp && dp->iterations > 0;
-  DevBuf       img, own[4];
-  if (int rc = dev_alloc(ctx, img, npix * 16)) return rc;
-  if (!ctx->d_display.p || ctx->d_display.bytes < npix * 4)
-    if (int rc = dev_alloc(ctx, ctx->d_display, npix * 4)) return rc;
-  // one feature pass for both stages: object and position always, normal / albedo where the filter reads them
-  void*      planes[11] = {};
-  const int  slot[4] = {0, 5, 6, 9};
-  const bool want[4] = {true, true, filter && dp->sigma_normal > 0, filter && dp->demodulate != 0};
-  for (int k = 0; k < 4; k++) {
-    if (!want[k]) continue;
-    if (int rc = dev_alloc(ctx, own[k], npix * (k == 0 ? 4 : 12))) return rc;
-    planes[slot[k]] = own[k].p;
+  if (int rc = enter_device(ctx)) return rc;
+  Staged     s(ctx);
+  void*      img = s.scratch((size_t)ctx->state.width * ctx->state.height * 16);
+  yh_gbuffer g{};
+  PassTime   t;
+  if (s.rc) return s.rc;
+  if (int rc = ensure_display(ctx, false)) return rc;
+  if (int rc = trace_guides(s, who, display_planes(dp), g)) return rc;  // one feature pass for both stages
+  t.add(ctx);
+  if (int rc = step_on_device(ctx, who, *tp, nullptr, 0, g, img)) return rc;
+  t.add(ctx);
+  if (filter_planes(dp)) {  // (the filter runs)
+    if (int rc = denoise_with_planes(ctx, who, *dp, img, g, img)) return rc;
+    t.add(ctx);
   }
-  if (int rc = gbuffer_pass(ctx, who, YH_GBUFFER_CENTRE, planes)) return rc;
-  float ms       = ctx->last_ms;
-  int   launches = 1;
-  if (int rc = step_on_device(ctx, who, *tp, nullptr, 0, (const int*)planes[0], (const float*)planes[5], img.p)) return rc;
-  ms += ctx->last_ms, launches += ctx->last_launches;
-  if (filter) {
-    if (int rc = denoise_with_planes(ctx, who, *dp, img.p, (const int*)planes[0], (const float*)planes[6], (const float*)planes[5], (const float*)planes[9], img.p)) return rc;
-    ms += ctx->last_ms, launches += ctx->last_launches;
-  }
-  HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int e = yhk_display_image(img.p, w, h, exposure, filmic ? 1 : 0, srgb ? 1 : 0, ctx->d_display.p, ctx->stream);
-  if (e) return fail(ctx, YH_E_DEVICE, "%s: k_display_image launch: %s", who, hipGetErrorString((hipError_t)e));
-  HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  HIPCHK(ctx, hipMemcpyAsync(rgba8, ctx->d_display.p, npix * 4, hipMemcpyDeviceToHost, ctx->stream));
-  YH_WAIT(ctx);
-  float tm = 0;
-  HIPCHK(ctx, hipEventElapsedTime(&tm, ctx->ev0, ctx->ev1));
-  ctx->last_ms = ms + tm, ctx->last_launches = launches + 1;
-  return YH_OK;
+  return display_tail(ctx, who, img, exposure, filmic, srgb, rgba8, t);
 }
 
 // ---- the unit-level pair ----------------------------------------------------------------------------------------------------------------
@@ -293,50 +252,35 @@ int yh_reproject_gpu(yh_context* ctx, int w, int h, const yh_temporal_params* p,
       usable, out_rgba, out_length};
   if (!unit_args_ok(a))
     return fail(ctx, YH_E_INVALID, "%s: an empty image, max_history or samples outside 1 .. 2^30, a NULL params, image, plane, camera or output, a history or frames given in part", who);
-  if (ctx->poisoned) return refuse_poisoned(ctx);
-  if (ctx->async_pending) return fail(ctx, YH_E_STATE, "%s with an asynchronous launch pending: call yh_synchronize first", who);
-  HIPCHK(ctx, hipSetDevice(ctx->device));
-  YH_WAIT(ctx);
+  if (int rc = state_checks(ctx, who, CHECK_POISONED)) return rc;
+  if (int rc = enter_device(ctx)) return rc;
   const size_t npix = (size_t)w * h;
   const bool   have = hist_length != nullptr, moving = have && frames && num_objects > 0;
-  DevBuf       img, d_obj, d_pos, hc[2], hg[2], d_fr, d_inv, d_prev, d_use, d_len;
-  const auto   up = [&](DevBuf& b, const void* src, size_t bytes) -> int {
-    if (int rc = dev_alloc(ctx, b, bytes)) return rc;
-    HIPCHK(ctx, hipMemcpy(b.p, src, bytes, hipMemcpyHostToDevice));
-    return YH_OK;
-  };
-  if (int rc = up(img, rgba, npix * 16)) return rc;
-  if (int rc = up(d_obj, object, npix * 4)) return rc;
-  if (int rc = up(d_pos, position, npix * 12)) return rc;
-  for (DevBuf* b : {&hc[1], &hg[1], &d_len})
-    if (int rc = dev_alloc(ctx, *b, b == &d_len ? npix * 4 : npix * 16)) return rc;
+  Staged       s(ctx);
+  void*        img = s.in(rgba, npix * 16);
+  yh_gbuffer   g{};
+  g.object = (int*)s.in(object, plane_bytes[PLANE_object] * npix), g.position = (float*)s.in(position, plane_bytes[PLANE_position] * npix);
+  void *hc[2] = {nullptr, s.scratch(npix * 16)}, *hg[2] = {nullptr, s.scratch(npix * 16)}, *d_len = s.scratch(npix * 4);
   if (have) {
-    std::vector<V4> c, g;
-    pack_history(a, c, g);
-    if (int rc = up(hc[0], c.data(), npix * 16)) return rc;
-    if (int rc = up(hg[0], g.data(), npix * 16)) return rc;
+    std::vector<V4> c, hgv;
+    pack_history(a, c, hgv);
+    hc[0] = s.in(c.data(), npix * 16), hg[0] = s.in(hgv.data(), npix * 16);
   }
   yht::Motion m{nullptr, nullptr, nullptr, nullptr, 0, 0};
   if (moving) {
     const std::vector<float> inv   = inverses_of(frames, num_objects);
     const size_t             bytes = (size_t)num_objects * 48;
-    if (int rc = up(d_fr, frames, bytes)) return rc;
-    if (int rc = up(d_inv, inv.data(), bytes)) return rc;
-    if (int rc = up(d_prev, prev_frames, bytes)) return rc;
-    if (usable)
-      if (int rc = up(d_use, usable, (size_t)num_objects * 4)) return rc;
-    m = yht::Motion{(const float*)d_fr.p, (const float*)d_inv.p, (const float*)d_prev.p, (const int*)d_use.p, 12, num_objects};
+    const float *            d_fr = (const float*)s.in(frames, bytes), *d_inv = (const float*)s.in(inv.data(), bytes), *d_prev = (const float*)s.in(prev_frames, bytes);
+    m = yht::Motion{d_fr, d_inv, d_prev, usable ? (const int*)s.in(usable, (size_t)num_objects * 4) : nullptr, 12, num_objects};
   }
-  HIPCHK(ctx, hipEventRecord(ctx->ev0, ctx->stream));
-  int e = yhk_reproject(img.p, nullptr, samples, (const int*)d_obj.p, (const float*)d_pos.p, w, h, hc[0].p, hg[0].p, have ? 1 : 0, floats_of(*camera),
-      floats_of(have ? *prev_camera : *camera), moving ? &m : nullptr, p, hc[1].p, hg[1].p, img.p, ctx->stream);
-  if (!e) e = yhk_tp_lengths(hc[1].p, w, h, (int*)d_len.p, ctx->stream);
+  if (s.rc) return s.rc;
+  if (int rc = timed_begin(ctx)) return rc;
+  int e = yhk_reproject(img, nullptr, samples, g.object, g.position, w, h, hc[0], hg[0], have ? 1 : 0, floats_of(*camera),
+      floats_of(have ? *prev_camera : *camera), moving ? &m : nullptr, p, hc[1], hg[1], img, ctx->stream);
+  if (!e) e = yhk_tp_lengths(hc[1], w, h, (int*)d_len, ctx->stream);
   if (e) return fail(ctx, YH_E_DEVICE, "%s: k_reproject launch: %s", who, hipGetErrorString((hipError_t)e));
-  HIPCHK(ctx, hipEventRecord(ctx->ev1, ctx->stream));
-  YH_WAIT(ctx);
-  HIPCHK(ctx, hipEventElapsedTime(&ctx->last_ms, ctx->ev0, ctx->ev1));
-  ctx->last_launches = 2;
-  HIPCHK(ctx, hipMemcpy(out_rgba, img.p, npix * 16, hipMemcpyDeviceToHost));
-  HIPCHK(ctx, hipMemcpy(out_length, d_len.p, npix * 4, hipMemcpyDeviceToHost));
+  if (int rc = timed_end(ctx, 2)) return rc;
+  HIPCHK(ctx, hipMemcpy(out_rgba, img, npix * 16, hipMemcpyDeviceToHost));
+  HIPCHK(ctx, hipMemcpy(out_length, d_len, npix * 4, hipMemcpyDeviceToHost));
   return YH_OK;
 }
