@@ -22,6 +22,8 @@
 #include <stdint.h>
 #include <string.h>
 
+#include "launchers.h"
+
 namespace {
 
 __device__ __forceinline__ unsigned int fkey(float f) {  // order-preserving float -> uint

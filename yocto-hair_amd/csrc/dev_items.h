@@ -1,5 +1,6 @@
-// dev_items.h — the persistent sample loop of the quad kernels (k_trace, k_trace_shader, k_trace_exact): included by
-// csrc/kernels.hip and by csrc/exact.hip (the same loop compiled with the exact hair-BSDF arithmetic, YH_HAIR_FAST=0).
+// dev_items.h — the persistent sample loop of the k_trace kernels (k_trace, k_trace_shader, k_trace_sbs, k_trace_exact): included by
+// csrc/kernels.hip (which holds nothing but the quad forms and their launch), csrc/wide.hip and by csrc/exact.hip (the same loop
+// compiled with the exact hair-BSDF arithmetic, YH_HAIR_FAST=0).
 #ifndef YH_DEV_ITEMS_H_
 #define YH_DEV_ITEMS_H_
 #include "dev_path.h"
@@ -207,8 +208,8 @@ YH_DEV void trace_items(const yhd_scene& sc, const yhd_state& st, int nsamples, 
 // ---------------------------------------------------------------------------
 // The sample-loop kernels (instantiated by csrc/kernels.hip: quads over 4-wide nodes, the other shaders; csrc/wide.hip: octets,
 // sixteen lanes per path, side by side; csrc/exact.hip has its own)
+// (their type: trace_kernel_t, csrc/launchers.h)
 // ---------------------------------------------------------------------------
-typedef void (*trace_kernel_t)(const yhd_scene, const yhd_state, int, yhd_counters*);
 #define YH_OCT_BLOCK 256 /* workgroup of the wide forms (launch shapes 4, 6, 7, 8) */
 template <bool COUNT, bool GENERAL, int BLOCK, int WAVES, int MODE = YH_MODE_QUAD, bool ONCE = false>
 __global__ __launch_bounds__(BLOCK, WAVES) void k_trace(const yhd_scene sc, const yhd_state st,

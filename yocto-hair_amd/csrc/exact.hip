@@ -11,6 +11,7 @@
 
 #define YH_HAIR_FAST 0
 #include "yhair.h"
+#include "launchers.h"
 #include "dev_items.h"
 
 template <bool GENERAL>

@@ -29,6 +29,7 @@
 #include <hip/hip_runtime.h>
 
 #include "yhair.h"
+#include "launchers.h"
 #include "dev_path.h"
 
 using namespace yhd;

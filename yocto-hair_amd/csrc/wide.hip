@@ -1,12 +1,13 @@
 // wide.hip — the sample-loop kernels that give a path MORE than four lanes (gfx950): octets over 8-wide nodes (YH_SHAPE_OCT,
 // _OCT_PAIRS), sixteen lanes over 16-wide nodes (_HEX, _HEX_GROUPS) and the side-by-side launch (_SBS: quads + the top items as octets in one kernel).
-// Split from kernels.hip in round 4 (one translation unit took 77 s to compile); same templates (csrc/dev_items.h), same bits.
+// A translation unit beside csrc/kernels.hip's quad forms (together they took 77 s to compile); same templates (csrc/dev_items.h), same bits.
 // Compiled with -ffp-contract=off (see dev_math.h).
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
 
 #include "yhair.h"
+#include "launchers.h"
 #include "dev_items.h"
 
 extern "C" {

@@ -1,13 +1,6 @@
 // gbuffer.cpp — yh_trace_gbuffer / yh_trace_gbuffer_device: the first-hit feature pass (unit/gbuffer.hip) over the image of yh_init_state.
 #include "image_pass.h"
 
-extern "C" {
-int yhk_gbuffer_waves(void);
-int yhk_gbuffer_occupancy(const yhd_scene* sc);
-int yhk_gbuffer(const yhd_scene* sc, const yhd_scene* sc_dev, const yhd_state* st, int mode, void* const planes[PLANES], int* cursor,
-    unsigned int* stack_ovf, int ovf_entries, int grid_blocks, hipStream_t stream);
-}
-
 namespace {
 // The pass into `out` (device pointers, NULL = skipped). Reads the render state, writes none of it.
 int gbuffer_impl(yh_context* ctx, const char* who, int mode, const yh_gbuffer& out) {

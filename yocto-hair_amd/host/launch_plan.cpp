@@ -334,7 +334,7 @@ void build_work_items(const yh_context* ctx, std::vector<int>& items) {
 // from the start, and the launch is as long as the longest chain (C1: the most expensive quadrant takes 14.8 ms per 64
 // samples, the median expensive one 9 ms). The same handful of quadrants tops EVERY launch, and the octet form runs an item
 // in 0.74 x the time for two waves instead of one — so the first K items of the cost-sorted list run as octets and
-// everything else as quads, in ONE launch (csrc/kernels.hip: k_trace_sbs): its first workgroups take the octet entries,
+// everything else as quads, in ONE launch (csrc/wide.hip: k_trace_sbs): its first workgroups take the octet entries,
 // the others the quad items. The first workgroups of a launch get the fastest wave slots (prepare_work_list below), the
 // workgroups are of one size, and there is one dispatch order — the three things the earlier forms of this idea lacked
 // (two kernels on two streams: the streams raced for the slots and the workgroup sizes did not pack, 14.8 -> 18.7 ms;

@@ -27,7 +27,7 @@ def shard_pixels(width, height, rank, world):
 
 
 def pack_tiles_host(image, rank, world):
-    """Host restatement of k_pack (csrc/kernels.hip) for tests: image (H, W, 4) -> (ntiles*64, 4)."""
+    """Host restatement of k_pack (unit/framebuffer.hip) for tests: image (H, W, 4) -> (ntiles*64, 4)."""
     h, w, _ = image.shape
     tx, _ = tiles_xy(w, h)
     tiles = shard_tiles(w, h, rank, world)

@@ -21,6 +21,7 @@
 // entries run; form 0 stays reachable through yh_atrous_filter_gpu as the comparison. pack 27 VGPRs, form 0 40, form 1 38; no scratch, no spill.
 #include <hip/hip_runtime.h>
 
+#include "launchers.h"
 #include "atrous_math.h"
 
 using namespace yha;
@@ -46,7 +47,7 @@ __global__ __launch_bounds__(256) void k_dn_pack(const V4* rgba_in, const V4* ac
   V4 c;
   if (rgba_in) {
     c = rgba_in[pix];
-  } else {  // k_resolve's division (csrc/kernels.hip)
+  } else {  // k_resolve's division (unit/framebuffer.hip)
     const V4    a = accum[pix];
     const float n = (float)samples;
     c = samples > 0 ? V4{a.x / n, a.y / n, a.z / n, a.w / n} : V4{0, 0, 0, 0};

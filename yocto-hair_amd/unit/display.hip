@@ -5,6 +5,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../csrc/yh_device.h"
+#include "../csrc/launchers.h"
 
 namespace {
 

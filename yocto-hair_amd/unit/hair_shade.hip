@@ -3,4 +3,5 @@
 // k_stream). A translation unit of its own, outside csrc/: the sample-loop kernels compile to exactly the code they compiled to without it.
 #define YH_HAIR_SHADE_KERNEL k_hair_shade
 #define YH_HAIR_SHADE_LAUNCH yhk_hair_shade
+#include "launchers.h"
 #include "hair_shade.h"

@@ -4,4 +4,5 @@
 #define YH_HAIR_FAST 0
 #define YH_HAIR_SHADE_KERNEL k_hair_shade_exact
 #define YH_HAIR_SHADE_LAUNCH yhk_hair_shade_exact
+#include "launchers.h"
 #include "hair_shade.h"

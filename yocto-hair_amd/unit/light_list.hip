@@ -15,6 +15,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../csrc/yh_device.h"
+#include "../csrc/launchers.h"
 #include "light_list.h"
 #include "light_math.h"
 

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../csrc/yh_device.h"
+#include "../csrc/launchers.h"
 #include "object_math.h"
 #include "yhair.h"
 

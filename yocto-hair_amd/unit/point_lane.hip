@@ -3,4 +3,5 @@
 #define YH_LANE 1
 #define YH_POINT_KERNEL k_point_lanes
 #define YH_POINT_LAUNCH yhk_point_lanes
+#include "launchers.h"
 #include "point_shade.h"

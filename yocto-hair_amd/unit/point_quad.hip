@@ -3,4 +3,5 @@
 // translation unit of its own, outside csrc/, as unit/volume_quad.hip.
 #define YH_POINT_KERNEL k_point_quads
 #define YH_POINT_LAUNCH yhk_point_quads
+#include "launchers.h"
 #include "point_shade.h"

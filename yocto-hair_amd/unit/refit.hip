@@ -19,6 +19,8 @@
 
 #include <algorithm>
 
+#include "launchers.h"
+
 namespace {
 
 __device__ __forceinline__ float fmin_(float a, float b) { return (a < b) ? a : b; }  // math.h:1779

@@ -15,6 +15,7 @@
 // levels it feeds (profiles/temporal/latency.txt): the launch, not the 60 - 110 MB it moves, is what it costs.
 #include <hip/hip_runtime.h>
 
+#include "launchers.h"
 #include "reproject_math.h"
 
 using namespace yht;
@@ -44,7 +45,7 @@ __global__ __launch_bounds__(256) void k_reproject(const V4* rgba_in, const V4* 
   V4 c;
   if (rgba_in) {
     c = rgba_in[pix];
-  } else {  // k_resolve's division (csrc/kernels.hip)
+  } else {  // k_resolve's division (unit/framebuffer.hip)
     const V4    a = accum[pix];
     const float n = (float)samples;
     c = V4{a.x / n, a.y / n, a.z / n, a.w / n};

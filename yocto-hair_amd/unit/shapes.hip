@@ -12,6 +12,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../csrc/yh_device.h"
+#include "../csrc/launchers.h"
 #include "yhair.h"
 
 namespace {

@@ -3,4 +3,5 @@
 #define YH_LANE 1
 #define YH_VOLUME_KERNEL k_volume_lanes
 #define YH_VOLUME_LAUNCH yhk_volume_lanes
+#include "launchers.h"
 #include "volume_shade.h"

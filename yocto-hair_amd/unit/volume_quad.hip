@@ -3,6 +3,7 @@
 // own, outside csrc/, as unit/lights_quad.hip.
 #define YH_VOLUME_KERNEL k_volume_quads
 #define YH_VOLUME_LAUNCH yhk_volume_quads
+#include "launchers.h"
 #include "volume_shade.h"
 
 // sample_hemisphere_cos_quad (dev_surface.h) next to sample_hemisphere_cos, quad_div (dev_math.h) next to a / b: a quad per row, all
