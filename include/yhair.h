@@ -954,6 +954,42 @@ int yh_point_batch(yh_context* ctx, int form, int n, const int* object,
 #define YH_QUAD_FORMS_FLOATS 12
 int yh_quad_forms_batch(yh_context* ctx, int n, const float* normal,
     const float* rn, const float* a, const float* b, float* out);
+/* The start and the end of a path, row by row: what every sample of every
+ * sample-loop kernel runs around its bounces (csrc/dev_path.h: path_begin
+ * with sample_camera / sample_camera_lane, pt.cpp:211-229 and 1676-1682;
+ * path_continue, pt.cpp:1499-1507; path_end, pt.cpp:1683-1689). form 0: a
+ * quad per row, as the quad loops run them; form 1: a lane per row, as the
+ * streaming kernel runs them. Per row of `op`:
+ *   YH_PATH_BEGIN     fin: the camera as the kernels hold it, 17 floats =
+ *     frame[12], lens, film x, film y, focus, aperture; iin: i, j, w, h; rng:
+ *     state, inc. Form 0 runs path_begin; form 1 the four draws (lens u, v,
+ *     then pixel u, v) and sample_camera_lane. fout: ray origin[3],
+ *     direction[3], then radiance[3] and weight[3]; iout: bounce, hit,
+ *     in_medium as path_begin leaves them (form 1: zeros, it runs no
+ *     path_begin); state: the stream's state afterwards.
+ *   YH_PATH_CONTINUE  fin: weight[3]; iin: bounce, bounces; rng: state, inc.
+ *     path_continue: the weight check, Russian roulette from the fifth
+ *     bounce on, the bounce count. fout: weight[3]; iout: the flag it
+ *     returns (1: the path goes on), bounce; state.
+ *   YH_PATH_END       fin: radiance[3], clamp, acc[4]; iin: hit. path_end: a
+ *     non-finite radiance becomes zero, one whose largest component exceeds
+ *     clamp is scaled by clamp / that component, then acc += {rgb, hit}.
+ *     fout: acc[4]. rng, iout and state are not used and may be NULL.
+ * YH_E_INVALID for n < 1, an unknown op or form, or a NULL pointer among those
+ * the op uses.                                                              */
+#define YH_PATH_BEGIN 0
+#define YH_PATH_CONTINUE 1
+#define YH_PATH_END 2
+#define YH_PATH_OPS 3
+#define YH_PATH_BEGIN_IN 17
+#define YH_PATH_BEGIN_OUT 12
+#define YH_PATH_CONTINUE_IN 3
+#define YH_PATH_CONTINUE_OUT 3
+#define YH_PATH_END_IN 8
+#define YH_PATH_END_OUT 4
+int yh_path_ends_batch(yh_context* ctx, int op, int form, int n,
+    const float* fin, const int* iin, const uint64_t* rng, float* fout,
+    int* iout, uint64_t* state);
 
 /* The four Monte-Carlo self-tests of yocto_extension.cpp:555-693 on the
  * device: 0 white_furnace, 1 white_furnace_sampled, 2 sampling_weights,

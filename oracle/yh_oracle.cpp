@@ -1616,6 +1616,25 @@ Ray sample_camera(const Camera& cam, int i, int j, int w, int h, float pu, float
 struct Vec4 {
   float x, y, z, w;
 };
+// End of a bounce (pt.cpp:1499-1507, and the same lines of trace_naive, 1570-1578): the weight check and Russian roulette. false: the
+// path ends. The loops of trace_path and trace_naive call it, and so does yo_path_ends_batch.
+inline bool roulette(V3& weight, int bounce, Rng& rng) {
+  if (weight == V3{0, 0, 0} || !finite3(weight)) return false;
+  if (bounce > 3) {
+    auto rr_prob = fmin_((float)0.99, hmax(weight));
+    if (rand1f(rng) >= rr_prob) return false;
+    weight = weight * (1 / rr_prob);
+  }
+  return true;
+}
+// The tail of trace_sample (pt.cpp:1683-1686): sanitize, clamp, accumulate. trace_sample calls it, and so does yo_path_ends_batch.
+inline void accumulate_sample(Vec4& accumulated, const Vec4& shaded, float clamp) {
+  auto rgb = V3{shaded.x, shaded.y, shaded.z};
+  if (!finite3(rgb)) rgb = {0, 0, 0};
+  if (hmax(rgb) > clamp) rgb = rgb * (clamp / hmax(rgb));
+  accumulated.x += rgb.x, accumulated.y += rgb.y;
+  accumulated.z += rgb.z, accumulated.w += shaded.w;
+}
 // ---------------------------------------------------------------------------
 // Homogeneous volumes (pt.cpp:498-533, 1360-1377; math.h:4758-4822)
 // ---------------------------------------------------------------------------
@@ -1732,12 +1751,7 @@ Vec4 trace_path(const yo_scene& scene, const Ray& ray_, Rng& rng, int bounces) {
                             (0.5f * sample_scattering_pdf(vsdf, outgoing, incoming) +
                                 0.5f * sample_lights_pdf(scene, position, incoming)));
       ray = Ray{position, incoming};
-      if (weight == V3{0, 0, 0} || !finite3(weight)) break;
-      if (bounce > 3) {
-        auto rr_prob = fmin_((float)0.99, hmax(weight));
-        if (rand1f(rng) >= rr_prob) break;
-        weight = weight * (1 / rr_prob);
-      }
+      if (!roulette(weight, bounce, rng)) break;  // pt.cpp:1499-1507
       continue;
     }
     auto outgoing = -ray.d;
@@ -1788,12 +1802,7 @@ Vec4 trace_path(const yo_scene& scene, const Ray& ray_, Rng& rng, int bounces) {
       else volume_stack.pop_back();
     }
     ray = Ray{position, incoming};
-    if (weight == V3{0, 0, 0} || !finite3(weight)) break;
-    if (bounce > 3) {
-      auto rr_prob = fmin_((float)0.99, hmax(weight));
-      if (rand1f(rng) >= rr_prob) break;
-      weight = weight * (1 / rr_prob);
-    }
+    if (!roulette(weight, bounce, rng)) break;  // pt.cpp:1499-1507
   }
   return {radiance.x, radiance.y, radiance.z, hit ? 1.0f : 0.0f};
 }
@@ -1840,12 +1849,7 @@ Vec4 trace_naive(const yo_scene& scene, const Ray& ray_, Rng& rng, int bounces) 
       weight   = weight * (eval_delta(brdf, normal, outgoing, incoming) /
                             sample_delta_pdf(brdf, normal, outgoing, incoming));
     }
-    if (weight == V3{0, 0, 0} || !finite3(weight)) break;
-    if (bounce > 3) {
-      auto rr_prob = fmin_((float)0.99, hmax(weight));
-      if (rand1f(rng) >= rr_prob) break;
-      weight = weight * (1 / rr_prob);
-    }
+    if (!roulette(weight, bounce, rng)) break;  // pt.cpp:1499-1507
     ray = Ray{position, incoming};
   }
   return {radiance.x, radiance.y, radiance.z, hit ? 1.0f : 0.0f};
@@ -1921,11 +1925,7 @@ Vec4 trace_sample(const yo_scene& scene, Pixel& pixel, int i, int j, int w, int 
                 : shader == YH_SHADER_EYELIGHT ? trace_eyelight(scene, ray, pixel.rng, bounces)
                 : shader == YH_SHADER_NORMAL   ? trace_normal(scene, ray, pixel.rng, bounces)
                                                : trace_path(scene, ray, pixel.rng, bounces);
-  auto rgb    = V3{shaded.x, shaded.y, shaded.z};
-  if (!finite3(rgb)) rgb = {0, 0, 0};
-  if (hmax(rgb) > clamp) rgb = rgb * (clamp / hmax(rgb));
-  pixel.accumulated.x += rgb.x, pixel.accumulated.y += rgb.y;
-  pixel.accumulated.z += rgb.z, pixel.accumulated.w += shaded.w;
+  accumulate_sample(pixel.accumulated, shaded, clamp);
   pixel.samples += 1;
   tls_counters.samples++;
   auto n = (float)pixel.samples;
@@ -2259,6 +2259,48 @@ void yo_surface_bsdf(int n, const yh_material* materials, const float* normal,
       w = sample_delta(b, nn, wo, rnl);
     }
     o[22] = f.x, o[23] = f.y, o[24] = f.z, o[25] = pdf, o[26] = w.x, o[27] = w.y, o[28] = w.z;
+  }
+}
+
+// The start and the end of a path, row by row, in the row layout of yh_path_ends_batch (include/yhair.h: YH_PATH_*), by the functions
+// the renders run: the four draws of trace_sample and sample_camera (pt.cpp:1676-1682, 211-229), roulette with the loop's bounce count
+// (pt.cpp:1395, 1499-1507) and accumulate_sample (pt.cpp:1683-1686). begin: radiance, weight, bounce, hit and in_medium are trace_path's
+// locals at its head (pt.cpp:1383-1387).
+void yo_path_ends_batch(int op, int n, const float* fin, const int* iin, const uint64_t* rng_in, float* fout, int* iout, uint64_t* state) {
+  for (int r = 0; r < n; r++) {
+    if (op == YH_PATH_BEGIN) {
+      Camera cam;
+      static_assert(sizeof(Camera) == 4 * YH_PATH_BEGIN_IN, "a row of YH_PATH_BEGIN is the camera");
+      std::memcpy(&cam, fin + YH_PATH_BEGIN_IN * (size_t)r, sizeof(Camera));
+      auto ii = iin + 4 * (size_t)r;
+      Rng  rng;
+      rng.state = rng_in[2 * (size_t)r], rng.inc = rng_in[2 * (size_t)r + 1];
+      auto lu = rand1f(rng), lv = rand1f(rng);  // as trace_sample
+      auto pu = rand1f(rng), pv = rand1f(rng);
+      auto ray = sample_camera(cam, ii[0], ii[1], ii[2], ii[3], pu, pv, lu, lv);
+      auto o   = fout + YH_PATH_BEGIN_OUT * (size_t)r;
+      o[0] = ray.o.x, o[1] = ray.o.y, o[2] = ray.o.z, o[3] = ray.d.x, o[4] = ray.d.y, o[5] = ray.d.z;
+      o[6] = o[7] = o[8] = 0.0f, o[9] = o[10] = o[11] = 1.0f;
+      iout[3 * (size_t)r] = 0, iout[3 * (size_t)r + 1] = 0, iout[3 * (size_t)r + 2] = 0;
+      state[r] = rng.state;
+    } else if (op == YH_PATH_CONTINUE) {
+      auto weight = v3(fin + 3 * (size_t)r);
+      auto bounce = iin[2 * (size_t)r], bounces = iin[2 * (size_t)r + 1];
+      Rng  rng;
+      rng.state = rng_in[2 * (size_t)r], rng.inc = rng_in[2 * (size_t)r + 1];
+      auto goes_on = roulette(weight, bounce, rng);
+      if (goes_on) bounce++, goes_on = bounce < bounces;  // the loop's `bounce++` and `bounce < bounces`
+      auto o = fout + 3 * (size_t)r;
+      o[0] = weight.x, o[1] = weight.y, o[2] = weight.z;
+      iout[2 * (size_t)r] = goes_on ? 1 : 0, iout[2 * (size_t)r + 1] = bounce;
+      state[r] = rng.state;
+    } else {
+      auto f   = fin + YH_PATH_END_IN * (size_t)r;
+      Vec4 acc = {f[4], f[5], f[6], f[7]};
+      accumulate_sample(acc, Vec4{f[0], f[1], f[2], iin[r] ? 1.0f : 0.0f}, f[3]);
+      auto o = fout + 4 * (size_t)r;
+      o[0] = acc.x, o[1] = acc.y, o[2] = acc.z, o[3] = acc.w;
+    }
   }
 }
 

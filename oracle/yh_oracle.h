@@ -67,6 +67,11 @@ void yo_surface_bsdf(int n, const yh_material* materials, const float* normal,
 void yo_volume_batch(int tex, int n, const yh_material* materials, const float* normal, const float* outgoing,
     const float* incoming, const float* texval, const float* rn, float* out);
 
+/* The start and the end of a path (pt.cpp:211-229, 1499-1507, 1676-1689), row by row, by the functions yo_render runs: the
+ * counterpart of yh_path_ends_batch, same arguments (without the form) and the same rows (include/yhair.h: YH_PATH_*).        */
+void yo_path_ends_batch(int op, int n, const float* fin, const int* iin, const uint64_t* rng, float* fout, int* iout,
+    uint64_t* state);
+
 /* math.h:3426-3505,3544-3554 */
 void yo_intersect_line(int n, const float* rays, const float* p0,
     const float* p1, const float* r0, const float* r1, int* hit, float* uv,

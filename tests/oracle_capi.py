@@ -134,6 +134,7 @@ class Oracle(_UnitApi):
         lib.yo_hair_lobe_pdfs.argtypes = [C.c_int, fp, fp, fp]
         lib.yo_surface_bsdf.argtypes = [C.c_int, C.POINTER(yh.Material), fp, fp, fp, fp, fp]
         lib.yo_volume_batch.argtypes = [C.c_int, C.c_int, C.POINTER(yh.Material), fp, fp, fp, fp, fp, fp]
+        lib.yo_path_ends_batch.argtypes = [C.c_int, C.c_int, fp, ip, u64p, fp, ip, u64p]
         lib.yo_scene_create.restype = C.c_void_p
         lib.yo_scene_create.argtypes = [C.POINTER(yh.SceneDesc)]
         lib.yo_scene_create_maps.restype = C.c_void_p
@@ -178,6 +179,25 @@ class Oracle(_UnitApi):
         self.lib.yo_volume_batch(tex, len(normal), mats, yh.fptr(normal), yh.fptr(wo), yh.fptr(wi), yh.fptr(texval4), yh.fptr(rn5),
                                  yh.fptr(out))
         return out
+
+    def path_ends(self, op, fin, iin, rng=None):
+        """The start and the end of a path by the functions the oracle's renders run, the counterpart of yh_path_ends_batch: (fout,
+        iout, state) in its rows; iout and state None for "end"."""
+        op = yh.PATH_OPS.get(op, op)
+        nfi, nii, nfo, nio = yh.PATH_ROWS[op]
+        fin, iin = _f(fin).reshape(-1, nfi), np.ascontiguousarray(iin, np.int32).reshape(-1, nii)
+        n = len(fin)
+        assert len(iin) == n
+        fout = np.zeros((n, nfo), np.float32)
+        if op == yh.PATH_END:
+            self.lib.yo_path_ends_batch(op, n, yh.fptr(fin), yh.iptr(iin), None, yh.fptr(fout), None, None)
+            return fout, None, None
+        rng = np.ascontiguousarray(rng, np.uint64).reshape(-1, 2)
+        assert len(rng) == n
+        iout, state = np.zeros((n, nio), np.int32), np.zeros(n, np.uint64)
+        self.lib.yo_path_ends_batch(op, n, yh.fptr(fin), yh.iptr(iin), rng.ctypes.data_as(u64p), yh.fptr(fout), yh.iptr(iout),
+                                    state.ctypes.data_as(u64p))
+        return fout, iout, state
 
     def scene(self, desc, maps=None):
         """yo_scene_create, or yo_scene_create_maps with `maps`: one MaterialMaps per material (e.g. SceneFile.maps)."""

@@ -91,6 +91,9 @@ int yhk_volume_quads(const yhd_scene* sc, int n, const void* mats, const float* 
 int yhk_volume_lanes(const yhd_scene* sc, int n, const void* mats, const float* normal, const float* outgoing, const float* incoming, const float* texval,
     const float* rn, void* slots, float* out, hipStream_t);
 int yhk_quad_forms(int n, const float* normal, const float* rn, const float* a, const float* b, float* out, hipStream_t);  // unit/volume_quad.hip
+// unit/path_ends_quad.hip, unit/path_ends_lane.hip (yh_path_ends_batch): op = YH_PATH_*, the rows of include/yhair.h; rng 2n (state, inc), state n
+int yhk_path_ends_quads(int op, int n, const float* fin, const int* iin, const uint64_t* rng, float* fout, int* iout, uint64_t* state, hipStream_t);
+int yhk_path_ends_lanes(int op, int n, const float* fin, const int* iin, const uint64_t* rng, float* fout, int* iout, uint64_t* state, hipStream_t);
 // unit/display.hip
 int yhk_display(const yhd_state*, int samples, float exposure, int filmic, int srgb, void* rgba8, hipStream_t);
 int yhk_display_image(const void* rgba, int width, int height, float exposure, int filmic, int srgb, void* rgba8, hipStream_t);  // ... of a float4 image in device memory

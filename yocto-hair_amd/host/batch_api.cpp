@@ -452,6 +452,33 @@ int yh_quad_forms_batch(yh_context* ctx, int n, const float* normal, const float
   return finish(ctx, yhk_quad_forms(n, dn, dr, da, db, o, ctx->stream), out, o, 4 * YH_QUAD_FORMS_FLOATS * (size_t)n);
 }
 
+// The start and the end of a path (dev_path.h: path_begin with sample_camera / sample_camera_lane, path_continue, path_end), row by row.
+int yh_path_ends_batch(yh_context* ctx, int op, int form, int n, const float* fin, const int* iin, const uint64_t* rng, float* fout, int* iout,
+    uint64_t* state) {
+  if (!ctx || n < 1 || op < 0 || op >= YH_PATH_OPS || (form != 0 && form != 1) || !fin || !iin || !fout) return YH_E_INVALID;
+  const bool draws = op != YH_PATH_END;  // (path_end draws nothing and returns no ints)
+  if (draws && (!rng || !iout || !state)) return YH_E_INVALID;
+  static const size_t floats_in[YH_PATH_OPS] = {YH_PATH_BEGIN_IN, YH_PATH_CONTINUE_IN, YH_PATH_END_IN}, ints_in[YH_PATH_OPS] = {4, 2, 1};
+  static const size_t floats_out[YH_PATH_OPS] = {YH_PATH_BEGIN_OUT, YH_PATH_CONTINUE_OUT, YH_PATH_END_OUT}, ints_out[YH_PATH_OPS] = {3, 2, 0};
+  static_assert(sizeof(yhd_camera) == 4 * YH_PATH_BEGIN_IN, "a row of YH_PATH_BEGIN is the kernels' camera");
+  HIPCHK(ctx, hipSetDevice(ctx->device));
+  const size_t rows = (size_t)n;
+  Staged s(ctx);
+  auto   df = (float*)s.in(fin, 4 * floats_in[op] * rows);
+  auto   di = (int*)s.in(iin, 4 * ints_in[op] * rows);
+  auto   dr = draws ? (uint64_t*)s.in(rng, 16 * rows) : nullptr;
+  auto   of = (float*)s.out(4 * floats_out[op] * rows);
+  auto   oi = draws ? (int*)s.out(4 * ints_out[op] * rows) : nullptr;
+  auto   os = draws ? (uint64_t*)s.out(8 * rows) : nullptr;
+  if (s.rc) return s.rc;
+  int e = form == 0 ? yhk_path_ends_quads(op, n, df, di, dr, of, oi, os, ctx->stream) : yhk_path_ends_lanes(op, n, df, di, dr, of, oi, os, ctx->stream);
+  if (int rc = finish(ctx, e, fout, of, 4 * floats_out[op] * rows)) return rc;
+  if (!draws) return YH_OK;
+  HIPCHK(ctx, hipMemcpy(iout, oi, 4 * ints_out[op] * rows, hipMemcpyDeviceToHost));
+  HIPCHK(ctx, hipMemcpy(state, os, 8 * rows, hipMemcpyDeviceToHost));
+  return YH_OK;
+}
+
 // ---- the four self-tests (ext.cpp:555-693) ---------------------------------
 // The host replays the reference's serial structure (seed, loop bounds with
 // the accumulating float counters, per-block draw counts) and hands every

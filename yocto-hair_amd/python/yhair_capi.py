@@ -19,6 +19,10 @@ HAIR_SHADE_FLOATS = 15
 SURFACE_BSDF_FLOATS = 29
 VOLUME_FLOATS = 24
 QUAD_FORMS_FLOATS = 12
+# yh_path_ends_batch: the operations and, per operation, the floats in, ints in, floats out, ints out of a row (include/yhair.h: YH_PATH_*)
+PATH_BEGIN, PATH_CONTINUE, PATH_END = 0, 1, 2
+PATH_OPS = {"begin": PATH_BEGIN, "continue": PATH_CONTINUE, "end": PATH_END}
+PATH_ROWS = {PATH_BEGIN: (17, 4, 12, 3), PATH_CONTINUE: (3, 2, 3, 2), PATH_END: (8, 1, 4, 0)}
 INTERSECT_FORMS = 7  # yh_intersect_plain_batch: forms 0 .. 6
 INTERSECT_TABLE_IN_MEMORY = 16  # ... and, on forms 3 .. 6, the scene level read from memory
 # yh_point_batch: the columns of a row (include/yhair.h: YH_POINT_*)
@@ -290,6 +294,8 @@ _SIGS = {
                                   c_float_p, c_float_p]),
     "yh_point_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_int_p, c_int_p, c_float_p, c_float_p, c_float_p]),
     "yh_quad_forms_batch": (C.c_int, [C.c_void_p, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p]),
+    "yh_path_ends_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, c_float_p, c_int_p, C.POINTER(C.c_uint64), c_float_p, c_int_p,
+                                     C.POINTER(C.c_uint64)]),
     "yh_selftest": (C.c_int, [C.c_void_p, C.c_int, c_float_p]),
     "yh_scene_load": (C.c_void_p, [C.c_char_p, C.c_char_p, C.c_char_p, C.c_int]),
     "yh_scene_get": (C.POINTER(SceneDesc), [C.c_void_p]),
@@ -1004,6 +1010,28 @@ class Context:
         out = np.zeros((n, QUAD_FORMS_FLOATS), np.float32)
         self._chk(self.lib.yh_quad_forms_batch(self.h, n, *(fptr(v) for v in x), fptr(out)))
         return out
+
+    def path_ends(self, op, form, fin, iin, rng=None):
+        """yh_path_ends_batch: the start and the end of a path, row by row (form 0: a quad per row, 1: a lane per row). op, or its
+        name in PATH_OPS: PATH_BEGIN (fin (n, 17) the camera, iin (n, 4) i j w h, rng (n, 2) uint64), PATH_CONTINUE (fin (n, 3) the
+        weight, iin (n, 2) bounce bounces, rng) or PATH_END (fin (n, 8) radiance clamp acc, iin (n, 1) hit). Returns (fout, iout,
+        state): the rows of include/yhair.h, iout and state None for PATH_END."""
+        op = PATH_OPS.get(op, op)
+        nfi, nii, nfo, nio = PATH_ROWS[op]
+        fin, iin = np.ascontiguousarray(fin, np.float32).reshape(-1, nfi), np.ascontiguousarray(iin, np.int32).reshape(-1, nii)
+        n = len(fin)
+        assert len(iin) == n
+        u64 = C.POINTER(C.c_uint64)
+        fout = np.zeros((n, nfo), np.float32)
+        if op == PATH_END:
+            self._chk(self.lib.yh_path_ends_batch(self.h, op, form, n, fptr(fin), iptr(iin), None, fptr(fout), None, None))
+            return fout, None, None
+        rng = np.ascontiguousarray(rng, np.uint64).reshape(-1, 2)
+        assert len(rng) == n
+        iout, state = np.zeros((n, nio), np.int32), np.zeros(n, np.uint64)
+        self._chk(self.lib.yh_path_ends_batch(self.h, op, form, n, fptr(fin), iptr(iin), rng.ctypes.data_as(u64), fptr(fout), iptr(iout),
+                                              state.ctypes.data_as(u64)))
+        return fout, iout, state
 
     def bvh_refit_wide_gpu(self, boxes, primitives, width, slots):
         """yh_bvh_refit_wide_gpu: the refitted copy of `slots` (device form, as from yh_bvh_build_wide_gpu) under the new `boxes`
