@@ -633,6 +633,100 @@ int yh_reproject_gpu(yh_context* ctx, int w, int h, const yh_temporal_params* p,
     const yh_camera* camera, const yh_camera* prev_camera, int num_objects, const float* frames, const float* prev_frames,
     const int* usable, float* out_rgba, int* out_length);
 
+/* VARIANCE (an extension: the reference has no counterpart; the variance estimate of SVGF, Schied et al. 2017, and the filter it steers).
+ * A third image pass beside DENOISE and TEMPORAL: luminance moments ride through TEMPORAL's reprojection (stage M), a spatial estimate
+ * stands in where the moment history is short (stage S), and the a-trous levels filter the variance with the colour and scale their
+ * colour edge stop by it (stage F). lum(v) = (0.2126f v.x + 0.7152f v.y) + 0.0722f v.z. + - x / and comparisons only
+ * (unit/variance_math.h, one text for host and device), so device, host and a float32 restatement give the same bits.
+ *   M moments          per pixel, besides TEMPORAL's quantities: an optional albedo plane and a moment history {M1, M2, steps}, steps an
+ *                      int, 0: none. l = lum(c.rgb / effective albedo), DENOISE's effective albedo (1 without the plane, 1 on a miss);
+ *                      m = (l, l l). Taps, weights, validity, S, N and the blend factor a are TEMPORAL's steps 1 - 7, computed once and
+ *                      shared with the colour: the colour output and length_out have yh_reproject's bits whatever the moments do.
+ *                      Hm = sum w m_q / S over the added taps, summed in tap order; T = the smallest steps among them. There is a moment
+ *                      history when there is a colour history, T > 0 and both of Hm are finite: M_out = Hm + (m - Hm) a and
+ *                      steps_out = min(T, YH_VARIANCE_MAX_STEPS - 1) + 1; without one M_out = m and steps_out = 1. A pass-through pixel
+ *                      (TEMPORAL step 1) gets M_out = 0 and steps_out = 0. vt = d > 0 ? d : 0 with d = M2_out - M1_out M1_out.
+ *   S spatial          after M, over its outputs. steps_out >= min_steps: var = vt. steps_out = 0: var = 0. Otherwise a 7 x 7 window,
+ *                      dy = -3..3 outer, dx = -3..3 inner; a tap counts when it lies inside the image, its steps > 0, it has the pixel's id
+ *                      where `match_object` is set, |x_p - x_q|^2 <= sigma_position^2 of the temporal parameters (TEMPORAL's dot; no test
+ *                      when sigma_position <= 0), and both its moments are finite. Weight 1, one float accumulator per moment, summed
+ *                      in tap order, k the count: A = sum M / (float)k, e = A2 - A1 A1, vs = e > 0 ? e : 0 (0 with no tap),
+ *                      var = vt > vs ? vt : vs.
+ *   F level            per pixel the working colour u of DENOISE and a variance v; the guides are DENOISE's.
+ *                      g = sum k3 v_q / sum k3 over the 3 x 3 neighbours at spacing 1 whatever the level, dy outer, dx inner,
+ *                      k3 = 1/4, 1/8, 1/16 for |dx| + |dy| = 0, 1, 2; taps outside the image, of another id under `match_object`, or
+ *                      with v not finite are skipped; g = 0 with no tap left. The 25 taps are DENOISE's with its h, xn and xx;
+ *                      xl = sigma_luminance > 0 ? (lum(u_p) - lum(u_q))^2 / (sigma_luminance^2 g + epsilon) : 0, x = xn + xx + xl,
+ *                      w = h / (1 + x + 0.5 x x). A tap is skipped under DENOISE's rules and when v_q is not finite.
+ *                      u' = sum w u_q / sum w, v' = sum w w v_q / (sum w sum w). A pixel DENOISE passes unchanged (a miss, sum w = 0,
+ *                      u_p not finite) passes u and v unchanged. After the last level the albedo comes back and the input's alpha; the
+ *                      variance stays that of the working colour's luminance. With sigma_luminance <= 0 the rgb output has the bits of
+ *                      yh_atrous_filter with sigma_color = 0 and otherwise the same parameters.
+ * The moment history lives and dies with TEMPORAL's colour history: kept and dropped by the same events, under the same `usable` rule. A
+ * plain yh_temporal_accumulate* in between advances the colour and marks the moment history as none: the next variance call starts at
+ * steps = 1 with the spatial estimate. The entries change no accumulator, stream, sample count, item cost, trial record or launch shape.
+ * Refusals are TEMPORAL's and DENOISE's, and YH_E_INVALID for guides without the albedo plane where `demodulate` is set, min_steps < 1
+ * and an epsilon that is not > 0; every refusal comes before the first write.                                                          */
+#define YH_VARIANCE_MAX_STEPS 1024
+typedef struct yh_variance_params {
+  int   iterations;
+  float sigma_luminance, sigma_normal, sigma_position;
+  int   demodulate, match_object;
+  float epsilon;
+  int   min_steps;
+} yh_variance_params;
+/* The defaults: 4 iterations, sigma_luminance 2, epsilon 1e-2, min_steps 4, settled on the CPU with the host's forms on the eight-step
+ * orbit of tools/variance_quality.py (profiles/variance/quality.txt); sigma_normal, sigma_position (0.05 x the scene's diagonal, 0
+ * with ctx NULL or before an upload), demodulate and match_object are those of yh_denoise_default_params.                             */
+int yh_variance_default_params(const yh_context* ctx, yh_variance_params* p);
+/* Stages M and S on the context's history. Everything a DEVICE pointer, as yh_temporal_accumulate_device takes them; guides NULL: the
+ * call traces object, position and (where vp->demodulate is set) albedo itself. variance_out: one float per pixel (NULL: kept in the
+ * context only, for yh_denoise_variance_image_device).                                                                               */
+int yh_temporal_accumulate_variance_device(yh_context* ctx, const yh_temporal_params* tp, const yh_variance_params* vp, const void* rgba_in,
+    int samples_in, const yh_gbuffer* guides, void* rgba_out, float* variance_out);
+/* The same with HOST pointers, staged.                                                                                             */
+int yh_temporal_accumulate_variance(yh_context* ctx, const yh_temporal_params* tp, const yh_variance_params* vp, const float* rgba_in,
+    int samples_in, const yh_gbuffer* guides, float* rgba_out, float* variance_out);
+/* Stage F. DEVICE pointers as yh_denoise_image_device takes them (rgba_in is required); variance_in NULL: the variance the context
+ * kept from its last yh_temporal_accumulate_variance* (YH_E_STATE without one of the state's size); variance_out may be NULL.        */
+int yh_denoise_variance_image_device(yh_context* ctx, const yh_variance_params* vp, const void* rgba_in, const float* variance_in,
+    const yh_gbuffer* guides, void* rgba_out, float* variance_out);
+/* The same with HOST pointers, staged; the guides are traced by the call where `guides` is NULL.                                    */
+int yh_denoise_variance_image(yh_context* ctx, const yh_variance_params* vp, const float* rgba_in, const float* variance_in,
+    const yh_gbuffer* guides, float* rgba_out, float* variance_out);
+/* One feature pass (object, normal, position, albedo), then M, S and F on the context's own render, then the tone map, as bytes.     */
+int yh_svgf_display(yh_context* ctx, const yh_temporal_params* tp, const yh_variance_params* vp, float exposure, int filmic, int srgb,
+    uint8_t* rgba8);
+/* The moment history's steps, one int per pixel (steps may be NULL), as yh_temporal_lengths: the pixel count, 0 without a moment
+ * history, < 0 on an error.                                                                                                         */
+int yh_temporal_steps(yh_context* ctx, int* steps);
+/* The stages at unit level on the caller's arrays (HOST pointers; w x h pixels). The plain names are the host's forms (no GPU, no
+ * context), the _gpu names the same arrays through the device kernels. Same bits.
+ * yh_reproject_moments: yh_reproject's arguments, plus albedo (3 floats per pixel, NULL: none), hist_moments (2 floats per pixel) and
+ * hist_steps of the previous step (read only where hist_length is given; both NULL: no moment history, steps 0 everywhere), and the
+ * outputs out_moments and out_steps.
+ * yh_variance_spatial: stage S over a step's outputs; tp gives sigma_position and match_object.
+ * yh_atrous_variance_filter: stage F, all levels; variance one float per pixel; out may be rgba, out_variance may be variance or NULL.
+ * form 0: every tap from memory; form 1: the levels with s <= 4 from a 16 x 16 tile staged with its halo in LDS. After
+ * yh_atrous_variance_filter_gpu, yh_atrous_level_ms reports its kernels as it does yh_atrous_filter_gpu's.                         */
+int yh_reproject_moments(int w, int h, const yh_temporal_params* p, const float* rgba, int samples, const int* object, const float* position,
+    const float* albedo, const float* hist_rgba, const int* hist_length, const int* hist_object, const float* hist_position,
+    const float* hist_moments, const int* hist_steps, const yh_camera* camera, const yh_camera* prev_camera, int num_objects,
+    const float* frames, const float* prev_frames, const int* usable, float* out_rgba, int* out_length, float* out_moments, int* out_steps);
+int yh_reproject_moments_gpu(yh_context* ctx, int w, int h, const yh_temporal_params* p, const float* rgba, int samples, const int* object,
+    const float* position, const float* albedo, const float* hist_rgba, const int* hist_length, const int* hist_object,
+    const float* hist_position, const float* hist_moments, const int* hist_steps, const yh_camera* camera, const yh_camera* prev_camera,
+    int num_objects, const float* frames, const float* prev_frames, const int* usable, float* out_rgba, int* out_length, float* out_moments,
+    int* out_steps);
+int yh_variance_spatial(int w, int h, const yh_temporal_params* tp, int min_steps, const float* moments, const int* steps, const int* object,
+    const float* position, float* out_variance);
+int yh_variance_spatial_gpu(yh_context* ctx, int w, int h, const yh_temporal_params* tp, int min_steps, const float* moments, const int* steps,
+    const int* object, const float* position, float* out_variance);
+int yh_atrous_variance_filter(int w, int h, const yh_variance_params* p, const float* rgba, const float* variance, const int* object,
+    const float* normal, const float* position, const float* albedo, float* out, float* out_variance);
+int yh_atrous_variance_filter_gpu(yh_context* ctx, int form, int w, int h, const yh_variance_params* p, const float* rgba, const float* variance,
+    const int* object, const float* normal, const float* position, const float* albedo, float* out, float* out_variance);
+
 /* Work counters of the launches since the last reset (instrumented build of
  * the same kernel; 0 = ok).                                                  */
 int yh_trace_samples_counted(yh_context* ctx, int nsamples, yh_workcounts* out);

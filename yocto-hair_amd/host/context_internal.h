@@ -206,11 +206,13 @@ struct yh_context {
   int              dn_ms_count = 0;
   // the history of the temporal stage (temporal.cpp; include/yhair.h: TEMPORAL): per pixel hc = {rgb, length bits} and hg = {position, id
   // bits}, twice over — a step reads side `side` and writes the other —, the camera and the objects' frames (12 floats each, copied from
-  // the object rows on the device) it was made under, and per object whether its pixels may be reused (the edits clear it, a step sets it)
+  // the object rows on the device) it was made under, and per object whether its pixels may be reused (the edits clear it, a step sets it).
+  // The variance stage's moment history (include/yhair.h: VARIANCE) is a third plane beside them, hm = {M1, M2, steps bits, vt}, valid while
+  // have_moments (which implies have: it lives and dies with the colour's), and d_var the variance plane of the last step that made one.
   struct Temporal {
-    bool             have = false;
+    bool             have = false, have_moments = false;
     int              width = 0, height = 0, side = 0, num_objects = 0;
-    DevBuf           hc[2], hg[2], d_frames, d_usable;
+    DevBuf           hc[2], hg[2], hm[2], d_var, d_frames, d_usable;
     yh_camera        camera{};
     std::vector<int> usable;
   } tp;

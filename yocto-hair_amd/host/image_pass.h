@@ -5,6 +5,7 @@
 #define YH_IMAGE_PASS_H_
 #include "context_internal.h"
 #include "image_planes.h"
+#include "../unit/variance_launchers.h"  // (the variance stage's kernels, declared outside csrc/: the reason is in that header)
 
 #pragma GCC visibility push(hidden)  // internal to libyhair.so
 // ---- refusals, before anything is written ----
@@ -54,5 +55,15 @@ struct PassTime {
 int ensure_display(yh_context* ctx, bool wait_first);
 // the tone map of the float4 device image `d_img` into d_display (ensured by the caller), timed as a stage of `t`, copied to rgba8, waited for
 int display_tail(yh_context* ctx, const char* who, const void* d_img, float exposure, int filmic, int srgb, uint8_t* rgba8, PassTime& t);
+
+// ---- the temporal history (temporal.cpp), for the variance stage (variance.cpp) that advances it too ----
+// TEMPORAL's refusals with the guide planes of `planes`; one step over given device planes, and one with the guides traced where `guides`
+// is NULL. vp NULL: the plain step; else stages M and S of include/yhair.h: VARIANCE, the variance kept in ctx->tp.d_var and copied to
+// d_var_out where that is not NULL.
+int temporal_checks(yh_context* ctx, const char* who, const yh_temporal_params* p, bool own_render, int samples_in, const yh_gbuffer* guides, unsigned planes);
+int temporal_step(yh_context* ctx, const char* who, const yh_temporal_params& P, const void* d_in, int samples, const yh_gbuffer& g, void* d_out,
+    const yh_variance_params* vp, float* d_var_out);
+int temporal_accumulate(yh_context* ctx, const char* who, const yh_temporal_params& P, const void* d_in, int samples, const yh_gbuffer* guides, void* d_out,
+    const yh_variance_params* vp, float* d_var_out);
 #pragma GCC visibility pop
 #endif

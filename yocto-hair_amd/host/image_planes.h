@@ -56,6 +56,15 @@ inline unsigned filter_planes(const yh_denoise_params* p) {
 // ... the temporal step, and yh_temporal_display's one feature pass for both
 constexpr unsigned temporal_planes() { return plane_bit(PLANE_object) | plane_bit(PLANE_position); }
 inline unsigned    display_planes(const yh_denoise_params* p) { return temporal_planes() | filter_planes(p); }
+// ... the variance stage (include/yhair.h: VARIANCE). Stage M and S (p NULL: the plain temporal step): the temporal planes and, where
+// `demodulate` is set, the albedo. Stage F: what the a-trous filter reads under the same parameters. yh_svgf_display: one feature pass for all.
+inline unsigned moment_planes(const yh_variance_params* p) { return temporal_planes() | (p && p->demodulate ? plane_bit(PLANE_albedo) : 0); }
+inline unsigned variance_filter_planes(const yh_variance_params* p) {
+  if (!p || p->iterations <= 0) return 0;
+  return plane_bit(PLANE_object) | (p->sigma_normal > 0 ? plane_bit(PLANE_normal) : 0) | (p->sigma_position > 0 ? plane_bit(PLANE_position) : 0) |
+         (p->demodulate ? plane_bit(PLANE_albedo) : 0);
+}
+inline unsigned svgf_planes(const yh_variance_params* p) { return moment_planes(p) | variance_filter_planes(p); }
 
 // The guide planes in the order the refusals name them and the passes allocate them.
 constexpr Plane guide_order[4] = {PLANE_object, PLANE_normal, PLANE_position, PLANE_albedo};

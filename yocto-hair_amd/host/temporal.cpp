@@ -13,12 +13,13 @@ static_assert(sizeof(yhd_object) % 4 == 0 && offsetof(yhd_object, frame) == 0 &&
 const float* floats_of(const yh_camera& c) { return c.frame; }  // (frame, lens, film, focus, aperture: contiguous)
 
 // what every context entry refuses, before anything is written
-int context_checks(yh_context* ctx, const char* who, const yh_temporal_params* p, bool own_render, int samples_in, const yh_gbuffer* guides) {
+int context_checks(yh_context* ctx, const char* who, const yh_temporal_params* p, bool own_render, int samples_in, const yh_gbuffer* guides,
+    unsigned planes = temporal_planes()) {
   if (!p) return fail(ctx, YH_E_INVALID, "%s: params is NULL", who);
   if (!yht::params_ok(*p)) return fail(ctx, YH_E_INVALID, "%s: max_history %d (1 .. 2^30)", who, p->max_history);
   if (!own_render && !yht::samples_ok(samples_in)) return fail(ctx, YH_E_INVALID, "%s: an image with %d samples (1 .. 2^30)", who, samples_in);
   if (guides)
-    if (const char* m = missing_plane(temporal_planes(), *guides)) return fail(ctx, YH_E_INVALID, "%s: the guide plane `%s` is NULL", who, m);
+    if (const char* m = missing_plane(planes, *guides)) return fail(ctx, YH_E_INVALID, "%s: the guide plane `%s` is NULL", who, m);
   if (int rc = state_checks(ctx, who, CHECK_POISONED | NEED_SCENE | NEED_STATE | (own_render ? OWN_RENDER : 0))) return rc;
   if (own_render && ctx->state.samples_done < 1) return fail(ctx, YH_E_STATE, "%s: rgba_in is NULL and no sample has been traced", who);
   if (own_render && !yht::samples_ok(ctx->state.samples_done)) return fail(ctx, YH_E_INVALID, "%s: too many samples", who);
@@ -28,15 +29,20 @@ int context_checks(yh_context* ctx, const char* who, const yh_temporal_params* p
 
 // One step on the device, blocking: d_in (NULL: the own render) with `samples` samples and the device planes object / position of `g` ->
 // d_out (may be NULL, or d_in) and the other side of the history, which becomes the history. Sets yh_last_trace_ms.
-int step_on_device(yh_context* ctx, const char* who, const yh_temporal_params& P, const void* d_in, int samples, const yh_gbuffer& g, void* d_out) {
+// vp NULL: the plain step, which marks the moment history as none. Else stages M and S of include/yhair.h: VARIANCE — the moment history
+// beside the colour's, g.albedo where vp->demodulate is set, the variance into the context's plane and (d_var_out not NULL) a copy there.
+int step_on_device(yh_context* ctx, const char* who, const yh_temporal_params& P, const void* d_in, int samples, const yh_gbuffer& g, void* d_out,
+    const yh_variance_params* vp = nullptr, float* d_var_out = nullptr) {
   yh_context::Temporal& T = ctx->tp;
   const int    w = ctx->state.width, h = ctx->state.height, nobj = ctx->scene.num_objects;
   const size_t npix = (size_t)w * h;
   const bool   have = T.have && T.width == w && T.height == h && T.num_objects == nobj;
   const int    from = T.side, to = 1 - T.side;
-  for (DevBuf* b : {&T.hc[to], &T.hg[to]})
-    if (b->bytes < npix * 16)
+  for (DevBuf* b : {&T.hc[to], &T.hg[to], &T.hm[to]})
+    if (b->bytes < npix * 16 && (vp || b != &T.hm[to]))
       if (int rc = dev_alloc(ctx, *b, npix * 16)) return rc;
+  if (vp && T.d_var.bytes < npix * 4)
+    if (int rc = dev_alloc(ctx, T.d_var, npix * 4)) return rc;
   if (T.d_frames.bytes < (size_t)nobj * 48)
     if (int rc = dev_alloc(ctx, T.d_frames, (size_t)nobj * 48)) return rc;
   if (T.d_usable.bytes < (size_t)nobj * 4)
@@ -49,36 +55,59 @@ int step_on_device(yh_context* ctx, const char* who, const yh_temporal_params& P
   }
   const yh_camera now = ctx->key_camera;
   if (int rc = timed_begin(ctx)) return rc;
-  int e = yhk_reproject(d_in, ctx->state.accum, d_in ? samples : ctx->state.samples_done, g.object, g.position, w, h, T.hc[from].p, T.hg[from].p, have ? 1 : 0,
-      floats_of(now), floats_of(have ? T.camera : now), have && nobj > 0 ? &m : nullptr, &P, T.hc[to].p, T.hg[to].p, d_out, ctx->stream);
-  if (e) return fail(ctx, YH_E_DEVICE, "%s: k_reproject launch: %s", who, hipGetErrorString((hipError_t)e));
+  const int n = d_in ? samples : ctx->state.samples_done;
+  int       e;
+  if (vp) {
+    e = yhk_reproject_m(d_in, ctx->state.accum, n, g.object, g.position, vp->demodulate ? g.albedo : nullptr, w, h, T.hc[from].p, T.hg[from].p,
+        have && T.have_moments ? T.hm[from].p : nullptr, have ? 1 : 0, floats_of(now), floats_of(have ? T.camera : now), have && nobj > 0 ? &m : nullptr, &P,
+        T.hc[to].p, T.hg[to].p, T.hm[to].p, d_out, ctx->stream);
+    if (!e) e = yhk_var_spatial(w, h, &P, vp->min_steps, T.hm[to].p, T.hg[to].p, (float*)T.d_var.p, ctx->stream);
+  } else {
+    e = yhk_reproject(d_in, ctx->state.accum, n, g.object, g.position, w, h, T.hc[from].p, T.hg[from].p, have ? 1 : 0, floats_of(now),
+        floats_of(have ? T.camera : now), have && nobj > 0 ? &m : nullptr, &P, T.hc[to].p, T.hg[to].p, d_out, ctx->stream);
+  }
+  if (e) return fail(ctx, YH_E_DEVICE, "%s: %s launch: %s", who, vp ? "k_reproject_m / k_var_spatial" : "k_reproject", hipGetErrorString((hipError_t)e));
   if (int rc = timed_stop(ctx)) return rc;
+  if (vp && d_var_out) HIPCHK(ctx, hipMemcpyAsync(d_var_out, T.d_var.p, npix * 4, hipMemcpyDeviceToDevice, ctx->stream));
   if (nobj > 0)  // the frames this step's history was made under: the rows' own, after the kernel that read the previous ones
     HIPCHK(ctx, hipMemcpy2DAsync(T.d_frames.p, 48, ctx->d_objects.p, sizeof(yhd_object), 48, (size_t)nobj, hipMemcpyDeviceToDevice, ctx->stream));
-  T.have = false;  // (an error below leaves no history)
-  if (int rc = timed_read(ctx, 1)) return rc;
-  T.have = true, T.width = w, T.height = h, T.side = to, T.num_objects = nobj, T.camera = now;
+  T.have = T.have_moments = false;  // (an error below leaves no history)
+  if (int rc = timed_read(ctx, vp ? 2 : 1)) return rc;
+  T.have = true, T.have_moments = vp != nullptr, T.width = w, T.height = h, T.side = to, T.num_objects = nobj, T.camera = now;
   T.usable.assign((size_t)nobj, 1);
   return YH_OK;
 }
 
 // ... with the guides traced here where none are given (guides: DEVICE planes)
-int accumulate_on_device(yh_context* ctx, const char* who, const yh_temporal_params& P, const void* d_in, int samples, const yh_gbuffer* guides, void* d_out) {
-  if (guides) return step_on_device(ctx, who, P, d_in, samples, *guides, d_out);
+int accumulate_on_device(yh_context* ctx, const char* who, const yh_temporal_params& P, const void* d_in, int samples, const yh_gbuffer* guides, void* d_out,
+    const yh_variance_params* vp = nullptr, float* d_var_out = nullptr) {
+  if (guides) return step_on_device(ctx, who, P, d_in, samples, *guides, d_out, vp, d_var_out);
   Staged     own(ctx);
   yh_gbuffer g{};
   PassTime   t;
-  if (int rc = trace_guides(own, who, temporal_planes(), g)) return rc;
+  if (int rc = trace_guides(own, who, moment_planes(vp), g)) return rc;
   t.add(ctx);
-  if (int rc = step_on_device(ctx, who, P, d_in, samples, g, d_out)) return rc;
+  if (int rc = step_on_device(ctx, who, P, d_in, samples, g, d_out, vp, d_var_out)) return rc;
   t.add(ctx);
   return YH_OK;
 }
 }  // namespace
 
-void temporal_drop(yh_context* ctx) { ctx->tp.have = false; }
+void temporal_drop(yh_context* ctx) { ctx->tp.have = ctx->tp.have_moments = false; }
 void temporal_mark_object(yh_context* ctx, int object) {
   if (ctx->tp.have && object >= 0 && (size_t)object < ctx->tp.usable.size()) ctx->tp.usable[(size_t)object] = 0;
+}
+// for variance.cpp (image_pass.h): the history is this file's, whichever stage advances it
+int temporal_checks(yh_context* ctx, const char* who, const yh_temporal_params* p, bool own_render, int samples_in, const yh_gbuffer* guides, unsigned planes) {
+  return context_checks(ctx, who, p, own_render, samples_in, guides, planes);
+}
+int temporal_step(yh_context* ctx, const char* who, const yh_temporal_params& P, const void* d_in, int samples, const yh_gbuffer& g, void* d_out,
+    const yh_variance_params* vp, float* d_var_out) {
+  return step_on_device(ctx, who, P, d_in, samples, g, d_out, vp, d_var_out);
+}
+int temporal_accumulate(yh_context* ctx, const char* who, const yh_temporal_params& P, const void* d_in, int samples, const yh_gbuffer* guides, void* d_out,
+    const yh_variance_params* vp, float* d_var_out) {
+  return accumulate_on_device(ctx, who, P, d_in, samples, guides, d_out, vp, d_var_out);
 }
 
 int yh_temporal_default_params(const yh_context* ctx, yh_temporal_params* p) {

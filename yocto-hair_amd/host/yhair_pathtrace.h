@@ -728,6 +728,31 @@ inline image<vec4f> accumulate_image(state* st, const scene*, const camera*, con
   if (dparams) detail::check(yh_denoise(ctx, dparams, (const float*)out.pixels.data(), (float*)out.pixels.data()), ctx);
   return out;
 }
+// EXTENSION (no reference counterpart; off unless called): accumulate_image with the variance stage (include/yhair.h: VARIANCE) — the state's
+// image accumulated with luminance moments beside the colour, the per-pixel variance estimated from them, and the accumulated image through
+// the a-trous levels that variance steers. `variance` (optional) receives the filtered variance, one float per pixel. The history is
+// accumulate_image's: a call of either advances it, a plain accumulate_image in between starts the moments afresh.
+using variance_params = yh_variance_params;
+inline variance_params default_variance_params() {
+  variance_params p;
+  detail::check(yh_variance_default_params(detail::require_context(), &p));
+  return p;
+}
+inline image<vec4f> accumulate_image_variance(state* st, const scene*, const camera*, const trace_params&, const temporal_params& tparams,
+    const variance_params& vparams, std::vector<float>* variance = nullptr, bool filtered = true) {
+  bind_state(st);
+  download(st);
+  image<vec4f> out;
+  out.width = st->width, out.height = st->height, out.pixels.resize((size_t)st->width * st->height);
+  if (variance) variance->resize(out.pixels.size());
+  auto   ctx = detail::require_context();
+  float* var = variance ? variance->data() : nullptr;
+  detail::check(yh_temporal_accumulate_variance(ctx, &tparams, &vparams, (const float*)st->render.data(), st->samples, nullptr, (float*)out.pixels.data(),
+                    filtered ? nullptr : var), ctx);
+  if (filtered)  // (else: the accumulated image and the variance estimate as they are, for a caller that filters the last step only)
+    detail::check(yh_denoise_variance_image(ctx, &vparams, (const float*)out.pixels.data(), nullptr, nullptr, (float*)out.pixels.data(), var), ctx);
+  return out;
+}
 inline void reset_accumulation() { detail::check(yh_temporal_reset(detail::require_context())); }
 }  // namespace yhair::pathtrace
 #endif

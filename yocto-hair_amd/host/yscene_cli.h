@@ -174,7 +174,34 @@ inline void save_denoised(ptr::state* state, const ptr::scene* scene, const ptr:
 // (ptr::accumulate_image with the library's default parameters, on context 0 whatever --gpus says); at the last step the accumulated
 // image is written to `name` and, with --denoise FILE given too, denoised (the library's defaults) to `denoised_name`
 inline void accumulate_step(ptr::state* state, const ptr::scene* scene, const ptr::camera* camera, const ptr::trace_params& params, const std::string& name,
-    const std::string& denoised_name, bool last) {
+    const std::string& denoised_name, bool last, bool variance_guided = false, const std::string& variance_name = "") {
+  if (variance_guided || !variance_name.empty()) {
+    // "--variance-guided" / "--variance FILE": the steps accumulate with the variance stage's moments beside the colour
+    // (ptr::accumulate_image_variance, the library's defaults); at the last step the accumulated image goes to `name`, the variance estimate
+    // as a grey image to `variance_name`, and `denoised_name` holds the accumulated image through the variance-guided levels
+    // (--variance-guided) or through yh_denoise's
+    const auto         vp = ptr::default_variance_params();
+    std::vector<float> var;
+    auto               img = ptr::accumulate_image_variance(state, scene, camera, params, ptr::default_temporal_params(), vp, &var, false);
+    if (!last) return;
+    char error[512];
+    if (yh_save_image(name.c_str(), img.width, img.height, (const float*)img.pixels.data(), error, sizeof(error)) != YH_OK) print_fatal(error);
+    printf("save accumulated: %s\n", name.c_str());
+    if (!variance_name.empty()) {
+      std::vector<vec4f> grey(var.size());
+      for (size_t i = 0; i < var.size(); i++) grey[i] = {var[i], var[i], var[i], 1.0f};
+      if (yh_save_image(variance_name.c_str(), img.width, img.height, (const float*)grey.data(), error, sizeof(error)) != YH_OK) print_fatal(error);
+      printf("save variance: %s\n", variance_name.c_str());
+    }
+    if (denoised_name.empty()) return;
+    const auto dp = ptr::default_denoise_params();
+    const int  rc = variance_guided ? yh_denoise_variance_image(yhair::detail::context(), &vp, (const float*)img.pixels.data(), nullptr, nullptr, (float*)img.pixels.data(), nullptr)
+                                    : yh_denoise(yhair::detail::context(), &dp, (const float*)img.pixels.data(), (float*)img.pixels.data());
+    if (rc != YH_OK) print_fatal("the filter of the accumulated image failed");
+    if (yh_save_image(denoised_name.c_str(), img.width, img.height, (const float*)img.pixels.data(), error, sizeof(error)) != YH_OK) print_fatal(error);
+    printf("save accumulated and denoised: %s\n", denoised_name.c_str());
+    return;
+  }
   auto img = ptr::accumulate_image(state, scene, camera, params, ptr::default_temporal_params());
   if (!last) return;
   char error[512];

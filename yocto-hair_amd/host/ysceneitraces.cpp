@@ -53,9 +53,9 @@ static void update_turntable(frame3f& frame, float& focus, const vec2f& rotate) 
 
 int main(int argc, const char* argv[]) {
   auto        params = ptr::trace_params{};
-  std::string camera_name, imagename = "out.hdr", preview_name, filename, shader = "path", features, features_mode_name = "centre", denoise, temporal;
+  std::string camera_name, imagename = "out.hdr", preview_name, filename, shader = "path", features, features_mode_name = "centre", denoise, temporal, variance;
   int         stop_after_ms = -1, gpus = 1, first_device = 0, turntable = 0;
-  bool        turn_objects = false, sway_refit = false;
+  bool        turn_objects = false, sway_refit = false, variance_guided = false;
   int         sway = 0;
   std::string device_list;
   for (int i = 1; i < argc; i++) {
@@ -69,7 +69,7 @@ int main(int argc, const char* argv[]) {
              "                     [--bounces,-b N] [--clamp F] [--output,-o FILE] [--pratio N] [--preview-image FILE]\n"
              "                     [--stop-after-ms N] [--seed N] [--device N] [--gpus N] [--devices A,B,..] [--turntable STEPS [--turntable-objects]]\n"
              "                     [--sway STEPS [--sway-refit]] [--features PREFIX] [--features-mode centre|next] [--denoise FILE]\n"
-             "                     [--temporal FILE] scene\n"
+             "                     [--temporal FILE [--variance-guided] [--variance FILE]] scene\n"
              "Progressive path tracing of hair scenes on MI355X (headless: preview pass, then samples until done or stopped)\n");
       return 0;
     } else if (a == "--camera") camera_name = next();
@@ -94,6 +94,8 @@ int main(int argc, const char* argv[]) {
     else if (a == "--features-mode") features_mode_name = next();
     else if (a == "--denoise") denoise = next();
     else if (a == "--temporal") temporal = next();
+    else if (a == "--variance-guided") variance_guided = true;
+    else if (a == "--variance") variance = next();
     else if (!a.empty() && a[0] == '-') print_fatal("unknown option " + a);
     else filename = a;
   }
@@ -102,6 +104,8 @@ int main(int argc, const char* argv[]) {
   if (sway_refit && sway <= 0) print_fatal("--sway-refit needs --sway STEPS");
   if (sway > 0 && turntable > 0) print_fatal("--sway and --turntable are gestures of their own");
   if (!temporal.empty() && turntable <= 0) print_fatal("--temporal needs --turntable STEPS");
+  if (variance_guided && (temporal.empty() || denoise.empty())) print_fatal("--variance-guided needs --temporal FILE and --denoise FILE");
+  if (!variance.empty() && temporal.empty()) print_fatal("--variance needs --temporal FILE");
   if (!temporal.empty()) params.pratio = 1;  // (the history lives at one image size: the preview pass has the render's)
   yh_set_trial_cache_dir(yh_default_trial_cache_dir());  // the command line keeps its kernel-trial record on disk (include/yhair.h); a library caller has to ask
   set_devices(first_device, gpus, device_list);
@@ -176,8 +180,9 @@ int main(int argc, const char* argv[]) {
     if (yh_save_image(imagename.c_str(), W, H, (const float*)render.data(), error, sizeof(error)) != YH_OK) print_fatal(error);
     printf("save image: %s\n", imagename.c_str());
     // --temporal FILE: this step's finished render joins the steps before it (yscene_cli.h: accumulate_step); the last step's accumulated
-    // image is written, and with --denoise FILE that file holds it denoised
-    if (!temporal.empty() && render_state->samples > 0) accumulate_step(render_state.get(), scene.get(), camera, params, temporal, denoise, last);
+    // image is written, and with --denoise FILE that file holds it denoised — by the variance-guided levels with --variance-guided;
+    // --variance FILE holds the last step's variance estimate
+    if (!temporal.empty() && render_state->samples > 0) accumulate_step(render_state.get(), scene.get(), camera, params, temporal, denoise, last, variance_guided, variance);
     };
     if (sway > 0) {  // the vertex edit's gesture: step k displaces the first line shape by x += a_k y^2, a_k = 0.1 k / STEPS, tangents recomputed
       const size_t slash = imagename.find_last_of('/'), dot = imagename.find_last_of('.');

@@ -139,6 +139,21 @@ class TemporalParams(C.Structure):
         return q
 
 
+VARIANCE_MAX_STEPS = 1024
+
+
+class VarianceParams(C.Structure):
+    """yh_variance_params (include/yhair.h: VARIANCE)."""
+    _fields_ = [("iterations", C.c_int), ("sigma_luminance", C.c_float), ("sigma_normal", C.c_float), ("sigma_position", C.c_float),
+                ("demodulate", C.c_int), ("match_object", C.c_int), ("epsilon", C.c_float), ("min_steps", C.c_int)]
+
+    def copy(self, **changes):
+        q = VarianceParams.from_buffer_copy(self)
+        for k, v in changes.items():
+            setattr(q, k, v)
+        return q
+
+
 class WorkCounts(C.Structure):
     _fields_ = [(n, C.c_uint64) for n in ("samples", "rays", "nodes", "seg_tests", "tri_tests",
                                           "hair_shades", "surf_shades", "env_lookups",
@@ -254,6 +269,27 @@ _SIGS = {
                                C.POINTER(Camera), C.POINTER(Camera), C.c_int, c_float_p, c_float_p, c_int_p, c_float_p, c_int_p]),
     "yh_reproject_gpu": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(TemporalParams), c_float_p, C.c_int, c_int_p, c_float_p, c_float_p, c_int_p, c_int_p,
                                    c_float_p, C.POINTER(Camera), C.POINTER(Camera), C.c_int, c_float_p, c_float_p, c_int_p, c_float_p, c_int_p]),
+    "yh_variance_default_params": (C.c_int, [C.c_void_p, C.POINTER(VarianceParams)]),
+    "yh_temporal_accumulate_variance_device": (C.c_int, [C.c_void_p, C.POINTER(TemporalParams), C.POINTER(VarianceParams), C.c_void_p, C.c_int, C.POINTER(GBuffer),
+                                                         C.c_void_p, C.c_void_p]),
+    "yh_temporal_accumulate_variance": (C.c_int, [C.c_void_p, C.POINTER(TemporalParams), C.POINTER(VarianceParams), c_float_p, C.c_int, C.POINTER(GBuffer),
+                                                  c_float_p, c_float_p]),
+    "yh_denoise_variance_image_device": (C.c_int, [C.c_void_p, C.POINTER(VarianceParams), C.c_void_p, C.c_void_p, C.POINTER(GBuffer), C.c_void_p, C.c_void_p]),
+    "yh_denoise_variance_image": (C.c_int, [C.c_void_p, C.POINTER(VarianceParams), c_float_p, c_float_p, C.POINTER(GBuffer), c_float_p, c_float_p]),
+    "yh_svgf_display": (C.c_int, [C.c_void_p, C.POINTER(TemporalParams), C.POINTER(VarianceParams), C.c_float, C.c_int, C.c_int, C.POINTER(C.c_uint8)]),
+    "yh_temporal_steps": (C.c_int, [C.c_void_p, c_int_p]),
+    "yh_reproject_moments": (C.c_int, [C.c_int, C.c_int, C.POINTER(TemporalParams), c_float_p, C.c_int, c_int_p, c_float_p, c_float_p, c_float_p, c_int_p, c_int_p,
+                                       c_float_p, c_float_p, c_int_p, C.POINTER(Camera), C.POINTER(Camera), C.c_int, c_float_p, c_float_p, c_int_p, c_float_p, c_int_p,
+                                       c_float_p, c_int_p]),
+    "yh_reproject_moments_gpu": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(TemporalParams), c_float_p, C.c_int, c_int_p, c_float_p, c_float_p, c_float_p, c_int_p,
+                                           c_int_p, c_float_p, c_float_p, c_int_p, C.POINTER(Camera), C.POINTER(Camera), C.c_int, c_float_p, c_float_p, c_int_p, c_float_p,
+                                           c_int_p, c_float_p, c_int_p]),
+    "yh_variance_spatial": (C.c_int, [C.c_int, C.c_int, C.POINTER(TemporalParams), C.c_int, c_float_p, c_int_p, c_int_p, c_float_p, c_float_p]),
+    "yh_variance_spatial_gpu": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.POINTER(TemporalParams), C.c_int, c_float_p, c_int_p, c_int_p, c_float_p, c_float_p]),
+    "yh_atrous_variance_filter": (C.c_int, [C.c_int, C.c_int, C.POINTER(VarianceParams), c_float_p, c_float_p, c_int_p, c_float_p, c_float_p, c_float_p, c_float_p,
+                                            c_float_p]),
+    "yh_atrous_variance_filter_gpu": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(VarianceParams), c_float_p, c_float_p, c_int_p, c_float_p, c_float_p,
+                                                c_float_p, c_float_p, c_float_p]),
     "yh_trace_samples_counted": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(WorkCounts)]),
     "yh_last_trace_ms": (C.c_int, [C.c_void_p, c_float_p, c_int_p]),
     "yh_launch_shape": (C.c_int, [C.c_void_p]),
@@ -447,6 +483,78 @@ def reproject(params, rgba, samples, object, position, history, camera, prev_cam
     if rc != YH_OK:
         raise YhError(f"yhair error {rc}: yh_reproject")
     return out, length
+
+
+# the variance stage (include/yhair.h: VARIANCE)
+def variance_default_params(ctx=None):
+    """yh_variance_default_params: the defaults, sigma_position from the scene `ctx` (a Context) has uploaded, 0 without one."""
+    p = VarianceParams()
+    rc = load().yh_variance_default_params(ctx.h if ctx is not None else None, C.byref(p))
+    if rc != YH_OK:
+        raise YhError(f"yhair error {rc}: yh_variance_default_params")
+    return p
+
+
+def _moment_args(rgba, samples, object, position, albedo, history, moment_history, camera, prev_camera, frames, prev_frames, usable):
+    """The arguments of yh_reproject_moments after (w, h, params): _reproject_args' with albedo (H, W, 3) or None and
+    moment_history = None or (moments (H, W, 2), steps (H, W)) of the previous step."""
+    w, h, held, a, out, length = _reproject_args(rgba, samples, object, position, history, camera, prev_camera, frames, prev_frames, usable)
+    albedo = np.ascontiguousarray(albedo, np.float32) if albedo is not None else None
+    hm = [None, None]
+    if moment_history is not None:
+        hm = [np.ascontiguousarray(moment_history[0], np.float32), np.ascontiguousarray(moment_history[1], np.int32)]
+        assert hm[0].shape == (h, w, 2) and hm[1].shape == (h, w)
+    assert albedo is None or albedo.shape == (h, w, 3)
+    moments, steps = np.zeros((h, w, 2), np.float32), np.zeros((h, w), np.int32)
+    held += [albedo] + hm
+    opt = lambda x, f: f(x) if x is not None else None  # noqa: E731
+    args = a[:4] + [opt(albedo, fptr)] + a[4:8] + [opt(hm[0], fptr), opt(hm[1], iptr)] + a[8:] + [fptr(moments), iptr(steps)]
+    return w, h, held, args, (out, length, moments, steps)
+
+
+def reproject_moments(params, rgba, samples, object, position, albedo, history, moment_history, camera, prev_camera=None, frames=None, prev_frames=None,
+                      usable=None):
+    """yh_reproject_moments (host, no GPU): stage M; returns (out_rgba, out_length, out_moments, out_steps)."""
+    w, h, held, args, outs = _moment_args(rgba, samples, object, position, albedo, history, moment_history, camera, prev_camera, frames, prev_frames, usable)
+    rc = load().yh_reproject_moments(w, h, C.byref(params) if params is not None else None, *args)
+    if rc != YH_OK:
+        raise YhError(f"yhair error {rc}: yh_reproject_moments")
+    return outs
+
+
+def _spatial_args(moments, steps, object, position):
+    moments, steps = np.ascontiguousarray(moments, np.float32), np.ascontiguousarray(steps, np.int32)
+    object, position = np.ascontiguousarray(object, np.int32), np.ascontiguousarray(position, np.float32)
+    h, w = steps.shape
+    assert moments.shape == (h, w, 2) and object.shape == (h, w) and position.shape == (h, w, 3)
+    out = np.zeros((h, w), np.float32)
+    return w, h, [moments, steps, object, position], [fptr(moments), iptr(steps), iptr(object), fptr(position), fptr(out)], out
+
+
+def variance_spatial(temporal_params, min_steps, moments, steps, object, position):
+    """yh_variance_spatial (host, no GPU): stage S over a step's moments and steps; returns the (H, W) variance."""
+    w, h, held, ptrs, out = _spatial_args(moments, steps, object, position)
+    rc = load().yh_variance_spatial(w, h, C.byref(temporal_params), int(min_steps), *ptrs)
+    if rc != YH_OK:
+        raise YhError(f"yhair error {rc}: yh_variance_spatial")
+    return out
+
+
+def _vfilter_args(rgba, variance, object, normal, position, albedo):
+    w, h, held, ptrs, out = _filter_args(rgba, object, normal, position, albedo)
+    variance = np.ascontiguousarray(variance, np.float32)
+    assert variance.shape == (h, w)
+    out_variance = np.zeros((h, w), np.float32)
+    return w, h, held + [variance], ptrs[:1] + [fptr(variance)] + ptrs[1:] + [fptr(out), fptr(out_variance)], (out, out_variance)
+
+
+def atrous_variance_filter(params, rgba, variance, object, normal=None, position=None, albedo=None):
+    """yh_atrous_variance_filter (host, no GPU): stage F; returns (out (H, W, 4), out_variance (H, W))."""
+    w, h, held, ptrs, outs = _vfilter_args(rgba, variance, object, normal, position, albedo)
+    rc = load().yh_atrous_variance_filter(w, h, C.byref(params), *ptrs)
+    if rc != YH_OK:
+        raise YhError(f"yhair error {rc}: yh_atrous_variance_filter")
+    return outs
 
 
 def set_trial_cache_dir(path=None, default=False):
@@ -895,6 +1003,126 @@ class Context:
         w, h, held, args, out, length = _reproject_args(rgba, samples, object, position, history, camera, prev_camera, frames, prev_frames, usable)
         self._chk(self.lib.yh_reproject_gpu(self.h, w, h, C.byref(params) if params is not None else None, *args))
         return out, length
+
+    # the variance stage (include/yhair.h: VARIANCE)
+    def variance_default_params(self):
+        return variance_default_params(self)
+
+    def _variance_guides(self, planes):
+        """A GBuffer of host arrays from {name: array or None}; None when no plane is given."""
+        kinds = {n: (t, c) for n, t, c in GBUFFER_PLANES}
+        g, held = GBuffer(), []
+        for n, a in planes.items():
+            if a is not None:
+                held.append(np.ascontiguousarray(a, kinds[n][0]))
+                setattr(g, n, iptr(held[-1]) if kinds[n][0] is np.int32 else fptr(held[-1]))
+        return (g, held) if held else (None, held)
+
+    def temporal_accumulate_variance(self, params=None, variance_params=None, rgba=None, samples=0, object=None, position=None, albedo=None):
+        """yh_temporal_accumulate_variance: temporal_accumulate with the moment history beside the colour's (stages M and S); returns
+        (accumulated image (H, W, 4), variance (H, W)). object / position / albedo: centre-mode planes (none: traced by the call)."""
+        params = params if params is not None else self.temporal_default_params()
+        variance_params = variance_params if variance_params is not None else self.variance_default_params()
+        rgba = np.ascontiguousarray(rgba, np.float32) if rgba is not None else None
+        h, w = getattr(self, "height", 0), getattr(self, "width", 0)
+        out, var = np.zeros((h, w, 4), np.float32), np.zeros((h, w), np.float32)
+        assert rgba is None or rgba.shape == out.shape
+        g, held = self._variance_guides(dict(object=object, position=position, albedo=albedo))
+        self._chk(self.lib.yh_temporal_accumulate_variance(self.h, C.byref(params), C.byref(variance_params), fptr(rgba) if rgba is not None else None,
+                                                           int(samples), C.byref(g) if g is not None else None, fptr(out), fptr(var)))
+        return out, var
+
+    def denoise_variance_image(self, variance_params, rgba, variance=None, **guides):
+        """yh_denoise_variance_image: stage F over the (H, W, 4) image `rgba`; variance None: the one the context kept from its last
+        temporal_accumulate_variance; guides: object / normal / position / albedo host planes, none: traced by the call. Returns
+        (filtered image, filtered variance)."""
+        rgba = np.ascontiguousarray(rgba, np.float32)
+        variance = np.ascontiguousarray(variance, np.float32) if variance is not None else None
+        out, var = np.zeros_like(rgba), np.zeros(rgba.shape[:2], np.float32)
+        g, held = self._variance_guides(guides)
+        self._chk(self.lib.yh_denoise_variance_image(self.h, C.byref(variance_params), fptr(rgba), fptr(variance) if variance is not None else None,
+                                                     C.byref(g) if g is not None else None, fptr(out), fptr(var)))
+        return out, var
+
+    def _device_call(self, what, tensors):
+        """data_ptr()s of contiguous torch tensors on the GPU (None stays None): {name: (tensor, dtype name, comps)}"""
+        import torch
+        npix, ptrs = self.height * self.width, {}
+        for n, (t, dtype, comps) in tensors.items():
+            dtype = getattr(torch, dtype)
+            if t is not None and (not isinstance(t, torch.Tensor) or not t.is_cuda or t.dtype != dtype or not t.is_contiguous() or t.numel() < npix * comps):
+                raise YhError(f"{what}: {n} must be a contiguous {dtype} tensor on the GPU of at least {self.height} x {self.width} x {comps} elements")
+            ptrs[n] = t.data_ptr() if t is not None else None
+        torch.cuda.synchronize()
+        return ptrs
+
+    def _device_guides(self, ptrs, names):
+        if all(ptrs[n] is None for n in names):
+            return None
+        g = GBuffer()
+        for n in names:
+            if ptrs[n] is not None:
+                setattr(g, n, C.cast(ptrs[n], c_int_p if n == "object" else c_float_p))
+        return g
+
+    def temporal_accumulate_variance_device(self, params, variance_params, rgba_out=None, variance_out=None, rgba_in=None, samples=0, object=None, position=None,
+                                            albedo=None):
+        """yh_temporal_accumulate_variance_device: contiguous torch tensors on the context's device, as temporal_accumulate_device takes
+        them, with a float32 (H, W) variance_out and a float32 (H, W, 3) albedo."""
+        p = self._device_call("temporal_accumulate_variance_device", dict(
+            rgba_out=(rgba_out, "float32", 4), variance_out=(variance_out, "float32", 1), rgba_in=(rgba_in, "float32", 4), object=(object, "int32", 1),
+            position=(position, "float32", 3), albedo=(albedo, "float32", 3)))
+        g = self._device_guides(p, ("object", "position", "albedo"))
+        self._chk(self.lib.yh_temporal_accumulate_variance_device(self.h, C.byref(params), C.byref(variance_params), p["rgba_in"], int(samples),
+                                                                  C.byref(g) if g is not None else None, p["rgba_out"], p["variance_out"]))
+
+    def denoise_variance_image_device(self, variance_params, rgba_out, rgba_in, variance_in=None, variance_out=None, object=None, normal=None, position=None,
+                                      albedo=None):
+        """yh_denoise_variance_image_device: contiguous torch tensors on the context's device (variance_in None: the context's own)."""
+        p = self._device_call("denoise_variance_image_device", dict(
+            rgba_out=(rgba_out, "float32", 4), rgba_in=(rgba_in, "float32", 4), variance_in=(variance_in, "float32", 1), variance_out=(variance_out, "float32", 1),
+            object=(object, "int32", 1), normal=(normal, "float32", 3), position=(position, "float32", 3), albedo=(albedo, "float32", 3)))
+        g = self._device_guides(p, ("object", "normal", "position", "albedo"))
+        self._chk(self.lib.yh_denoise_variance_image_device(self.h, C.byref(variance_params), p["rgba_in"], p["variance_in"], C.byref(g) if g is not None else None,
+                                                            p["rgba_out"], p["variance_out"]))
+
+    def svgf_display(self, params=None, variance_params=None, exposure=0.0, filmic=False, srgb=True):
+        """yh_svgf_display: the own render through stages M, S and F and the tone map, as (H, W, 4) bytes."""
+        params = params if params is not None else self.temporal_default_params()
+        variance_params = variance_params if variance_params is not None else self.variance_default_params()
+        img = np.zeros((getattr(self, "height", 0), getattr(self, "width", 0), 4), np.uint8)
+        self._chk(self.lib.yh_svgf_display(self.h, C.byref(params), C.byref(variance_params), exposure, int(filmic), int(srgb),
+                                           img.ctypes.data_as(C.POINTER(C.c_uint8))))
+        return img
+
+    def temporal_steps(self):
+        """yh_temporal_steps: the moment history's steps as an (H, W) int32 array, or None without a moment history."""
+        n = self.lib.yh_temporal_steps(self.h, None)
+        self._chk(min(n, 0))
+        if n == 0:
+            return None
+        out = np.zeros(n, np.int32)
+        self._chk(min(self.lib.yh_temporal_steps(self.h, iptr(out)), 0))
+        return out.reshape(self.height, self.width) if n == getattr(self, "height", 0) * getattr(self, "width", 0) else out
+
+    def reproject_moments_gpu(self, params, rgba, samples, object, position, albedo, history, moment_history, camera, prev_camera=None, frames=None,
+                              prev_frames=None, usable=None):
+        """yh_reproject_moments_gpu: reproject_moments' arrays through the device kernel."""
+        w, h, held, args, outs = _moment_args(rgba, samples, object, position, albedo, history, moment_history, camera, prev_camera, frames, prev_frames, usable)
+        self._chk(self.lib.yh_reproject_moments_gpu(self.h, w, h, C.byref(params) if params is not None else None, *args))
+        return outs
+
+    def variance_spatial_gpu(self, temporal_params, min_steps, moments, steps, object, position):
+        """yh_variance_spatial_gpu: variance_spatial's arrays through the device kernel."""
+        w, h, held, ptrs, out = _spatial_args(moments, steps, object, position)
+        self._chk(self.lib.yh_variance_spatial_gpu(self.h, w, h, C.byref(temporal_params), int(min_steps), *ptrs))
+        return out
+
+    def atrous_variance_filter_gpu(self, form, params, rgba, variance, object, normal=None, position=None, albedo=None):
+        """yh_atrous_variance_filter_gpu: atrous_variance_filter's arrays through the device kernels (form 0: taps from memory, 1: from an LDS tile)."""
+        w, h, held, ptrs, outs = _vfilter_args(rgba, variance, object, normal, position, albedo)
+        self._chk(self.lib.yh_atrous_variance_filter_gpu(self.h, form, w, h, C.byref(params), *ptrs))
+        return outs
 
     def shard_pixels(self, rank, world):
         return int(self.lib.yh_shard_pixels(self.h, rank, world))
