@@ -953,6 +953,16 @@ int yh_lights_const_env(const yh_context* ctx);
  * hair set-up, sampling branch, BSDF value and pdf, lights pdf, weight and
  * continuation, path end. Writes min(capacity, 27) numbers, returns 27.     */
 int yh_shade_regions(const yh_context* ctx, uint64_t* out, int capacity);
+/* Developer diagnostics: which work items the next yh_trace_samples_counted
+ * launches count — the first `items` of the cost-ordered work list (the most
+ * expensive ones by the costs of the launch before; tools/top_items.py:
+ * expensive_count says how many are within 5 x of the top), so that the
+ * per-iteration figures describe the sample chains a chain-bound launch waits
+ * for and not the average over its background items. Every item still runs
+ * the instrumented kernel; the others add nothing to the work counts, the
+ * cycle stamps, the branch counts and the regions. 0 (the default): every
+ * item, as before. Product launches are unaffected.                          */
+int yh_set_count_bound(yh_context* ctx, int items);
 
 /* The light code on the uploaded scene, row by row: sample_lights and
  * sample_lights_pdf (yocto_pathtrace.cpp:1283-1358) and eval_environment

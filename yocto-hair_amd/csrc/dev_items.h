@@ -161,12 +161,14 @@ YH_DEV void trace_items(const yhd_scene& sc, const yhd_state& st, int nsamples, 
       YH_REGION_MARK("loop_tail");
       if (COUNT) cyc_shade += clock64() - c1;
     }
+    // (the instrumented build) an item outside the host's bound — yhd_counters::counted_items — runs stamped like every other and adds nothing
+    const bool item_counted = COUNT && (counters->counted_items == nullptr || counters->counted_items[item] != 0);
     if (COUNT) {  // flush this item's counters: one wave reduction, one atomic per counter
       unsigned int v[11] = {stats.samples, stats.rays, stats.nodes, stats.seg, stats.tri, stats.hair, stats.surf,
           stats.envl, stats.envs, l_steps, l_iters};
       for (int k = 0; k < 11; k++)
         for (int off = 32; off > 0; off >>= 1) v[k] += (unsigned int)__shfl_xor((int)v[k], off, 64);
-      if (lane == 0) {
+      if (lane == 0 && item_counted) {
         atomicAdd(&counters->samples, (unsigned long long)v[0]), atomicAdd(&counters->rays, (unsigned long long)v[1]);
         atomicAdd(&counters->nodes, (unsigned long long)v[2]), atomicAdd(&counters->seg, (unsigned long long)v[3]);
         atomicAdd(&counters->tri, (unsigned long long)v[4]), atomicAdd(&counters->hair, (unsigned long long)v[5]);
@@ -176,7 +178,7 @@ YH_DEV void trace_items(const yhd_scene& sc, const yhd_state& st, int nsamples, 
         atomicAdd(&counters->cyc_trace, cyc_trace), atomicAdd(&counters->cyc_shade, cyc_shade);
         atomicAdd(&counters->wave_iters, (unsigned long long)w_iters), atomicAdd(&counters->wave_steps, (unsigned long long)w_steps);
       }
-      if (lane == 0) {
+      if (lane == 0 && item_counted) {
         atomicAdd(&counters->c_geom, stats.c_geom), atomicAdd(&counters->c_sample, stats.c_sample);
         atomicAdd(&counters->c_eval, stats.c_eval), atomicAdd(&counters->c_rest, stats.c_rest);
       }
@@ -185,11 +187,14 @@ YH_DEV void trace_items(const yhd_scene& sc, const yhd_state& st, int nsamples, 
             stats.l_enter, stats.t_scene, stats.l_scene};
         for (int k = 0; k < 10; k++) {
           for (int off = 32; off > 0; off >>= 1) b[k] += (unsigned int)__shfl_xor((int)b[k], off, 64);
-          if (lane == 0) atomicAdd(&counters->branch[k], (unsigned long long)b[k]);
+          if (lane == 0 && item_counted) atomicAdd(&counters->branch[k], (unsigned long long)b[k]);
         }
       }
       unsigned long long* sums = stats.r;
-      if (lane < 3 * YH_REGIONS) atomicAdd(&counters->region[lane], sums[lane]), sums[lane] = 0;
+      if (lane < 3 * YH_REGIONS) {
+        if (item_counted) atomicAdd(&counters->region[lane], sums[lane]);
+        sums[lane] = 0;
+      }
       stats = stats_t{};
       stats.r = sums;
     }
@@ -201,7 +206,7 @@ YH_DEV void trace_items(const yhd_scene& sc, const yhd_state& st, int nsamples, 
       unsigned int dt = (unsigned int)(wall_clock64() - t0);
       if (YH_IS_OCT(MODE) || YH_IS_HEX(MODE)) atomicAdd(&st.tile_cost[item], dt);  // the halves / quarters of a quadrant add up (zeroed before the launch)
       else st.tile_cost[item] = dt;
-      if (COUNT) atomicAdd(&counters->cyc_tile, (unsigned long long)dt);
+      if (COUNT && item_counted) atomicAdd(&counters->cyc_tile, (unsigned long long)dt);
     }
   }
 }

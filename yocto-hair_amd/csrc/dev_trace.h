@@ -81,12 +81,31 @@ struct hit_t {
 // RAW (the traversal loop below): `a` = dot(rd, rd) is handed in (the same for every segment a ray meets inside one object) and an
 // accepted hit returns vv = d2 and rr = r instead of vv = sqrt(d2) / r — the loop evaluates that once, for the hit that survives
 // (same operands, same operations: same bits).
-template <bool STRAIGHT = false, bool RAW = false>
+// ONE_RETURN (with RAW; the once-per-ray trip): of the three returns only the middle one is left, as the one branch of the test — it
+// skips the second half (the point on the segment, d2, r: 41 of the 81 vector instructions) when no lane's t lies in the ray's range.
+// The first never skips (a degenerate segment) and the last skips nothing but the three result moves, yet each costs every leaf step
+// an exec-mask save, a branch, a restore and the re-initialisation of the results on the not-taken side (profiles/trip_flow/): they
+// are folded into the predicate as in STRAIGHT. Same operands, same operations: same bits.
+template <bool STRAIGHT = false, bool RAW = false, bool ONE_RETURN = false>
 YH_DEV bool intersect_line(f3 ro, f3 rd, float tmin, float tmax, f3 p0, f3 p1, float r0,
     float r1, float& uu, float& vv, float& dist, float a_in = 0.0f, float* rr = nullptr) {
   f3    u = rd, v = p1 - p0, w = ro - p0;
   float a = RAW ? a_in : dot(u, u), b = dot(u, v), c = dot(v, v), d = dot(u, w), e = dot(v, w);
   float det = a * c - b * b;
+  if (ONE_RETURN) {
+    static_assert(!ONE_RETURN || RAW, "the one-return form hands out the raw results");
+    float t = (b * e - c * d) / det;
+    float s = (a * e - b * d) / det;
+    if (!(det != 0 && !(t < tmin || t > tmax))) return false;
+    s         = fclamp(s, 0.0f, 1.0f);
+    f3    pr  = ro + rd * t;
+    f3    pl  = p0 + (p1 - p0) * s;
+    f3    prl = pr - pl;
+    float d2  = dot(prl, prl);
+    float r   = r0 * (1 - s) + r1 * s;
+    uu = s, vv = d2, *rr = r, dist = t;
+    return !(d2 > r * r);
+  }
   if (STRAIGHT) {
     float t   = (b * e - c * d) / det;
     float s   = (a * e - b * d) / det;
@@ -140,6 +159,23 @@ YH_DEV bool intersect_triangle(f3 ro, f3 rd, float tmin, float tmax, f3 p0, f3 p
   uu = u, vv = v;
   dist = t;
   return true;
+}
+// The same with ONE of its four returns (the once-per-ray trip; intersect_line's ONE_RETURN says why): the test of u, which skips the
+// second cross product and two dot products; a zero det makes u inf or NaN — the first return folded into it — and the tests of v
+// and t are the predicate. The results are written whatever it says: the caller reads them only where it holds.
+YH_DEV bool intersect_triangle_one_return(f3 ro, f3 rd, float tmin, float tmax, f3 p0, f3 p1, f3 p2, float& uu, float& vv, float& dist) {
+  f3    edge1 = p1 - p0, edge2 = p2 - p0;
+  f3    pvec = cross(rd, edge2);
+  float det  = dot(edge1, pvec);
+  float inv_det = 1.0f / det;
+  f3    tvec    = ro - p0;
+  float u       = dot(tvec, pvec) * inv_det;
+  if (!(det != 0 && !(u < 0 || u > 1))) return false;
+  f3    qvec = cross(tvec, edge1);
+  float v    = dot(rd, qvec) * inv_det;
+  float t    = dot(edge2, qvec) * inv_det;
+  uu = u, vv = v, dist = t;
+  return !(v < 0 || u + v > 1) && !(t < tmin || t > tmax);
 }
 // math.h:3544-3554
 YH_DEV bool intersect_bbox(f3 ro, f3 dinv, float tmin_, float tmax_, f3 bmin, f3 bmax) {
@@ -379,11 +415,13 @@ YH_DEV bool exact_ancestors_pass(f3 lo, f3 ldinv, float tmin, float tmax, f3 bmi
 // the scene level is resolved once per ray, ahead of the loop. The scene node's box test, the padded-box slabs of each of the
 // leaf's (at most four) objects and the ENTER arithmetic of every object whose box passes at the ray's first `tmax` — pure
 // functions of (ray, object) — run in a prologue with all live quads of the wave together, instead of in whichever trips the
-// quads reach them, and leave one record per (path, object) in LDS:
-//   rows of STRIDE float4, row 4 k + r of the path's column:  {lo, t0} {ld, far} {1 / ld, dot(ld, ld)} {sign bits, kind, root, object}
-// Popping an ENTER entry culls with the CURRENT `tmax` from t0 and far alone, goes on to the next entry in the same trip when the
-// cull fails, and otherwise loads the record and fetches the shape's root; the loop has no scene-node branch and the world ray is
-// dead in it. A ray that would put a NaN into a slab takes the second pass, which keeps the in-loop scene level (ONCE = false): the
+// quads reach them, and leave one record per (path, surviving object) in LDS:
+//   rows of STRIDE float4, row 4 s + r of the path's column:  {lo, t0} {ld, far} {1 / ld, dot(ld, ld)} {sign bits, kind, root, object}
+// The first object is entered by the prologue itself. The others wait as a COUNT (their ENTER entries would lie below every shape's:
+// they are met with the traversal stack empty and only then); a lane whose stack is empty culls them with the CURRENT `tmax` from t0
+// and far alone, all at once and without a loop, loads the first survivor's record and has the shape's root as its next entry. The
+// loop — written for the shape of its control flow, below — has no scene-node branch, no ENTER entry, and the world ray is dead in
+// it. A ray that would put a NaN into a slab takes the second pass, which keeps the in-loop scene level (ONCE = false): the
 // compare-and-select form's NaN semantics depend on operand order, so nothing precomputed is carried over to it.
 template <bool COUNT, int STRIDE, bool EXACT, bool LDS_SCENE = false, int MODE = YH_MODE_QUAD, bool ONCE = false>
 YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_object, unsigned int* steps_out, bool& redo) {
@@ -430,10 +468,13 @@ YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_obj
   };
   static_assert(!ONCE || (LDS_SCENE && !EXACT), "the prologue form reads the scene level from LDS and leaves NaN slabs to the second pass");
   unsigned int cur;
+  int          ent = 0;  // ONCE: objects of the prologue not yet entered
   if constexpr (ONCE) {
     // THE PROLOGUE (first_object is -1: the sample loop's main rays). The scene's one node, counted and tested as the loop does
-    // (pt.cpp:1005-1023), then its objects from the last to the first, so that the entries behind the first survivor lie on the
-    // stack in reverse order, as the scene leaf pushes them.
+    // (pt.cpp:1005-1023), then its objects from the last to the first: the survivors' records fill the path's column from row 0,
+    // so the `ent` records that wait lie in rows 4 (ent - 1) .. 0 in the order the scene leaf enters them — the stack the
+    // in-loop form pushes its ENTER entries on, kept as one count (those entries lie below every shape's: they are met with the
+    // traversal stack empty, and only then).
     cur = YH_NONE;
     const v4f n0 = lds_snodes[0], n1 = lds_snodes[1];
     if (q == 0) n_nodes++;
@@ -459,22 +500,159 @@ YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_obj
         const int sg = (di.x < 0 ? 1 : 0) | (di.y < 0 ? 2 : 0) | (di.z < 0 ? 4 : 0);
         if (!(finite3(di) && finite3(o_))) redo = true;  // a slab of this object could hold a NaN: second pass
         const int root = __float_as_int(YH_IS_HEX(MODE) ? ob[10].w : YH_IS_OCT(MODE) ? ob[10].z : ob[10].x);
-        YH_LDS v4f* rec = tc.lds_once + 4 * k * STRIDE;  // (every lane of the path's quads writes the same four rows)
+        YH_LDS v4f* rec = tc.lds_once + 4 * ent * STRIDE;  // (every lane of the path's quads writes the same four rows)
         rec[0]          = v4f{o_.x, o_.y, o_.z, t0};
         rec[STRIDE]     = v4f{d_.x, d_.y, d_.z, far};
         rec[2 * STRIDE] = v4f{di.x, di.y, di.z, dot(d_, d_)};
         rec[3 * STRIDE] = v4f{__int_as_float(sg), ob[6].x, __int_as_float(root), __int_as_float(obj)};
-        if (cur != YH_NONE) push(cur);
-        cur = YH_TAG_ENTER | (unsigned)k;
+        ent++;
+        // ... and in the loop's registers: the last survivor met here is the first object the ray enters
+        lo = o_, ld = d_, ldinv = di, ld2 = dot(d_, d_);
+        lsign = sg, kind = __float_as_int(ob[6].x), node_base = root, cur_obj = obj;
       }
     }
-    if (redo) cur = YH_NONE, sp = 0;  // (leaves the loop at its head)
+    if (ent > 0) ent--, cur = YH_TAG_SHAPE | (unsigned)node_base;  // the first object's root: no record read, no cull (its box passed at this very `tmax`)
+    if (redo) ent = 0, cur = YH_NONE;  // (the loop is not entered)
   } else if (first_object >= 0) {
     cur = YH_TAG_ENTER | (unsigned)first_object;
   } else {
     if (sc.num_scene_nodes == 0) return hit;
     cur = YH_TAG_SCENE | 0u;
   }
+  if constexpr (ONCE) {
+    // THE TRIP OF THE ONCE FORM, written for the shape of its control flow: a lone wave pays an issue slot for every exec-mask
+    // save, branch and restore, so the trip is ONE address and two loads, two sibling regions — node and leaf, each under its own
+    // mask and restored once, the leaf's two kinds side by side inside it, every primitive test with one return (three siblings
+    // under one mask cost a trip without a leaf lane, 59 % of them, a second empty region: profiles/trip_flow/isa_counts.txt) —
+    // and a tail that finds the next entry (the stack's top, or the next object when the stack is empty) for the lanes that
+    // have none; the loop's one exit is its latch. What a trip computes is the loop's below, operation for operation.
+    static_assert(MODE == YH_MODE_QUAD || MODE == YH_MODE_OCT, "the once-per-ray form exists for quads and octets");
+    // The surviving hit is kept in the hit record alone — row 3: object << 28 | test record (a scene of this form has at most four
+    // objects and a test record's index has 27 bits and a carry), all ones = none; its distance is `tmax`.
+    hrec[3 * STRIDE] = YH_NONE;
+    if (cur != YH_NONE) do {
+      if (COUNT) n_steps++;
+      const bool         is_leaf = (cur & YH_TAG_MASK) == YH_TAG_LEAF;
+      const bool         lines   = kind == YH_KIND_LINES;
+      const unsigned int leaf_start = cur & 0x07FFFFFFu, leaf_num = (cur >> 27) & 7u;
+      const bool         mine  = q < leaf_num;  // lanes beyond the leaf's count re-read its last record
+      const unsigned int pq    = mine ? q : leaf_num - 1u;
+      const unsigned int nslot = MODE == YH_MODE_QUAD ? q : (__lane_id() & 7u);
+      // ONE ADDRESS FORM: the lane's 32 bytes in the blob — slot (lane of the group) of the node, or the test record of primitive
+      // pq of the leaf — chosen by selects ahead of the two loads
+      const unsigned int unit = is_leaf ? leaf_start + (lines ? pq : 2u * pq) : cur + nslot;
+      const yhd_float4*  addr = sc.lane_blob + 2 * (size_t)unit;
+      const v4f          s0 = ldg4(addr), s1 = ldg4(addr + 1);
+      // what a leaf's region ends with: the quad's survivor by the reference's sequential accept rule (the loop below says why)
+      auto leaf_end = [&](bool ok, float uu, float vv, float dist, float rr) {
+        // (a lane without a hit takes part with t = +inf and place -1: it loses to every hit — a hit's t is finite — and two of them
+        // leave things as they are, so the merge asks for t and place alone)
+        const int my_i  = (int)q;
+        int       key_i = ok ? my_i : -1;
+        float     key_t = ok ? dist : __builtin_inff();
+#define YH_KEY_MERGE(CTRL)                                                   \
+  {                                                                         \
+    int   oi = dpp_i<CTRL>(key_i);                                          \
+    float ot = dpp_f<CTRL>(key_t);                                          \
+    bool  take = (ot < key_t) | ((ot == key_t) & (oi > key_i));             \
+    key_i = take ? oi : key_i, key_t = take ? ot : key_t;                   \
+  }
+        YH_KEY_MERGE(YH_QUAD_XOR1)
+        YH_KEY_MERGE(YH_QUAD_XOR2)
+#undef YH_KEY_MERGE
+        tmax = key_i >= 0 ? key_t : tmax;
+        // the survivor's lane (my_i >= 0; the octet form runs the same path in both quads: either of the identical writers) leaves
+        // u, raw v, r and — row 3 — the hit's object and test record, which the loop therefore does not carry
+        if (key_i == my_i) {
+          hrec[0] = __float_as_uint(uu), hrec[STRIDE] = __float_as_uint(vv), hrec[2 * STRIDE] = __float_as_uint(rr);
+          hrec[3 * STRIDE] = ((unsigned)cur_obj << 28) | (leaf_start + (lines ? q : 2u * q));
+        }
+        cur = YH_NONE;
+      };
+      if (!is_leaf) {
+        if (q == 0) n_nodes++;
+        if (COUNT) count_branch<COUNT>(tc.stats->t_node, tc.stats->l_node);
+        const unsigned int ref  = __float_as_uint(s1.z);
+        const unsigned int axes = __float_as_uint(s1.w);
+        const bool h = intersect_bbox_nonan(lo, ldinv, ray.tmin, tmax, f3{s0.x, s0.y, s0.z}, f3{s0.w, s1.x, s1.y}) && ref != YH_NONE;  // (an empty slot's inverted box still passes the min / max slab test)
+        unsigned int rank, M;
+        if (MODE == YH_MODE_QUAD) {  // slot q of a 4-wide node: the loop below says how the visiting order becomes a rank
+          const unsigned int pair = q >> 1;
+          const unsigned int sgn  = (lsign >> ((axes >> (2 + 2 * pair)) & 3)) & 1;
+          const unsigned int s0_  = (lsign >> (axes & 3)) & 1;
+          rank = ((pair ^ s0_) << 1) | ((q & 1) ^ sgn);
+        } else {  // slot o of an 8-wide node
+          const unsigned int g  = (__lane_id() & 7u) >> 1;
+          const unsigned int n0 = (lsign >> (axes & 3)) & 1;
+          const unsigned int n1 = (lsign >> ((axes >> (2 + 2 * (g >> 1))) & 3)) & 1;
+          const unsigned int n2 = (lsign >> ((axes >> (6 + 2 * g)) & 3)) & 1;
+          rank = ((((g >> 1) ^ n0) << 2) | (((g & 1) ^ n1) << 1)) | ((__lane_id() & 1u) ^ n2);
+        }
+        const unsigned int bit = h ? (1u << rank) : 0u;
+        M = bit | (unsigned int)dpp_i<YH_QUAD_XOR1>((int)bit);
+        M |= (unsigned int)dpp_i<YH_QUAD_XOR2>((int)M);
+        if (MODE == YH_MODE_OCT) M |= (unsigned int)dpp_i<YH_ROW_HALF_MIRROR>((int)M);  // hits in visiting order, bit k = k-th visited
+        const bool first = h && (M & (bit - 1)) == 0;
+        if (h && !first) YH_STK(sp + (int)__popc(M >> (rank + 1))) = ref;  // the hit slots visited after this one lie above it
+        unsigned int head = first ? ref : 0u;  // child refs are never 0
+        head |= (unsigned int)dpp_i<YH_QUAD_XOR1>((int)head);
+        head |= (unsigned int)dpp_i<YH_QUAD_XOR2>((int)head);
+        if (MODE == YH_MODE_OCT) head |= (unsigned int)dpp_i<YH_ROW_HALF_MIRROR>((int)head);
+        const int nh = __popc(M);
+        sp += nh > 0 ? nh - 1 : 0;
+        cur = nh > 0 ? head : YH_NONE;
+      }
+      if (is_leaf) {
+        // (a lane beyond the leaf's count tests the last record again and its verdict is dropped: no branch around the test)
+        if (lines) {
+          if (COUNT) count_branch<COUNT>(tc.stats->t_line, tc.stats->l_line);
+          float uu, vv, dist, rr;
+          if (mine) n_seg++;
+          const bool ok = intersect_line<(STRIDE == 64), true, (STRIDE != 64)>(lo, ld, ray.tmin, tmax, xyz(s0), xyz(s1), s0.w, s1.w, uu, vv, dist, HOIST_A ? ld2 : dot(ld, ld), &rr);  // (the octet half: 64 columns, the STRAIGHT test, as before)
+          leaf_end(ok & mine, uu, vv, dist, rr);
+        } else {
+          if (COUNT) count_branch<COUNT>(tc.stats->t_tri, tc.stats->l_tri);
+          const v4f s2 = ldg4(addr + 2);
+          float     uu, vv, dist;
+          if (mine) n_tri++;
+          const bool ok = intersect_triangle_one_return(lo, ld, ray.tmin, tmax, xyz(s0), xyz(s1), xyz(s2), uu, vv, dist);
+          leaf_end(ok & mine, uu, vv, dist, 1.0f);
+        }
+      }
+      // THE NEXT ENTRY: the stack's top or, with the stack empty, the next object that waits
+      if (cur == YH_NONE) {
+        if (sp > 0) {
+          cur = pop();
+        } else if (ent > 0) {
+          // Without a loop. The records that wait are rows 4 s, s < ent, entered from the highest s down; each is culled by the
+          // reference's box test with the CURRENT `tmax`, decomposed: the prologue kept t0 = max(slab mins, tmin) and
+          // far = min(slab maxes), and min(far, tmax) is the t1 intersect_bbox_nonan forms (min and max are exact and associative
+          // on NaN-free operands, and the sign of a zero is not observable through `* 1.00000024f` and `<=`): bit for bit the
+          // decision the in-loop ENTER takes. The first survivor's root is the next trip's node; the ones passed over are gone.
+          if (COUNT) count_branch<COUNT>(tc.stats->t_enter, tc.stats->l_enter);
+          int take = -1;
+#pragma unroll
+          for (int s = 0; s < 3; s++) {  // (at most four objects, and the first was entered by the prologue)
+            if (s + 1 >= sc.scene_once) break;  // (wave-uniform: a scene of two objects reads one record's pair)
+            const YH_LDS float* w  = (const YH_LDS float*)(tc.lds_once + 4 * s * STRIDE);
+            const float         t0 = w[3], far = w[4 * STRIDE + 3];
+            const bool          in = (s < ent) & (t0 <= __builtin_fminf(far, tmax) * 1.00000024f);
+            take = in ? s : take;
+          }
+          ent = take < 0 ? 0 : take;
+          if (take >= 0) {
+            const YH_LDS v4f* rec = tc.lds_once + 4 * take * STRIDE;
+            const v4f         r0 = rec[0], r1 = rec[STRIDE], r2 = rec[2 * STRIDE], r3 = rec[3 * STRIDE];
+            lo = xyz(r0), ld = xyz(r1), ldinv = xyz(r2), ld2 = r2.w;
+            lsign = __float_as_int(r3.x), kind = __float_as_int(r3.y), node_base = __float_as_int(r3.z), cur_obj = __float_as_int(r3.w);
+            cur = YH_TAG_SHAPE | (unsigned)node_base;
+          }
+        }
+      }
+    } while (cur != YH_NONE);
+    const unsigned int packed = hrec[3 * STRIDE];
+    if (packed != YH_NONE) hit.object = (int)(packed >> 28), hit.slot = (int)(packed & 0x0FFFFFFFu), hit.distance = tmax;
+  } else
   // One loop, one dependent fetch per iteration: whatever a quad holds — a wide
   // node or a leaf — every lane fetches "its" 32 bytes (slot q of the node, or
   // the test half of primitive q of the leaf) with the same two load
@@ -492,32 +670,6 @@ YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_obj
     // shape chain inside ONE iteration, so a ray pays one memory round trip per
     // object it enters instead of three.
     bool scene_node = false;  // this step's node is a 4-wide node of the scene level
-    if constexpr (ONCE) {
-      if (tag == YH_TAG_ENTER) {
-        // An object of the prologue. The cull is the reference's box test with the CURRENT `tmax`, decomposed: the prologue kept
-        // t0 = max(slab mins, tmin) and far = min(slab maxes), and min(far, tmax) is the t1 intersect_bbox_nonan forms (min and
-        // max are exact and associative on NaN-free operands, and the sign of a zero is not observable through `* 1.00000024f`
-        // and `<=`): bit for bit the decision the in-loop ENTER takes. An object that fails costs no trip: the entries below an
-        // ENTER entry are ENTER entries (a shape's entries lie above it and are gone by now), so the next one is tried at once.
-        if (COUNT) count_branch<COUNT>(tc.stats->t_enter, tc.stats->l_enter);
-        const YH_LDS v4f* rec;
-        v4f               r0, r1;
-        while (true) {
-          rec = tc.lds_once + 4 * (int)(cur & 3u) * STRIDE;
-          r0 = rec[0], r1 = rec[STRIDE];
-          if (r0.w <= __builtin_fminf(r1.w, tmax) * 1.00000024f) break;
-          cur = YH_NONE;
-          if (sp == 0) break;
-          cur = pop();
-        }
-        if (cur == YH_NONE) continue;
-        const v4f r2 = rec[2 * STRIDE], r3 = rec[3 * STRIDE];
-        lo = xyz(r0), ld = xyz(r1), ldinv = xyz(r2), ld2 = r2.w;
-        lsign = __float_as_int(r3.x), kind = __float_as_int(r3.y), node_base = __float_as_int(r3.z), cur_obj = __float_as_int(r3.w);
-        cur = YH_TAG_SHAPE | (unsigned)node_base;  // shape root: fetched in this same iteration
-        tag = YH_TAG_SHAPE;
-      }
-    } else {
     if (!LDS_SCENE && tag == YH_TAG_SCENE && wide_scene) {
       // THE SCENE LEVEL AS 4-WIDE NODES (a scene table in memory, yh_device.h: scene_wide_root): the entry is a node's offset in the blob
       // — fetched and tested below like a shape's, lane q slot q, against the WORLD ray: the ray-in-the-object registers are free up here
@@ -614,7 +766,6 @@ YH_DEV hit_t trace_ray_loop(const trace_ctx& tc, const ray_t& ray, int first_obj
       cur = YH_TAG_SHAPE | (unsigned)node_base;  // shape root: fetched in this same iteration
       tag = YH_TAG_SHAPE;
     }
-    }  // !ONCE
     {
       bool is_leaf    = tag == YH_TAG_LEAF;
       // LEAF GROUPS (YH_MODE_OCTP: pairs, YH_MODE_HEXP: up to four): when the entry is a leaf and the entries on top of the

@@ -339,6 +339,9 @@ typedef struct yhd_counters {
   // the regions of a wave iteration's shading pass (dev_path.h: path_step; dev_items.h): per region the wave's cycles, the trips that ran
   // it and the lanes it ran with, added where the region ends (dev_trace.h: count_region)
   unsigned long long region[3 * 9];
+  // which work items add to all of the above: one byte per item (tile * 4 + quadrant), non-zero = counted; NULL = every item
+  // (yh_set_count_bound: the first N items of the cost-ordered list, the ones whose sample chain the launch waits for)
+  const unsigned char* counted_items;
 } yhd_counters;
 enum yhd_region {
   YH_REGION_REGEN = 0,   // the loop head: path_begin of the quads that start a sample (outside cyc_shade)

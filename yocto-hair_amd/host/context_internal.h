@@ -196,6 +196,8 @@ struct yh_context {
   DevBuf           d_textures, d_tex_texels, d_vtex, d_maps;
   DevBuf           d_rng_state, d_rng_inc, d_accum, d_tiles, d_image, d_counters, d_tile_cursor, d_tile_cost, d_display;
   unsigned long long last_regions[3 * YH_REGIONS] = {};  // yhd_counters::region of the last yh_trace_samples_counted (yh_shade_regions)
+  int              count_bound = 0;  // yh_set_count_bound: a counted launch counts the first `count_bound` items of the cost-ordered list (0: all)
+  DevBuf           d_counted_items;  // ... as one byte per work item (yhd_counters::counted_items)
   std::vector<int> owned;      // owned tile ids, increasing
   std::vector<unsigned int>  item_cost;  // per work item (tile * 4 + quadrant): last measured cost (scheduling hint, kept across init_state)
   int              rank = 0, world = 1;

@@ -340,6 +340,18 @@ int yh_trace_samples_counted(yh_context* ctx, int nsamples, yh_workcounts* out) 
   if (!ctx->have_state) return fail(ctx, YH_E_STATE, "yh_trace_samples_counted before yh_init_state");
   HIPCHK(ctx, hipSetDevice(ctx->device));
   HIPCHK(ctx, hipMemsetAsync(ctx->d_counters.p, 0, sizeof(yhd_counters), ctx->stream));
+  if (ctx->count_bound > 0) {
+    // The items that count: the head of the cost-ordered list as build_work_items makes it from the costs at hand — by item, not by
+    // place in the launch's list, whose head prepare_work_list lays out by wave slot.
+    std::vector<int> items;
+    build_work_items(ctx, items);
+    std::vector<unsigned char> counted(ctx->item_cost.size(), 0);
+    for (size_t k = 0; k < items.size() && k < (size_t)ctx->count_bound; k++) counted[(size_t)items[k]] = 1;
+    if (int urc = upload_keep(ctx, ctx->d_counted_items, counted.data(), counted.size())) return urc;
+    const unsigned char* flags = (const unsigned char*)ctx->d_counted_items.p;
+    HIPCHK(ctx, hipMemcpyAsync((char*)ctx->d_counters.p + offsetof(yhd_counters, counted_items), &flags, sizeof(flags), hipMemcpyHostToDevice, ctx->stream));
+    YH_WAIT(ctx);  // (`flags` is a local)
+  }
   int rc = trace_impl(ctx, nsamples, true, true);
   if (rc) return rc;
   yhd_counters c;
@@ -351,6 +363,11 @@ int yh_trace_samples_counted(yh_context* ctx, int nsamples, yh_workcounts* out) 
   out->cyc_geom = c.c_geom, out->cyc_sample = c.c_sample, out->cyc_eval = c.c_eval, out->cyc_rest = c.c_rest;
   for (int k = 0; k < 10; k++) out->branch[k] = c.branch[k];
   for (int k = 0; k < 3 * YH_REGIONS; k++) ctx->last_regions[k] = c.region[k];
+  return YH_OK;
+}
+int yh_set_count_bound(yh_context* ctx, int items) {
+  if (!ctx || items < 0) return YH_E_INVALID;
+  ctx->count_bound = items;
   return YH_OK;
 }
 int yh_shade_regions(const yh_context* ctx, uint64_t* out, int capacity) {

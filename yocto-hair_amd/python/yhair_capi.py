@@ -325,6 +325,7 @@ _SIGS = {
     "yh_scene_once": (C.c_int, [C.c_void_p]),
     "yh_lights_const_env": (C.c_int, [C.c_void_p]),
     "yh_shade_regions": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint64), C.c_int]),
+    "yh_set_count_bound": (C.c_int, [C.c_void_p, C.c_int]),
     "yh_lights_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_float_p, c_float_p, c_float_p, c_float_p]),
     "yh_volume_batch": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(Material), c_float_p, c_float_p, c_float_p, c_float_p,
                                   c_float_p, c_float_p]),
@@ -1311,6 +1312,10 @@ class Context:
         out = (C.c_uint64 * 27)()
         self.lib.yh_shade_regions(self.h, out, 27)
         return {nm: (int(out[3 * k]), int(out[3 * k + 1]), int(out[3 * k + 2])) for k, nm in enumerate(self.SHADE_REGIONS)}
+
+    def set_count_bound(self, items):
+        """yh_set_count_bound: trace_samples_counted counts the first `items` work items of the cost-ordered list only (0: all)."""
+        self._chk(self.lib.yh_set_count_bound(self.h, int(items)))
 
     def lights(self, form, position, direction, rn4):
         """yh_lights_batch on the uploaded scene (form 0: a quad per row, 1: a lane per row): (n, 8) = sample_lights
